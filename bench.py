@@ -11,8 +11,13 @@ over a chunk of `--chunk` synthetic documents already resident in HBM as packed 
 N > 1 (one rank per GPU; `python bench.py --gpus N` re-launches itself under torch.distributed.run when
 it was not started by it): every rank owns its own corpus shard (weak scaling: work per GPU fixed);
 queries are encoded sharded and all-gathered once over RCCL; at the end the per-rank top-k lists are
-all-gathered and merged.  No data-path collective inside a step.  After the timed region the sharded
-search is checked against a single-rank search over the same documents.
+all-gathered and merged.  No data-path collective inside a step.
+
+A plain run sets up, warms up, times `--steps` steps and prints the headline (with the live GEMM roofline of those
+steps).  `--full` adds every other leg after the timed region: the same steps without event records, the host-pack
++ H2D steps, the sharded-vs-single-rank check (N > 1), queries/sec at the job corpus and at 1M documents, variable
+lengths, the other precision modes, the CPU baseline + parity probe, and the short runs of the larger SGPT shapes.
+`--dump-outputs DIR` writes what the last timed step returned (top-(k+1) scores and ids, that step's embeddings).
 
 Prints ONE JSON line on rank 0.
 """
@@ -158,6 +163,25 @@ def hf_cpu_baseline(ocfg, ow, sample, repeats=3, mask=None, hf=None, slice_note=
                                    f"({', '.join(f'{x:.1f}' for x in times)} s)"}, hf
 
 
+DUMP_EMB_BYTES = 48 << 20     # the embeddings' share of the 64 MB output budget (the top-k lists: 12 bytes per kept hit)
+
+
+def dump_outputs(out_dir, fv, fi, emb32):
+    """What the last timed step hands its caller: the running top-(k+1) scores (fp32) and global document ids (float64:
+    exact below 2^53), and the fp32 embeddings of that step's documents -- a fixed, seeded row sample (row ids stored
+    beside it) when they exceed DUMP_EMB_BYTES."""
+    os.makedirs(out_dir, exist_ok=True)
+    emb = emb32.cpu().numpy()
+    rows = np.arange(emb.shape[0])
+    max_rows = DUMP_EMB_BYTES // emb[0].nbytes
+    if emb.shape[0] > max_rows:
+        rows = np.sort(np.random.default_rng(0).choice(emb.shape[0], size=max_rows, replace=False))
+    arrays = {"topk_scores": fv.cpu().numpy().astype(np.float32), "topk_doc_ids": fi.cpu().numpy().astype(np.float64),
+              "last_step_doc_embeddings": emb[rows].astype(np.float32), "last_step_doc_embedding_rows": rows.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -207,7 +231,11 @@ def main():
     ap.add_argument("--equal-calls", action="store_true", help="A/B: round 4's equal token budgets per sgpt_encode call instead of the round-aware ones (variable-length leg)")
     ap.add_argument("--no-modes", action="store_true", help="skip the precision-mode leg (f16x3 and exact-fp32 encode rates beside the headline)")
     ap.add_argument("--no-other-models", action="store_true", help="skip the short runs of BASELINE configs[2..4]'s shapes (SGPT-1.3B, 5.8B bf16, bloom-7b1 fp8 MFMA)")
+    ap.add_argument("--full", action="store_true", help="after the headline, run every other leg (the --no-* options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's results as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         relaunch_distributed(args.gpus)
@@ -312,6 +340,8 @@ def main():
         dt = float(tt.item())
     assert torch.isfinite(fv[:, : args.topk]).all() and (fi[:, : args.topk] >= 0).all()
     model._check_range()                                    # dtype f16: no activation left the half range (raises otherwise)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fv, fi, emb32)
 
     sentences = world * args.steps * args.chunk
     sent_per_s = sentences / dt
@@ -319,7 +349,7 @@ def main():
     # ---- A/B of the measurement itself: the timed region above carries two hipEventRecord per projection launch
     # (the live GEMM durations of `roofline`); the same steps again with the recording off ----
     event_ab = None
-    if world == 1:
+    if world == 1 and args.full:
         run2 = run
         sync()
         t1 = time.perf_counter()
@@ -335,41 +365,43 @@ def main():
     # token ids from host memory (numpy [call, S] int64 -> the int32 arena in pinned memory) and copies them over PCIe
     # (one non-blocking H2D per call, two pinned arenas alternating: the copy of call i+1 overlaps the encode of call i).
     # `value` above starts with the packed ids resident in HBM (SURVEY 8d boundary); this is the PCIe-inclusive rate. ----
-    host_steps = min(args.steps, 8)
-    hrng = np.random.default_rng(3000 + rank)
-    host_ids = [[hrng.integers(0, min(50256, cfg.vocab_size), size=(min(args.call, args.chunk - c0), S), dtype=np.int64)
-                 for c0 in range(0, args.chunk, args.call)] for _ in range(host_steps)]
+    sent_per_s_host = host_steps = None
+    if args.full:
+        host_steps = min(args.steps, 8)
+        hrng = np.random.default_rng(3000 + rank)
+        host_ids = [[hrng.integers(0, min(50256, cfg.vocab_size), size=(min(args.call, args.chunk - c0), S), dtype=np.int64)
+                     for c0 in range(0, args.chunk, args.call)] for _ in range(host_steps)]
 
-    def host_step(i, run):
-        o = 0
-        for ids in host_ids[i]:
-            pb = model.pack(ids)                                    # host pack + pinned async H2D
-            model.encode_packed(pb, mode="weightedmean", normalize=True, out=emb32[o: o + pb.B])
-            o += pb.B
-        rows = corpus[i * args.chunk: (i + 1) * args.chunk]
-        if score_dt != torch.float32:
-            ctx.to_16(emb32, score_dt, out=rows)
-        else:
-            rows.copy_(emb32)
-        return ctx.score_topk(q, rows, k1, idx_base=rank * n_steps * args.chunk + i * args.chunk, run=run, dtype=score_dt)
-    hrun = host_step(0, None)
-    sync()
-    t = time.perf_counter()
-    for i in range(host_steps):
-        hrun = host_step(i, hrun)
-    sync()
-    hdt = time.perf_counter() - t
-    if dist_on:
-        th = torch.tensor([hdt], dtype=torch.float64, device=dev)
-        dist.all_reduce(th, op=dist.ReduceOp.MAX)
-        hdt = float(th.item())
-    sent_per_s_host = world * host_steps * args.chunk / hdt
-    del host_ids
+        def host_step(i, run):
+            o = 0
+            for ids in host_ids[i]:
+                pb = model.pack(ids)                                    # host pack + pinned async H2D
+                model.encode_packed(pb, mode="weightedmean", normalize=True, out=emb32[o: o + pb.B])
+                o += pb.B
+            rows = corpus[i * args.chunk: (i + 1) * args.chunk]
+            if score_dt != torch.float32:
+                ctx.to_16(emb32, score_dt, out=rows)
+            else:
+                rows.copy_(emb32)
+            return ctx.score_topk(q, rows, k1, idx_base=rank * n_steps * args.chunk + i * args.chunk, run=run, dtype=score_dt)
+        hrun = host_step(0, None)
+        sync()
+        t = time.perf_counter()
+        for i in range(host_steps):
+            hrun = host_step(i, hrun)
+        sync()
+        hdt = time.perf_counter() - t
+        if dist_on:
+            th = torch.tensor([hdt], dtype=torch.float64, device=dev)
+            dist.all_reduce(th, op=dist.ReduceOp.MAX)
+            hdt = float(th.item())
+        sent_per_s_host = world * host_steps * args.chunk / hdt
+        del host_ids
 
     # ---- N > 1: the sharded search (per-rank score+top-k with a global index base -> exchange -> merge) must equal a
     # single-rank search over the same documents.  Checked on the first `m` rows of every rank's shard. ----
     shard_check = None
-    if dist_on:
+    if dist_on and args.full:
         m = min(2048, args.chunk)
         mine_rows = corpus[:m].contiguous()
         from sgpt_amd.dist import get_comm
@@ -403,10 +435,10 @@ def main():
         sync()
         return args.nq * reps / (time.perf_counter() - t)
 
-    qps_job = time_search(corpus[args.warmup * args.chunk:])
+    qps_job = time_search(corpus[args.warmup * args.chunk:]) if args.full else None
     qps_1m = qps_1m_enc = projected = k1001 = qps_1m_fp32 = scorer_breakdown = query_latency = None
     qps_enc_by_nq, qps_enc_ll = {}, {}
-    if not args.no_1m:
+    if args.full and not args.no_1m:
         n1m = 1_000_000 // world                           # 1M-doc corpus sharded over the ranks
         big = torch.empty((n1m, d), dtype=score_dt, device=dev)
         blk = corpus[args.warmup * args.chunk:].float()
@@ -592,7 +624,7 @@ def main():
 
     # ---- the same step on documents of lengths ~U{16..128} (SURVEY 8d cfg2 asks for both) ----
     varlen = None
-    if not args.no_varlen:
+    if args.full and not args.no_varlen:
         vrng = np.random.default_rng(2000 + rank)
         v_steps = max(1, min(max(4, args.steps // 3), n_steps - 1))
         vpacked, v_tokens, v_flops = [], 0, 0.0
@@ -637,7 +669,7 @@ def main():
     # for an ill-conditioned checkpoint) and the exact-fp32 MFMA mode, the same 1024 x seq encode calls ----
     modes = None
     mode_probe_emb = {}
-    if world == 1 and args.model == "125m" and args.dtype == "f16" and not args.no_modes:
+    if args.full and world == 1 and args.model == "125m" and args.dtype == "f16" and not args.no_modes:
         modes = {"f16_sentences_per_s": round(sent_per_s, 1)}
         w2 = synthetic_weights(cfg, seed=1)
         probe_ids = np.random.default_rng(5).integers(0, 50256, size=(1024, S), dtype=np.int64)   # the CPU-baseline leg's probe call
@@ -715,7 +747,7 @@ def main():
     # The GPU encodes 1024 sentences in ONE call (131 072 tokens: every projection runs on the 256x256-tile throughput
     # kernels, the ones the timed region uses); every 16th row is checked against the CPU paths on the same ids.
     cpu = None
-    if not args.no_cpu_baseline and world == 1 and args.model == "125m":
+    if args.full and not args.no_cpu_baseline and world == 1 and args.model == "125m":
         from oracle import sgpt_oracle as O      # checker / reported baseline only, never the measured path
         ocfg = O.NeoConfig(**SGPT_125M)
         ow = O.synth_weights(ocfg, seed=1)
@@ -794,7 +826,7 @@ def main():
     # had builder-run numbers only): three short runs of this script (3 steps of 1024 documents, encode + pool + score) in
     # processes of their own, after this one has released the GPU memory it no longer needs ----
     other_configs = None
-    if world == 1 and args.model == "125m" and not args.no_other_models and not args.no_1m:
+    if args.full and world == 1 and args.model == "125m" and not args.no_other_models and not args.no_1m:
         del corpus, emb32
         torch.cuda.empty_cache()
         other_configs = {"note": "python bench.py --model M --dtype D --steps 3 --warmup 1 --chunk 1024 (1024-document steps, seq_len 128, same step "
@@ -835,23 +867,25 @@ def main():
                           "crest_max_ln1_ctx_ln2_h": [round(float(v), 1) for v in model.precision_report["crest"].max(0)],
                           "limits": model.precision_report["limits"]},
                       "split_plan_entries": int((model.precision_plan() != 0).sum()) if args.dtype in ("f16", "bf16") else 0},
-           "value_incl_host_pack_and_h2d": round(sent_per_s_host, 1),
-           "host_leg": f"{host_steps} of the same steps with every call's ids packed from host memory and copied over PCIe inside "
-                       "the clock (pinned double arena, async H2D overlapping the previous call's encode)",
-           "queries_per_sec_at_job_corpus": round(qps_job, 1),
-           "job_corpus_docs_per_gpu": args.steps * args.chunk,
-           "queries_per_sec_at_1M_corpus": None if qps_1m is None else round(qps_1m, 1),
-           "queries_per_sec_at_1M_corpus_fp32_scorer": None if qps_1m_fp32 is None else round(qps_1m_fp32, 1),
-           "queries_per_sec_at_1M_corpus_incl_query_encode": None if qps_1m_enc is None else round(qps_1m_enc, 1),
-           "queries_per_sec_at_1M_corpus_incl_query_encode_by_nq": {str(k_): round(v_, 1) for k_, v_ in qps_enc_by_nq.items()},
-           "queries_per_sec_at_1M_corpus_incl_query_encode_low_latency_mode": {str(k_): round(v_, 1) for k_, v_ in qps_enc_ll.items()},
-           "low_latency_mode_note": "round 6: layouts of <= 4096 token rows run csrc/qgemm.hip, which keeps the k-ascending sum and ignores the opt-in "
-                                    "k-group mode (sgpt_ctx_set_low_latency): these figures equal the default mode's to within noise",
-           "queries_per_sec_at_1M_corpus_k1001": k1001, "projected_8gpu": projected, "precision_modes": modes,
-           "varlen": varlen, "shard_check": shard_check,
-           "query_encode_latency": query_latency, "scorer_breakdown_1M_pass": scorer_breakdown, "event_record_ab": event_ab,
-           "other_configs": other_configs,
-           "roofline": roofline, "cpu_baseline": cpu}
+           "roofline": roofline}
+    if args.full:
+        out.update({
+            "value_incl_host_pack_and_h2d": round(sent_per_s_host, 1),
+            "host_leg": f"{host_steps} of the same steps with every call's ids packed from host memory and copied over PCIe inside "
+                        "the clock (pinned double arena, async H2D overlapping the previous call's encode)",
+            "queries_per_sec_at_job_corpus": round(qps_job, 1),
+            "job_corpus_docs_per_gpu": args.steps * args.chunk,
+            "queries_per_sec_at_1M_corpus": None if qps_1m is None else round(qps_1m, 1),
+            "queries_per_sec_at_1M_corpus_fp32_scorer": None if qps_1m_fp32 is None else round(qps_1m_fp32, 1),
+            "queries_per_sec_at_1M_corpus_incl_query_encode": None if qps_1m_enc is None else round(qps_1m_enc, 1),
+            "queries_per_sec_at_1M_corpus_incl_query_encode_by_nq": {str(k_): round(v_, 1) for k_, v_ in qps_enc_by_nq.items()},
+            "queries_per_sec_at_1M_corpus_incl_query_encode_low_latency_mode": {str(k_): round(v_, 1) for k_, v_ in qps_enc_ll.items()},
+            "low_latency_mode_note": "round 6: layouts of <= 4096 token rows run csrc/qgemm.hip, which keeps the k-ascending sum and ignores the opt-in "
+                                     "k-group mode (sgpt_ctx_set_low_latency): these figures equal the default mode's to within noise",
+            "queries_per_sec_at_1M_corpus_k1001": k1001, "projected_8gpu": projected, "precision_modes": modes,
+            "varlen": varlen, "shard_check": shard_check,
+            "query_encode_latency": query_latency, "scorer_breakdown_1M_pass": scorer_breakdown, "event_record_ab": event_ab,
+            "other_configs": other_configs, "cpu_baseline": cpu})
     print(json.dumps(out))
     if dist_on:
         dist.destroy_process_group()

@@ -4,7 +4,7 @@
 # Every stage writes under gpurun_out/ (merged back by gpurun); copy what is to be judged into profiles/rNN_*.
 #   tests      whole GPU suite with the parity log            -> pytest_full.log, parity.jsonl, parity_numbers.txt
 #   smoke      __graft_entry__.smoke()
-#   bench      default bench line                              -> bench_n1.json
+#   bench      bench.py --full line + digest of its legs       -> bench_n1.json
 #   yardstick  vendor GEMM vs gemm256d on the five shapes      -> hipblaslt_yardstick.txt
 #   prof       rocprofv3 --kernel-trace --stats of the bench   -> prof_summary.csv
 #   pmc        separate --pmc passes (FETCH, WRITE, MFMA busy) -> pmc_summary.csv, pmc_traffic.json
@@ -31,6 +31,7 @@ for stage in "$@"; do
       grep -E "^(FAILED|ERROR)" gpurun_out/pytest_full.log | cut -c1-300 ;;
     smoke) python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu | tail -6 ;;
     bench)
+      BENCH_ARGS="--full ${BENCH_ARGS}"
       ( timeout 900 python bench.py ${BENCH_ARGS} ) > gpurun_out/bench_full.log 2>&1; echo "bench rc=$?"
       grep '^{' gpurun_out/bench_full.log > gpurun_out/bench_n1.json; cut -c1-900 gpurun_out/bench_n1.json
       python - <<'PY'
@@ -76,13 +77,13 @@ PY
     ab_varlen)
       : > gpurun_out/ab_varlen.txt
       for rnd in 1 2 3; do for mode in "" "--equal-calls"; do
-        v=$( timeout 600 python bench.py ${VARLEN_BENCH_ARGS:---steps 9 --warmup 2 --no-1m} --no-cpu-baseline --no-modes $mode 2>/dev/null | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.read()); v=d['varlen']; print(v['sentences_per_s'], 'sent/s', v['end_to_end_frac_of_mfma_roofline'], v['rows_per_call'], '| fixed-128', d['value'])" )
+        v=$( timeout 600 python bench.py ${VARLEN_BENCH_ARGS:---steps 9 --warmup 2 --no-1m} --full --no-cpu-baseline --no-modes $mode 2>/dev/null | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.read()); v=d['varlen']; print(v['sentences_per_s'], 'sent/s', v['end_to_end_frac_of_mfma_roofline'], v['rows_per_call'], '| fixed-128', d['value'])" )
         echo "round $rnd calls ${mode:-round-aware}: $v" | tee -a gpurun_out/ab_varlen.txt
       done; done ;;
     ab_varlen_lib)
       : > gpurun_out/ab_varlen_lib.txt
       for rnd in 1 2 3; do for tag in default ${LIBS}; do
-        v=$( SGPT_HIP_LIB=$(libpath $tag) timeout 600 python bench.py ${VARLEN_BENCH_ARGS:---steps 9 --warmup 2 --no-1m} --no-cpu-baseline --no-modes 2>/dev/null | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.read()); v=d['varlen']; print(v['sentences_per_s'], 'sent/s', v['end_to_end_frac_of_mfma_roofline'], v['rows_per_call'], '| fixed-128', d['value'])" )
+        v=$( SGPT_HIP_LIB=$(libpath $tag) timeout 600 python bench.py ${VARLEN_BENCH_ARGS:---steps 9 --warmup 2 --no-1m} --full --no-cpu-baseline --no-modes 2>/dev/null | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.read()); v=d['varlen']; print(v['sentences_per_s'], 'sent/s', v['end_to_end_frac_of_mfma_roofline'], v['rows_per_call'], '| fixed-128', d['value'])" )
         echo "round $rnd lib $tag: $v" | tee -a gpurun_out/ab_varlen_lib.txt
       done; done ;;
     varlen_prof)

@@ -207,6 +207,7 @@ def main():
         _extras_cases()
         _tokenize_cases()
         _crossencoder_case()
+        _pooling_config_case(Pooling)
         return
     if only_j:
         _gptj_cases(Pooling)
@@ -237,6 +238,7 @@ def main():
     _extras_cases()
     _tokenize_cases()
     _crossencoder_case()
+    _pooling_config_case(Pooling)
 
     # ---------------- scoring / top-k (reference util.py + exact_search.py) ----------------
     _scoring_cases(U, ES)
@@ -493,6 +495,17 @@ def _crossencoder_case():
         json.dump({"cfg": cfg_kw, "seed": 51, "std": 0.08, "max_length": max_length, "instruction_len": instruction_len,
                    "requests": [[r[1], r[2]] for r in reqs], "loglikelihood": ref}, f)
     print("wrote crossencoder.json", [round(x, 3) for x in ref])
+
+
+def _pooling_config_case(Pooling):
+    """The 1_Pooling/config.json the reference's own Pooling.save writes for a 128-wide weightedmean pooling
+    (the file its Pooling.load reads back), stored as written."""
+    import shutil
+    import tempfile
+    with tempfile.TemporaryDirectory() as td:
+        Pooling.Pooling(128, pooling_mode="weightedmean").save(td)
+        shutil.copyfile(os.path.join(td, "config.json"), os.path.join(HERE, "pooling_weightedmean_128.json"))
+    print("wrote pooling_weightedmean_128.json (the reference's Pooling.save output)")
 
 
 def _scoring_cases(U, ES):
