@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 8
+#define SGPT_ABI_VERSION 9
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -458,6 +458,33 @@ sgpt_status sgpt_linear(sgpt_ctx* ctx, int32_t dtype, int32_t epi, int32_t out_d
 sgpt_status sgpt_linear_query(sgpt_ctx* ctx, int32_t dtype, int32_t epi, const void* A, const float* x, const float* ln_gamma,
                               const float* ln_beta, float ln_eps, const void* W, const float* bias, const float* resid, void* out,
                               void* out_vt, int32_t n_split, int32_t M, int32_t N, int32_t K, void* stream);
+
+/* The attention kernels of sgpt_encode, stand-alone (ABI v9; kernel-level tests): causal (+ sliding-window) softmax attention
+ * over packed variable-length sequences -- GPTNeoSelfAttention._attn (HF:gpt_neo:105-130) with BLOOM's ALiBi bias
+ * (HF:bloom:45-89).  Sequence b owns token rows [seq_off[b], seq_off[b+1]) (seq_off device int32[B+1], even entries, every
+ * difference <= max_alloc_len, seq_off[B] <= T); key j (counted from the sequence start) is visible to query i iff j <= i and,
+ * window > 0, j > i - window.  score = scale * q.k + alibi[h] * j (alibi device fp32[H] or NULL), exact softmax, P.V.
+ *   dtype SGPT_BF16 | SGPT_F16: q, k device [T][ldq] (head h at columns h * dh ..), v = V^T device [H * dh][ldvt] (ldvt >= T),
+ *     out device [T][ldo] in `dtype`: the 16-bit MFMA kernel.  dh 64 | 128 | 256.
+ *   dtype SGPT_F32: q, k, v device fp32 [T][ldq] (ldvt unused), out fp32 [T][ldo]: the exact-fp32 kernel.
+ *   out_fp8 = 1 (bf16 only): out holds e4m3fn codes of ctx / out_scale ([T][ldo] bytes); a saturated code (or NaN) ORs 4
+ *     (bit 2, as sgpt_model_range_check) into *range_flag (device int32, may be NULL).
+ *   ctx_lo_delta != 0 (16-bit; "MODE 1"): the context also leaves as lo = round16(v - hi) at out + ctx_lo_delta and, when
+ *     ctx_hi2_delta != 0, a second copy of hi at out + ctx_hi2_delta (element offsets).
+ *   x3 = 1 (16-bit, dh 64 | 128; "MODE 2"): q | k and V^T enter as hi + lo pairs, the lo halves qk_lo_delta / v_lo_delta
+ *     elements behind the hi halves (same leading dimensions).
+ * Over-read contract: the key tiles read up to 64 rows past the last sequence's allocation -- k rows (and their lo halves)
+ *   up to T + 63, V^T elements r * ldvt + c for c < T + 64 -- as masked keys whose p = 0 multiplies them: they must be readable
+ *   and finite (0 * NaN = NaN).  Query fragments load q rows up to T + 255 (never used past a sequence): readable.  Only the
+ *   out rows of the allocations [seq_off[b], seq_off[b+1]) are written.
+ * SGPT_ERR_INVALID (nothing launched) for: head_dim other than 64 | 128 | 256, T % 32, max_alloc_len odd or above 2048,
+ *   out_fp8 with f16 / fp32 operands or with a split-precision mode, x3 at head_dim 256, split modes with fp32 operands,
+ *   misaligned pointers / leading dimensions. */
+sgpt_status sgpt_attention(sgpt_ctx* ctx, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
+                           void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t dh,
+                           int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
+                           float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
+                           int64_t ctx_lo_delta, int64_t ctx_hi2_delta, void* stream);
 
 /* The fp8-MFMA building blocks of SGPT_FP8M, stand-alone (kernel-level tests, custom blocks).
  * sgpt_layernorm_fp8: nn.LayerNorm(x)[T,d] -> e4m3fn codes + one power-of-two scale per row (true value = code * scale).

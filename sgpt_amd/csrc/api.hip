@@ -1734,6 +1734,58 @@ sgpt_status sgpt_linear_split(sgpt_ctx* c, int32_t dtype, int32_t epi, const voi
     return SGPT_OK;
 }
 
+sgpt_status sgpt_attention(sgpt_ctx* c, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
+                           void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t dh,
+                           int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
+                           float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
+                           int64_t ctx_lo_delta, int64_t ctx_hi2_delta, void* stream) {
+    // every combination launch_attn_bf16 would abort() on is refused here, before anything is launched
+    auto mis = [](const void* p, unsigned a) { return ((uintptr_t)p & (a - 1)) != 0; };
+    if (!c || !q || !k || !v || !out || !seq_off || B <= 0 || T <= 0 || H <= 0 || window < 0 || !std::isfinite(scale))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_attention: bad arguments");
+    const bool in16 = dtype == SGPT_BF16 || dtype == SGPT_F16;
+    if (!in16 && dtype != SGPT_F32) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: dtype SGPT_F32 | SGPT_BF16 | SGPT_F16");
+    if (dh != 64 && dh != 128 && dh != 256) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: head_dim 64, 128 or 256");
+    if (T % 32) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: T % 32 == 0");
+    if (max_alloc_len <= 0 || max_alloc_len > 2048 || max_alloc_len % 2)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_attention: max_alloc_len even, in [2, 2048]");
+    const long d = (long)H * dh;
+    if (ldq < d || ldo < d) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: ldq, ldo >= H * head_dim");
+    const bool split_ctx = ctx_lo_delta != 0;
+    if (!in16 && (out_fp8 || x3 || split_ctx || ctx_hi2_delta))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_attention: out_fp8 / x3 / split context are 16-bit modes");
+    if (ctx_hi2_delta != 0 && !split_ctx) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: ctx_hi2_delta needs ctx_lo_delta");
+    if (out_fp8) {
+        if (dtype != SGPT_BF16) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: out_fp8 takes bf16 operands");
+        if (x3 || split_ctx) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: out_fp8 with a split-precision mode");
+        if (!(out_scale > 0.f) || !std::isfinite(out_scale)) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: out_scale > 0");
+    }
+    if (x3 && !attn_x3_supported(dh)) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: x3 needs head_dim 64 | 128");
+    if (x3 && (qk_lo_delta == 0 || v_lo_delta == 0)) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: x3 needs non-zero lo deltas");
+    if (in16) {
+        if (mis(q, 16) || mis(k, 16) || mis(v, 4) || mis(out, 16))
+            return fail(c, SGPT_ERR_INVALID, "sgpt_attention: 16-byte aligned q / k / out, 4-byte aligned V^T");
+        if (ldq % 8 || ldo % (out_fp8 ? 16 : 8) || qk_lo_delta % 8 || ctx_lo_delta % 8 || ctx_hi2_delta % 8 || ldvt % 2 || v_lo_delta % 2)
+            return fail(c, SGPT_ERR_INVALID, "sgpt_attention: ldq, ldo, qk / ctx deltas % 8 (out_fp8: ldo % 16); ldvt, v_lo_delta even");
+        if (ldvt < T) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: ldvt >= T");
+    } else if (mis(q, 16) || mis(k, 16) || mis(v, 16) || mis(out, 4) || ldq % 4) {
+        return fail(c, SGPT_ERR_INVALID, "sgpt_attention: fp32 q / k / v 16-byte aligned, ldq % 4");
+    }
+    HIPC(c, hipSetDevice(c->device));
+    AttnArgs at{};
+    at.q = q; at.k = k; at.v = v; at.ctx = out; at.seq_off = seq_off;
+    at.B = B; at.H = H; at.dh = dh; at.ldq = ldq; at.ldvt = ldvt; at.ldo = ldo;
+    at.window = window; at.scale = scale; at.max_alloc_len = max_alloc_len; at.alibi = alibi;
+    at.dtype = in16 ? dtype : SGPT_F32;
+    at.out_fp8 = out_fp8 ? 1 : 0; at.out_scale = out_scale; at.range_flag = range_flag;
+    at.x3 = x3 ? 1 : 0; at.qk_lo_delta = qk_lo_delta; at.v_lo_delta = v_lo_delta;
+    at.ctx_lo_delta = ctx_lo_delta; at.ctx_hi2_delta = ctx_hi2_delta;
+    if (in16) launch_attn_bf16(at, (hipStream_t)stream);
+    else launch_attn_f32(at, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
 sgpt_status sgpt_bench_gemm(sgpt_ctx* c, int32_t dtype, int32_t epi, int32_t out_dtype, int32_t M, int32_t N, int32_t K,
                             int32_t iters, float* ms_out) {
     if (!c || !ms_out || M <= 0 || N <= 0 || K <= 0 || iters <= 0) return fail(c, SGPT_ERR_INVALID, "sgpt_bench_gemm: bad arguments");

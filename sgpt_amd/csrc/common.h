@@ -347,7 +347,7 @@ struct AttnArgs {
     const float* alibi;  // [H] ALiBi slopes (BLOOM) or null: score += slope_h * key_index (HF:bloom:45-89)
     int dtype;           // DT_BF16 | DT_F16 (16-bit path)
     // SGPT_FP8M: the context is written as e4m3 codes of ctx / out_scale ([T][ldo] bytes: the A operand of the fp8
-    // out-projection); a saturated code raises bit 1 of *range_flag
+    // out-projection); a saturated code ORs 4 (bit 2, the attention-context bit of sgpt_model_range_check) into *range_flag
     int out_fp8;
     float out_scale;
     int* range_flag;

@@ -265,6 +265,34 @@ class Context:
                                              _p(out), ldo, lo, hi2, M, N, K, _stream_ptr(self.device)), "sgpt_linear_split")
         return out
 
+    # ---- the attention kernels stand-alone (kernel-level tests) ----
+    def attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, seq_off: torch.Tensor,
+                  H: int, dh: int, max_alloc_len: int, window: int = 0, scale: float = 1.0, alibi: Optional[torch.Tensor] = None,
+                  out_scale: float = 0.0, range_flag: Optional[torch.Tensor] = None, x3: bool = False, qk_lo_delta: int = 0,
+                  v_lo_delta: int = 0, ctx_lo_delta: int = 0, ctx_hi2_delta: int = 0) -> torch.Tensor:
+        """include/sgpt_hip.h::sgpt_attention on caller-laid-out buffers (the over-read contract there is the caller's): q, k
+        [T, >= H dh] row views of one leading dimension; v = V^T [H dh, >= T] (16-bit) or [T, ...] with q's leading dimension
+        (fp32); out [T, ...] in q's dtype, or uint8 (e4m3 codes of ctx / out_scale, bf16 operands).  Deltas in elements."""
+        T = q.shape[0]
+        out_fp8 = out.dtype == torch.uint8
+        if q.dtype not in DT_CODE:
+            raise ValueError(f"attention: operands are fp32, bf16 or f16, got {q.dtype}")
+        if k.stride(0) != q.stride(0) or q.stride(1) != 1 or k.stride(1) != 1 or v.stride(1) != 1 or out.stride(1) != 1:
+            raise ValueError("attention: q and k share one leading dimension; unit column strides")
+        if k.dtype != q.dtype or v.dtype != q.dtype:
+            raise ValueError("attention: q, k and v have one dtype")
+        if out.dtype != q.dtype and not (out_fp8 and q.dtype == torch.bfloat16):
+            raise ValueError("attention: out has q's dtype (or uint8 e4m3 codes for bf16 operands)")
+        if q.dtype == torch.float32 and v.stride(0) != q.stride(0):
+            raise ValueError("attention: fp32 v rows share q's leading dimension (the fp32 kernel reads v with ldq)")
+        so = seq_off.to(device=self.device, dtype=torch.int32).contiguous()
+        al = None if alibi is None else alibi.to(device=self.device, dtype=torch.float32).contiguous()
+        self._chk(self.lib.sgpt_attention(self.handle, DT_CODE[q.dtype], _p(q), _p(k), _p(v), q.stride(0), v.stride(0), _p(out),
+                                          out.stride(0), _p(so), so.numel() - 1, T, H, dh, window, scale, _p(al), max_alloc_len,
+                                          1 if out_fp8 else 0, out_scale, _p(range_flag), 1 if x3 else 0, qk_lo_delta,
+                                          v_lo_delta, ctx_lo_delta, ctx_hi2_delta, _stream_ptr(self.device)), "sgpt_attention")
+        return out
+
     # ---- fp8-MFMA building blocks (dtype='fp8mfma'): quantising LayerNorm, e4m3 x e4m3 projection ----
     def layernorm_fp8(self, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5):
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
