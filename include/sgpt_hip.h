@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 9
+#define SGPT_ABI_VERSION 10
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -427,6 +427,41 @@ sgpt_status sgpt_fold_gathered_topk(sgpt_ctx* ctx, const float* gathered_val, co
  * (exact_search.py:102-108; util.semantic_search util.py:241).  NaN -> -1 first (:99). */
 sgpt_status sgpt_topk(sgpt_ctx* ctx, const float* scores, int32_t nq, int64_t n, int64_t ld,
                       int32_t k, int64_t idx_base, float* out_val, int64_t* out_idx, void* stream);
+
+/* -- evaluation: retrieval metrics from device-resident ranked lists (ABI v10; csrc/eval.hip) ---------------------------- */
+/* Replaces, for an evaluation run, the D2H copy of the result lists, the Dict[qid, Dict[doc_id, float]] built from them and the
+ * pytrec_eval pass of beir.EvaluateRetrieval.evaluate (biencoder/beir/beir_dense_retriever.py:442-446), and the Python loops of
+ * InformationRetrievalEvaluator.compute_metrics (sentence_transformers/evaluation/InformationRetrievalEvaluator.py:189-271):
+ * the per-query, per-cut sums every one of those metrics is made of, taken from the lists sgpt_topk_merge / sgpt_exchange_topk
+ * leave on the device.
+ *   idx      device int64[nq, K]  corpus positions in rank order (descending score, ties by ascending position -- the order
+ *            documented above for run_idx / out_idx); a position < 0 is padding and ENDS the list
+ *   val      device fp32[nq, K]   the scores; read only when check_order != 0 (may be NULL otherwise)
+ *   qrel_off device int32[nq + 1] CSR offsets of the judgements: query q owns entries [qrel_off[q], qrel_off[q + 1])
+ *   qrel_pos device int64[]       judged corpus positions, ascending within a query; a judged document that is not in the corpus
+ *            carries a position no list can hold (INT64_MAX): it counts in R and never matches
+ *   qrel_rel device int32[]       the grade of each entry of qrel_pos (relevant: grade > 0; the gain of a grade is max(grade, 0))
+ *   ideal_rel device int32[]      the same CSR layout: the query's grades sorted descending (the ideal ranking of IDCG)
+ *   k_values HOST int32[nk]       the cuts: positive, strictly ascending, k_values[nk - 1] <= K, nk <= SGPT_EVAL_MAX_CUTS
+ * Outputs, device, [nq, nk] unless noted, with n = length of the list and i counting ranks from 1:
+ *   out_hits  int32  relevant documents among ranks 1 .. min(k, n)
+ *   out_first int32  rank of the first relevant document if it is <= k, else 0
+ *   out_dcg   fp32   sum_{i <= min(k, n)} max(rel_i, 0) / log2(i + 1)
+ *   out_idcg  fp32   the same sum over ideal_rel
+ *   out_sp    fp32   sum over the relevant ranks i <= min(k, n) of hits@i / i   (average precision x R)
+ *   out_R     int32[nq]  judged documents with grade > 0
+ * The integer outputs are exact.  The float sums are taken in one fixed order (64 consecutive ranks by an xor butterfly, the
+ * groups in ascending order), so they do not depend on the launch geometry; no float atomics.
+ * check_order != 0: the call also verifies val[i] >= val[i + 1] over the entries of every list and, if a row breaks it, returns
+ *   SGPT_ERR_INVALID (one device word ORed by the kernel, read back: the call then synchronises `stream`).  Lists that come
+ *   from the scorer are sorted by construction; lists packed by a caller may not be.  0: asynchronous like every other call.
+ * Exactly equal scores are ties; trec_eval's tie-break by document id is not reproduced.  nq == 0 is a valid, empty call. */
+#define SGPT_EVAL_MAX_CUTS 16
+sgpt_status sgpt_eval_ranked(sgpt_ctx* ctx, const int64_t* idx, const float* val, int32_t nq, int32_t K,
+                             const int32_t* qrel_off, const int64_t* qrel_pos, const int32_t* qrel_rel,
+                             const int32_t* ideal_rel, const int32_t* k_values, int32_t nk, int32_t check_order,
+                             int32_t* out_hits, int32_t* out_first, float* out_dcg, float* out_idcg, float* out_sp,
+                             int32_t* out_R, void* stream);
 
 /* -- the projection GEMM with its fused epilogues, as a stand-alone op ----------------------------------------------- */
 /* out = epilogue(A . W^T): the nn.Linear calls of the transformer blocks (HF:gpt_neo:141-143,155,304-309) with the

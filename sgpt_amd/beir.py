@@ -202,7 +202,22 @@ class DenseRetrievalExactSearch:
 
     def search(self, corpus: Dict[str, Dict[str, str]], queries: Dict[str, str], top_k: int, score_function: str,
                return_sorted: bool = False, **kwargs) -> Dict[str, Dict[str, float]]:
-        """Single process: the reference's loop (exact_search.py:34-134) with scoring / top-k / merge on the GPU.
+        """The reference's result contract: search_ranked (below), then one D2H copy of the lists and the
+        Dict[qid, Dict[doc_id, float]] built from them (assemble_results).  An evaluation run that only wants the metrics
+        skips both: sgpt_amd.evaluation.EvaluateRetrieval.retrieve_ranked / evaluate_ranked."""
+        self.results = {qid: {} for qid in queries}
+        ranked = self.search_ranked(corpus, queries, top_k, score_function, **kwargs)
+        if ranked.val.shape[1] > 0:
+            self.results = assemble_results(ranked.query_ids, ranked.corpus_ids, ranked.val.cpu().numpy(), ranked.idx.cpu().numpy())
+        return self.results
+
+    def search_ranked(self, corpus: Dict[str, Dict[str, str]], queries: Dict[str, str], top_k: int, score_function: str,
+                      **kwargs):
+        """-> sgpt_amd.evaluation.RankedLists: the merged top-(k+1) lists as they stand on the device (fp32 scores and int64
+        positions into the length-sorted corpus, [nq, min(top_k + 1, corpus size)], descending score, ties to the lower
+        position, (-inf, -1) tail) -- no D2H copy, no dict.
+
+        Single process: the reference's loop (exact_search.py:34-134) with scoring / top-k / merge on the GPU.
 
         Under an initialised torch.distributed group of N > 1 ranks (one process per GPU, `torchrun ... beir_dense_retriever`)
         the SAME call is the corpus-sharded search of SURVEY 8e: every rank takes one contiguous range of the
@@ -210,7 +225,8 @@ class DenseRetrievalExactSearch:
         longest documents), tokenises, encodes and scores only that range (its embeddings never leave its HBM); the
         queries are encoded sharded and all-gathered once over RCCL; the per-rank top-(k+1) lists are exchanged and merged
         on the device (C ABI: sgpt_allgather_rows, sgpt_exchange_topk).  Every rank returns the same, complete dict --
-        equal to the single-process result (the encoder is batch-invariant bit for bit, ties go to the lower index)."""
+        equal to the single-process result (the encoder is batch-invariant bit for bit, ties go to the lower index); likewise every
+        rank holds the same, complete merged lists."""
         if score_function not in self.score_function_desc:
             raise ValueError(
                 "score function: {} must be either (cos_sim) for cosine similarity or (dot) for dot product".format(
@@ -226,7 +242,6 @@ class DenseRetrievalExactSearch:
         logger.info("Encoding Queries...")
         query_ids = list(queries.keys())
         nq = len(query_ids)
-        self.results = {qid: {} for qid in query_ids}
         qlist = [(qid, queries[qid]) for qid in queries]
         sgpt = getattr(self.model, "model", None)
         if comm is not None and hasattr(sgpt, "sync_precision") and hasattr(self.model, "tokenize") and qlist:
@@ -333,9 +348,11 @@ class DenseRetrievalExactSearch:
                 pv[:, : run_val.shape[1]] = run_val
                 pi[:, : run_idx.shape[1]] = run_idx
             run_val, run_idx = comm.exchange_topk(pv, pi, min(k1, len(corpus_ids)), exclude_idx=self_idx)
-        if run_val is not None:
-            self.results = assemble_results(query_ids, corpus_ids, run_val.cpu().numpy(), run_idx.cpu().numpy())
-        return self.results
+        if run_val is None:           # no document at all: lists of no column
+            run_val = torch.empty((nq, 0), dtype=torch.float32, device=ctx.device)
+            run_idx = torch.empty((nq, 0), dtype=torch.int64, device=ctx.device)
+        from .evaluation import RankedLists
+        return RankedLists(query_ids, corpus_ids, run_val, run_idx, pos_of)
 
 
 def _host_ext():

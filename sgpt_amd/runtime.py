@@ -429,6 +429,41 @@ class Context:
                                      _stream_ptr(self.device)), "sgpt_topk")
         return ov, oi
 
+    # ---- evaluation: per-query, per-cut metric sums from device-resident ranked lists ----
+    def eval_ranked(self, idx: torch.Tensor, val: Optional[torch.Tensor], qrel_off, qrel_pos, qrel_rel, ideal_rel, k_values,
+                    check_order: bool = True) -> dict:
+        """include/sgpt_hip.h::sgpt_eval_ranked.  idx int64 [nq, K] (position < 0 = padding, ends the list), val fp32 [nq, K];
+        the qrels as a CSR in the same position space (sgpt_amd.evaluation.pack_qrels builds it); k_values ascending, <= K.
+        -> {"hits", "first" int32 [nq, nk]; "dcg", "idcg", "sp" fp32 [nq, nk]; "R" int32 [nq]} on the device.
+        check_order=True synchronises the stream and raises ValueError (SGPT_ERR_INVALID) when a row is not sorted by
+        descending score."""
+        idx = idx.to(device=self.device, dtype=torch.int64).contiguous()
+        nq, K = idx.shape
+        if val is not None:
+            val = val.to(device=self.device, dtype=torch.float32).contiguous()
+            if val.shape != idx.shape:
+                raise ValueError(f"eval_ranked: val {tuple(val.shape)} and idx {tuple(idx.shape)} differ in shape")
+        i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(self.device) if not isinstance(a, torch.Tensor) \
+            else a.to(device=self.device, dtype=torch.int32).contiguous()  # noqa: E731
+        off, rel, ideal = i32(qrel_off), i32(qrel_rel), i32(ideal_rel)
+        pos = (qrel_pos if isinstance(qrel_pos, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(qrel_pos, dtype=np.int64)))
+        pos = pos.to(device=self.device, dtype=torch.int64).contiguous()
+        if off.numel() != nq + 1 or not (pos.numel() == rel.numel() == ideal.numel()):
+            raise ValueError("eval_ranked: qrel_off has nq + 1 entries; qrel_pos, qrel_rel and ideal_rel have one length")
+        if pos.numel() == 0:        # no judgement at all: the kernel reads none, the C entry still wants addressable arrays
+            pos, rel, ideal = (torch.zeros((1,), dtype=t.dtype, device=self.device) for t in (pos, rel, ideal))
+        ks = [int(k) for k in k_values]
+        nk = len(ks)
+        kv = (C.c_int32 * max(nk, 1))(*ks)
+        out = {n: torch.zeros((nq, nk), dtype=torch.int32, device=self.device) for n in ("hits", "first")}
+        out.update({n: torch.zeros((nq, nk), dtype=torch.float32, device=self.device) for n in ("dcg", "idcg", "sp")})
+        out["R"] = torch.zeros((nq,), dtype=torch.int32, device=self.device)
+        self._chk(self.lib.sgpt_eval_ranked(self.handle, _p(idx), _p(val), nq, K, _p(off), _p(pos), _p(rel), _p(ideal), kv, nk,
+                                            1 if check_order else 0, _p(out["hits"]), _p(out["first"]), _p(out["dcg"]),
+                                            _p(out["idcg"]), _p(out["sp"]), _p(out["R"]), _stream_ptr(self.device)),
+                  "sgpt_eval_ranked")
+        return out
+
     # ---- measurement hooks (bench.py) ----
     def prof_enable(self, on: bool):
         self._chk(self.lib.sgpt_prof_enable(self.handle, 1 if on else 0), "sgpt_prof_enable")
