@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 10
+#define SGPT_ABI_VERSION 11
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -51,7 +51,7 @@ typedef struct sgpt_model sgpt_model;
 enum { SGPT_F32 = 0, SGPT_BF16 = 1, SGPT_FP8W = 2, SGPT_F16 = 3, SGPT_FP8M = 4 };   /* element types; FP8W / FP8M: model compute_dtype only */
 enum { SGPT_ARCH_GPTNEO = 0, SGPT_ARCH_GPTJ = 1, SGPT_ARCH_BLOOM = 2 };
 enum { SGPT_POOL_WEIGHTEDMEAN = 0, SGPT_POOL_MEAN = 1, SGPT_POOL_LASTTOKEN = 2, SGPT_POOL_LEARNTMEAN = 3 };
-enum { SGPT_COS = 0, SGPT_DOT = 1 };
+enum { SGPT_COS = 0, SGPT_DOT = 1, SGPT_NEG_L2 = 2 };   /* SGPT_NEG_L2 (ABI v11): -||x - y||_2, sgpt_eval_groups only */
 
 /* Model hyper-parameters = the fields of HF GPTNeoConfig the forward pass reads
  * (HF:gpt_neo/configuration_gpt_neo.py; values of the SGPT checkpoints in SURVEY.md 8). */
@@ -462,6 +462,81 @@ sgpt_status sgpt_eval_ranked(sgpt_ctx* ctx, const int64_t* idx, const float* val
                              const int32_t* ideal_rel, const int32_t* k_values, int32_t nk, int32_t check_order,
                              int32_t* out_hits, int32_t* out_first, float* out_dcg, float* out_idcg, float* out_sp,
                              int32_t* out_R, void* stream);
+
+/* -- evaluation, USEB: grouped re-ranking and pair statistics (ABI v11; csrc/useb_eval.hip) ----------------------------- */
+/* sgpt_eval_groups: score, rank and reduce candidate groups.  Replaces, per query, the 21-sentence embedder call, the D2H copy,
+ * the host matmul, `rank_by_score` and `ap_score` / `reciprocal_rank` of useb/evaluators/askubuntu.py:139-155, and the per-query
+ * scoring plus the pytrec_eval pass of useb/evaluators/scidocs.py:67-90: every unique sentence is embedded once, the task is a CSR
+ * of groups over those rows, and one call leaves the per-group sums every metric of the two tasks is made of.
+ *   emb       device fp32[n_rows, d]  one row per unique sentence; not read (may be NULL) when scores_in is given
+ *   mode      SGPT_COS     x.y / (max(|x|, 1e-8) max(|y|, 1e-8))   (F.cosine_similarity, scidocs.py:80)
+ *             SGPT_DOT     x.y                                       (torch.matmul of the embeddings, askubuntu.py:147)
+ *             SGPT_NEG_L2  -||x - y||_2                              (scidocs.py:79)
+ *   scores_in device fp32[n_cand] or NULL: when given, candidate j's score is scores_in[j] and emb, q_row, cand_row, mode are not
+ *             used (re-rankers that score elsewhere -- the cross-encoder's log-probabilities -- share the ranking and the sums)
+ *   G, grp_off  number of groups; device int32[G + 1] CSR offsets: group g owns candidates [grp_off[g], grp_off[g + 1])
+ *   n_cand    HOST: grp_off[G], the length of the per-candidate arrays
+ *   max_group HOST: the size of the largest group (the caller built the CSR).  Above SGPT_EVAL_MAX_GROUP: SGPT_ERR_INVALID,
+ *             nothing launched.  The kernels do not rely on it: a group that is larger than SGPT_EVAL_MAX_GROUP all the same, or
+ *             whose offsets leave [0, n_cand], is a caller error they answer with out_R[g] = -1 and zeros in the group's other
+ *             [G] outputs (its per-candidate outputs are not written; no access out of bounds).
+ *   q_row     device int32[G]       embedding row of the group's query
+ *   cand_row  device int32[n_cand]  embedding row of each candidate; a row outside [0, n_rows) scores NaN
+ *   cand_rel  device int32[n_cand]  grade of each candidate (relevant: grade > 0; gain: max(grade, 0))
+ *   R_extra   device int32[G] or NULL: relevant judged documents that are NOT among the candidates; they count in out_R, as in
+ *             trec_eval and as sgpt_eval_ranked counts judged documents outside the corpus
+ *   ideal_off, ideal_rel  device int32[G + 1] / int32[n_ideal]: CSR of each group's judged grades sorted descending (IDCG); both
+ *             NULL when NDCG is not wanted (out_idcg is then 0)
+ *   n_ideal   HOST: the length of ideal_rel; a group's range is clipped to [0, n_ideal)
+ * Ranking: descending score, equal scores (-0 == +0) to the lower position inside the group -- Python's stable
+ * sorted(..., reverse=True) of `rank_by_score`; a caller that lists candidates by descending document id gets trec_eval's
+ * tie-break.  NaN scores rank last (after -inf), among themselves by position.
+ * Outputs (device; per candidate in the group's CSR range, or [G]); i counts ranks from 1, n = size of the group:
+ *   out_scores fp32[n_cand] or NULL   the score of each candidate (input order)
+ *   out_order  int32[n_cand] or NULL  out_order[grp_off[g] + i - 1] = group-local index of the candidate at rank i
+ *   out_hits1, out_hits5 int32[G]     relevant candidates among the first min(1, n) / min(5, n) ranks
+ *   out_first  int32[G]               rank of the first relevant candidate, 0 if none
+ *   out_R      int32[G]               relevant candidates + R_extra
+ *   out_sp     fp32[G]                sum over the relevant ranks i of hits@i / i   (full list)
+ *   out_dcg, out_idcg fp32[G]         sum_i max(rel_i, 0) / log2(i + 1) over the ranked list / over ideal_rel (full lists)
+ * Integer outputs are exact.  A score depends on the values of the two rows, d and the mode only (one wavefront, one fixed
+ * summation order), so the same pair scored twice gives the same bits whatever its position, group or grid; the float sums are
+ * taken as in sgpt_eval_ranked (64 consecutive ranks by an xor butterfly, the chunks in ascending order).  No float atomics,
+ * no allocation, asynchronous on `stream`.  G == 0 is a valid, empty call; a group may be empty (all outputs 0, R = R_extra).
+ * SGPT_ERR_INVALID: max_group > SGPT_EVAL_MAX_GROUP, negative G / n_cand / max_group / n_ideal, unknown mode, d < 1, ideal_off without
+ * ideal_rel or the reverse, a required pointer NULL. */
+#define SGPT_EVAL_MAX_GROUP 1024
+sgpt_status sgpt_eval_groups(sgpt_ctx* ctx, const float* emb, int32_t n_rows, int32_t d, int32_t mode, const float* scores_in,
+                             int32_t G, const int32_t* grp_off, int32_t n_cand, int32_t max_group, const int32_t* q_row,
+                             const int32_t* cand_row, const int32_t* cand_rel, const int32_t* R_extra,
+                             const int32_t* ideal_off, const int32_t* ideal_rel, int32_t n_ideal, float* out_scores,
+                             int32_t* out_order, int32_t* out_hits1, int32_t* out_hits5, int32_t* out_first, int32_t* out_R, float* out_sp,
+                             float* out_dcg, float* out_idcg, void* stream);
+
+/* sgpt_eval_pairs: global ranking statistics of n scored pairs.  Replaces what follows the cosine in
+ * useb/evaluators/twitterpara.py:110-117 (the cosine itself is sgpt_pairwise_scores): the D2H copy of the scores,
+ * sklearn.metrics.average_precision_score and the ranking half of scipy.stats.spearmanr.
+ *   score  device fp32[n]
+ *   label  device int32[n]   > 0 positive, 0 negative, < 0 left out of the average precision but still ranked (`is_para is None`)
+ *   check_nan  != 0: a NaN score makes the call return SGPT_ERR_INVALID (one device word ORed by the kernel, read back: the call
+ *          then synchronises `stream`, as check_order of sgpt_eval_ranked does).  0: asynchronous; NaN then sorts above every
+ *          number and the statistics mean nothing.
+ * Outputs (device):
+ *   out_rank2  int32[n]  twice the 1-based ascending rank of score[i], ties averaged: 2 x scipy.stats.rankdata (an exact integer;
+ *              -0 == +0).  Spearman is host arithmetic: the float64 Pearson correlation of out_rank2 with the doubled ranks of
+ *              the gold scores (sums of squared ranks reach n^3 / 3: not a device fp32 sum).
+ *   out_n_pos, out_n_used  int64 scalars: rows with label > 0, rows with label >= 0
+ *   out_ap_num fp64 scalar: with the used rows sorted by descending score, tie groups j = 1 .. ending at count N_j and holding
+ *              TP_j positives cumulatively, sum_j (TP_j - TP_{j-1}) TP_j / N_j.  average_precision_score = out_ap_num / out_n_pos
+ *              (equal scores are one threshold, as in scikit-learn); undefined for n_pos == 0, where out_ap_num is 0.
+ *              Accumulated in fp64: 256 terms by an LDS tree per workgroup, the partials by one workgroup in a fixed order.
+ * A full device sort of 64-bit (score, index) keys (bitonic; the keys are unique), so nothing depends on launch geometry; no
+ * float atomics; workspace from the ctx (grow-only, 2 x 8 bytes per key of the next power of two >= max(n, 2048)).
+ * n == 0 is a valid call (the three scalars become 0).  SGPT_ERR_INVALID: n < 0 or n > SGPT_EVAL_MAX_PAIRS, a NULL pointer,
+ * a NaN score under check_nan. */
+#define SGPT_EVAL_MAX_PAIRS (1 << 24)
+sgpt_status sgpt_eval_pairs(sgpt_ctx* ctx, const float* score, const int32_t* label, int32_t n, int32_t check_nan,
+                            int32_t* out_rank2, int64_t* out_n_pos, int64_t* out_n_used, double* out_ap_num, void* stream);
 
 /* -- the projection GEMM with its fused epilogues, as a stand-alone op ----------------------------------------------- */
 /* out = epilogue(A . W^T): the nn.Linear calls of the transformer blocks (HF:gpt_neo:141-143,155,304-309) with the

@@ -464,6 +464,90 @@ class Context:
                   "sgpt_eval_ranked")
         return out
 
+    # ---- evaluation, USEB: grouped re-ranking and pair statistics ----
+    def _i32(self, a) -> torch.Tensor:
+        if isinstance(a, torch.Tensor):
+            return a.to(device=self.device, dtype=torch.int32).contiguous()
+        return torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+
+    def eval_groups(self, grp_off, cand_rel, emb: Optional[torch.Tensor] = None, q_row=None, cand_row=None, mode: str = "cos",
+                    scores_in: Optional[torch.Tensor] = None, R_extra=None, ideal_off=None, ideal_rel=None) -> dict:
+        """include/sgpt_hip.h::sgpt_eval_groups.  grp_off: HOST int array [G + 1] (the CSR the caller built; its largest group and
+        its total are read here); cand_rel [grp_off[G]]; either emb fp32 [n, d] with q_row [G], cand_row and mode "cos" | "dot" |
+        "neg_l2", or scores_in fp32 [grp_off[G]].  -> {"scores" fp32, "order" int32 (per candidate); "hits1", "hits5", "first",
+        "R" int32 [G]; "sp", "dcg", "idcg" fp32 [G]} on the device.  Asynchronous."""
+        off_h = np.ascontiguousarray(grp_off.cpu().numpy() if isinstance(grp_off, torch.Tensor) else grp_off, dtype=np.int64)
+        if off_h.ndim != 1 or off_h.size < 1 or off_h[0] != 0 or (np.diff(off_h) < 0).any() or off_h[-1] >= 2 ** 31:
+            raise ValueError("eval_groups: grp_off must be a CSR offset array: G + 1 ascending entries starting at 0")
+        G, n_cand = off_h.size - 1, int(off_h[-1])
+        max_group = int(np.diff(off_h).max()) if G else 0
+        rel = self._i32(cand_rel)
+        if rel.numel() != n_cand:
+            raise ValueError(f"eval_groups: cand_rel has {rel.numel()} entries, the groups hold {n_cand}")
+        if scores_in is not None:
+            scores_in = scores_in.to(device=self.device, dtype=torch.float32).contiguous()
+            if scores_in.numel() != n_cand:
+                raise ValueError(f"eval_groups: scores_in has {scores_in.numel()} entries, the groups hold {n_cand}")
+            if n_cand == 0:                         # the C entry tells "scores given" by the pointer: keep it addressable
+                scores_in = torch.zeros((1,), dtype=torch.float32, device=self.device)
+            emb_t, qr, cr, n_rows, d, mode_code = None, None, None, 0, 1, _lib.SGPT_COS
+        else:
+            modes = {"cos": _lib.SGPT_COS, "dot": _lib.SGPT_DOT, "neg_l2": _lib.SGPT_NEG_L2}
+            if mode not in modes:
+                raise ValueError(f"eval_groups: mode {mode!r} is not one of {sorted(modes)}")
+            if emb is None or q_row is None or cand_row is None:
+                raise ValueError("eval_groups: emb, q_row and cand_row are needed when scores_in is not given")
+            emb_t = emb.to(device=self.device, dtype=torch.float32).contiguous()
+            if emb_t.dim() != 2:
+                raise ValueError("eval_groups: emb must be [n, d]")
+            n_rows, d = emb_t.shape
+            qr, cr, mode_code = self._i32(q_row), self._i32(cand_row), modes[mode]
+            if qr.numel() != G or cr.numel() != n_cand:
+                raise ValueError("eval_groups: q_row has one entry per group, cand_row one per candidate")
+        rx = None if R_extra is None else self._i32(R_extra)
+        if rx is not None and rx.numel() != G:
+            raise ValueError("eval_groups: R_extra has one entry per group")
+        if (ideal_off is None) != (ideal_rel is None):
+            raise ValueError("eval_groups: ideal_off and ideal_rel go together")
+        io = ir = None
+        n_ideal = 0
+        if ideal_off is not None:
+            io_h = np.ascontiguousarray(ideal_off.cpu().numpy() if isinstance(ideal_off, torch.Tensor) else ideal_off, dtype=np.int64)
+            ir = self._i32(ideal_rel)
+            if io_h.size != G + 1 or io_h[0] != 0 or (np.diff(io_h) < 0).any() or io_h[-1] != ir.numel():
+                raise ValueError("eval_groups: ideal_off must be a CSR offset array over ideal_rel with G + 1 entries")
+            io, n_ideal = self._i32(io_h), int(ir.numel())
+            if ir.numel() == 0:
+                ir = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        off = self._i32(off_h)
+        out = {"scores": torch.zeros((n_cand,), dtype=torch.float32, device=self.device),
+               "order": torch.zeros((n_cand,), dtype=torch.int32, device=self.device)}
+        out.update({n: torch.zeros((G,), dtype=torch.int32, device=self.device) for n in ("hits1", "hits5", "first", "R")})
+        out.update({n: torch.zeros((G,), dtype=torch.float32, device=self.device) for n in ("sp", "dcg", "idcg")})
+        self._chk(self.lib.sgpt_eval_groups(self.handle, _p(emb_t), n_rows, d, mode_code, _p(scores_in), G, _p(off), n_cand, max_group,
+                                            _p(qr), _p(cr), _p(rel), _p(rx), _p(io), _p(ir), n_ideal, _p(out["scores"]), _p(out["order"]),
+                                            _p(out["hits1"]), _p(out["hits5"]), _p(out["first"]), _p(out["R"]), _p(out["sp"]),
+                                            _p(out["dcg"]), _p(out["idcg"]), _stream_ptr(self.device)), "sgpt_eval_groups")
+        return out
+
+    def eval_pairs(self, score: torch.Tensor, label, check_nan: bool = True) -> dict:
+        """include/sgpt_hip.h::sgpt_eval_pairs.  score fp32 [n]; label int [n] (> 0 positive, 0 negative, < 0 ranked but left out
+        of the average precision).  -> {"rank2" int32 [n]: twice the tie-averaged ascending rank; "n_pos", "n_used" int64 [1];
+        "ap_num" float64 [1]} on the device.  check_nan=True synchronises and raises ValueError on a NaN score."""
+        score = score.to(device=self.device, dtype=torch.float32).contiguous().reshape(-1)
+        lab = self._i32(label).reshape(-1)
+        n = score.numel()
+        if lab.numel() != n:
+            raise ValueError(f"eval_pairs: {n} scores and {lab.numel()} labels")
+        out = {"rank2": torch.zeros((n,), dtype=torch.int32, device=self.device),
+               "n_pos": torch.zeros((1,), dtype=torch.int64, device=self.device),
+               "n_used": torch.zeros((1,), dtype=torch.int64, device=self.device),
+               "ap_num": torch.zeros((1,), dtype=torch.float64, device=self.device)}
+        self._chk(self.lib.sgpt_eval_pairs(self.handle, _p(score), _p(lab), n, 1 if check_nan else 0, _p(out["rank2"]),
+                                           _p(out["n_pos"]), _p(out["n_used"]), _p(out["ap_num"]), _stream_ptr(self.device)),
+                  "sgpt_eval_pairs")
+        return out
+
     # ---- measurement hooks (bench.py) ----
     def prof_enable(self, on: bool):
         self._chk(self.lib.sgpt_prof_enable(self.handle, 1 if on else 0), "sgpt_prof_enable")
