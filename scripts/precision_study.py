@@ -4,7 +4,7 @@ fixture: which operand classes of which blocks have to enter their GEMM as hi + 
 (tests/golden/outlier_125m.npz) to land inside the 1e-3 bar, and what statistic of the operand predicts it?
   Not a product or test path; self-contained apart from the oracle's weight generator.
 
-Classes (the producer -> consumer pairs of sgpt_amd/csrc/api.hip): ln1 (LayerNorm-1 output -> Q/K/V projection),
+Classes (the producer -> consumer pairs of sgpt_amd/csrc/encode.hip): ln1 (LayerNorm-1 output -> Q/K/V projection),
 ctx (attention context -> out-projection), ln2 (LayerNorm-2 output -> fc1), h (GELU output -> fc2).  A split class enters
 its GEMM as a_hi.W_hi + a_lo.W_hi + a_hi.W_lo (hi = round16(v), lo = round16(v - hi)), exactly what the K' = 3K launch does.
 `qk3`: q / k themselves stored as hi + lo pairs and the logits as three MFMA passes (attention kernel variant)."""

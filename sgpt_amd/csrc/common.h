@@ -231,7 +231,7 @@ __device__ __forceinline__ bool cand_room(const int* cnt, int cap) {
     return __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap;
 }
 
-// ---- launch descriptors shared between the .hip translation units and api.cpp ----
+// ---- launch descriptors shared between the kernel translation units and the host ones (host.h) ----
 enum GemmEpi {
     EPI_STORE = 0,        // out[m][n] = acc                          (row-major, OutT)
     EPI_BIAS_GELU = 1,    // out[m][n] = gelu_new(acc + bias[n])      (row-major, OutT)

@@ -1,4 +1,4 @@
-// The context object behind `sgpt_ctx*` (include/sgpt_hip.h), shared by api.hip and comm.hip.
+// The context object behind `sgpt_ctx*` (include/sgpt_hip.h), shared by the host translation units (host.h) and comm.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,0 +1,389 @@
+// C ABI (include/sgpt_hip.h): the forward -- one block function per arithmetic (16-bit, fp32, fp8 MFMA) under encode_impl -- and the LM head.
+// Host-side C++ only -- every device op is one of the hand-written kernels in this directory.
+#include "host.h"
+
+namespace {
+
+// What the block functions of one forward share: the call's token layout, the operand format, the launch path and the workspace.
+struct Fwd {
+    sgpt_model* m; sgpt_ctx* c; hipStream_t s;
+    const int32_t *pos, *seq_off;
+    int B, T, max_alloc;
+    int dt;               // operand format of the projections: SGPT_F32 | SGPT_BF16 | SGPT_F16
+    int* range_flag;      // the model's range words (SGPT_F16 stores, e4m3 codes of the fp8-MFMA block) or null
+    bool can_split;       // the format takes a precision plan (prec[])
+    bool qpath, qln;      // query-sized kernels (qgemm.hip); with the LayerNorms of a block inside their prologues
+    float* x;             // residual stream fp32
+    // LayerNorm output; attention context; 16-bit: [T][2d] q | k + V^T [d][T] (x3 attention: the lo halves att_lo elements behind),
+    // fp32: [T][3d]; MLP hidden
+    void *a, *ctx, *qkv, *vt, *h;
+    void* a8; float* sa;  // fp8-MFMA block: LayerNorm output as e4m3 codes + one scale per row
+    long att_lo;
+};
+
+// Descriptor of one projection, out[T][N] = (resid +) A[T][K] . W[N][K]^T (+ bias), from the per-call base.  Built for one launch: the
+// caller adds what that launch has more (shifts, split-precision fields, fp8 scales) and lets it go out of scope.
+GemmArgs proj(const Fwd& f, const void* A, long lda, const void* W, int N, int K, void* out, long ldo, const float* bias,
+              const float* resid = nullptr) {
+    GemmArgs g{};
+    g.M = f.T; g.m_valid = f.T; g.range_flag = f.range_flag;
+    g.A = A; g.lda = lda; g.W = W; g.ldw = K; g.N = N; g.K = K; g.out = out; g.ldo = ldo; g.bias = bias; g.resid = resid;
+    return g;
+}
+
+// A split-precision A operand ([hi | lo | hi] rows of 3 k) contracts as ONE K' = 3 k against the [W_hi | W_hi | W_lo] rows of W3:
+// a_hi.W_hi + a_lo.W_hi + a_hi.W_lo  (nblk = 2: the activation alone is split -- the first TWO blocks of both layouts)
+void split_w(GemmArgs& g, const void* W3, int k, int nblk = 3) { g.W = W3; g.K = nblk * k; g.ldw = 3 * k; g.k_algo = k; }
+
+AttnArgs attn_base(const Fwd& f, const LayerW& l, int k_qkv) {
+    const sgpt_model_desc& d = f.m->d;
+    const int dm = d.d_model;
+    AttnArgs at{};
+    at.dtype = f.dt;
+    at.seq_off = f.seq_off; at.B = f.B; at.H = d.n_heads; at.dh = dm / d.n_heads; at.window = l.is_local ? d.window : 0;
+    at.scale = d.attn_scale * pow2f(2 * k_qkv);      // q and k are both stored down-shifted
+    at.max_alloc_len = f.max_alloc; at.ctx = f.ctx; at.ldo = dm; at.alibi = f.m->alibi;
+    at.q = f.qkv;
+    if (f.vt) { at.k = (bf16_t*)f.qkv + dm; at.v = f.vt; at.ldq = 2 * dm; at.ldvt = f.T; }
+    else { at.k = (float*)f.qkv + dm; at.v = (float*)f.qkv + 2 * dm; at.ldq = 3 * dm; }
+    return at;
+}
+
+// ---- fp32 block (SGPT_F32): plain operands, q | k | v rows in one buffer ----
+void block_f32(const Fwd& f, const LayerW& l) {
+    const sgpt_model_desc& d = f.m->d;
+    const int dm = d.d_model, ffn = d.d_ffn, T = f.T;
+    const bool gptj = d.arch == SGPT_ARCH_GPTJ;
+    launch_layernorm(f.x, l.ln1_g, l.ln1_b, f.a, SGPT_F32, T, dm, d.ln_eps, f.s);
+    gemm(f.c, SGPT_F32, EPI_STORE, SGPT_F32, proj(f, f.a, dm, l.w_qkv, 3 * dm, dm, f.qkv, 3 * dm, l.b_qkv), f.s);
+    if (gptj) launch_rope(f.qkv, SGPT_F32, 3 * dm, dm, f.pos, f.m->rot_sin, f.m->rot_cos, T, d.n_heads, dm / d.n_heads, d.rotary_dim, f.s);
+    launch_attn_f32(attn_base(f, l, 0), f.s);
+    gemm(f.c, SGPT_F32, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dm, l.w_o, dm, dm, f.x, dm, l.b_o, f.x), f.s);   // x += ctx . Wo^T (+ bo)
+    // GPT-Neo: x += MLP(LN2(x));  GPT-J (parallel block, HF:gptj:400-411): x += MLP(LN1(x_old)), `a` still holds it
+    if (!gptj) launch_layernorm(f.x, l.ln2_g, l.ln2_b, f.a, SGPT_F32, T, dm, d.ln_eps, f.s);
+    gemm(f.c, SGPT_F32, EPI_BIAS_GELU, SGPT_F32, proj(f, f.a, dm, l.w_fc, ffn, dm, f.h, ffn, l.b_fc), f.s);
+    gemm(f.c, SGPT_F32, EPI_BIAS_RESID, SGPT_F32, proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x), f.s);
+}
+
+// ---- fp8-MFMA block (SGPT_FP8M with calibrated activation scales): the e4m3 weight codes feed the MFMA directly ----
+void block_fp8(const Fwd& f, const LayerW& l, int li) {
+    const sgpt_model_desc& d = f.m->d;
+    const int dm = d.d_model, ffn = d.d_ffn, T = f.T;
+    const bool gptj = d.arch == SGPT_ARCH_GPTJ;
+    const float s_h = f.m->act_scale[li], s_c = f.m->act_scale[d.n_layers + li];     // scales of the GELU output's / the context's codes
+    auto launch = [&](int epi, int out_dtype, const GemmArgs& q) { Prof pr(f.c, f.s, 2.0 * T * (double)q.N * q.K); launch_gemm_fp8(epi, out_dtype, q, f.s); };
+    // attention projections: a8 = e4m3(LN1(x) / sa[row]) feeds Q, K (row-major 16-bit) and V^T
+    launch_layernorm_q8(f.x, l.ln1_g, l.ln1_b, f.a8, f.sa, nullptr, f.dt, T, dm, d.ln_eps, f.s);
+    GemmArgs qk = proj(f, f.a8, dm, l.w_qkv, 2 * dm, dm, f.qkv, 2 * dm, l.b_qkv);
+    qk.a_scale = f.sa; qk.a_scalar = 1.0f; qk.w_scale = l.s_qkv;
+    launch(EPI_STORE, f.dt, qk);
+    GemmArgs v = proj(f, f.a8, dm, (const uint8_t*)l.w_qkv + (size_t)2 * dm * dm, dm, dm, f.vt, T, l.b_qkv ? l.b_qkv + 2 * dm : nullptr);
+    v.a_scale = f.sa; v.a_scalar = 1.0f; v.w_scale = l.s_qkv + 2 * dm;
+    launch(EPI_VT, f.dt, v);
+    if (gptj) launch_rope(f.qkv, f.dt, 2 * dm, dm, f.pos, f.m->rot_sin, f.m->rot_cos, T, d.n_heads, dm / d.n_heads, d.rotary_dim, f.s);
+    AttnArgs at = attn_base(f, l, 0);
+    at.out_fp8 = 1; at.out_scale = s_c; at.range_flag = f.range_flag;
+    launch_attn_bf16(at, f.s);                         // context as e4m3 codes of ctx / s_c, [T][dm] bytes
+    GemmArgs o = proj(f, f.ctx, dm, l.w_o, dm, dm, f.x, dm, l.b_o, f.x);
+    o.a_scalar = s_c; o.w_scale = l.s_o;
+    launch(EPI_BIAS_RESID, 0, o);
+    // a8 = e4m3(LN(x) / sa[row]);  h8 = e4m3(gelu(a8 . W1_8^T * sa * s1 + b1) / s_h);  x += h8 . W2_8^T * s_h * s2 + b2
+    // (GPT-J, parallel block: a8 still holds LN1(x_old))
+    if (!gptj) launch_layernorm_q8(f.x, l.ln2_g, l.ln2_b, f.a8, f.sa, nullptr, f.dt, T, dm, d.ln_eps, f.s);
+    GemmArgs fc = proj(f, f.a8, dm, l.w_fc, ffn, dm, f.h, ffn, l.b_fc);
+    fc.a_scale = f.sa; fc.a_scalar = 1.0f; fc.w_scale = l.s_fc; fc.out_scale = s_h;
+    launch(EPI_BIAS_GELU, 0, fc);
+    GemmArgs p = proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x);
+    p.a_scalar = s_h; p.w_scale = l.s_proj;
+    launch(EPI_BIAS_RESID, 0, p);
+}
+
+// A LayerNorm of the residual stream in front of the projection `q` that reads it: inside that projection's prologue (qln), or
+// one launch into `a` -- [hi | lo | hi] rows of 3 d when the plan splits this class -- with the crest probe behind it.
+void block_ln(const Fwd& f, QGemmArgs& q, const float* g, const float* b, int k, bool split, unsigned* crest) {
+    const int dm = f.m->d.d_model;
+    const float eps = f.m->d.ln_eps;
+    q.eps = eps;
+    if (f.qln) { q.x = f.x; q.ln_g = g; q.ln_b = b; q.ln_mul = pow2f(-k); return; }
+    if (split) launch_layernorm_split(f.x, g, b, f.a, f.dt, f.T, dm, eps, f.s, pow2f(-k));
+    else launch_layernorm(f.x, g, b, f.a, f.dt, f.T, dm, eps, f.s, pow2f(-k));
+    if (crest) launch_crest16(f.a, f.T, dm, q.g.lda, f.dt, crest, f.s);
+}
+
+// One projection of a 16-bit block: the query-sized kernels on the query path, the bulk launchers otherwise.
+sgpt_status launch16(const Fwd& f, int epi, int out_dtype, const QGemmArgs& q, const char* what) {
+    if (!f.qpath) gemm(f.c, f.dt, epi, out_dtype, q.g, f.s);
+    else if (!qgemm(f.c, f.dt, epi, out_dtype, q, f.s)) return fail(f.c, SGPT_ERR_INVALID, std::string("query path: ") + what + " not served");
+    return SGPT_OK;
+}
+
+// ---- 16-bit block (bf16 / f16 operands; FP8W and un-calibrated FP8M with l's weights de-quantised to bf16) ----
+// [LN1 +] QKV -> (rope) -> attention -> out-proj + residual -> [LN2 +] fc1 + GELU -> fc2 + residual
+sgpt_status block_16(const Fwd& f, const LayerW& l, int li) {
+    sgpt_model* m = f.m;
+    sgpt_ctx* c = f.c;
+    hipStream_t s = f.s;
+    const int dm = m->d.d_model, ffn = m->d.d_ffn, T = f.T, dt = f.dt;
+    const bool gptj = m->d.arch == SGPT_ARCH_GPTJ;
+    // SGPT_F16 range shifts of this block (all 0 unless the checkpoint needed them): class stored as value * 2^-k
+    const bool f16m = dt == SGPT_F16;
+    const int* sh = &m->shift[(size_t)li * RS_N];
+    const int k_ln1 = f16m ? sh[RS_LN1] : 0, k_qkv = f16m ? sh[RS_QKV] : 0, k_h = f16m ? sh[RS_H] : 0;
+    const int k_ln2 = f16m ? (gptj ? sh[RS_LN1] : sh[RS_LN2]) : 0;     // GPT-J: ln_1's output feeds the MLP too
+    unsigned* slots = m->range_dev + 1 + (size_t)li * RS_N;
+    // this block's precision plan
+    const int* pc = &m->prec[(size_t)li * PC_N];
+    const int p_ln1 = f.can_split ? pc[PC_LN1] : 0;                  // 0 | 1 (q, k split) | 2 (q, k, v split) | 3 (q, k: activation split only)
+    const bool p_att = f.can_split && pc[PC_ATT] != 0, p_ctx = f.can_split && pc[PC_CTX] != 0, p_h = f.can_split && pc[PC_H] != 0;
+    const bool p_ln2 = f.can_split && pc[PC_LN2] != 0 && (!gptj || p_ln1 != 0);   // GPT-J: fc1 reads ln_1's output (its [hi | lo | hi] rows)
+    unsigned* crest = (m->probing && m->crest_dev) ? m->crest_dev + (size_t)li * RS_N : nullptr;
+    // row strides of this block's LayerNorm-1 output, of fc1's input (GPT-J: ln_1's output again), of the context and the GELU output
+    const long lda1 = p_ln1 ? 3 * dm : dm, lda2 = gptj ? lda1 : (p_ln2 ? 3 * dm : dm), ldc = p_ctx ? 3 * dm : dm, ldh = p_h ? 3 * ffn : ffn;
+    sgpt_status st;
+    {   // Q,K -> qk[T][2d] row-major ; V -> V^T[d][T]   (p_att: each also as a lo half, att_lo elements behind)
+        QGemmArgs q{};
+        q.g = proj(f, f.a, lda1, l.w_qkv, 3 * dm, dm, f.qkv, 2 * dm, l.b_qkv);                           // bias: BLOOM only
+        q.g.in_mul = pow2f(k_ln1); q.g.out_mul = q.g.out_mul2 = pow2f(-k_qkv); q.g.range_amax = f16m ? slots + RS_QKV : nullptr;
+        q.g.lo_delta = q.g.lo_delta2 = p_att ? f.att_lo : 0;
+        block_ln(f, q, l.ln1_g, l.ln1_b, k_ln1, p_ln1 != 0, crest ? crest + RS_LN1 : nullptr);
+        // ONE EPI_QKV launch: the query path always; a query-sized batch on the bulk path (a launch costs ~8 us there); a bulk batch
+        // with plain operands and no bias (GPT-Neo / GPT-J) on the 256x256 kernel -- the V column tiles run with swapped operand
+        // roles and leave through the same whole-row store epilogue (gemm.hip); the LayerNorm output panel is read once, one launch
+        // boundary less per block.  Same sums: identical bits.
+        if (f.qpath || ((p_ln1 == 0 || p_ln1 == 2) && gemm_qkv_one_launch(T, 2 * dm, c->force256 != 0)) ||
+            (p_ln1 == 0 && !p_att && l.b_qkv == nullptr && gemm_qkv_bulk(T, 3 * dm, dm, 2 * dm, c->force256 != 0))) {
+            if (p_ln1 == 2) split_w(q.g, l.w_qkv3, dm);
+            q.g.n_split = 2 * dm; q.g.out2 = f.vt; q.g.ldo2 = T;
+            if ((st = launch16(f, EPI_QKV, dt, q, "QKV projection")) != SGPT_OK) return st;
+        } else {
+            // Q | K (split: K' = 3d, or 2d for p_ln1 == 3), then V from the hi block alone unless the plan splits it too (p_ln1 == 2)
+            GemmArgs qk = q.g, v = q.g;
+            if (p_ln1) split_w(qk, l.w_qkv3, dm, p_ln1 == 3 ? 2 : 3);
+            qk.N = 2 * dm;
+            gemm(c, dt, EPI_STORE, dt, qk, s);
+            if (p_ln1 == 2) split_w(v, (bf16_t*)l.w_qkv3 + (size_t)2 * dm * 3 * dm, dm);
+            else v.W = (bf16_t*)l.w_qkv + (size_t)2 * dm * dm;
+            v.N = dm; v.out = f.vt; v.ldo = T; v.bias = l.b_qkv ? l.b_qkv + 2 * dm : nullptr;
+            gemm(c, dt, EPI_VT, dt, v, s);
+        }
+    }
+    if (gptj) launch_rope(f.qkv, dt, 2 * dm, dm, f.pos, m->rot_sin, m->rot_cos, T, m->d.n_heads, dm / m->d.n_heads, m->d.rotary_dim, s);
+    AttnArgs at = attn_base(f, l, k_qkv);
+    at.x3 = p_att ? 1 : 0; at.qk_lo_delta = f.att_lo; at.v_lo_delta = f.att_lo;
+    at.ldo = ldc; at.ctx_lo_delta = p_ctx ? dm : 0; at.ctx_hi2_delta = p_ctx ? 2 * dm : 0;
+    launch_attn_bf16(at, s);
+    if (crest) launch_crest16(f.ctx, T, dm, ldc, dt, crest + RS_QKV, s);
+    if (m->calibrating)   // FP8M calibration: range of this block's attention context
+        launch_absmax16(f.ctx, (long)T * dm, dt, m->h_amax + m->d.n_layers + li, s);
+    {   // x += ctx . Wo^T (+ bo)      (the context carries v's shift; split context: K' = 3d against [Wo_hi | Wo_hi | Wo_lo])
+        QGemmArgs q{};
+        q.g = proj(f, f.ctx, ldc, l.w_o, dm, dm, f.x, dm, l.b_o, f.x);
+        if (p_ctx) split_w(q.g, l.w_o3, dm);
+        q.g.in_mul = pow2f(k_qkv);
+        if ((st = launch16(f, EPI_BIAS_RESID, SGPT_F32, q, "out-projection")) != SGPT_OK) return st;
+    }
+    {   // GPT-Neo: x += MLP(LN2(x));  GPT-J (parallel block, HF:gptj:400-411): x += MLP(LN1(x_old)), `a` still holds it
+        QGemmArgs q{};
+        q.g = proj(f, f.a, lda2, l.w_fc, ffn, dm, f.h, ldh, l.b_fc);
+        if (p_ln2) split_w(q.g, l.w_fc3, dm);
+        if (p_h) { q.g.lo_delta = ffn; q.g.hi2_delta = 2 * ffn; }       // the GELU output as a [hi | lo | hi] row for fc2
+        q.g.in_mul = pow2f(k_ln2); q.g.out_mul = pow2f(-k_h); q.g.range_amax = f16m ? slots + RS_H : nullptr;
+        if (!gptj) block_ln(f, q, l.ln2_g, l.ln2_b, k_ln2, p_ln2, crest ? crest + RS_LN2 : nullptr);
+        if ((st = launch16(f, EPI_BIAS_GELU, dt, q, "fc1")) != SGPT_OK) return st;
+    }
+    if (crest) launch_crest16(f.h, T, ffn, ldh, dt, crest + RS_H, s);
+    if (m->calibrating) launch_absmax16(f.h, (long)T * ffn, dt, m->h_amax + li, s);   // FP8M calibration: range of this block's GELU output
+    QGemmArgs q{};
+    q.g = proj(f, f.h, ldh, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x);
+    if (p_h) split_w(q.g, l.w_proj3, ffn);
+    q.g.in_mul = pow2f(k_h);
+    return launch16(f, EPI_BIAS_RESID, SGPT_F32, q, "fc2");
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------
+// One forward over the packed token axis.  `layer_out` (fp32 [n_layers+1, B, d]) additionally receives the pooled
+// vector of every hidden state on the way (sgpt_encode_layers).
+static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t* pos, const int32_t* seq_off,
+                               const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t T, int32_t max_alloc,
+                               int32_t pool_mode, int32_t n_layers_run, int32_t apply_final_ln, int32_t normalize,
+                               float* out, float* hidden_out, float* layer_out, float* layer_mean, void* stream) {
+    if (!m) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    if (!ids || !pos || !seq_off || !seq_len || B <= 0 || T <= 0 || T % 32 || max_alloc <= 0 || max_alloc % 2)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_encode: bad token layout (T_pad % 32, max_alloc_len % 2)");
+    if (n_layers_run < 0 || n_layers_run > m->d.n_layers) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: n_layers_run out of range");
+    if (pool_mode < 0 || pool_mode > 3) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: bad pool_mode");
+    if (pool_mode == SGPT_POOL_LEARNTMEAN && (out || layer_out || layer_mean)) {
+        if (!m->pool_w) return fail(c, SGPT_ERR_MISSING, "sgpt_encode: learntmean needs sgpt_model_set_pool_weights first");
+        // with pad_left on the device the longest padded position is not known here: the kernel clamps the table index,
+        // and the Python host checks max(pad_left + len) before the call (model.py::_check_learnt)
+        // (allocations are 8-row aligned: the longest sequence has at least max_alloc - 7 tokens)
+        if (!pad_left && max_alloc - 7 > m->pool_w_n)
+            return fail(c, SGPT_ERR_INVALID, "sgpt_encode: fewer learnt position weights than the longest sequence");
+    }
+    if (max_alloc > 2048) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: sequence longer than 2048 tokens");
+    if (!out && !hidden_out && !layer_out && !layer_mean) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: no output requested");
+    HIPC(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int dm = m->d.d_model, ffn = m->d.d_ffn;
+    const bool fp8m = m->d.compute_dtype == SGPT_FP8M;
+    const bool fp8 = m->d.compute_dtype == SGPT_FP8W || fp8m;
+    const bool bf = m->d.compute_dtype != SGPT_F32;                 // 16-bit MFMA operands (bf16 or f16)
+    const int dt = !bf ? SGPT_F32 : (m->d.compute_dtype == SGPT_F16 ? SGPT_F16 : SGPT_BF16);
+    const size_t esz = bf ? 2 : 4;
+    const size_t SLACK = 64;  // rows of zeroed slack behind buffers the attention key tiles may over-read
+
+    const bool gptj = m->d.arch == SGPT_ARCH_GPTJ;
+    // workspace carve (all offsets 256-B aligned)
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    const size_t o_x = carve((size_t)T * dm * 4);                        // residual stream fp32
+    // Precision plan (prec[]): a split class is stored as [hi | lo | hi] rows of 3 x its width (the consuming GEMM contracts over
+    // all three blocks against [W_hi | W_hi | W_lo]; a consumer that is not split reads the first block alone).  Any split at
+    // all: the attention context gets its own buffer (the LayerNorm buffer has 3 d rows then).
+    const bool can_split = bf && !fp8;
+    bool any_ln = false, any_att = false, any_ctx = false, any_h = false;
+    if (can_split)
+        for (int li = 0; li < n_layers_run; ++li) {
+            const int* pc = &m->prec[(size_t)li * PC_N];
+            any_ln |= pc[PC_LN1] != 0 || pc[PC_LN2] != 0; any_att |= pc[PC_ATT] != 0; any_ctx |= pc[PC_CTX] != 0; any_h |= pc[PC_H] != 0;
+        }
+    const bool split = any_ln || any_att || any_ctx || any_h;
+    const size_t o_a = carve((size_t)T * dm * esz * (any_ln ? 3 : 1));    // LN output (GPT-Neo: also attention ctx)
+    const size_t o_c = (gptj || split) ? carve((size_t)T * dm * esz * (any_ctx ? 3 : 1)) : o_a;   // GPT-J: ctx separate (ln_1 output feeds the MLP too)
+    const size_t qkv_bytes = ((size_t)T + SLACK) * 3 * dm * esz;
+    const size_t o_qkv = carve(qkv_bytes * (any_att ? 2 : 1));           // bf16: [T][2d] qk + V^T [d][T] (x3 attention: the lo halves behind); fp32: [T][3d]
+    const size_t o_h = carve((size_t)T * ffn * esz * (any_h ? 3 : 1));                     // MLP hidden (FP8M: e4m3 codes in the same region)
+    // FP8M: fp8 MFMA on all four projections when the shapes fit the 256x256x128 kernel and the activation scales are
+    // calibrated; otherwise (and while calibrating) the block runs the SGPT_FP8W arithmetic (weights de-quantised to bf16)
+    const bool shapes8 = gemm_fp8_shape_ok(T, ffn, dm) && gemm_fp8_shape_ok(T, dm, ffn) && gemm_fp8_shape_ok(T, 2 * dm, dm);
+    const bool mlp8 = fp8m && !m->calibrating && shapes8;
+    if (mlp8)
+        for (int li = 0; li < n_layers_run; ++li)
+            if (!(m->act_scale[li] > 0.f) || !(m->act_scale[m->d.n_layers + li] > 0.f))
+                return fail(c, SGPT_ERR_INVALID, "SGPT_FP8M: activation scales are not set (sgpt_model_calibrate_begin / _end, or sgpt_model_set_act_scales)");
+    // Query-sized batches (round 6; qgemm.hip): at most QGEMM_MAX_ROWS token rows, plain 16-bit operands, no probe / calibration
+    // pass riding on the forward.  Every projection takes the register-staged deep-prefetch kernel; at d = 512 / 768 / 1024 the two
+    // LayerNorms of a sequential block (GPT-Neo, BLOOM) run inside the prologues of the projections they feed: five launches per block
+    // instead of seven.  Same arithmetic per element as the bulk path (identical bits); sgpt_ctx_set_tile_policy(1 | 2) keeps the bulk kernels.
+    const bool qpath = bf && !fp8 && !split && !(m->probing && m->crest_dev) && !m->calibrating && !c->force256 && !c->no_qpath && T <= QGEMM_MAX_ROWS &&
+                       qgemm_shape_ok(T, 3 * dm, dm, EPI_QKV, 2 * dm) && qgemm_shape_ok(T, dm, dm, EPI_BIAS_RESID, 0) &&
+                       qgemm_shape_ok(T, ffn, dm, EPI_BIAS_GELU, 0) && qgemm_shape_ok(T, dm, ffn, EPI_BIAS_RESID, 0);
+    const bool qln = qpath && !gptj && qgemm_ln_ok(T, 3 * dm, dm, EPI_QKV, 2 * dm) && qgemm_ln_ok(T, ffn, dm, EPI_BIAS_GELU, 0);
+    const size_t o_a8 = mlp8 ? carve((size_t)T * dm) : 0;                // FP8M: LayerNorm output as e4m3 codes
+    const size_t o_sa = mlp8 ? carve((size_t)T * 4) : 0;                 //       + one scale per row
+    const size_t o_lp = (layer_mean && !layer_out) ? carve((size_t)(m->d.n_layers + 1) * B * dm * 4) : 0;
+    sgpt_status st = ensure(c, &c->ws, &c->ws_bytes, off);
+    if (st != SGPT_OK) return st;
+    char* base = (char*)c->ws;
+    if (layer_mean && !layer_out) layer_out = (float*)(base + o_lp);     // per-layer pooled vectors, scratch
+    Fwd f{};
+    f.m = m; f.c = c; f.s = s; f.pos = pos; f.seq_off = seq_off; f.B = B; f.T = T; f.max_alloc = max_alloc;
+    f.dt = dt; f.range_flag = (mlp8 || dt == SGPT_F16) ? (int*)m->range_dev : nullptr;
+    f.can_split = can_split; f.qpath = qpath; f.qln = qln;
+    f.x = (float*)(base + o_x); f.a = base + o_a; f.ctx = base + o_c; f.qkv = base + o_qkv; f.h = base + o_h;
+    f.vt = bf ? (void*)((bf16_t*)f.qkv + ((size_t)T + SLACK) * 2 * dm) : nullptr;
+    if (mlp8) { f.a8 = base + o_a8; f.sa = (float*)(base + o_sa); }
+    f.att_lo = (long)(qkv_bytes / 2);      // element distance of the lo halves of q | k and of V^T (x3 attention)
+    float* x = f.x;
+
+    // Rows that are over-read by the attention key tiles but never written in this call must be finite
+    // (a masked key contributes p = 0, and 0 * NaN = NaN): the slack behind the q/k/v buffers, and -- when
+    // the attention context has its own buffer (GPT-J) -- the filler rows past the last sequence.  The
+    // workspace is reused across calls / dtypes, so stale bytes there can decode to NaN.
+    if (bf) {
+        HIPC(c, hipMemsetAsync((bf16_t*)f.qkv + (size_t)T * 2 * dm, 0, SLACK * 2 * dm * esz, s));
+        HIPC(c, hipMemsetAsync((bf16_t*)f.vt + (size_t)T * dm, 0, SLACK * dm * esz, s));
+        if (any_att) {
+            HIPC(c, hipMemsetAsync((bf16_t*)f.qkv + f.att_lo + (size_t)T * 2 * dm, 0, SLACK * 2 * dm * esz, s));
+            HIPC(c, hipMemsetAsync((bf16_t*)f.vt + f.att_lo + (size_t)T * dm, 0, SLACK * dm * esz, s));
+        }
+    } else {
+        HIPC(c, hipMemsetAsync((float*)f.qkv + (size_t)T * 3 * dm, 0, SLACK * 3 * dm * esz, s));
+    }
+    // (query path with the LayerNorm inside the projections: no LayerNorm launch fills the buffer the context shares with it)
+    if (gptj || mlp8 || split || qln) HIPC(c, hipMemsetAsync(f.ctx, 0, (size_t)T * dm * esz * (any_ctx ? 3 : 1), s));   // (fp8: stale bytes would decode to NaN codes)
+    launch_embed(ids, pos, m->wte, m->wpe, x, T, dm, m->d.vocab, m->d.max_pos, s);
+    if (m->emb_ln_g) launch_layernorm(x, m->emb_ln_g, m->emb_ln_b, x, SGPT_F32, T, dm, m->d.ln_eps, s);   // BLOOM :499
+    for (int li = 0; li < n_layers_run; ++li) {
+        LayerW l = m->L[li];
+        if (layer_out)   // hidden_states[li] = input of block li (HF:gpt_neo:475-478)
+            launch_lnf_pool(x, m->lnf_g, m->lnf_b, seq_off, seq_len, pad_left, B, dm, m->d.ln_eps, 0, pool_mode,
+                            normalize, m->pool_w, m->pool_w_n, layer_out + (size_t)li * B * dm, s);
+        if (fp8 && !mlp8) {  // this block's weights: e4m3fn codes * 2^k -> bf16, exact; <1 % of the block's time at T >= 16k
+            launch_fp8_dequant_rows(l.w_qkv, l.s_qkv, (long)3 * dm, dm, m->dq[0], SGPT_BF16, s);
+            launch_fp8_dequant_rows(l.w_o, l.s_o, dm, dm, m->dq[1], SGPT_BF16, s);
+            launch_fp8_dequant_rows(l.w_fc, l.s_fc, ffn, dm, m->dq[2], SGPT_BF16, s);
+            launch_fp8_dequant_rows(l.w_proj, l.s_proj, dm, ffn, m->dq[3], SGPT_BF16, s);
+            l.w_qkv = m->dq[0]; l.w_o = m->dq[1]; l.w_fc = m->dq[2]; l.w_proj = m->dq[3];
+        }
+        if (mlp8) block_fp8(f, l, li);
+        else if (!bf) block_f32(f, l);
+        else if ((st = block_16(f, l, li)) != SGPT_OK) return st;
+    }
+    if (hidden_out) {
+        if (apply_final_ln) launch_layernorm(x, m->lnf_g, m->lnf_b, hidden_out, SGPT_F32, T, dm, m->d.ln_eps, s);
+        else HIPC(c, hipMemcpyAsync(hidden_out, x, (size_t)T * dm * 4, hipMemcpyDeviceToDevice, s));
+    }
+    if (out)
+        launch_lnf_pool(x, m->lnf_g, m->lnf_b, seq_off, seq_len, pad_left, B, dm, m->d.ln_eps, apply_final_ln,
+                        pool_mode, normalize, m->pool_w, m->pool_w_n, out, s,
+                        m->d.compute_dtype == SGPT_F16 ? (int*)m->range_dev : nullptr);
+    if (layer_out)
+        launch_lnf_pool(x, m->lnf_g, m->lnf_b, seq_off, seq_len, pad_left, B, dm, m->d.ln_eps, apply_final_ln,
+                        pool_mode, normalize, m->pool_w, m->pool_w_n, layer_out + (size_t)n_layers_run * B * dm, s);
+    if (layer_mean) launch_mean_over_axis0(layer_out, n_layers_run + 1, (long)B * dm, layer_mean, s);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+extern "C" {
+
+sgpt_status sgpt_encode(sgpt_model* m, const int32_t* ids, const int32_t* pos, const int32_t* seq_off,
+                        const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t T, int32_t max_alloc,
+                        int32_t pool_mode, int32_t n_layers_run, int32_t apply_final_ln, int32_t normalize,
+                        float* out, float* hidden_out, void* stream) {
+    return encode_impl(m, ids, pos, seq_off, seq_len, pad_left, B, T, max_alloc, pool_mode, n_layers_run,
+                       apply_final_ln, normalize, out, hidden_out, nullptr, nullptr, stream);
+}
+
+sgpt_status sgpt_encode_layers(sgpt_model* m, const int32_t* ids, const int32_t* pos, const int32_t* seq_off,
+                               const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t T, int32_t max_alloc,
+                               int32_t pool_mode, int32_t normalize, float* out_layers, float* out_mean, void* stream) {
+    if (!m) return SGPT_ERR_INVALID;
+    if (!out_layers && !out_mean) return fail(m->ctx, SGPT_ERR_INVALID, "sgpt_encode_layers: no output requested");
+    return encode_impl(m, ids, pos, seq_off, seq_len, pad_left, B, T, max_alloc, pool_mode, m->d.n_layers, 1, normalize,
+                       nullptr, nullptr, out_layers, out_mean, stream);
+}
+
+sgpt_status sgpt_lm_logprobs(sgpt_model* m, const float* hidden, const int32_t* row_idx, const int32_t* targets,
+                             int32_t n, float* out_logprob, int32_t* out_greedy, void* stream) {
+    if (!m) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    if (!hidden || !row_idx || !targets || !out_logprob || n <= 0) return fail(c, SGPT_ERR_INVALID, "sgpt_lm_logprobs: bad arguments");
+    HIPC(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int dm = m->d.d_model, V = m->d.vocab;
+    const long ldv = (V + 3) / 4 * 4;
+    const int R = n < 1024 ? n : 1024;                       // rows per chunk: logits chunk [R, V] fp32 (206 MB at V = 50 257)
+    const size_t rows_bytes = align_up((size_t)R * dm * 4, 256), lg_bytes = align_up((size_t)R * ldv * 4, 256);
+    sgpt_status st = ensure(c, &c->ws2, &c->ws2_bytes, rows_bytes + lg_bytes);
+    if (st != SGPT_OK) return st;
+    float* rows = (float*)c->ws2;
+    float* logits = (float*)((char*)c->ws2 + rows_bytes);
+    for (int r0 = 0; r0 < n; r0 += R) {
+        const int nr = (n - r0) < R ? (n - r0) : R;
+        launch_gather_rows(hidden, row_idx + r0, nr, dm, rows, s);
+        GemmArgs g{};
+        g.A = rows; g.lda = dm; g.W = m->lm_w; g.ldw = dm; g.M = nr; g.m_valid = nr; g.N = V; g.K = dm;
+        g.out = logits; g.ldo = ldv; g.bias = m->lm_b;
+        gemm(c, SGPT_F32, EPI_STORE, SGPT_F32, g, s);          // exact fp32 MFMA: scores are sums of ~30 log-probabilities
+        launch_logprob_rows(logits, ldv, V, targets + r0, nr, out_logprob + r0, out_greedy ? out_greedy + r0 : nullptr, s);
+    }
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+}  // extern "C"

@@ -36,10 +36,10 @@ constexpr bool RESID_NT = SGPT_RESID_NT != 0;
 #endif
 constexpr bool RESID_LD_NT = SGPT_RESID_LD_NT != 0;
 #ifndef SGPT_FOLD_TAIL_SCORE
-#define SGPT_FOLD_TAIL_SCORE 1   // the same for the materialised-score launch (api.hip has the same switch)
+#define SGPT_FOLD_TAIL_SCORE 1   // the same for the materialised-score launch (score.hip has the same switch)
 #endif
 #ifndef SGPT_FOLD_TAIL
-#define SGPT_FOLD_TAIL 1     // 0: A/B builds without the ragged-tail handling of the filtered scorer launch (api.hip has the same switch)
+#define SGPT_FOLD_TAIL 1     // 0: A/B builds without the ragged-tail handling of the filtered scorer launch (score.hip has the same switch)
 #endif
 #ifndef SGPT_THV_UNCOND
 #define SGPT_THV_UNCOND 1
@@ -1176,7 +1176,7 @@ bool gemm_qkv_bulk(int M, int N, int K, int n_split, bool force256) {
     return M % 256 == 0 && N % 256 == 0 && n_split % 256 == 0 && n_split < N && K % 64 == 0 && K >= 128 &&
            (long)(M / 256) * (n_split / 256) > SGPT_FEW_TILES;
 }
-// THE predicate of the folded ragged tail (api.hip asks it before folding; launch_gemm16 re-checks it): a scorer launch of M padded
+// THE predicate of the folded ragged tail (score.hip asks it before folding; launch_gemm16 re-checks it): a scorer launch of M padded
 // query rows against N = (whole 256-document tiles + 256) documents of width K takes the 256x256 kernel with the documents as its
 // streamed operand -- the only kernel that honours GemmArgs.n_valid.
 bool gemm_score_tail_foldable(int M, long N, int K) {

@@ -1,0 +1,488 @@
+// C ABI (include/sgpt_hip.h): packed weights (load / free), learnt pooling weights, FP8M calibration, the f16 range guard and
+// the precision plan of a model.
+// Host-side C++ only -- every device op is one of the hand-written kernels in this directory.
+#include "host.h"
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------------
+sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_tensor_view* tv, size_t nt,
+                            sgpt_model** out) {
+    if (!c || !d || !tv || !out) return SGPT_ERR_INVALID;
+    *out = nullptr;
+    HIPC(c, hipSetDevice(c->device));
+    if (d->arch != SGPT_ARCH_GPTNEO && d->arch != SGPT_ARCH_GPTJ && d->arch != SGPT_ARCH_BLOOM)
+        return fail(c, SGPT_ERR_INVALID, "arch must be SGPT_ARCH_GPTNEO, SGPT_ARCH_GPTJ or SGPT_ARCH_BLOOM");
+    const bool gptj = d->arch == SGPT_ARCH_GPTJ, bloom = d->arch == SGPT_ARCH_BLOOM;
+    const int dm = d->d_model, ffn = d->d_ffn, H = d->n_heads;
+    if (dm % 128 || ffn % 128 || H <= 0 || dm % H) return fail(c, SGPT_ERR_INVALID, "d_model and d_ffn must be multiples of 128");
+    const int dh = dm / H;
+    if (d->compute_dtype != SGPT_F32 && dh != 64 && dh != 128 && dh != 256)
+        return fail(c, SGPT_ERR_INVALID, "16-bit attention supports head_dim 64, 128 or 256");
+    if (dh > 256 || dh % 4) return fail(c, SGPT_ERR_INVALID, "head_dim must be <= 256 and a multiple of 4");
+    if (dm > 4096) return fail(c, SGPT_ERR_INVALID, "d_model > 4096 not supported");
+    if (d->compute_dtype != SGPT_BF16 && d->compute_dtype != SGPT_F32 && d->compute_dtype != SGPT_FP8W &&
+        d->compute_dtype != SGPT_F16 && d->compute_dtype != SGPT_FP8M)
+        return fail(c, SGPT_ERR_INVALID, "bad compute_dtype");
+    if (gptj && (d->rotary_dim <= 0 || d->rotary_dim > dh || d->rotary_dim % 2))
+        return fail(c, SGPT_ERR_INVALID, "GPT-J needs an even rotary_dim in (0, head_dim]");
+    if ((d->qk_split != 0 || d->split_weights != 0) && d->compute_dtype != SGPT_F16 && d->compute_dtype != SGPT_BF16)
+        return fail(c, SGPT_ERR_INVALID, "qk_split / split_weights apply to SGPT_F16 / SGPT_BF16 models");
+
+    std::unordered_map<std::string, const sgpt_tensor_view*> byname;
+    for (size_t i = 0; i < nt; ++i) byname[tv[i].name] = &tv[i];
+    sgpt_model* m = new sgpt_model();
+    m->ctx = c;
+    m->d = *d;
+    m->d.layer_is_local = nullptr;
+    const bool fp8 = d->compute_dtype == SGPT_FP8W || d->compute_dtype == SGPT_FP8M;
+    const bool f16 = d->compute_dtype == SGPT_F16;
+    const bool bf = d->compute_dtype == SGPT_BF16 || f16;          // 16-bit packed weights
+    const size_t esz = fp8 ? 1 : (bf ? 2 : 4);
+    sgpt_status st = SGPT_OK;
+    // SGPT_F16 range audit: stats[0] = max|matmul weight|, [1] = max|LayerNorm gamma|, [2] = max|LayerNorm beta|
+    unsigned* stats = nullptr;
+    if (f16) {
+        if (hipMalloc((void**)&stats, 16) != hipSuccess) { delete m; return fail(c, SGPT_ERR_OOM, "hipMalloc failed"); }
+        (void)hipMemsetAsync(stats, 0, 16, 0);
+    }
+
+    auto find = [&](const std::string& name, int64_t numel) -> const float* {
+        auto it = byname.find(name);
+        if (it == byname.end()) { st = fail(c, SGPT_ERR_MISSING, "missing weight tensor: " + name); return nullptr; }
+        if (it->second->numel != numel) { st = fail(c, SGPT_ERR_INVALID, "wrong numel for " + name); return nullptr; }
+        return it->second->ptr;
+    };
+    auto dalloc = [&](size_t bytes) -> void* {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) { st = fail(c, SGPT_ERR_OOM, "hipMalloc weights failed"); return nullptr; }
+        m->allocs.push_back(p);
+        return p;
+    };
+    auto copy_f32 = [&](const std::string& name, int64_t numel) -> float* {
+        const float* src = find(name, numel);
+        if (!src) return nullptr;
+        float* dst = (float*)dalloc(numel * 4);
+        if (!dst) return nullptr;
+        if (hipMemcpyAsync(dst, src, numel * 4, hipMemcpyDeviceToDevice, 0) != hipSuccess) st = fail(c, SGPT_ERR_HIP, "memcpy " + name);
+        return dst;
+    };
+    // LayerNorm parameters whose output is rounded to the 16-bit GEMM operand format
+    auto copy_ln = [&](const std::string& base, float** g, float** b) {
+        *g = copy_f32(base + ".weight", dm);
+        *b = copy_f32(base + ".bias", dm);
+        if (f16 && *g && *b) { launch_absmax(*g, dm, stats + 1, 0); launch_absmax(*b, dm, stats + 2, 0); }
+    };
+    // matmul weight [rows, cols] -> packed dtype at row `row_off` of dst (fp8: codes + one scale per row)
+    auto pack_rows = [&](const float* src, int64_t rows, int64_t cols, void* dst, int64_t row_off, float* scale) {
+        const int64_t off = row_off * cols, numel = rows * cols;
+        if (fp8) launch_fp8_quant_rows(src, rows, cols, (uint8_t*)dst + off, scale + row_off, 0);
+        else if (bf) {
+            launch_f32_to_16(src, numel, (bf16_t*)dst + off, f16 ? DT_F16 : DT_BF16, 0);
+            if (f16) launch_absmax(src, numel, stats + 0, 0);
+        }
+        else if (hipMemcpyAsync((float*)dst + off, src, numel * 4, hipMemcpyDeviceToDevice, 0) != hipSuccess)
+            st = fail(c, SGPT_ERR_HIP, "memcpy weight");
+    };
+    auto pack_w = [&](const std::string& name, int64_t rows, int64_t cols, void* dst, int64_t row_off, float* scale) {
+        const float* src = find(name, rows * cols);
+        if (src) pack_rows(src, rows, cols, dst, row_off, scale);
+    };
+
+    m->wte = copy_f32(bloom ? "word_embeddings.weight" : "wte.weight", (int64_t)d->vocab * dm);
+    if (gptj) {
+        m->rot_sin = copy_f32("rotary.sin", (int64_t)d->max_pos * (d->rotary_dim / 2));
+        m->rot_cos = copy_f32("rotary.cos", (int64_t)d->max_pos * (d->rotary_dim / 2));
+    } else if (bloom) {
+        m->emb_ln_g = copy_f32("word_embeddings_layernorm.weight", dm);
+        m->emb_ln_b = copy_f32("word_embeddings_layernorm.bias", dm);
+        m->alibi = copy_f32("alibi.slopes", H);
+    } else {
+        m->wpe = copy_f32("wpe.weight", (int64_t)d->max_pos * dm);
+    }
+    // LM head of the cross-encoder scorer (crossencoder/beir/sgptce.py): GPT-Neo / BLOOM tie it to the embedding
+    // (HF tie_word_embeddings), GPT-J carries lm_head.weight / lm_head.bias
+    m->lm_w = m->wte;
+    if (byname.count("lm_head.weight")) {
+        m->lm_w = copy_f32("lm_head.weight", (int64_t)d->vocab * dm);
+        if (byname.count("lm_head.bias")) m->lm_b = copy_f32("lm_head.bias", d->vocab);
+    }
+    m->lnf_g = copy_f32("ln_f.weight", dm);
+    m->lnf_b = copy_f32("ln_f.bias", dm);
+    m->zero_bias = (float*)dalloc((size_t)(ffn > dm ? ffn : dm) * 4);
+    if (m->zero_bias && hipMemsetAsync(m->zero_bias, 0, (size_t)(ffn > dm ? ffn : dm) * 4, 0) != hipSuccess)
+        st = fail(c, SGPT_ERR_HIP, "memset zero_bias");
+    m->L.resize(d->n_layers);
+    // HF state-dict names
+    //   GPT-Neo h.N.attn.attention.{q,k,v,out}_proj / mlp.c_fc / mlp.c_proj          (HF:gpt_neo:84-87,302-303)
+    //   GPT-J   h.N.attn.{q,k,v,out}_proj (no biases) / mlp.fc_in / mlp.fc_out          (HF:gptj:98-101,368-369)
+    //   BLOOM   h.N.self_attention.{query_key_value,dense} / mlp.dense_h_to_4h / mlp.dense_4h_to_h,
+    //           input_layernorm / post_attention_layernorm                               (HF:bloom:197-198,320-322,351-354)
+    const std::string attn = gptj ? "attn." : "attn.attention.";
+    const std::string fc1 = bloom ? "mlp.dense_h_to_4h" : (gptj ? "mlp.fc_in" : "mlp.c_fc");
+    const std::string fc2 = bloom ? "mlp.dense_4h_to_h" : (gptj ? "mlp.fc_out" : "mlp.c_proj");
+    const std::string ln1 = bloom ? "input_layernorm" : "ln_1", ln2 = bloom ? "post_attention_layernorm" : "ln_2";
+    float* stage = nullptr;   // BLOOM: fp32 staging for the de-interleaved fused QKV weight
+    if (bloom) stage = (float*)dalloc((size_t)3 * dm * dm * 4);
+    for (int i = 0; i < d->n_layers && st == SGPT_OK; ++i) {
+        const std::string p = "h." + std::to_string(i) + ".";
+        LayerW& l = m->L[i];
+        l.is_local = (gptj || bloom) ? 0 : (d->layer_is_local ? d->layer_is_local[i] : (i & 1));
+        copy_ln(p + ln1, &l.ln1_g, &l.ln1_b);
+        if (!gptj) copy_ln(p + ln2, &l.ln2_g, &l.ln2_b);
+        else l.ln2_g = l.ln2_b = nullptr;
+        if (gptj) l.b_o = m->zero_bias;
+        else l.b_o = copy_f32(p + (bloom ? std::string("self_attention.dense.bias") : attn + "out_proj.bias"), dm);
+        l.b_fc = copy_f32(p + fc1 + ".bias", ffn);
+        l.b_proj = copy_f32(p + fc2 + ".bias", dm);
+        l.w_qkv = dalloc((size_t)3 * dm * dm * esz);
+        l.w_o = dalloc((size_t)dm * dm * esz);
+        l.w_fc = dalloc((size_t)ffn * dm * esz);
+        l.w_proj = dalloc((size_t)dm * ffn * esz);
+        if (fp8) {
+            l.s_qkv = (float*)dalloc((size_t)3 * dm * 4); l.s_o = (float*)dalloc((size_t)dm * 4);
+            l.s_fc = (float*)dalloc((size_t)ffn * 4); l.s_proj = (float*)dalloc((size_t)dm * 4);
+        }
+        if (st != SGPT_OK) break;
+        const bool split_all = m->d.split_weights != 0;
+        const bool split = m->d.qk_split != 0 || split_all;
+        if (split) { l.w_qkv3 = dalloc((size_t)(split_all ? 3 : 2) * dm * 3 * dm * 2); if (!l.w_qkv3) break; }
+        if (split_all) {
+            l.w_o3 = dalloc((size_t)dm * 3 * dm * 2); l.w_fc3 = dalloc((size_t)ffn * 3 * dm * 2); l.w_proj3 = dalloc((size_t)dm * 3 * ffn * 2);
+            if (!l.w_o3 || !l.w_fc3 || !l.w_proj3) break;
+        }
+        const int dt16 = f16 ? DT_F16 : DT_BF16;
+        auto pack3 = [&](const std::string& name, int64_t rows, int64_t cols, void* dst3) {
+            const float* src = find(name, rows * cols);
+            if (src) launch_pack_split_rows(src, rows, cols, dst3, dt16, 0);
+        };
+        if (bloom) {
+            const float* wq = find(p + "self_attention.query_key_value.weight", (int64_t)3 * dm * dm);
+            const float* bq = find(p + "self_attention.query_key_value.bias", (int64_t)3 * dm);
+            l.b_qkv = (float*)dalloc((size_t)3 * dm * 4);
+            if (!wq || !bq || !l.b_qkv || !stage) break;
+            launch_qkv_deinterleave(wq, stage, H, dh, dm, 0);          // rows [h,3,dh] -> [q | k | v]
+            launch_qkv_deinterleave(bq, l.b_qkv, H, dh, 1, 0);
+            pack_rows(stage, (int64_t)3 * dm, dm, l.w_qkv, 0, l.s_qkv);
+            if (split) launch_pack_split_rows(stage, (long)(split_all ? 3 : 2) * dm, dm, l.w_qkv3, dt16, 0);      // q and k (and v) rows
+            pack_w(p + "self_attention.dense.weight", dm, dm, l.w_o, 0, l.s_o);
+            if (split_all) pack3(p + "self_attention.dense.weight", dm, dm, l.w_o3);
+        } else {
+            if (split) {
+                const float* wq = find(p + attn + "q_proj.weight", (int64_t)dm * dm);
+                const float* wk = find(p + attn + "k_proj.weight", (int64_t)dm * dm);
+                if (!wq || !wk) break;
+                launch_pack_split_rows(wq, dm, dm, l.w_qkv3, dt16, 0);
+                launch_pack_split_rows(wk, dm, dm, (bf16_t*)l.w_qkv3 + (size_t)dm * 3 * dm, dt16, 0);
+                if (split_all) pack3(p + attn + "v_proj.weight", dm, dm, (bf16_t*)l.w_qkv3 + (size_t)2 * dm * 3 * dm);
+            }
+            pack_w(p + attn + "q_proj.weight", dm, dm, l.w_qkv, 0, l.s_qkv);
+            pack_w(p + attn + "k_proj.weight", dm, dm, l.w_qkv, dm, l.s_qkv);
+            pack_w(p + attn + "v_proj.weight", dm, dm, l.w_qkv, (int64_t)2 * dm, l.s_qkv);
+            pack_w(p + attn + "out_proj.weight", dm, dm, l.w_o, 0, l.s_o);
+            if (split_all) pack3(p + attn + "out_proj.weight", dm, dm, l.w_o3);
+        }
+        pack_w(p + fc1 + ".weight", ffn, dm, l.w_fc, 0, l.s_fc);
+        pack_w(p + fc2 + ".weight", dm, ffn, l.w_proj, 0, l.s_proj);
+        if (split_all) { pack3(p + fc1 + ".weight", ffn, dm, l.w_fc3); pack3(p + fc2 + ".weight", dm, ffn, l.w_proj3); }
+    }
+    if (fp8 && st == SGPT_OK) {
+        m->dq[0] = dalloc((size_t)3 * dm * dm * 2); m->dq[1] = dalloc((size_t)dm * dm * 2);
+        m->dq[2] = dalloc((size_t)ffn * dm * 2); m->dq[3] = dalloc((size_t)dm * ffn * 2);
+    }
+    if (d->compute_dtype == SGPT_FP8M && st == SGPT_OK) {
+        m->act_scale.assign(2 * (size_t)d->n_layers, 0.0f);   // 0 = not calibrated
+        m->h_amax = (unsigned*)dalloc((size_t)d->n_layers * 8);
+        if (m->h_amax && hipMemsetAsync(m->h_amax, 0, (size_t)d->n_layers * 8, 0) != hipSuccess) st = fail(c, SGPT_ERR_HIP, "memset");
+    }
+    m->shift.assign((size_t)d->n_layers * RS_N, 0);
+    m->ln_floor.assign((size_t)d->n_layers, 0);
+    m->prec.assign((size_t)d->n_layers * PC_N, 0);
+    m->split_all = d->split_weights != 0;
+    m->qkv3_rows = d->split_weights != 0 ? 3 : (d->qk_split != 0 ? 2 : 0);
+    if (d->qk_split != 0)              // the round-3 switch: the Q / K projection of every block contracts over hi + lo pairs
+        for (int i = 0; i < d->n_layers; ++i) m->prec[(size_t)i * PC_N + PC_LN1] = 1;
+    if (st == SGPT_OK && bf && !fp8) {
+        m->crest_dev = (unsigned*)dalloc((size_t)d->n_layers * RS_N * 4);
+        if (m->crest_dev && hipMemsetAsync(m->crest_dev, 0, (size_t)d->n_layers * RS_N * 4, 0) != hipSuccess) st = fail(c, SGPT_ERR_HIP, "memset");
+    }
+    if (st == SGPT_OK) {
+        m->range_dev = (unsigned*)dalloc((size_t)(1 + d->n_layers * RS_N) * 4);
+        if (m->range_dev && hipMemsetAsync(m->range_dev, 0, (size_t)(1 + d->n_layers * RS_N) * 4, 0) != hipSuccess) st = fail(c, SGPT_ERR_HIP, "memset");
+    }
+    if (st == SGPT_OK && hipDeviceSynchronize() != hipSuccess) st = fail(c, SGPT_ERR_HIP, "sync after weight pack");
+    if (f16) {
+        // f16 has 5 exponent bits.  A LayerNorm output is bounded by max|gamma| * sqrt(d) + max|beta| (|x_hat| <= sqrt(d-1)):
+        // when that bound can leave the format the LayerNorm outputs are stored under a power-of-two down-shift that the
+        // consuming GEMMs undo on their fp32 accumulators (exact; shift[] above).  Activations behind the GEMMs are
+        // range-checked on the device at run time (RangeTrack in the store epilogues -> sgpt_model_range_check /
+        // sgpt_model_range_adapt).  Only a weight outside the format is refused.
+        unsigned h[4] = {0, 0, 0, 0};
+        if (st == SGPT_OK && hipMemcpy(h, stats, 12, hipMemcpyDeviceToHost) != hipSuccess) st = fail(c, SGPT_ERR_HIP, "range audit");
+        (void)hipFree(stats);
+        float wmax, gmax, bmax;
+        memcpy(&wmax, &h[0], 4); memcpy(&gmax, &h[1], 4); memcpy(&bmax, &h[2], 4);
+        const float bound = gmax * sqrtf((float)dm) + bmax;
+        if (st == SGPT_OK && (!(wmax < 65504.f) || !std::isfinite(bound)))
+            st = fail(c, SGPT_ERR_RANGE, "SGPT_F16: a matmul weight exceeds the f16 range (or a LayerNorm parameter is not finite); load with SGPT_BF16");
+        if (st == SGPT_OK && !(bound < 32768.f)) {
+            int k = (int)std::ceil(std::log2(bound / 16384.f));
+            k = k < 1 ? 1 : k;
+            if (k > RS_MAX_SHIFT) st = fail(c, SGPT_ERR_RANGE, "SGPT_F16: LayerNorm parameters beyond any usable range shift; load with SGPT_BF16");
+            for (int i = 0; i < d->n_layers && st == SGPT_OK; ++i) {
+                m->shift[(size_t)i * RS_N + RS_LN1] = m->shift[(size_t)i * RS_N + RS_LN2] = k;
+                m->ln_floor[i] = k;
+            }
+        }
+    }
+    if (st != SGPT_OK) { sgpt_model_free(m); return st; }
+    *out = m;
+    return SGPT_OK;
+}
+
+void sgpt_model_free(sgpt_model* m) {
+    if (!m) return;
+    (void)hipSetDevice(m->ctx->device);
+    (void)hipDeviceSynchronize();
+    for (void* p : m->allocs) (void)hipFree(p);
+    delete m;
+}
+
+sgpt_status sgpt_model_set_pool_weights(sgpt_model* m, const float* w, int32_t n) {
+    if (!m) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    if (!w || n <= 0) return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_pool_weights: bad arguments");
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipDeviceSynchronize());      // an in-flight encode may still read the previous table
+    if (n > m->pool_w_n) {
+        float* p = nullptr;
+        if (hipMalloc((void**)&p, (size_t)n * 4) != hipSuccess) return fail(c, SGPT_ERR_OOM, "hipMalloc pool weights failed");
+        m->allocs.push_back(p);           // the old, smaller table is released with the model
+        m->pool_w = p;
+        c->generation++;                  // captured graphs still point at the old table
+    }
+    m->pool_w_n = n;
+    HIPC(c, hipMemcpy(m->pool_w, w, (size_t)n * 4, hipMemcpyDeviceToDevice));
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_model_calibrate_begin(sgpt_model* m) {
+    if (!m) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    if (m->d.compute_dtype != SGPT_FP8M) return fail(c, SGPT_ERR_INVALID, "calibration applies to SGPT_FP8M models");
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipDeviceSynchronize());
+    HIPC(c, hipMemset(m->h_amax, 0, (size_t)m->d.n_layers * 8));
+    m->calibrating = true;
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_model_calibrate_end(sgpt_model* m, float margin, float* scales_out) {
+    if (!m) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    if (m->d.compute_dtype != SGPT_FP8M || !m->calibrating) return fail(c, SGPT_ERR_INVALID, "sgpt_model_calibrate_end without _begin");
+    m->calibrating = false;
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipDeviceSynchronize());
+    const int ns = 2 * m->d.n_layers;
+    std::vector<float> amax(ns);
+    HIPC(c, hipMemcpy(amax.data(), m->h_amax, (size_t)ns * 4, hipMemcpyDeviceToHost));
+    if (!(margin >= 1.0f)) margin = 2.0f;
+    for (int i = 0; i < ns; ++i) {
+        // smallest power of two with margin * amax / scale <= 448 (head-room: later batches may exceed the sample's range;
+        // a saturated code raises bit 1 of the range flag)
+        const float need = amax[i] * margin / 448.0f;
+        float sc = 1.0f;
+        if (need > 0.f && std::isfinite(need)) sc = std::exp2(std::ceil(std::log2(need)));
+        m->act_scale[i] = sc;
+        if (scales_out) scales_out[i] = sc;
+    }
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_model_set_act_scales(sgpt_model* m, const float* scales, int32_t n) {
+    if (!m) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    if (m->d.compute_dtype != SGPT_FP8M || !scales || n != 2 * m->d.n_layers) return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_act_scales: needs 2 * n_layers scales");
+    for (int i = 0; i < n; ++i) {
+        int e = 0;
+        if (!(scales[i] > 0.f) || std::frexp(scales[i], &e) != 0.5f) return fail(c, SGPT_ERR_INVALID, "activation scales must be powers of two");
+        m->act_scale[i] = scales[i];
+    }
+    return SGPT_OK;
+}
+
+// ---- SGPT_F16 range guard, per model --------------------------------------------------------------------------------
+sgpt_status sgpt_model_range_check(sgpt_model* m, int32_t* flagged, int32_t reset, void* stream) {
+    if (!m || !flagged) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    HIPC(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    unsigned h = 0;
+    HIPC(c, hipMemcpyAsync(&h, m->range_dev, 4, hipMemcpyDeviceToHost, s));
+    HIPC(c, hipStreamSynchronize(s));
+    if (reset && h) HIPC(c, hipMemsetAsync(m->range_dev, 0, (size_t)(1 + m->d.n_layers * RS_N) * 4, s));
+    *flagged = (int32_t)h;
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_model_range_adapt(sgpt_model* m, int32_t* n_raised, void* stream) {
+    if (!m || !n_raised) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    *n_raised = 0;
+    if (m->d.compute_dtype != SGPT_F16) return fail(c, SGPT_ERR_INVALID, "sgpt_model_range_adapt applies to SGPT_F16 models");
+    HIPC(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int n = m->d.n_layers * RS_N;
+    std::vector<unsigned> h((size_t)n + 1);
+    HIPC(c, hipMemcpyAsync(h.data(), m->range_dev, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIPC(c, hipStreamSynchronize(s));
+    int raised = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!h[i + 1]) continue;
+        float amax;
+        memcpy(&amax, &h[i + 1], 4);
+        // the stored magnitude was amax >= RANGE_LIMIT: bring it to <= 16384 (a factor of two of head-room for later
+        // batches); infinite (the fp32 value itself overflowed f16 by an unknown factor): 8 binary orders per attempt
+        int need = std::isfinite(amax) ? (int)std::ceil(std::log2(amax / 16384.f)) : 8;
+        need = need < 1 ? 1 : need;
+        if (m->shift[i] + need > RS_MAX_SHIFT)
+            return fail(c, SGPT_ERR_RANGE, "SGPT_F16: an activation class needs a range shift beyond 2^40; load with SGPT_BF16");
+        m->shift[i] += need;
+        ++raised;
+    }
+    if (raised) {
+        HIPC(c, hipMemsetAsync(m->range_dev + 1, 0, (size_t)n * 4, s));
+        const unsigned keep = h[0] & ~1u;                 // bit 0 handled; fp8 saturation bits stay
+        HIPC(c, hipMemcpyAsync(m->range_dev, &keep, 4, hipMemcpyHostToDevice, s));
+        HIPC(c, hipStreamSynchronize(s));
+        c->generation++;                                  // captured graphs carry the old factors as kernel arguments
+    }
+    *n_raised = raised;
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_model_get_range_shifts(sgpt_model* m, int32_t* shifts, int32_t n) {
+    if (!m || !shifts || n != m->d.n_layers * RS_N) return m ? fail(m->ctx, SGPT_ERR_INVALID, "sgpt_model_get_range_shifts: n must be 4 * n_layers") : SGPT_ERR_INVALID;
+    for (int i = 0; i < n; ++i) shifts[i] = m->shift[i];
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_model_set_range_shifts(sgpt_model* m, const int32_t* shifts, int32_t n) {
+    if (!m) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    if (m->d.compute_dtype != SGPT_F16 || !shifts || n != m->d.n_layers * RS_N)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_range_shifts: SGPT_F16 models, n = 4 * n_layers");
+    for (int i = 0; i < n; ++i)
+        if (shifts[i] < 0 || shifts[i] > RS_MAX_SHIFT) return fail(c, SGPT_ERR_INVALID, "range shifts must lie in [0, 40]");
+    // the LayerNorm kernels have no run-time range tracker: their shifts may not go below the bound sgpt_model_load derived
+    // from THIS checkpoint's parameters (shifts pinned from another checkpoint would overflow to inf unnoticed)
+    for (int i = 0; i < n; ++i) {
+        const int cls = i % RS_N, blk = i / RS_N;
+        if ((cls == RS_LN1 || cls == RS_LN2) && shifts[i] < m->ln_floor[blk])
+            return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_range_shifts: a LayerNorm shift below the bound of this checkpoint's LayerNorm parameters (block " +
+                        std::to_string(blk) + ": at least " + std::to_string(m->ln_floor[blk]) + ")");
+    }
+    for (int i = 0; i < n; ++i) m->shift[i] = shifts[i];
+    c->generation++;
+    return SGPT_OK;
+}
+
+// ---- precision plan: split-precision (hi + lo) operand classes per block ----------------------------------------------
+sgpt_status sgpt_model_set_precision(sgpt_model* m, const int32_t* plan, int32_t n) {
+    if (!m) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    const int cd = m->d.compute_dtype;
+    if (!plan || n != m->d.n_layers * PC_N) return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision: n must be 5 * n_layers");
+    const int dh = m->d.d_model / m->d.n_heads;
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        const int cls = i % PC_N, v = plan[i];
+        if (v < 0 || v > (cls == PC_LN1 ? 3 : 1)) return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision: entries are 0 | 1 (LayerNorm-1 class: 0 ... 3)");
+        any |= v != 0;
+        const bool legacy_ok = cls == PC_LN1 && (v == 1 || v == 3 || (v == 2 && m->qkv3_rows == 3)) && m->L[i / PC_N].w_qkv3 != nullptr;
+        if (v != 0 && cls != PC_ATT && !m->split_all && !legacy_ok)      // (the attention class splits activations only)
+            return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision: the model was loaded without split weight copies (sgpt_model_desc.split_weights)");
+        if (cls == PC_ATT && v != 0 && (m->d.arch == SGPT_ARCH_GPTJ || !attn_x3_supported(dh)))
+            return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision: split-precision attention needs head_dim 64 or 128 and no rotary embedding (GPT-Neo / BLOOM)");
+        if (cls == PC_LN2 && m->d.arch == SGPT_ARCH_GPTJ && v != 0 && plan[i - PC_LN2 + PC_LN1] == 0)
+            return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision: GPT-J's MLP reads ln_1's output: a split fc1 needs a split LayerNorm-1 entry");
+    }
+    if (any && cd != SGPT_F16 && cd != SGPT_BF16) return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision applies to SGPT_F16 / SGPT_BF16 models");
+    for (int i = 0; i < n; ++i) m->prec[i] = plan[i];
+    c->generation++;                                      // captured graphs carry the old launch sequence
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_model_get_precision(sgpt_model* m, int32_t* plan, int32_t n) {
+    if (!m || !plan || n != m->d.n_layers * PC_N) return m ? fail(m->ctx, SGPT_ERR_INVALID, "sgpt_model_get_precision: n must be 5 * n_layers") : SGPT_ERR_INVALID;
+    for (int i = 0; i < n; ++i) plan[i] = m->prec[i];
+    return SGPT_OK;
+}
+
+// The [W_hi | W_hi | W_lo] copies of sgpt_model_desc.split_weights are 3 x the 16-bit weight bytes on top of the plain copy
+// (+35 GB at GPT-J-6B shape).  A model whose probe settled on plain operands gives them back here; a later plan
+// that needs them is refused by sgpt_model_set_precision as for a model loaded without them.  The round-3 qk_split copies
+// (q and k rows) stay when a plan entry still reads them.
+sgpt_status sgpt_model_release_split_weights(sgpt_model* m, int64_t* bytes_freed) {
+    if (!m) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    if (bytes_freed) *bytes_freed = 0;
+    if (!m->split_all) return SGPT_OK;
+    bool qk_used = false;
+    for (int i = 0; i < m->d.n_layers; ++i)
+        for (int cls = 0; cls < PC_N; ++cls) {
+            const int v = m->prec[(size_t)i * PC_N + cls];
+            if (v == 0 || cls == PC_ATT) continue;
+            if (cls == PC_LN1) { qk_used = true; continue; }            // any LayerNorm-1 level reads w_qkv3 (level 2: its V rows too): kept whole
+            return fail(c, SGPT_ERR_INVALID, "sgpt_model_release_split_weights: the installed precision plan reads the split copies");
+        }
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipDeviceSynchronize());
+    const size_t dm = m->d.d_model, ffn = m->d.d_ffn;
+    int64_t freed = 0;
+    auto drop = [&](void*& p, size_t bytes) {
+        if (!p) return;
+        for (size_t i = 0; i < m->allocs.size(); ++i)
+            if (m->allocs[i] == p) { m->allocs[i] = m->allocs.back(); m->allocs.pop_back(); break; }
+        (void)hipFree(p);
+        p = nullptr;
+        freed += (int64_t)bytes;
+    };
+    for (int i = 0; i < m->d.n_layers; ++i) {
+        LayerW& l = m->L[i];
+        drop(l.w_o3, dm * 3 * dm * 2); drop(l.w_fc3, ffn * 3 * dm * 2); drop(l.w_proj3, dm * 3 * ffn * 2);
+        if (!qk_used) drop(l.w_qkv3, 3 * dm * 3 * dm * 2);
+    }
+    if (!qk_used) m->qkv3_rows = 0;
+    m->split_all = false;
+    c->generation++;
+    if (bytes_freed) *bytes_freed = freed;
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_model_precision_probe_begin(sgpt_model* m) {
+    if (!m) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    if (!m->crest_dev) return fail(c, SGPT_ERR_INVALID, "the precision probe applies to SGPT_F16 / SGPT_BF16 models");
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipDeviceSynchronize());
+    HIPC(c, hipMemset(m->crest_dev, 0, (size_t)m->d.n_layers * RS_N * 4));
+    m->probing = true;
+    c->generation++;                                      // a graph captured while probing must not outlive the probe
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_model_precision_probe_end(sgpt_model* m, float* crest_out) {
+    if (!m) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    if (!m->probing) return fail(c, SGPT_ERR_INVALID, "sgpt_model_precision_probe_end without _begin");
+    m->probing = false;
+    c->generation++;
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipDeviceSynchronize());
+    if (crest_out) HIPC(c, hipMemcpy(crest_out, m->crest_dev, (size_t)m->d.n_layers * RS_N * 4, hipMemcpyDeviceToHost));
+    return SGPT_OK;
+}
+
+}  // extern "C"
