@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 11
+#define SGPT_ABI_VERSION 12
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -595,6 +595,51 @@ sgpt_status sgpt_attention(sgpt_ctx* ctx, int32_t dtype, const void* q, const vo
                            int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
                            float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
                            int64_t ctx_lo_delta, int64_t ctx_hi2_delta, void* stream);
+
+/* The encoder's row kernels, stand-alone (ABI v12; kernel-level tests: tests/test_gpu_rowops.py compares each with a float64
+ * restatement of the same operation).  These are the launches sgpt_encode / sgpt_lm_logprobs make between their GEMMs, on
+ * caller-owned device buffers.  Every entry returns SGPT_ERR_INVALID, with nothing launched, for a null pointer, a row width
+ * the kernels do not serve or an enum outside its range.  Indices the kernels read from device memory (ids, pos, targets) are
+ * clamped into their tables: a bad index gives the result of the nearest valid one, never an out-of-bounds read.
+ *
+ * sgpt_embed: out fp32[T, d] = wte[ids[t]] + wpe[pos[t]] -- `inputs_embeds + position_embeds`, HF:gpt_neo/modeling_gpt_neo.py:444,
+ *   462-463; wpe NULL = the token rows alone (GPT-J, HF:gptj/modeling_gptj.py:484; BLOOM).  d % 4 == 0; ids clamped into
+ *   [0, vocab), pos into [0, max_pos).
+ * sgpt_layernorm: nn.LayerNorm(eps) over rows of x fp32[T, d] (HF:gpt_neo:317-319,385,492), d % 4 == 0, d <= 4096.
+ *   out_dtype SGPT_F32 | SGPT_BF16 | SGPT_F16: out [T, d], the normalised row rounded once (RNE) to the format.  out_mul: a
+ *   positive power of two that multiplies an SGPT_F16 output before the rounding (the range shift of sgpt_model_desc
+ *   .compute_dtype SGPT_F16); 1 for the other formats.  split = 1 (16-bit only): out [T, 3 d] = [hi | lo | hi] with
+ *   hi = round16(v), lo = round16(v - hi), v = out_mul * LayerNorm(x) -- the operand of the split-precision projections
+ *   (sgpt_model_desc.qk_split).  out may alias x for SGPT_F32 (BLOOM's embedding LayerNorm, HF:bloom/modeling_bloom.py:499).
+ * sgpt_lnf_pool: the final LayerNorm fused with the pooling of a packed batch (layout of sgpt_encode: sequence i holds rows
+ *   [seq_off[i], seq_off[i] + seq_len[i]) of x fp32[T_pad, d]; rows outside are never read).  apply_ln: ln_f (HF:gpt_neo:492)
+ *   on every row first.  mode SGPT_POOL_*: weightedmean sum_t (P + t + 1) h_t / max(sum_t (P + t + 1), 1e-9) with P =
+ *   pad_left[i] (NULL = 0; weights follow the PADDED index, Pooling.py:99-125, beir_dense_retriever.py:258-270), mean
+ *   (Pooling.py:117-125), lasttoken (row seq_len - 1, beir_dense_retriever.py:271-282), learntmean w_t = pos_weights[min(P + t,
+ *   n_weights - 1)] (WeightedMeanPooling.py:21-39).  normalize: x / max(||x||, 1e-12) (SentenceTransformer.py:248-249).
+ *   out fp32[B, d]; a sequence of length 0 gives a zero row.  nonfinite_flag (or NULL): device word, bit 0 is OR-ed in when a
+ *   pooled row holds NaN / inf.  pad_left entries are >= 0 (the caller's contract).
+ * sgpt_rope: GPT-J rotary embedding in place (HF:gptj/modeling_gptj.py:57-67,190-210): for every row t < T, head h < H and pair
+ *   i < rotary_dim / 2, (x[2i], x[2i+1]) <- (x[2i] c - x[2i+1] s, x[2i+1] c + x[2i] s) with s, c = sin / cos[pos[t]][i] (tables fp32
+ *   [max_pos, rotary_dim / 2], create_sinusoidal_positions :47-50), on the columns h * head_dim + 2i of q (column 0) and k (column
+ *   k_off) of buf [T, ld] (dtype SGPT_F32 | SGPT_BF16 | SGPT_F16; 16-bit results rounded once).  Columns >= rotary_dim of a head
+ *   and everything outside the q / k blocks are not touched.  rotary_dim even, <= head_dim; head_dim, ld, k_off even;
+ *   k_off >= H * head_dim; ld >= k_off + H * head_dim.  pos clamped into [0, max_pos).
+ * sgpt_logprob_rows: out_logprob[r] = log_softmax(logits[r, :V])[targets[r]], out_greedy[r] (or NULL) = argmax, first maximum
+ *   (F.log_softmax + torch.gather + argmax, crossencoder/beir/sgptce.py:233,243,255); logits fp32 [n, ld], ld >= V, columns
+ *   [V, ld) are never read.  targets clamped into [0, V). */
+sgpt_status sgpt_embed(sgpt_ctx* ctx, const int32_t* ids, const int32_t* pos, const float* wte, const float* wpe, int32_t T,
+                       int32_t d, int32_t vocab, int32_t max_pos, float* out, void* stream);
+sgpt_status sgpt_layernorm(sgpt_ctx* ctx, const float* x, const float* gamma, const float* beta, int32_t T, int32_t d, float eps,
+                           void* out, int32_t out_dtype, float out_mul, int32_t split, void* stream);
+sgpt_status sgpt_lnf_pool(sgpt_ctx* ctx, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
+                          const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
+                          int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,
+                          int32_t* nonfinite_flag, void* stream);
+sgpt_status sgpt_rope(sgpt_ctx* ctx, void* buf, int32_t dtype, int64_t ld, int64_t k_off, const int32_t* pos, const float* sin,
+                      const float* cos, int32_t T, int32_t H, int32_t head_dim, int32_t rotary_dim, int32_t max_pos, void* stream);
+sgpt_status sgpt_logprob_rows(sgpt_ctx* ctx, const float* logits, int64_t ld, int32_t V, const int32_t* targets, int32_t n,
+                              float* out_logprob, int32_t* out_greedy, void* stream);
 
 /* The fp8-MFMA building blocks of SGPT_FP8M, stand-alone (kernel-level tests, custom blocks).
  * sgpt_layernorm_fp8: nn.LayerNorm(x)[T,d] -> e4m3fn codes + one power-of-two scale per row (true value = code * scale).

@@ -403,7 +403,7 @@ void launch_absmax(const float* in, long numel, unsigned* out_bits, hipStream_t 
 void launch_fill_f32(float* p, long n, float v, hipStream_t s);
 // GPT-J rotary embedding, in place on the q / k columns of the projection buffer
 void launch_rope(void* qk, int dtype, long ld, long k_off, const int* pos, const float* sin_t, const float* cos_t, int T,
-                 int H, int dh, int rotary_dim, hipStream_t s);
+                 int H, int dh, int rotary_dim, int max_pos, hipStream_t s);
 // BLOOM fused QKV rows [n_head, 3, head_dim] -> [q rows | k rows | v rows] (row_len floats per row; 1 for the bias)
 void launch_qkv_deinterleave(const float* src, float* dst, int H, int dh, long row_len, hipStream_t s);
 void launch_fill_rand(void* p, long n, int dtype, unsigned seed, float scale, hipStream_t s);

@@ -328,14 +328,16 @@ __global__ __launch_bounds__(256) void pairwise_kernel(const float* __restrict__
 template <typename T>
 __global__ __launch_bounds__(256) void rope_kernel(T* __restrict__ buf, long ld, long k_off, const int* __restrict__ pos,
                                                    const float* __restrict__ sin_t, const float* __restrict__ cos_t,
-                                                   int Tn, int H, int dh, int half) {
+                                                   int Tn, int H, int dh, int half, int max_pos) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     const long per_tok = (long)H * half;
     if (idx >= (long)Tn * per_tok) return;
     const int tkn = (int)(idx / per_tok);
     const int rem = (int)(idx - (long)tkn * per_tok);
     const int h = rem / half, i = rem - h * half;
-    const float sn = sin_t[(long)pos[tkn] * half + i], cs = cos_t[(long)pos[tkn] * half + i];
+    // the position is clamped into the tables, as embed_kernel does: a C-ABI caller's bad position reads a wrong row, never out of bounds
+    int ps = pos[tkn]; ps = ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps);
+    const float sn = sin_t[(long)ps * half + i], cs = cos_t[(long)ps * half + i];
     T* q = buf + (long)tkn * ld + (long)h * dh + 2 * i;
 #pragma unroll
     for (int which = 0; which < 2; ++which) {
@@ -499,7 +501,9 @@ __global__ __launch_bounds__(256) void logprob_rows_kernel(const float* __restri
     __syncthreads();
     if (t == 0) {
         const float tot = (s_f[0] + s_f[1]) + (s_f[2] + s_f[3]);
-        out_lp[r] = (x[targets[r]] - mx) - logf(tot);
+        // the target is clamped into the row, as embed_kernel does its ids: a bad target scores a wrong token, never out of bounds
+        int tg = targets[r]; tg = tg < 0 ? 0 : (tg >= V ? V - 1 : tg);
+        out_lp[r] = (x[tg] - mx) - logf(tot);
         if (out_arg) out_arg[r] = am;
     }
 }
@@ -758,16 +762,16 @@ void launch_fill_rand(void* p, long n, int dtype, unsigned seed, float scale, hi
 }
 
 void launch_rope(void* qk, int dtype, long ld, long k_off, const int* pos, const float* sin_t, const float* cos_t, int T,
-                 int H, int dh, int rotary_dim, hipStream_t s) {
+                 int H, int dh, int rotary_dim, int max_pos, hipStream_t s) {
     const int half = rotary_dim / 2;
     const long n = (long)T * H * half;
     const int grid = (int)((n + 255) / 256);
     if (dtype == DT_BF16)
-        hipLaunchKernelGGL(rope_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (bf16_t*)qk, ld, k_off, pos, sin_t, cos_t, T, H, dh, half);
+        hipLaunchKernelGGL(rope_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (bf16_t*)qk, ld, k_off, pos, sin_t, cos_t, T, H, dh, half, max_pos);
     else if (dtype == DT_F16)
-        hipLaunchKernelGGL(rope_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (f16_t*)qk, ld, k_off, pos, sin_t, cos_t, T, H, dh, half);
+        hipLaunchKernelGGL(rope_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (f16_t*)qk, ld, k_off, pos, sin_t, cos_t, T, H, dh, half, max_pos);
     else
-        hipLaunchKernelGGL(rope_kernel<float>, dim3(grid), dim3(256), 0, s, (float*)qk, ld, k_off, pos, sin_t, cos_t, T, H, dh, half);
+        hipLaunchKernelGGL(rope_kernel<float>, dim3(grid), dim3(256), 0, s, (float*)qk, ld, k_off, pos, sin_t, cos_t, T, H, dh, half, max_pos);
 }
 
 void launch_qkv_deinterleave(const float* src, float* dst, int H, int dh, long row_len, hipStream_t s) {

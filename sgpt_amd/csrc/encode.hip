@@ -56,7 +56,7 @@ void block_f32(const Fwd& f, const LayerW& l) {
     const bool gptj = d.arch == SGPT_ARCH_GPTJ;
     launch_layernorm(f.x, l.ln1_g, l.ln1_b, f.a, SGPT_F32, T, dm, d.ln_eps, f.s);
     gemm(f.c, SGPT_F32, EPI_STORE, SGPT_F32, proj(f, f.a, dm, l.w_qkv, 3 * dm, dm, f.qkv, 3 * dm, l.b_qkv), f.s);
-    if (gptj) launch_rope(f.qkv, SGPT_F32, 3 * dm, dm, f.pos, f.m->rot_sin, f.m->rot_cos, T, d.n_heads, dm / d.n_heads, d.rotary_dim, f.s);
+    if (gptj) launch_rope(f.qkv, SGPT_F32, 3 * dm, dm, f.pos, f.m->rot_sin, f.m->rot_cos, T, d.n_heads, dm / d.n_heads, d.rotary_dim, d.max_pos, f.s);
     launch_attn_f32(attn_base(f, l, 0), f.s);
     gemm(f.c, SGPT_F32, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dm, l.w_o, dm, dm, f.x, dm, l.b_o, f.x), f.s);   // x += ctx . Wo^T (+ bo)
     // GPT-Neo: x += MLP(LN2(x));  GPT-J (parallel block, HF:gptj:400-411): x += MLP(LN1(x_old)), `a` still holds it
@@ -80,7 +80,7 @@ void block_fp8(const Fwd& f, const LayerW& l, int li) {
     GemmArgs v = proj(f, f.a8, dm, (const uint8_t*)l.w_qkv + (size_t)2 * dm * dm, dm, dm, f.vt, T, l.b_qkv ? l.b_qkv + 2 * dm : nullptr);
     v.a_scale = f.sa; v.a_scalar = 1.0f; v.w_scale = l.s_qkv + 2 * dm;
     launch(EPI_VT, f.dt, v);
-    if (gptj) launch_rope(f.qkv, f.dt, 2 * dm, dm, f.pos, f.m->rot_sin, f.m->rot_cos, T, d.n_heads, dm / d.n_heads, d.rotary_dim, f.s);
+    if (gptj) launch_rope(f.qkv, f.dt, 2 * dm, dm, f.pos, f.m->rot_sin, f.m->rot_cos, T, d.n_heads, dm / d.n_heads, d.rotary_dim, d.max_pos, f.s);
     AttnArgs at = attn_base(f, l, 0);
     at.out_fp8 = 1; at.out_scale = s_c; at.range_flag = f.range_flag;
     launch_attn_bf16(at, f.s);                         // context as e4m3 codes of ctx / s_c, [T][dm] bytes
@@ -167,7 +167,7 @@ sgpt_status block_16(const Fwd& f, const LayerW& l, int li) {
             gemm(c, dt, EPI_VT, dt, v, s);
         }
     }
-    if (gptj) launch_rope(f.qkv, dt, 2 * dm, dm, f.pos, m->rot_sin, m->rot_cos, T, m->d.n_heads, dm / m->d.n_heads, m->d.rotary_dim, s);
+    if (gptj) launch_rope(f.qkv, dt, 2 * dm, dm, f.pos, m->rot_sin, m->rot_cos, T, m->d.n_heads, dm / m->d.n_heads, m->d.rotary_dim, m->d.max_pos, s);
     AttnArgs at = attn_base(f, l, k_qkv);
     at.x3 = p_att ? 1 : 0; at.qk_lo_delta = f.att_lo; at.v_lo_delta = f.att_lo;
     at.ldo = ldc; at.ctx_lo_delta = p_ctx ? dm : 0; at.ctx_hi2_delta = p_ctx ? 2 * dm : 0;

@@ -235,6 +235,91 @@ sgpt_status sgpt_attention(sgpt_ctx* c, int32_t dtype, const void* q, const void
     return SGPT_OK;
 }
 
+// ---- the encoder's row kernels stand-alone (elementwise.hip; tests/test_gpu_rowops.py): every argument a launch would index or
+// dispatch on is checked here, nothing is launched on a refusal ----
+static bool row_width_ok(int32_t d) { return d > 0 && d % 4 == 0 && d <= 4096; }   // RowLN: float4 per lane, NV <= 16
+static bool mis(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1)) != 0; }  // rows move as float4 / uint2 words
+
+sgpt_status sgpt_embed(sgpt_ctx* c, const int32_t* ids, const int32_t* pos, const float* wte, const float* wpe, int32_t T,
+                       int32_t d, int32_t vocab, int32_t max_pos, float* out, void* stream) {
+    if (!c || !ids || !wte || !out || T <= 0 || d <= 0 || d % 4 || vocab <= 0)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_embed: bad arguments (d % 4 == 0 required)");
+    if (wpe && (!pos || max_pos <= 0)) return fail(c, SGPT_ERR_INVALID, "sgpt_embed: a position table needs pos and max_pos > 0");
+    if (mis(wte, 16) || mis(wpe, 16) || mis(out, 16)) return fail(c, SGPT_ERR_INVALID, "sgpt_embed: 16-byte aligned tables and output");
+    HIPC(c, hipSetDevice(c->device));
+    launch_embed(ids, pos, wte, wpe, out, T, d, vocab, max_pos, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_layernorm(sgpt_ctx* c, const float* x, const float* gamma, const float* beta, int32_t T, int32_t d, float eps,
+                           void* out, int32_t out_dtype, float out_mul, int32_t split, void* stream) {
+    if (!c || !x || !gamma || !beta || !out || T <= 0 || !row_width_ok(d) || !(eps >= 0.f) || !std::isfinite(eps))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_layernorm: bad arguments (d % 4 == 0, d <= 4096)");
+    const bool o16 = out_dtype == SGPT_BF16 || out_dtype == SGPT_F16;
+    if (!o16 && out_dtype != SGPT_F32) return fail(c, SGPT_ERR_INVALID, "sgpt_layernorm: out_dtype SGPT_F32 | SGPT_BF16 | SGPT_F16");
+    int e = 0;
+    if (!(out_mul > 0.f) || !std::isfinite(out_mul) || std::frexp(out_mul, &e) != 0.5f)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_layernorm: out_mul must be a positive power of two");
+    if (out_mul != 1.0f && out_dtype != SGPT_F16) return fail(c, SGPT_ERR_INVALID, "sgpt_layernorm: out_mul != 1 is the range shift of an f16 output");
+    if (split != 0 && split != 1) return fail(c, SGPT_ERR_INVALID, "sgpt_layernorm: split 0 | 1");
+    if (split && !o16) return fail(c, SGPT_ERR_INVALID, "sgpt_layernorm: the [hi | lo | hi] split output is 16-bit");
+    if ((const void*)out == (const void*)x && (o16 || split)) return fail(c, SGPT_ERR_INVALID, "sgpt_layernorm: in place is fp32 only");
+    if (mis(x, 16) || mis(gamma, 16) || mis(beta, 16) || mis(out, o16 ? 8 : 16))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_layernorm: 16-byte aligned x / gamma / beta / fp32 out, 8-byte aligned 16-bit out");
+    HIPC(c, hipSetDevice(c->device));
+    if (split) launch_layernorm_split(x, gamma, beta, out, out_dtype, T, d, eps, (hipStream_t)stream, out_mul);
+    else launch_layernorm(x, gamma, beta, out, out_dtype, T, d, eps, (hipStream_t)stream, out_mul);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_lnf_pool(sgpt_ctx* c, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
+                          const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
+                          int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,
+                          int32_t* nonfinite_flag, void* stream) {
+    if (!c || !x || !seq_off || !seq_len || !out || B <= 0 || !row_width_ok(d))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool: bad arguments (d % 4 == 0, d <= 4096)");
+    if (mode < SGPT_POOL_WEIGHTEDMEAN || mode > SGPT_POOL_LEARNTMEAN) return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool: mode 0 .. 3");
+    if (apply_ln && (!gamma || !beta || !(eps >= 0.f) || !std::isfinite(eps)))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool: apply_ln needs gamma, beta and eps >= 0");
+    if (mode == SGPT_POOL_LEARNTMEAN && (!pos_weights || n_weights <= 0))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool: learntmean needs pos_weights and n_weights > 0");
+    if (mis(x, 16) || mis(gamma, 16) || mis(beta, 16)) return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool: 16-byte aligned x / gamma / beta");
+    HIPC(c, hipSetDevice(c->device));
+    launch_lnf_pool(x, gamma, beta, seq_off, seq_len, pad_left, B, d, eps, apply_ln ? 1 : 0, mode, normalize ? 1 : 0, pos_weights,
+                    n_weights, out, (hipStream_t)stream, nonfinite_flag);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_rope(sgpt_ctx* c, void* buf, int32_t dtype, int64_t ld, int64_t k_off, const int32_t* pos, const float* sin_t,
+                      const float* cos_t, int32_t T, int32_t H, int32_t head_dim, int32_t rotary_dim, int32_t max_pos, void* stream) {
+    if (!c || !buf || !pos || !sin_t || !cos_t || T <= 0 || H <= 0 || head_dim <= 0 || max_pos <= 0)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_rope: bad arguments");
+    if (dtype != SGPT_F32 && dtype != SGPT_BF16 && dtype != SGPT_F16) return fail(c, SGPT_ERR_INVALID, "sgpt_rope: dtype SGPT_F32 | SGPT_BF16 | SGPT_F16");
+    if (rotary_dim <= 0 || rotary_dim % 2 || rotary_dim > head_dim)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_rope: rotary_dim even, in [2, head_dim]");
+    // a thread moves one (x[2i], x[2i+1]) pair as one 8- / 4-byte word; q [0, H dh) and k [k_off, k_off + H dh) of one row must not overlap
+    const int64_t dm = (int64_t)H * head_dim;
+    if (head_dim % 2 || ld % 2 || k_off % 2 || k_off < dm || ld < k_off + dm || ((uintptr_t)buf & (dtype == SGPT_F32 ? 7u : 3u)))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_rope: head_dim, ld, k_off even; k_off >= H * head_dim; ld >= k_off + H * head_dim; buf aligned to a pair");
+    HIPC(c, hipSetDevice(c->device));
+    launch_rope(buf, dtype, ld, k_off, pos, sin_t, cos_t, T, H, head_dim, rotary_dim, max_pos, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_logprob_rows(sgpt_ctx* c, const float* logits, int64_t ld, int32_t V, const int32_t* targets, int32_t n,
+                              float* out_logprob, int32_t* out_greedy, void* stream) {
+    if (!c || !logits || !targets || !out_logprob || n <= 0 || V <= 0 || ld < V)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_logprob_rows: bad arguments (ld >= V)");
+    HIPC(c, hipSetDevice(c->device));
+    launch_logprob_rows(logits, ld, V, targets, n, out_logprob, out_greedy, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
 sgpt_status sgpt_bench_gemm(sgpt_ctx* c, int32_t dtype, int32_t epi, int32_t out_dtype, int32_t M, int32_t N, int32_t K,
                             int32_t iters, float* ms_out) {
     if (!c || !ms_out || M <= 0 || N <= 0 || K <= 0 || iters <= 0) return fail(c, SGPT_ERR_INVALID, "sgpt_bench_gemm: bad arguments");

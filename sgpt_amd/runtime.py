@@ -293,6 +293,82 @@ class Context:
                                           v_lo_delta, ctx_lo_delta, ctx_hi2_delta, _stream_ptr(self.device)), "sgpt_attention")
         return out
 
+    # ---- the encoder's row kernels stand-alone (kernel-level tests): include/sgpt_hip.h::sgpt_embed ... sgpt_logprob_rows ----
+    # Tensors are taken as they are (device, dtype, unit column stride are the caller's): a test hands in views of larger
+    # buffers and over-allocated outputs, and a silent copy would hide what it set up.
+    def _f32c(self, t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        return None if t is None else t.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def embed(self, ids: torch.Tensor, pos: Optional[torch.Tensor], wte: torch.Tensor, wpe: Optional[torch.Tensor] = None,
+              vocab: Optional[int] = None, max_pos: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """out fp32 [T, d] = wte[ids] + wpe[pos] (wpe None: wte[ids]).  vocab / max_pos: the table sizes the kernel clamps
+        into (default: the tables' row counts)."""
+        T, d = ids.numel(), wte.shape[1]
+        if wte.stride() != (d, 1) or (wpe is not None and wpe.stride() != (d, 1)):
+            raise ValueError("embed: tables are row-contiguous [rows, d]")
+        if out is None:
+            out = torch.empty((T, d), dtype=torch.float32, device=self.device)
+        self._chk(self.lib.sgpt_embed(self.handle, _p(ids), _p(pos), _p(wte), _p(wpe), T, d,
+                                      wte.shape[0] if vocab is None else int(vocab),
+                                      (wpe.shape[0] if wpe is not None else 0) if max_pos is None else int(max_pos), _p(out),
+                                      _stream_ptr(self.device)), "sgpt_embed")
+        return out
+
+    def layernorm(self, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, out_dtype=torch.float32,
+                  out_mul: float = 1.0, split: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """nn.LayerNorm over the rows of x fp32 [T, d] -> [T, d] in out_dtype (f16: times out_mul), or with split=True the
+        [T, 3 d] = [hi | lo | hi] operand of the split-precision projections.  out: written in place of a new tensor (x itself
+        for fp32; a larger buffer keeps its rows past T)."""
+        T, d = x.shape
+        if out is None:
+            out = torch.empty((T, 3 * d if split else d), dtype=out_dtype, device=self.device)
+        self._chk(self.lib.sgpt_layernorm(self.handle, _p(x), _p(self._f32c(gamma)), _p(self._f32c(beta)), T, d, float(eps), _p(out),
+                                          DT_CODE[out_dtype], float(out_mul), 1 if split else 0, _stream_ptr(self.device)),
+                  "sgpt_layernorm")
+        return out
+
+    def lnf_pool(self, x: torch.Tensor, seq_off: torch.Tensor, seq_len: torch.Tensor, pad_left: Optional[torch.Tensor] = None,
+                 ln=None, mode: str = "weightedmean", normalize: bool = False, position_weights: Optional[torch.Tensor] = None,
+                 n_weights: Optional[int] = None, nonfinite_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The fused final LayerNorm + pooling of a packed batch (include/sgpt_hip.h::sgpt_lnf_pool): x fp32 [T_pad, d], int32
+        seq_off / seq_len / pad_left on the device; ln = (gamma, beta, eps) or None (pool x as it is) -> fp32 [B, d]."""
+        if mode not in POOL_MODES:
+            raise ValueError(f"unknown pooling mode {mode}")
+        B, d = seq_len.numel(), x.shape[1]
+        g, b, eps = (self._f32c(ln[0]), self._f32c(ln[1]), float(ln[2])) if ln is not None else (None, None, 0.0)
+        pw = self._f32c(position_weights)
+        n_w = (0 if pw is None else pw.numel()) if n_weights is None else int(n_weights)
+        out = torch.empty((B, d), dtype=torch.float32, device=self.device)
+        self._chk(self.lib.sgpt_lnf_pool(self.handle, _p(x), _p(g), _p(b), _p(seq_off), _p(seq_len), _p(pad_left), B, d, eps,
+                                         0 if ln is None else 1, POOL_MODES[mode], 1 if normalize else 0, _p(pw), n_w, _p(out),
+                                         _p(nonfinite_flag), _stream_ptr(self.device)), "sgpt_lnf_pool")
+        return out
+
+    def rope(self, buf: torch.Tensor, pos: torch.Tensor, sin: torch.Tensor, cos: torch.Tensor, H: int, head_dim: int,
+             rotary_dim: int, k_off: int, T: Optional[int] = None, max_pos: Optional[int] = None) -> torch.Tensor:
+        """GPT-J rotary embedding in place on q (column 0) and k (column k_off) of the first T rows of buf [rows, ld]; sin / cos
+        fp32 [max_pos, rotary_dim / 2] (include/sgpt_hip.h::sgpt_rope)."""
+        if buf.dtype not in DT_CODE or buf.stride(1) != 1:
+            raise ValueError("rope: buf is fp32, bf16 or f16 with a unit column stride")
+        if sin.stride() != (rotary_dim // 2, 1) or cos.stride() != (rotary_dim // 2, 1):
+            raise ValueError("rope: sin / cos are row-contiguous [max_pos, rotary_dim / 2]")
+        self._chk(self.lib.sgpt_rope(self.handle, _p(buf), DT_CODE[buf.dtype], buf.stride(0), int(k_off), _p(pos), _p(sin), _p(cos),
+                                     buf.shape[0] if T is None else int(T), H, head_dim, rotary_dim,
+                                     sin.shape[0] if max_pos is None else int(max_pos), _stream_ptr(self.device)), "sgpt_rope")
+        return buf
+
+    def logprob_rows(self, logits: torch.Tensor, targets: torch.Tensor, V: Optional[int] = None, greedy: bool = True):
+        """-> (log_softmax(logits[r, :V])[targets[r]] fp32 [n], argmax int32 [n] or None); logits fp32 [n, ld >= V] with a unit
+        column stride (include/sgpt_hip.h::sgpt_logprob_rows)."""
+        if logits.dtype != torch.float32 or logits.stride(1) != 1:
+            raise ValueError("logprob_rows: logits are fp32 rows with a unit column stride")
+        n = logits.shape[0]
+        lp = torch.empty((n,), dtype=torch.float32, device=self.device)
+        am = torch.empty((n,), dtype=torch.int32, device=self.device) if greedy else None
+        self._chk(self.lib.sgpt_logprob_rows(self.handle, _p(logits), logits.stride(0), logits.shape[1] if V is None else int(V),
+                                             _p(targets), n, _p(lp), _p(am), _stream_ptr(self.device)), "sgpt_logprob_rows")
+        return lp, am
+
     # ---- fp8-MFMA building blocks (dtype='fp8mfma'): quantising LayerNorm, e4m3 x e4m3 projection ----
     def layernorm_fp8(self, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5):
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
