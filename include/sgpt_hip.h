@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 12
+#define SGPT_ABI_VERSION 13
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -49,8 +49,24 @@ typedef struct sgpt_ctx sgpt_ctx;
 typedef struct sgpt_model sgpt_model;
 
 enum { SGPT_F32 = 0, SGPT_BF16 = 1, SGPT_FP8W = 2, SGPT_F16 = 3, SGPT_FP8M = 4 };   /* element types; FP8W / FP8M: model compute_dtype only */
-enum { SGPT_ARCH_GPTNEO = 0, SGPT_ARCH_GPTJ = 1, SGPT_ARCH_BLOOM = 2 };
-enum { SGPT_POOL_WEIGHTEDMEAN = 0, SGPT_POOL_MEAN = 1, SGPT_POOL_LASTTOKEN = 2, SGPT_POOL_LEARNTMEAN = 3 };
+enum { SGPT_ARCH_GPTNEO = 0, SGPT_ARCH_GPTJ = 1, SGPT_ARCH_BLOOM = 2, SGPT_ARCH_BERT = 3 };
+/* SGPT_ARCH_BERT (ABI v13): HF BertModel (HF:bert/modeling_bert.py) -- the baseline of the reference's own scripts
+ * (biencoder/beir/beir_dense_retriever.py:36 defaults --modelname to bert-base-uncased; :131-132 frame [CLS] ... [SEP]).
+ *   x = LN_emb(wte[id] + wpe'[pos]);  per layer: q | k | v = x W^T + b; ctx = softmax(q.k^T / sqrt(dh)) v over ALL keys of the
+ *   sequence (bidirectional: causality follows from the arch); x = LN(x + ctx Wo^T + bo); x = LN(x + gelu(x W1^T + b1) W2^T + b2)
+ *   with the erf GELU.  Post-LayerNorm: there is no ln_f, apply_final_ln is ignored, hidden state i of sgpt_encode_layers is
+ *   the input of block i (i = 0: the embedding LayerNorm's output) and state L the last block's output, as HF numbers them.
+ *   Descriptor: attn_scale = 1 / sqrt(head_dim), window = 0, ln_eps from the config (1e-12), layer_is_local NULL, rotary_dim 0.
+ *   Token types are all 0 on this path (single-segment inputs): the CALLER adds token_type_embeddings[0] to every row of the
+ *   position table and passes the sum as "embeddings.position_embeddings.weight" (sgpt_amd/model.py does); the pooler head is
+ *   not read.  compute_dtype SGPT_F32 | SGPT_F16 | SGPT_BF16; SGPT_FP8W / SGPT_FP8M, qk_split, split_weights and any non-zero
+ *   precision plan are refused (SGPT_ERR_INVALID), as are SGPT_POOL_LEARNTMEAN, sgpt_lm_logprobs and the precision probe.
+ *   SGPT_F16 runs WITHOUT range shifts: every kernel that rounds an activation to f16 (the write-back LayerNorms included)
+ *   records |v| >= 32768 in the model's guard word as for the other families, but sgpt_model_range_adapt and
+ *   sgpt_model_set_range_shifts refuse -- a flagged model is reloaded as SGPT_BF16 / SGPT_F32.  16-bit head_dim 64 | 128.
+ *   Every layout (T_pad % 32) runs the bulk projection kernels: the query-sized kernels' LayerNorm prologues assume pre-LN. */
+enum { SGPT_POOL_WEIGHTEDMEAN = 0, SGPT_POOL_MEAN = 1, SGPT_POOL_LASTTOKEN = 2, SGPT_POOL_LEARNTMEAN = 3,
+       SGPT_POOL_CLS = 4 };   /* ABI v13: the first token row of each sequence (Pooling.py:103-105 `pooling_mode_cls_token`); sgpt_encode*, sgpt_pool */
 enum { SGPT_COS = 0, SGPT_DOT = 1, SGPT_NEG_L2 = 2 };   /* SGPT_NEG_L2 (ABI v11): -||x - y||_2, sgpt_eval_groups only */
 
 /* Model hyper-parameters = the fields of HF GPTNeoConfig the forward pass reads
@@ -112,6 +128,10 @@ typedef struct {
  *  GPT-J:   "wte.weight", "h.0.attn.q_proj.weight", "h.0.mlp.fc_in.weight", ..., plus the rotary tables
  *           "rotary.sin" / "rotary.cos" fp32[max_pos, rotary_dim/2] = HF create_sinusoidal_positions,
  *           HF:gptj/modeling_gptj.py:47-50, computed by the host so they match the reference bit for bit;
+ *  BERT:    "embeddings.word_embeddings.weight", "embeddings.position_embeddings.weight" (token_type_embeddings[0] added by the
+ *           caller), "embeddings.LayerNorm.{weight,bias}", "encoder.layer.0.attention.self.{query,key,value}.{weight,bias}" (fused
+ *           to [3d, d] by the library), "encoder.layer.0.attention.output.{dense,LayerNorm}.*", "encoder.layer.0.intermediate.dense.*",
+ *           "encoder.layer.0.output.{dense,LayerNorm}.*";
  *  BLOOM:   "word_embeddings.weight", "word_embeddings_layernorm.*", "h.0.self_attention.query_key_value.{weight,bias}"
  *           (fused, head-interleaved [n_head, 3, head_dim] rows, HF:bloom:214 -- de-interleaved by the library),
  *           "h.0.self_attention.dense.*", "h.0.mlp.dense_h_to_4h.*", ..., plus "alibi.slopes" fp32[n_head]
@@ -208,7 +228,8 @@ sgpt_status sgpt_lm_logprobs(sgpt_model* model, const float* hidden, const int32
  * Replaces Pooling.forward (sentence_transformers/models/Pooling.py:99-125,129-164) and
  * CustomEmbedder.embed_batcher's pooling branch (beir_dense_retriever.py:238-282).
  *   hidden device [B,S,d] (fp32 or bf16), mask device int32[B,S] (0/1, any padding side);
- *   weights follow the padded index t+1; weight sum clamped at 1e-9 (Pooling.py:122). */
+ *   weights follow the padded index t+1; weight sum clamped at 1e-9 (Pooling.py:122).
+ *   pool_mode SGPT_POOL_WEIGHTEDMEAN | _MEAN | _LASTTOKEN | _CLS (row 0 of every sequence, whatever the mask: Pooling.py:103-105). */
 sgpt_status sgpt_pool(sgpt_ctx* ctx, const void* hidden, int32_t hidden_dtype, const int32_t* mask,
                       int32_t B, int32_t S, int32_t d, int32_t pool_mode, float* out, void* stream);
 /* Same with per-position weights (SGPT_POOL_LEARNTMEAN): pos_weights device fp32[>= S]. */
@@ -547,6 +568,7 @@ sgpt_status sgpt_eval_pairs(sgpt_ctx* ctx, const float* score, const int32_t* la
  *   epi 1: out[M,N] = gelu_new(acc + bias)               out_dtype = dtype           (HF NewGELUActivation)
  *   epi 2: out[M,N] = resid + acc + bias                 fp32; out may alias resid (the residual stream, in place)
  *   epi 4: out[N,M] = acc (+ bias[n])                    16-bit transposed store (V^T for the attention P.V operand), M % 128 == 0
+ *   epi 9: out[M,N] = gelu(acc + bias), 0.5 u (1 + erf(u / sqrt 2))   out_dtype = dtype   (ABI v13; HF GELUActivation, the BERT family)
  * bias device fp32[N]; resid device fp32[M,N].  M % 256 == 0, N % 256 == 0, K % 64 == 0 with at least half a wave of
  * 256x256 tiles take the LDS-DMA throughput kernel, everything else the 128x128 / 64x64 register-staged one; both
  * feed every output element the same MFMA sequence, so the result does not depend on which one ran. */
@@ -596,6 +618,18 @@ sgpt_status sgpt_attention(sgpt_ctx* ctx, int32_t dtype, const void* q, const vo
                            float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
                            int64_t ctx_lo_delta, int64_t ctx_hi2_delta, void* stream);
 
+/* sgpt_attention_ex (ABI v13): sgpt_attention with the bidirectional mode of SGPT_ARCH_BERT (HF:bert/modeling_bert.py BertSelfAttention).
+ *   causal = 1, seq_len = NULL: sgpt_attention exactly (the same kernels, the same bits).
+ *   causal = 0: every query row of sequence b sees keys j in [0, seq_len[b]) of that sequence -- seq_len device int32[B], clamped
+ *     into [0, seq_off[b+1] - seq_off[b]]; NULL = the whole allocation -- and nothing of its neighbours on the packed axis.  A
+ *     sequence of no keys gives zero rows.  window = 0 and alibi = NULL; out_fp8, x3 and the split context are refused
+ *     (SGPT_ERR_INVALID), as is 16-bit head_dim 256.  Over-read contract as sgpt_attention. */
+sgpt_status sgpt_attention_ex(sgpt_ctx* ctx, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
+                              void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t dh,
+                              int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
+                              float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
+                              int64_t ctx_lo_delta, int64_t ctx_hi2_delta, int32_t causal, const int32_t* seq_len, void* stream);
+
 /* The encoder's row kernels, stand-alone (ABI v12; kernel-level tests: tests/test_gpu_rowops.py compares each with a float64
  * restatement of the same operation).  These are the launches sgpt_encode / sgpt_lm_logprobs make between their GEMMs, on
  * caller-owned device buffers.  Every entry returns SGPT_ERR_INVALID, with nothing launched, for a null pointer, a row width
@@ -611,6 +645,9 @@ sgpt_status sgpt_attention(sgpt_ctx* ctx, int32_t dtype, const void* q, const vo
  *   .compute_dtype SGPT_F16); 1 for the other formats.  split = 1 (16-bit only): out [T, 3 d] = [hi | lo | hi] with
  *   hi = round16(v), lo = round16(v - hi), v = out_mul * LayerNorm(x) -- the operand of the split-precision projections
  *   (sgpt_model_desc.qk_split).  out may alias x for SGPT_F32 (BLOOM's embedding LayerNorm, HF:bloom/modeling_bloom.py:499).
+ * sgpt_layernorm_writeback (ABI v13): the LayerNorm of a post-LN block (SGPT_ARCH_BERT): x fp32[T, d] <- nn.LayerNorm(eps)(x) IN PLACE
+ *   and, from the same registers, out16 [T, d] = the normalised row rounded once (RNE) to out_dtype SGPT_BF16 | SGPT_F16 -- the
+ *   next projection's operand.  An f16 value of magnitude >= 32768 raises bit 0 of sgpt_range_check.
  * sgpt_lnf_pool: the final LayerNorm fused with the pooling of a packed batch (layout of sgpt_encode: sequence i holds rows
  *   [seq_off[i], seq_off[i] + seq_len[i]) of x fp32[T_pad, d]; rows outside are never read).  apply_ln: ln_f (HF:gpt_neo:492)
  *   on every row first.  mode SGPT_POOL_*: weightedmean sum_t (P + t + 1) h_t / max(sum_t (P + t + 1), 1e-9) with P =
@@ -632,6 +669,8 @@ sgpt_status sgpt_embed(sgpt_ctx* ctx, const int32_t* ids, const int32_t* pos, co
                        int32_t d, int32_t vocab, int32_t max_pos, float* out, void* stream);
 sgpt_status sgpt_layernorm(sgpt_ctx* ctx, const float* x, const float* gamma, const float* beta, int32_t T, int32_t d, float eps,
                            void* out, int32_t out_dtype, float out_mul, int32_t split, void* stream);
+sgpt_status sgpt_layernorm_writeback(sgpt_ctx* ctx, float* x, const float* gamma, const float* beta, int32_t T, int32_t d, float eps,
+                                     void* out16, int32_t out_dtype, void* stream);
 sgpt_status sgpt_lnf_pool(sgpt_ctx* ctx, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
                           const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
                           int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,

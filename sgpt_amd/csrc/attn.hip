@@ -114,13 +114,19 @@ __device__ __forceinline__ float xor32_max(float v) { return fmaxf(v, __shfl_xor
 // the lo halves of q | k and V^T sit qk_lo_delta / v_lo_delta elements behind the hi halves (written by the projections'
 // split epilogues).  Twice the LDS and three times the MFMAs of an attention that is < 2 % of a block's FLOPs; 2 waves per
 // SIMD (the second fragment set does not fit 128 VGPRs).  Context split as MODE 1 when ctx_lo_delta != 0.
-template <typename H, int DH, bool OUT8, int NQ, int NW = 8, int MODE = 0, bool PIPE = false, bool ZZ = false>
+// CAUSAL = false (the BERT family, HF:bert/modeling_bert.py BertSelfAttention): every query of a sequence sees the keys
+// [0, klen) of that sequence, klen = seq_len[sq] (or the whole allocation when seq_len is null) -- the key tiles run to the
+// sequence end instead of the block's diagonal, and the per-score compare masks against klen - 1 instead of the query index.
+// Consecutive fragments only (no diagonal, so every fragment has the same work and the mirror pairing has nothing to balance),
+// MODE 0, no window, 16-bit context.  The causal instantiations do not see any of it (if constexpr).
+template <typename H, int DH, bool OUT8, int NQ, int NW = 8, int MODE = 0, bool PIPE = false, bool ZZ = false, bool CAUSAL = true>
 __global__ __launch_bounds__(64 * NW, MODE == 2 ? 2 : (NW <= 2 ? 3 : ATTN_WAVES_PER_SIMD))   // (NW = 2: 4 staging loads per thread)
 void attn16_lds_kernel(const AttnArgs p) {
     constexpr bool X3 = MODE == 2;
     static_assert(!(MODE != 0 && OUT8), "split-precision modes write 16-bit contexts");
     static_assert(!PIPE || (NQ == 1 && !X3 && DH <= 128), "pipelined variant: one fragment per wave, 16-bit operands");
     static_assert(ZZ ? NQ == 2 : NQ == 1, "two fragments per wave = the zig-zag pairing");
+    static_assert(CAUSAL || (MODE == 0 && !OUT8 && !PIPE && !ZZ), "bidirectional attention: plain 16-bit kernel, consecutive fragments");
     constexpr int KS = DH / 32, DT = DH / 16, CPR = DH / 8;  // CPR = 16-B chunks per K row
     constexpr int NT = 64 * NW, QW = 16 * NQ, QB = NW * QW;    // NW waves per block, QW queries per wave, QB per block
     constexpr int ORS = DH * 2 + 16;                           // output-transpose row stride (bytes)
@@ -187,6 +193,12 @@ void attn16_lds_kernel(const AttnArgs p) {
     if (p.window > 0) { j_lo = qb0 - p.window + 1; j_lo = j_lo < 0 ? 0 : (j_lo & ~63); }
     int j_hi = ZZ ? 16 * (((alloc + 15) >> 4) - 1 - blockIdx.x * NW) + 15 : qb0 + QB - 1;   // last key any query of the block may see
     if (j_hi > alloc - 1) j_hi = alloc - 1;
+    int klast = 0;                                   // bidirectional: last visible key of the sequence
+    if constexpr (!CAUSAL) {
+        int klen = p.seq_len ? p.seq_len[sq] : alloc;
+        klen = klen < 0 ? 0 : (klen > alloc ? alloc : klen);
+        klast = klen - 1; j_lo = 0; j_hi = klast;
+    }
     // ---- cooperative tile load (row-contiguous 16-B pieces), one tile ahead: the global loads of key tile j+1 are
     // issued before tile j is consumed from LDS, so a sequence of several key tiles (S >= 128) does not pay one
     // un-hidden global-load round trip per tile ----
@@ -269,7 +281,8 @@ void attn16_lds_kernel(const AttnArgs p) {
     auto softmax_frag = [&](int j0, int qf0, f32x4 (&s)[4], float& m_r, float& l_r, f32x4 (&oo_)[DT], uint32_t (&pw)[8], uint32_t (&pwl)[8]) {
         const int qi = qf0 + fr;
         // (DH = 128: the second code path costs 14 spilled VGPRs at 4 waves per SIMD -- lean path for DH = 64 only)
-        const bool full = DH <= 64 && (j0 + 63 <= qf0) && (p.window <= 0 || j0 > qf0 + 15 - p.window);
+        const bool full = CAUSAL ? DH <= 64 && (j0 + 63 <= qf0) && (p.window <= 0 || j0 > qf0 + 15 - p.window)
+                                 : DH <= 64 && (j0 + 63 <= klast);      // every key of the tile exists (all but the ragged last tile)
         float mx = -INFINITY;
         if (full && slope == 0.f) {                  // wave-uniform
 #pragma unroll
@@ -279,8 +292,9 @@ void attn16_lds_kernel(const AttnArgs p) {
                 mx = fmaxf(mx, fmaxf(fmaxf(s[nt][0], s[nt][1]), fmaxf(s[nt][2], s[nt][3])));
             }
         } else {
-            const int dq = qi - (j0 + 4 * g);         // key offset o = 16 nt + r is visible iff o <= dq (and o > dq - window)
-            const int dw = p.window > 0 ? dq - p.window : -(1 << 30);
+            // key offset o = 16 nt + r is visible iff o <= dq (and o > dq - window); bidirectional: iff the key exists, o <= klast - ..
+            const int dq = (CAUSAL ? qi : klast) - (j0 + 4 * g);
+            const int dw = (CAUSAL && p.window > 0) ? dq - p.window : -(1 << 30);
             const float ab = s2 * (float)(j0 + 4 * g);
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt)
@@ -342,6 +356,7 @@ void attn16_lds_kernel(const AttnArgs p) {
     // diagonal, and (local layers) not wholly below the window of its first query -- a skipped tile would contribute p = 0
     // everywhere (same bits)
     auto frag_visible = [&](int qf0, int j0) {
+        if constexpr (!CAUSAL) return wave_on && qf0 >= 0 && j0 <= j_hi;
         return wave_on && qf0 >= 0 && j0 <= j_hi && j0 <= qf0 + 15 && (!SGPT_ATTN_WINSKIP || p.window <= 0 || j0 + 63 > qf0 - p.window);
     };
     auto tile_compute = [&](const uint4* __restrict__ Kc, const uint4* __restrict__ Vc, int j0) {
@@ -481,7 +496,8 @@ void attn16_lds_kernel(const AttnArgs p) {
         float lr = l_run[f];
         lr += __shfl_xor(lr, 16, 64);
         lr += __shfl_xor(lr, 32, 64);
-        const float inv = 1.0f / lr;
+        float inv = 1.0f / lr;
+        if constexpr (!CAUSAL) inv = lr > 0.f ? inv : 0.f;      // a sequence of no tokens has no keys: zero rows, not 0 / 0
         if constexpr (OUT8) {
             constexpr int ORS8 = DH + 16, CPR8 = DH / 16, RPI8 = 64 / CPR8;
             const float sc = inv / p.out_scale;
@@ -545,6 +561,7 @@ void attn16_lds_kernel(const AttnArgs p) {
 
 // Exact fp32: one wave per query row.  Scores in LDS (max 2048 keys per wave).
 constexpr int F32_MAXKEYS = 2048;
+template <bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnArgs p) {
     __shared__ float sc[4][F32_MAXKEYS];
     __shared__ float qs[4][256];
@@ -561,7 +578,12 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnArgs p) {
     for (int c = lane; c < dh; c += 64) qs[wave][c] = qb[(long)(s0 + qi) * p.ldq + c];
     int lo = 0;
     if (p.window > 0) { lo = qi - p.window + 1; lo = lo < 0 ? 0 : lo; }
-    const int nkeys = qi - lo + 1;
+    int nkeys = qi - lo + 1;
+    if constexpr (!CAUSAL) {        // bidirectional: keys [0, seq_len) of the sequence
+        nkeys = p.seq_len ? p.seq_len[sq] : alloc;
+        nkeys = nkeys < 0 ? 0 : (nkeys > alloc ? alloc : nkeys);
+        lo = 0;
+    }
     const float slope = p.alibi ? p.alibi[head] : 0.f;
     float mx = -INFINITY;
     for (int jj = lane; jj < nkeys; jj += 64) {
@@ -584,7 +606,8 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnArgs p) {
         sum += e;
     }
     sum = wave_sum(sum);
-    const float inv = 1.0f / sum;
+    float inv = 1.0f / sum;
+    if constexpr (!CAUSAL) inv = sum > 0.f ? inv : 0.f;         // a sequence of no tokens has no keys: zero rows, not 0 / 0
     float* orow = static_cast<float*>(p.ctx) + (long)(s0 + qi) * p.ldo + (long)head * dh;
     for (int c = lane; c < dh; c += 64) {
         float a = 0.f;
@@ -597,6 +620,17 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnArgs p) {
 
 void launch_attn_bf16(const AttnArgs& a, hipStream_t s) {
     dim3 grid((a.max_alloc_len + 127) / 128, a.H, a.B);
+    if (a.noncausal) {
+        // bidirectional attention: 8-wave blocks of consecutive fragments (every fragment walks all of the sequence's key tiles)
+        if (a.x3 || a.ctx_lo_delta != 0 || a.out_fp8 || a.window > 0 || a.alibi != nullptr) abort();   // refused by the callers
+#define ATTN_BIDIR_CASE(H)                                                                                                              \
+        if (a.dh == 64) hipLaunchKernelGGL((attn16_lds_kernel<H, 64, false, 1, 8, 0, false, false, false>), grid, dim3(512), 0, s, a);   \
+        else if (a.dh == 128) hipLaunchKernelGGL((attn16_lds_kernel<H, 128, false, 1, 8, 0, false, false, false>), grid, dim3(512), 0, s, a); \
+        else abort();
+        if (a.dtype == DT_F16) { ATTN_BIDIR_CASE(f16_t) } else { ATTN_BIDIR_CASE(bf16_t) }
+#undef ATTN_BIDIR_CASE
+        return;
+    }
     if (a.x3 || a.ctx_lo_delta != 0) {
         // split-precision variants (MODE 2: hi + lo q / k / V^T / p; MODE 1: 16-bit attention, split context).  head_dim 256
         // has no MODE 2 (its lo tiles do not fit the LDS): the caller keeps x3 = 0 there (attn_x3_supported)
@@ -685,5 +719,6 @@ void launch_attn_bf16(const AttnArgs& a, hipStream_t s) {
 
 void launch_attn_f32(const AttnArgs& a, hipStream_t s) {
     dim3 grid((a.max_alloc_len + 3) / 4, a.H, a.B);
-    hipLaunchKernelGGL(attn_f32_kernel, grid, dim3(256), 0, s, a);
+    if (a.noncausal) hipLaunchKernelGGL(attn_f32_kernel<false>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(attn_f32_kernel<true>, grid, dim3(256), 0, s, a);
 }

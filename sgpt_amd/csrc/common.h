@@ -203,6 +203,11 @@ __device__ __forceinline__ float gelu_new(float u) {
     return 0.5f * u * (1.0f + tanhf(t));
 }
 
+// transformers.activations.GELUActivation (HF "gelu", the BERT family): 0.5 u (1 + erf(u / sqrt 2)) on the fp32 accumulator.
+// erff is the device library's (ocml) single-precision erf, no approximation of this project's own: its documented bound is
+// <= 4 ulp, i.e. <= 2.4e-7 absolute on [-6, 6] where |erf| <= 1 (tests/test_gpu_bert.py holds the epilogue to the float64 value).
+__device__ __forceinline__ float gelu_erf(float u) { return 0.5f * u * (1.0f + erff(u * 0.70710678118654752f)); }
+
 // bf16 path: 0.5u(1+tanh(t)) == u * sigmoid(2t) = u / (1 + 2^(-2t*log2e)), with the constants folded:
 // 3 mul/fma + v_exp_f32 + add + v_rcp_f32 + mul (the `1/x` spelled __frcp_rn costs an 11-instruction IEEE divide).
 __device__ __forceinline__ float gelu_new_fast(float u) {
@@ -243,9 +248,12 @@ enum GemmEpi {
                           // per-query candidate list instead of materialising the score tile
     EPI_SCORE_TOP2 = 8,   // scorer's threshold sample (round 5): per query row and (document tile, wave) the two best scores of the wave's
                           // 64 documents -> out[m][8 * (n0 / 256) + 2 * wn + {0, 1}]; nothing else leaves the registers (256x256 kernel only)
+    EPI_BIAS_GELU_ERF = 9,// out[m][n] = gelu_erf(acc + bias[n])      (row-major, OutT; the BERT family's "gelu")
     EPI_QKV = 7,          // fused QKV projection: columns < n_split -> out[m][n] (q | k, row-major), the rest -> out2[n - n_split][m]
                           // (V^T); one launch for query-sized batches, split into EPI_STORE + EPI_VT launches otherwise
 };
+
+__host__ __device__ constexpr bool epi_is_gelu(int epi) { return epi == EPI_BIAS_GELU || epi == EPI_BIAS_GELU_ERF; }
 
 struct GemmArgs {
     const void* A;      // [M][K] row-major, leading dim lda (elements)
@@ -356,6 +364,11 @@ struct AttnArgs {
     // when ctx_hi2_delta != 0, a second hi (ctx + ctx_hi2_delta)
     int x3;
     long qk_lo_delta, v_lo_delta, ctx_lo_delta, ctx_hi2_delta;
+    // bidirectional attention (SGPT_ARCH_BERT): noncausal = 1: every query of sequence b sees keys [0, seq_len[b]) of it (seq_len
+    // device int32[B], null = the whole allocation); window 0, no ALiBi, MODE 0, 16-bit / fp32 context, head_dim 64 | 128 (16-bit).
+    // 0 (every zero-initialised descriptor) = the causal kernels, unchanged.
+    int noncausal;
+    const int* seq_len;
 };
 inline bool attn_x3_supported(int dh) { return dh == 64 || dh == 128; }
 void launch_attn_bf16(const AttnArgs& a, hipStream_t s);   // 16-bit MFMA path (bf16 or f16 by a.dtype)
@@ -367,6 +380,10 @@ void launch_layernorm(const float* x, const float* g, const float* b, void* out,
                       float eps, hipStream_t s, float out_mul = 1.0f);   // out_mul: f16 range shift (power of two)
 // split-precision Q / K projection (elementwise.hip): LayerNorm output as [hi | lo | hi] rows of 3 * d, weights as
 // [W_hi | W_hi | W_lo] rows of 3 * cols
+// post-LayerNorm blocks (SGPT_ARCH_BERT): x <- LayerNorm(x) in fp32 IN PLACE and the same values, rounded once, to the 16-bit
+// operand buffer out16 [T][d] in one pass; range_flag (f16, or null): raised when a rounded magnitude reaches RANGE_LIMIT
+void launch_layernorm_writeback(float* x, const float* g, const float* b, void* out16, int out_dtype, int T, int d, float eps,
+                                int* range_flag, hipStream_t s);
 void launch_layernorm_split(const float* x, const float* g, const float* b, void* out, int out_dtype, int T, int d,
                             float eps, hipStream_t s, float out_mul);
 void launch_pack_split_rows(const float* src, long rows, long cols, void* dst, int out_dtype, hipStream_t s);

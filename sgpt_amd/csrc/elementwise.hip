@@ -59,6 +59,34 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     }
 }
 
+// Post-LayerNorm blocks (SGPT_ARCH_BERT, HF:bert/modeling_bert.py BertSelfOutput / BertOutput: `LayerNorm(dense(h) + input)`): the
+// normalised row IS the next residual stream, so it goes back to x in fp32, in place, and -- the same registers, rounded once -- to
+// the 16-bit operand buffer the next projection reads.  A wave owns its row (all loads precede all stores): in place is safe.
+// f16: every rounded value passes the range tracker (no load-time bound on gamma / beta is relied upon for this family).
+template <typename OutT, int NV>
+__global__ __launch_bounds__(256) void layernorm_writeback_kernel(float* __restrict__ x, const float* __restrict__ g,
+                                                                  const float* __restrict__ b, OutT* __restrict__ out16, int T,
+                                                                  int d, float eps, int* __restrict__ range_flag) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= T) return;
+    const int lane = threadIdx.x & 63;
+    RowLN<NV> r;
+    r.load(x + (long)row * d, d, lane);
+    r.normalize(g, b, d, eps, lane);
+    RangeTrack<OutT> range;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (i * 64 + lane) * 4;
+        if (c < d) {
+            *reinterpret_cast<float4*>(x + (long)row * d + c) = r.v[i];
+            range.note(r.v[i].x, r.v[i].y); range.note(r.v[i].z, r.v[i].w);
+            *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(out16) + (long)row * d + c) =
+                make_uint2(Half<OutT>::pack2(r.v[i].x, r.v[i].y), Half<OutT>::pack2(r.v[i].z, r.v[i].w));
+        }
+    }
+    range.finish(range_flag);
+}
+
 // LayerNorm for the split-precision Q / K projection (sgpt_model_desc.qk_split): the normalised row a is written as
 // [hi | lo | hi] with hi = round16(a), lo = round16(a - hi) -- three K blocks of a [T, 3d] operand.  Against weights packed as
 // [W_hi | W_hi | W_lo] (pack_split_rows_kernel) one ordinary GEMM over K' = 3d computes a_hi.W_hi + a_lo.W_hi + a_hi.W_lo:
@@ -174,19 +202,20 @@ __global__ __launch_bounds__(256) void lnf_pool_kernel(const float* __restrict__
     for (int i = 0; i < NV; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     float den = 0.f;
     const int t_lo = mode == 2 ? (len > 0 ? len - 1 : 0) : 0;
+    const int t_hi = mode == 4 ? (len > 0 ? 1 : 0) : len;        // cls (mode 4): the first row alone (Pooling.py:103-105)
     // A wave's rows t = wave, wave + 4, ... are accumulated in that order; their LOADS go out LPB rows at a time (round 6: one
     // sequence of 30 tokens is eight dependent load -> normalise -> accumulate round trips per wave otherwise -- 14 us of a
     // 0.43 ms single-query encode; a bulk call has thousands of workgroups to hide the latency behind).  Same sums, same bits.
     constexpr int LPB = NV <= 4 ? 4 : 2;
-    for (int t = t_lo + wave; t < len; t += 4 * LPB) {
+    for (int t = t_lo + wave; t < t_hi; t += 4 * LPB) {
         RowLN<NV> r[LPB];
 #pragma unroll
         for (int u = 0; u < LPB; ++u)
-            if (t + 4 * u < len) r[u].load(x + (long)(s0 + t + 4 * u) * d, d, lane);
+            if (t + 4 * u < t_hi) r[u].load(x + (long)(s0 + t + 4 * u) * d, d, lane);
 #pragma unroll
         for (int u = 0; u < LPB; ++u) {
             const int tt = t + 4 * u;
-            if (tt >= len) break;
+            if (tt >= t_hi) break;
             if (apply_ln) r[u].template normalize<true>(g, b, d, eps, lane);
             // mode 3 (learntmean): trained per-position weights, indexed like the padded position
             // (WeightedMeanPooling.py:21-39; useb_dense_retriever.py:253-270)
@@ -208,7 +237,7 @@ __global__ __launch_bounds__(256) void lnf_pool_kernel(const float* __restrict__
     if (lane == 0) red[wave] = den;
     __syncthreads();
     float dsum = (red[0] + red[1]) + (red[2] + red[3]);
-    if (mode != 2) dsum = fmaxf(dsum, 1e-9f);  // Pooling.py:122
+    if (mode != 2 && mode != 4) dsum = fmaxf(dsum, 1e-9f);  // Pooling.py:122
     else dsum = 1.0f;
     float ss = 0.f;
     for (int c = threadIdx.x; c < d; c += 256) {
@@ -255,7 +284,9 @@ __global__ __launch_bounds__(256) void pool_kernel(const T* __restrict__ h, cons
     const T* hb = h + (long)bq * S * d + c;
     const int* mb = mask + (long)bq * S;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (mode == 2) {
+    if (mode == 4) {            // cls: `token_embeddings[:, 0]`, whatever the mask says (Pooling.py:103-105)
+        acc = load4<T>(hb);
+    } else if (mode == 2) {
         int last = 0;
         for (int t = 0; t < S; ++t) if (mb[t] != 0) last = t;
         acc = load4<T>(hb + (long)last * d);
@@ -613,6 +644,22 @@ void launch_layernorm(const float* x, const float* g, const float* b, void* out,
     else if (nv <= 4) { LN_CASE(4) } else if (nv <= 8) { LN_CASE(8) } else if (nv <= 10) { LN_CASE(10) }
     else { LN_CASE(16) }
 #undef LN_CASE
+}
+
+void launch_layernorm_writeback(float* x, const float* g, const float* b, void* out16, int out_dtype, int T, int d, float eps,
+                                int* range_flag, hipStream_t s) {
+#define LW_CASE(NV)                                                                                                  \
+    if (out_dtype == DT_F16)                                                                                         \
+        hipLaunchKernelGGL((layernorm_writeback_kernel<f16_t, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, b,     \
+                           (f16_t*)out16, T, d, eps, range_flag);                                                    \
+    else                                                                                                             \
+        hipLaunchKernelGGL((layernorm_writeback_kernel<bf16_t, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, b,    \
+                           (bf16_t*)out16, T, d, eps, range_flag);
+    const int nv = (d + 255) / 256;
+    if (nv <= 1) { LW_CASE(1) } else if (nv <= 2) { LW_CASE(2) } else if (nv <= 3) { LW_CASE(3) }
+    else if (nv <= 4) { LW_CASE(4) } else if (nv <= 8) { LW_CASE(8) } else if (nv <= 10) { LW_CASE(10) }
+    else { LW_CASE(16) }
+#undef LW_CASE
 }
 
 void launch_layernorm_split(const float* x, const float* g, const float* b, void* out, int out_dtype, int T, int d,

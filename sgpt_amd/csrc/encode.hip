@@ -7,7 +7,7 @@ namespace {
 // What the block functions of one forward share: the call's token layout, the operand format, the launch path and the workspace.
 struct Fwd {
     sgpt_model* m; sgpt_ctx* c; hipStream_t s;
-    const int32_t *pos, *seq_off;
+    const int32_t *pos, *seq_off, *seq_len;
     int B, T, max_alloc;
     int dt;               // operand format of the projections: SGPT_F32 | SGPT_BF16 | SGPT_F16
     int* range_flag;      // the model's range words (SGPT_F16 stores, e4m3 codes of the fp8-MFMA block) or null
@@ -47,6 +47,53 @@ AttnArgs attn_base(const Fwd& f, const LayerW& l, int k_qkv) {
     if (f.vt) { at.k = (bf16_t*)f.qkv + dm; at.v = f.vt; at.ldq = 2 * dm; at.ldvt = f.T; }
     else { at.k = (float*)f.qkv + dm; at.v = (float*)f.qkv + 2 * dm; at.ldq = 3 * dm; }
     return at;
+}
+
+// ---- the BERT family (SGPT_ARCH_BERT; HF:bert/modeling_bert.py BertLayer): post-LayerNorm blocks, bidirectional attention ----
+//   q|k|v = x W_qkv^T + b ; ctx = attention(non-causal) ; x = LN_att(x + ctx Wo^T + bo) ; x = LN_out(x + gelu_erf(x W1^T + b1) W2^T + b2)
+// Every block ends in a LayerNorm whose output IS the residual stream.  No range shifts (every f16 store is tracked), no precision
+// plan, bulk kernels at every layout (the LayerNorm prologues of the query-sized projections assume pre-LN).
+AttnArgs attn_bidir(const Fwd& f, const LayerW& l) {
+    AttnArgs at = attn_base(f, l, 0);
+    at.noncausal = 1; at.seq_len = f.seq_len; at.window = 0; at.alibi = nullptr;
+    return at;
+}
+
+// fp32: the projections read the residual stream itself
+void block_bert_f32(const Fwd& f, const LayerW& l) {
+    const sgpt_model_desc& d = f.m->d;
+    const int dm = d.d_model, ffn = d.d_ffn, T = f.T;
+    gemm(f.c, SGPT_F32, EPI_STORE, SGPT_F32, proj(f, f.x, dm, l.w_qkv, 3 * dm, dm, f.qkv, 3 * dm, l.b_qkv), f.s);
+    launch_attn_f32(attn_bidir(f, l), f.s);
+    gemm(f.c, SGPT_F32, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dm, l.w_o, dm, dm, f.x, dm, l.b_o, f.x), f.s);
+    launch_layernorm(f.x, l.ln1_g, l.ln1_b, f.x, SGPT_F32, T, dm, d.ln_eps, f.s);
+    gemm(f.c, SGPT_F32, EPI_BIAS_GELU_ERF, SGPT_F32, proj(f, f.x, dm, l.w_fc, ffn, dm, f.h, ffn, l.b_fc), f.s);
+    gemm(f.c, SGPT_F32, EPI_BIAS_RESID, SGPT_F32, proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x), f.s);
+    launch_layernorm(f.x, l.ln2_g, l.ln2_b, f.x, SGPT_F32, T, dm, d.ln_eps, f.s);
+}
+
+// 16-bit: `a` holds the 16-bit copy of x the previous write-back LayerNorm (or the embedding LayerNorm) left; the context shares
+// its buffer (a is consumed by the Q | K | V projection before the attention writes)
+void block_bert16(const Fwd& f, const LayerW& l) {
+    const sgpt_model_desc& d = f.m->d;
+    const int dm = d.d_model, ffn = d.d_ffn, T = f.T, dt = f.dt;
+    GemmArgs q = proj(f, f.a, dm, l.w_qkv, 3 * dm, dm, f.qkv, 2 * dm, l.b_qkv);
+    if (gemm_qkv_one_launch(T, 2 * dm, f.c->force256 != 0)) {        // query-sized batch: q | k and V^T from one launch
+        q.n_split = 2 * dm; q.out2 = f.vt; q.ldo2 = T;
+        gemm(f.c, dt, EPI_QKV, dt, q, f.s);
+    } else {
+        GemmArgs qk = q, v = q;
+        qk.N = 2 * dm;
+        gemm(f.c, dt, EPI_STORE, dt, qk, f.s);
+        v.W = (bf16_t*)l.w_qkv + (size_t)2 * dm * dm; v.N = dm; v.out = f.vt; v.ldo = T; v.bias = l.b_qkv + 2 * dm;
+        gemm(f.c, dt, EPI_VT, dt, v, f.s);
+    }
+    launch_attn_bf16(attn_bidir(f, l), f.s);
+    gemm(f.c, dt, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dm, l.w_o, dm, dm, f.x, dm, l.b_o, f.x), f.s);
+    launch_layernorm_writeback(f.x, l.ln1_g, l.ln1_b, f.a, dt, T, dm, d.ln_eps, f.range_flag, f.s);
+    gemm(f.c, dt, EPI_BIAS_GELU_ERF, dt, proj(f, f.a, dm, l.w_fc, ffn, dm, f.h, ffn, l.b_fc), f.s);
+    gemm(f.c, dt, EPI_BIAS_RESID, SGPT_F32, proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x), f.s);
+    launch_layernorm_writeback(f.x, l.ln2_g, l.ln2_b, f.a, dt, T, dm, d.ln_eps, f.range_flag, f.s);
 }
 
 // ---- fp32 block (SGPT_F32): plain operands, q | k | v rows in one buffer ----
@@ -214,7 +261,11 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
     if (!ids || !pos || !seq_off || !seq_len || B <= 0 || T <= 0 || T % 32 || max_alloc <= 0 || max_alloc % 2)
         return fail(c, SGPT_ERR_INVALID, "sgpt_encode: bad token layout (T_pad % 32, max_alloc_len % 2)");
     if (n_layers_run < 0 || n_layers_run > m->d.n_layers) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: n_layers_run out of range");
-    if (pool_mode < 0 || pool_mode > 3) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: bad pool_mode");
+    if (pool_mode < 0 || pool_mode > SGPT_POOL_CLS) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: bad pool_mode");
+    const bool bert = m->d.arch == SGPT_ARCH_BERT;
+    if (bert && pool_mode == SGPT_POOL_LEARNTMEAN)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_encode: learntmean pooling (trained position weights of the SGPT checkpoints) is not available for SGPT_ARCH_BERT");
+    if (bert) apply_final_ln = 0;      // no ln_f in this family: the last block's LayerNorm output is hidden_states[-1]
     if (pool_mode == SGPT_POOL_LEARNTMEAN && (out || layer_out || layer_mean)) {
         if (!m->pool_w) return fail(c, SGPT_ERR_MISSING, "sgpt_encode: learntmean needs sgpt_model_set_pool_weights first");
         // with pad_left on the device the longest padded position is not known here: the kernel clamps the table index,
@@ -268,7 +319,7 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
     // pass riding on the forward.  Every projection takes the register-staged deep-prefetch kernel; at d = 512 / 768 / 1024 the two
     // LayerNorms of a sequential block (GPT-Neo, BLOOM) run inside the prologues of the projections they feed: five launches per block
     // instead of seven.  Same arithmetic per element as the bulk path (identical bits); sgpt_ctx_set_tile_policy(1 | 2) keeps the bulk kernels.
-    const bool qpath = bf && !fp8 && !split && !(m->probing && m->crest_dev) && !m->calibrating && !c->force256 && !c->no_qpath && T <= QGEMM_MAX_ROWS &&
+    const bool qpath = bf && !fp8 && !split && !bert && !(m->probing && m->crest_dev) && !m->calibrating && !c->force256 && !c->no_qpath && T <= QGEMM_MAX_ROWS &&
                        qgemm_shape_ok(T, 3 * dm, dm, EPI_QKV, 2 * dm) && qgemm_shape_ok(T, dm, dm, EPI_BIAS_RESID, 0) &&
                        qgemm_shape_ok(T, ffn, dm, EPI_BIAS_GELU, 0) && qgemm_shape_ok(T, dm, ffn, EPI_BIAS_RESID, 0);
     const bool qln = qpath && !gptj && qgemm_ln_ok(T, 3 * dm, dm, EPI_QKV, 2 * dm) && qgemm_ln_ok(T, ffn, dm, EPI_BIAS_GELU, 0);
@@ -280,7 +331,7 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
     char* base = (char*)c->ws;
     if (layer_mean && !layer_out) layer_out = (float*)(base + o_lp);     // per-layer pooled vectors, scratch
     Fwd f{};
-    f.m = m; f.c = c; f.s = s; f.pos = pos; f.seq_off = seq_off; f.B = B; f.T = T; f.max_alloc = max_alloc;
+    f.m = m; f.c = c; f.s = s; f.pos = pos; f.seq_off = seq_off; f.seq_len = seq_len; f.B = B; f.T = T; f.max_alloc = max_alloc;
     f.dt = dt; f.range_flag = (mlp8 || dt == SGPT_F16) ? (int*)m->range_dev : nullptr;
     f.can_split = can_split; f.qpath = qpath; f.qln = qln;
     f.x = (float*)(base + o_x); f.a = base + o_a; f.ctx = base + o_c; f.qkv = base + o_qkv; f.h = base + o_h;
@@ -304,9 +355,11 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
         HIPC(c, hipMemsetAsync((float*)f.qkv + (size_t)T * 3 * dm, 0, SLACK * 3 * dm * esz, s));
     }
     // (query path with the LayerNorm inside the projections: no LayerNorm launch fills the buffer the context shares with it)
-    if (gptj || mlp8 || split || qln) HIPC(c, hipMemsetAsync(f.ctx, 0, (size_t)T * dm * esz * (any_ctx ? 3 : 1), s));   // (fp8: stale bytes would decode to NaN codes)
+    // (BERT fp32: no LayerNorm ever writes the buffer the context lives in)
+    if (gptj || mlp8 || split || qln || (bert && !bf)) HIPC(c, hipMemsetAsync(f.ctx, 0, (size_t)T * dm * esz * (any_ctx ? 3 : 1), s));   // (fp8: stale bytes would decode to NaN codes)
     launch_embed(ids, pos, m->wte, m->wpe, x, T, dm, m->d.vocab, m->d.max_pos, s);
-    if (m->emb_ln_g) launch_layernorm(x, m->emb_ln_g, m->emb_ln_b, x, SGPT_F32, T, dm, m->d.ln_eps, s);   // BLOOM :499
+    if (bert && bf) launch_layernorm_writeback(x, m->emb_ln_g, m->emb_ln_b, f.a, dt, T, dm, m->d.ln_eps, f.range_flag, s);   // x and its 16-bit copy
+    else if (m->emb_ln_g) launch_layernorm(x, m->emb_ln_g, m->emb_ln_b, x, SGPT_F32, T, dm, m->d.ln_eps, s);   // BLOOM :499
     for (int li = 0; li < n_layers_run; ++li) {
         LayerW l = m->L[li];
         if (layer_out)   // hidden_states[li] = input of block li (HF:gpt_neo:475-478)
@@ -319,7 +372,8 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
             launch_fp8_dequant_rows(l.w_proj, l.s_proj, dm, ffn, m->dq[3], SGPT_BF16, s);
             l.w_qkv = m->dq[0]; l.w_o = m->dq[1]; l.w_fc = m->dq[2]; l.w_proj = m->dq[3];
         }
-        if (mlp8) block_fp8(f, l, li);
+        if (bert) { if (bf) block_bert16(f, l); else block_bert_f32(f, l); }
+        else if (mlp8) block_fp8(f, l, li);
         else if (!bf) block_f32(f, l);
         else if ((st = block_16(f, l, li)) != SGPT_OK) return st;
     }
@@ -363,6 +417,7 @@ sgpt_status sgpt_lm_logprobs(sgpt_model* m, const float* hidden, const int32_t* 
     if (!m) return SGPT_ERR_INVALID;
     sgpt_ctx* c = m->ctx;
     if (!hidden || !row_idx || !targets || !out_logprob || n <= 0) return fail(c, SGPT_ERR_INVALID, "sgpt_lm_logprobs: bad arguments");
+    if (m->d.arch == SGPT_ARCH_BERT) return fail(c, SGPT_ERR_INVALID, "sgpt_lm_logprobs: SGPT_ARCH_BERT carries no causal LM head");
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int dm = m->d.d_model, V = m->d.vocab;

@@ -263,7 +263,7 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void gemm_kernel(const G
     // not depend on the product, so they are fetched HERE, under the k-loop, instead of one dependent L2 round trip per 16x16
     // piece at the end (the residual is updated in place: every piece's load also waited for the previous piece's store).
     // Same values, same arithmetic: identical bits.
-    constexpr bool PRE = NI == 2 && SWAP && (EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_GELU || EPI == EPI_STORE || EPI == EPI_QKV);
+    constexpr bool PRE = NI == 2 && SWAP && (EPI == EPI_BIAS_RESID || epi_is_gelu(EPI) || EPI == EPI_STORE || EPI == EPI_QKV);
     float4 bpre[PRE ? NI : 1], rpre[(PRE && EPI == EPI_BIAS_RESID) ? NI : 1][NI];
     if constexpr (PRE) {
         if (kg == 0) {
@@ -381,8 +381,8 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void gemm_kernel(const G
                 // shifts): store (acc * in_mul + bias) * out_mul as one fma; gelu(fma(acc, in_mul, bias)) * out_mul
                 float om = p.out_mul;
                 if constexpr (EPI == EPI_QKV) om = n >= p.n_split ? p.out_mul2 : p.out_mul;
-                const float cs = (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID) ? p.in_mul : p.in_mul * om;
-                const float bsc = EPI == EPI_BIAS_GELU ? 1.0f : om;
+                const float cs = (epi_is_gelu(EPI) || EPI == EPI_BIAS_RESID) ? p.in_mul : p.in_mul * om;
+                const float bsc = epi_is_gelu(EPI) ? 1.0f : om;
                 if constexpr (EPI == EPI_BIAS_RESID) {
                     // acc (* in_mul) + (bias + resid): the association of gemm256_kernel's epilogue, bit for bit
                     float4 bb, rr;
@@ -393,7 +393,7 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void gemm_kernel(const G
                     }
                     v[0] = __builtin_fmaf(v[0], cs, bb.x + rr.x); v[1] = __builtin_fmaf(v[1], cs, bb.y + rr.y);
                     v[2] = __builtin_fmaf(v[2], cs, bb.z + rr.z); v[3] = __builtin_fmaf(v[3], cs, bb.w + rr.w);
-                } else if (EPI == EPI_BIAS_GELU || ((EPI == EPI_STORE || EPI == EPI_QKV) && p.bias != nullptr)) {
+                } else if (epi_is_gelu(EPI) || ((EPI == EPI_STORE || EPI == EPI_QKV) && p.bias != nullptr)) {
                     if (full) {
                         float4 bb;
                         if constexpr (PRE) bb = bpre[j]; else bb = *reinterpret_cast<const float4*>(p.bias + n);
@@ -411,6 +411,10 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void gemm_kernel(const G
                     const float ginv = 1.0f / om;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = sizeof(T) == 2 ? gelu_new_fast_scaled(v[r], ginv) : gelu_new(v[r]);
+                }
+                if constexpr (EPI == EPI_BIAS_GELU_ERF) {       // (om: the f16 range shift of the output, 1 unless a model carries one)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]) * om;
                 }
                 if constexpr (EPI == EPI_SCORE) {
 #pragma unroll
@@ -1101,7 +1105,7 @@ void launch_gemm16(int epi, int out_dtype, const GemmArgs& a, hipStream_t s) {
     // (the GELU launch -- N = 4 d, a VALU-heavy epilogue -- wants a whole round of 256x256 tiles before the LDS-DMA kernel pays:
     //  fc1 at 3072 / 4096 rows is 144 / 192 tiles, 43.3 / 43.5 us there against 32.4 / 38.8 us on the small tiles; the other
     //  launches are faster on 256x256 tiles from half a round on -- Q/K at 6144 rows: 22.6 us against 31.7)
-    const long few_limit = epi == EPI_BIAS_GELU ? 255 : SGPT_FEW_TILES;
+    const long few_limit = epi_is_gelu(epi) ? 255 : SGPT_FEW_TILES;
     const bool few = small_tiles && !a.force256 && !scorer && (long)(a.M / 256) * (a.N / 256) <= few_limit;
     static const bool use256 = exp_env("SGPT_GEMM128") == nullptr;
     const bool shape256 = a.M % 256 == 0 && a.N % 256 == 0 && a.K % 64 == 0 && a.K >= 128;
@@ -1142,6 +1146,7 @@ void launch_gemm16(int epi, int out_dtype, const GemmArgs& a, hipStream_t s) {
         if (epi == EPI_STORE && o16) return launch256d<H, EPI_STORE, H, true>(a, s, deep_a);
         if (epi == EPI_VT) return launch256d<H, EPI_VT, H, false>(a, s, deep_a);
         if (epi == EPI_BIAS_GELU) return launch256d<H, EPI_BIAS_GELU, H, true>(a, s, deep_a);
+        if (epi == EPI_BIAS_GELU_ERF) return launch256d<H, EPI_BIAS_GELU_ERF, H, true>(a, s, deep_a);
         if (epi == EPI_BIAS_RESID) return launch256d<H, EPI_BIAS_RESID, float, true>(a, s, deep_a);
         if (epi == EPI_NONE) return launch256d<H, EPI_NONE, H, true>(a, s, deep_a);
     }
@@ -1149,6 +1154,7 @@ void launch_gemm16(int epi, int out_dtype, const GemmArgs& a, hipStream_t s) {
     if (epi == EPI_STORE && !o16) return launch<H, EPI_STORE, float, true>(a, s);
     if (epi == EPI_VT) return launch<H, EPI_VT, H, false>(a, s);
     if (epi == EPI_BIAS_GELU) return launch<H, EPI_BIAS_GELU, H, true>(a, s);
+    if (epi == EPI_BIAS_GELU_ERF) return launch<H, EPI_BIAS_GELU_ERF, H, true>(a, s);
     if (epi == EPI_BIAS_RESID) return launch<H, EPI_BIAS_RESID, float, true>(a, s);
     if (epi == EPI_SCORE) return launch<H, EPI_SCORE, float, true>(a, s);
     abort();
@@ -1198,6 +1204,7 @@ void launch_gemm(int dtype, int epi, int out_dtype, const GemmArgs& a0, hipStrea
     if (dtype == DT_F16) return launch_gemm16<f16_t>(epi, out_dtype, a, s);
     if (epi == EPI_STORE) return launch<float, EPI_STORE, float, true>(a, s);
     if (epi == EPI_BIAS_GELU) return launch<float, EPI_BIAS_GELU, float, true>(a, s);
+    if (epi == EPI_BIAS_GELU_ERF) return launch<float, EPI_BIAS_GELU_ERF, float, true>(a, s);
     if (epi == EPI_BIAS_RESID) return launch<float, EPI_BIAS_RESID, float, true>(a, s);
     if (epi == EPI_SCORE) return launch<float, EPI_SCORE, float, true>(a, s);
     abort();

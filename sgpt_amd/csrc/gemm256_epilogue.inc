@@ -181,7 +181,7 @@
             constexpr int RS = 144;
             const int rrow = lane >> 3, rchunk = lane & 7;
             float4 bb[4];
-            const bool has_bias = EPI == EPI_BIAS_GELU || p.bias != nullptr;   // plain store + bias: BLOOM Q/K projection
+            const bool has_bias = epi_is_gelu(EPI) || p.bias != nullptr;   // plain store + bias: BLOOM Q/K projection
             // f16 range shifts (powers of two, 1 by default -- fma(acc, 1, b) == acc + b bit for bit):
             //   store: out = (acc * in_mul + bias) * out_mul = fma(acc, in_mul * out_mul, bias * out_mul)
             //   gelu : out = gelu(fma(acc, in_mul, bias)) * out_mul, the factor riding in the sigmoid's reciprocal
@@ -194,8 +194,8 @@
             if constexpr (EPI == EPI_QKV) {
                 if (n0 >= p.n_split) { e_out = static_cast<OutT*>(p.out2); e_ldo = p.ldo2; e_m0 = n0 - p.n_split; e_n0 = m0; e_om = p.out_mul2; }
             }
-            const float cs = EPI == EPI_BIAS_GELU ? p.in_mul : p.in_mul * e_om;
-            const float bsc = EPI == EPI_BIAS_GELU ? 1.0f : e_om;
+            const float cs = epi_is_gelu(EPI) ? p.in_mul : p.in_mul * e_om;
+            const float bsc = epi_is_gelu(EPI) ? 1.0f : e_om;
             const float ginv = 1.0f / e_om;
             if (has_bias) {
 #pragma unroll
@@ -220,6 +220,10 @@
                     if constexpr (EPI == EPI_BIAS_GELU) {
                         v[0] = gelu_new_fast_scaled(v[0], ginv); v[1] = gelu_new_fast_scaled(v[1], ginv);
                         v[2] = gelu_new_fast_scaled(v[2], ginv); v[3] = gelu_new_fast_scaled(v[3], ginv);
+                    }
+                    if constexpr (EPI == EPI_BIAS_GELU_ERF) {
+                        v[0] = gelu_erf(v[0]) * e_om; v[1] = gelu_erf(v[1]) * e_om;
+                        v[2] = gelu_erf(v[2]) * e_om; v[3] = gelu_erf(v[3]) * e_om;
                     }
                     range.note(v[0], v[1]); range.note(v[2], v[3]);
                     const uint32_t h01 = Half<OutT>::pack2(v[0], v[1]), h23 = Half<OutT>::pack2(v[2], v[3]);

@@ -11,9 +11,9 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
     if (!c || !d || !tv || !out) return SGPT_ERR_INVALID;
     *out = nullptr;
     HIPC(c, hipSetDevice(c->device));
-    if (d->arch != SGPT_ARCH_GPTNEO && d->arch != SGPT_ARCH_GPTJ && d->arch != SGPT_ARCH_BLOOM)
-        return fail(c, SGPT_ERR_INVALID, "arch must be SGPT_ARCH_GPTNEO, SGPT_ARCH_GPTJ or SGPT_ARCH_BLOOM");
-    const bool gptj = d->arch == SGPT_ARCH_GPTJ, bloom = d->arch == SGPT_ARCH_BLOOM;
+    if (d->arch != SGPT_ARCH_GPTNEO && d->arch != SGPT_ARCH_GPTJ && d->arch != SGPT_ARCH_BLOOM && d->arch != SGPT_ARCH_BERT)
+        return fail(c, SGPT_ERR_INVALID, "arch must be SGPT_ARCH_GPTNEO, SGPT_ARCH_GPTJ, SGPT_ARCH_BLOOM or SGPT_ARCH_BERT");
+    const bool gptj = d->arch == SGPT_ARCH_GPTJ, bloom = d->arch == SGPT_ARCH_BLOOM, bert = d->arch == SGPT_ARCH_BERT;
     const int dm = d->d_model, ffn = d->d_ffn, H = d->n_heads;
     if (dm % 128 || ffn % 128 || H <= 0 || dm % H) return fail(c, SGPT_ERR_INVALID, "d_model and d_ffn must be multiples of 128");
     const int dh = dm / H;
@@ -28,6 +28,17 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
         return fail(c, SGPT_ERR_INVALID, "GPT-J needs an even rotary_dim in (0, head_dim]");
     if ((d->qk_split != 0 || d->split_weights != 0) && d->compute_dtype != SGPT_F16 && d->compute_dtype != SGPT_BF16)
         return fail(c, SGPT_ERR_INVALID, "qk_split / split_weights apply to SGPT_F16 / SGPT_BF16 models");
+
+    if (bert) {
+        // the post-LayerNorm block has one arithmetic per operand format: no fp8 storage / MFMA, no split-precision operands
+        if (d->compute_dtype == SGPT_FP8W || d->compute_dtype == SGPT_FP8M)
+            return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_BERT: compute_dtype SGPT_F32, SGPT_F16 or SGPT_BF16 (no fp8 mode for this family)");
+        if (d->qk_split != 0 || d->split_weights != 0)
+            return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_BERT: qk_split / split_weights (split-precision operands) are not available for this family");
+        if (d->compute_dtype != SGPT_F32 && dh != 64 && dh != 128)
+            return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_BERT: 16-bit bidirectional attention supports head_dim 64 or 128");
+        if (d->window != 0) return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_BERT: window must be 0");
+    }
 
     std::unordered_map<std::string, const sgpt_tensor_view*> byname;
     for (size_t i = 0; i < nt; ++i) byname[tv[i].name] = &tv[i];
@@ -89,8 +100,12 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
         if (src) pack_rows(src, rows, cols, dst, row_off, scale);
     };
 
-    m->wte = copy_f32(bloom ? "word_embeddings.weight" : "wte.weight", (int64_t)d->vocab * dm);
-    if (gptj) {
+    m->wte = copy_f32(bert ? "embeddings.word_embeddings.weight" : (bloom ? "word_embeddings.weight" : "wte.weight"), (int64_t)d->vocab * dm);
+    if (bert) {
+        // position table with token_type_embeddings[0] already added by the caller (single-segment inputs; include/sgpt_hip.h)
+        m->wpe = copy_f32("embeddings.position_embeddings.weight", (int64_t)d->max_pos * dm);
+        copy_ln("embeddings.LayerNorm", &m->emb_ln_g, &m->emb_ln_b);
+    } else if (gptj) {
         m->rot_sin = copy_f32("rotary.sin", (int64_t)d->max_pos * (d->rotary_dim / 2));
         m->rot_cos = copy_f32("rotary.cos", (int64_t)d->max_pos * (d->rotary_dim / 2));
     } else if (bloom) {
@@ -107,8 +122,10 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
         m->lm_w = copy_f32("lm_head.weight", (int64_t)d->vocab * dm);
         if (byname.count("lm_head.bias")) m->lm_b = copy_f32("lm_head.bias", d->vocab);
     }
-    m->lnf_g = copy_f32("ln_f.weight", dm);
-    m->lnf_b = copy_f32("ln_f.bias", dm);
+    if (!bert) {        // (BERT has no final LayerNorm: every block ends in one)
+        m->lnf_g = copy_f32("ln_f.weight", dm);
+        m->lnf_b = copy_f32("ln_f.bias", dm);
+    }
     m->zero_bias = (float*)dalloc((size_t)(ffn > dm ? ffn : dm) * 4);
     if (m->zero_bias && hipMemsetAsync(m->zero_bias, 0, (size_t)(ffn > dm ? ffn : dm) * 4, 0) != hipSuccess)
         st = fail(c, SGPT_ERR_HIP, "memset zero_bias");
@@ -124,7 +141,36 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
     const std::string ln1 = bloom ? "input_layernorm" : "ln_1", ln2 = bloom ? "post_attention_layernorm" : "ln_2";
     float* stage = nullptr;   // BLOOM: fp32 staging for the de-interleaved fused QKV weight
     if (bloom) stage = (float*)dalloc((size_t)3 * dm * dm * 4);
-    for (int i = 0; i < d->n_layers && st == SGPT_OK; ++i) {
+    // BERT  encoder.layer.N.attention.self.{query,key,value} / attention.output.{dense,LayerNorm} / intermediate.dense /
+    //       output.{dense,LayerNorm}; `pooler.*` is not read                         (HF:bert/modeling_bert.py BertLayer)
+    // ln1 = the LayerNorm behind the attention (attention.output.LayerNorm), ln2 = the one behind the MLP (output.LayerNorm)
+    for (int i = 0; bert && i < d->n_layers && st == SGPT_OK; ++i) {
+        const std::string p = "encoder.layer." + std::to_string(i) + ".";
+        LayerW& l = m->L[i];
+        l.is_local = 0;
+        copy_ln(p + "attention.output.LayerNorm", &l.ln1_g, &l.ln1_b);
+        copy_ln(p + "output.LayerNorm", &l.ln2_g, &l.ln2_b);
+        l.b_o = copy_f32(p + "attention.output.dense.bias", dm);
+        l.b_fc = copy_f32(p + "intermediate.dense.bias", ffn);
+        l.b_proj = copy_f32(p + "output.dense.bias", dm);
+        l.b_qkv = (float*)dalloc((size_t)3 * dm * 4);
+        l.w_qkv = dalloc((size_t)3 * dm * dm * esz);
+        l.w_o = dalloc((size_t)dm * dm * esz);
+        l.w_fc = dalloc((size_t)ffn * dm * esz);
+        l.w_proj = dalloc((size_t)dm * ffn * esz);
+        if (st != SGPT_OK) break;
+        const char* qkv[3] = {"query", "key", "value"};
+        for (int j = 0; j < 3 && st == SGPT_OK; ++j) {          // fused [q rows | k rows | v rows], biases alike
+            pack_w(p + "attention.self." + qkv[j] + ".weight", dm, dm, l.w_qkv, (int64_t)j * dm, nullptr);
+            const float* bj = find(p + "attention.self." + qkv[j] + ".bias", dm);
+            if (bj && hipMemcpyAsync(l.b_qkv + (size_t)j * dm, bj, (size_t)dm * 4, hipMemcpyDeviceToDevice, 0) != hipSuccess)
+                st = fail(c, SGPT_ERR_HIP, "memcpy qkv bias");
+        }
+        pack_w(p + "attention.output.dense.weight", dm, dm, l.w_o, 0, nullptr);
+        pack_w(p + "intermediate.dense.weight", ffn, dm, l.w_fc, 0, nullptr);
+        pack_w(p + "output.dense.weight", dm, ffn, l.w_proj, 0, nullptr);
+    }
+    for (int i = 0; !bert && i < d->n_layers && st == SGPT_OK; ++i) {
         const std::string p = "h." + std::to_string(i) + ".";
         LayerW& l = m->L[i];
         l.is_local = (gptj || bloom) ? 0 : (d->layer_is_local ? d->layer_is_local[i] : (i & 1));
@@ -225,7 +271,8 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
         const float bound = gmax * sqrtf((float)dm) + bmax;
         if (st == SGPT_OK && (!(wmax < 65504.f) || !std::isfinite(bound)))
             st = fail(c, SGPT_ERR_RANGE, "SGPT_F16: a matmul weight exceeds the f16 range (or a LayerNorm parameter is not finite); load with SGPT_BF16");
-        if (st == SGPT_OK && !(bound < 32768.f)) {
+        // (BERT: shifts stay 0 -- its write-back LayerNorm carries a run-time range tracker instead of relying on this bound)
+        if (st == SGPT_OK && !(bound < 32768.f) && !bert) {
             int k = (int)std::ceil(std::log2(bound / 16384.f));
             k = k < 1 ? 1 : k;
             if (k > RS_MAX_SHIFT) st = fail(c, SGPT_ERR_RANGE, "SGPT_F16: LayerNorm parameters beyond any usable range shift; load with SGPT_BF16");
@@ -331,6 +378,8 @@ sgpt_status sgpt_model_range_adapt(sgpt_model* m, int32_t* n_raised, void* strea
     sgpt_ctx* c = m->ctx;
     *n_raised = 0;
     if (m->d.compute_dtype != SGPT_F16) return fail(c, SGPT_ERR_INVALID, "sgpt_model_range_adapt applies to SGPT_F16 models");
+    if (m->d.arch == SGPT_ARCH_BERT)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_model_range_adapt: SGPT_ARCH_BERT runs without range shifts; a flagged f16 model must be loaded with SGPT_BF16 or SGPT_F32");
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int n = m->d.n_layers * RS_N;
@@ -373,6 +422,7 @@ sgpt_status sgpt_model_set_range_shifts(sgpt_model* m, const int32_t* shifts, in
     sgpt_ctx* c = m->ctx;
     if (m->d.compute_dtype != SGPT_F16 || !shifts || n != m->d.n_layers * RS_N)
         return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_range_shifts: SGPT_F16 models, n = 4 * n_layers");
+    if (m->d.arch == SGPT_ARCH_BERT) return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_range_shifts: SGPT_ARCH_BERT runs without range shifts");
     for (int i = 0; i < n; ++i)
         if (shifts[i] < 0 || shifts[i] > RS_MAX_SHIFT) return fail(c, SGPT_ERR_INVALID, "range shifts must lie in [0, 40]");
     // the LayerNorm kernels have no run-time range tracker: their shifts may not go below the bound sgpt_model_load derived
@@ -408,6 +458,7 @@ sgpt_status sgpt_model_set_precision(sgpt_model* m, const int32_t* plan, int32_t
         if (cls == PC_LN2 && m->d.arch == SGPT_ARCH_GPTJ && v != 0 && plan[i - PC_LN2 + PC_LN1] == 0)
             return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision: GPT-J's MLP reads ln_1's output: a split fc1 needs a split LayerNorm-1 entry");
     }
+    if (any && m->d.arch == SGPT_ARCH_BERT) return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision: no split-precision operands for SGPT_ARCH_BERT");
     if (any && cd != SGPT_F16 && cd != SGPT_BF16) return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision applies to SGPT_F16 / SGPT_BF16 models");
     for (int i = 0; i < n; ++i) m->prec[i] = plan[i];
     c->generation++;                                      // captured graphs carry the old launch sequence
@@ -464,7 +515,7 @@ sgpt_status sgpt_model_release_split_weights(sgpt_model* m, int64_t* bytes_freed
 sgpt_status sgpt_model_precision_probe_begin(sgpt_model* m) {
     if (!m) return SGPT_ERR_INVALID;
     sgpt_ctx* c = m->ctx;
-    if (!m->crest_dev) return fail(c, SGPT_ERR_INVALID, "the precision probe applies to SGPT_F16 / SGPT_BF16 models");
+    if (!m->crest_dev || m->d.arch == SGPT_ARCH_BERT) return fail(c, SGPT_ERR_INVALID, "the precision probe applies to SGPT_F16 / SGPT_BF16 models of the decoder families");
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipDeviceSynchronize());
     HIPC(c, hipMemset(m->crest_dev, 0, (size_t)m->d.n_layers * RS_N * 4));

@@ -6,8 +6,8 @@ extern "C" {
 
 sgpt_status sgpt_pool(sgpt_ctx* c, const void* hidden, int32_t dtype, const int32_t* mask, int32_t B, int32_t S,
                       int32_t d, int32_t mode, float* out, void* stream) {
-    if (!c || !hidden || !mask || !out || B <= 0 || S <= 0 || d <= 0 || d % 4 || mode < 0 || mode > 2)
-        return fail(c, SGPT_ERR_INVALID, "sgpt_pool: bad arguments (d % 4 == 0 required)");
+    if (!c || !hidden || !mask || !out || B <= 0 || S <= 0 || d <= 0 || d % 4 || mode < 0 || (mode > 2 && mode != SGPT_POOL_CLS))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_pool: bad arguments (d % 4 == 0 required; mode 0 | 1 | 2 | 4)");
     HIPC(c, hipSetDevice(c->device));
     launch_pool(hidden, dtype, mask, B, S, d, mode, nullptr, out, (hipStream_t)stream);
     HIPC(c, hipGetLastError());
@@ -119,12 +119,12 @@ sgpt_status sgpt_linear(sgpt_ctx* c, int32_t dtype, int32_t epi, int32_t out_dty
     if (!c || !A || !W || !out || M <= 0 || N <= 0 || K <= 0) return fail(c, SGPT_ERR_INVALID, "sgpt_linear: bad arguments");
     const bool in16 = dtype == SGPT_BF16 || dtype == SGPT_F16, o16 = out_dtype == SGPT_BF16 || out_dtype == SGPT_F16;
     if (!in16 && dtype != SGPT_F32) return fail(c, SGPT_ERR_INVALID, "sgpt_linear: bad dtype");
-    if (epi != EPI_STORE && epi != EPI_BIAS_GELU && epi != EPI_BIAS_RESID && epi != EPI_VT)
-        return fail(c, SGPT_ERR_INVALID, "sgpt_linear: epi must be 0 (store), 1 (bias+gelu), 2 (bias+residual) or 4 (transposed store)");
-    if ((epi == EPI_BIAS_GELU || epi == EPI_BIAS_RESID) && !bias) return fail(c, SGPT_ERR_INVALID, "sgpt_linear: bias required");
+    if (epi != EPI_STORE && !epi_is_gelu(epi) && epi != EPI_BIAS_RESID && epi != EPI_VT)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_linear: epi must be 0 (store), 1 (bias+gelu), 2 (bias+residual), 4 (transposed store) or 9 (bias+erf gelu)");
+    if ((epi_is_gelu(epi) || epi == EPI_BIAS_RESID) && !bias) return fail(c, SGPT_ERR_INVALID, "sgpt_linear: bias required");
     if (epi == EPI_BIAS_RESID && (!resid || out_dtype != SGPT_F32)) return fail(c, SGPT_ERR_INVALID, "sgpt_linear: residual epilogue is fp32");
     if (epi == EPI_VT && (!in16 || out_dtype != dtype || M % 128)) return fail(c, SGPT_ERR_INVALID, "sgpt_linear: transposed store is 16-bit, M % 128 == 0");
-    if (epi == EPI_BIAS_GELU && out_dtype != dtype) return fail(c, SGPT_ERR_INVALID, "sgpt_linear: gelu output has the operand dtype");
+    if (epi_is_gelu(epi) && out_dtype != dtype) return fail(c, SGPT_ERR_INVALID, "sgpt_linear: gelu output has the operand dtype");
     if (in16 && (o16 ? out_dtype != dtype : false)) return fail(c, SGPT_ERR_INVALID, "sgpt_linear: 16-bit output must match the operand format");
     if (!in16 && o16) return fail(c, SGPT_ERR_INVALID, "sgpt_linear: fp32 operands give fp32 output");
     if (K % (in16 ? 8 : 4) || (epi != EPI_STORE && N % 4)) return fail(c, SGPT_ERR_INVALID, "sgpt_linear: K % 8 (16-bit) / 4 (fp32), N % 4");
@@ -183,11 +183,19 @@ sgpt_status sgpt_linear_split(sgpt_ctx* c, int32_t dtype, int32_t epi, const voi
     return SGPT_OK;
 }
 
-sgpt_status sgpt_attention(sgpt_ctx* c, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
-                           void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t dh,
-                           int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
-                           float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
-                           int64_t ctx_lo_delta, int64_t ctx_hi2_delta, void* stream) {
+sgpt_status sgpt_attention_ex(sgpt_ctx* c, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
+                              void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t dh,
+                              int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
+                              float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
+                              int64_t ctx_lo_delta, int64_t ctx_hi2_delta, int32_t causal, const int32_t* seq_len, void* stream) {
+    if (causal != 0 && causal != 1) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_ex: causal 0 | 1");
+    if (causal && seq_len) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_ex: seq_len belongs to the bidirectional mode (causal = 0)");
+    if (!causal) {
+        if (window != 0 || alibi != nullptr) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_ex: bidirectional attention takes no window and no ALiBi");
+        if (out_fp8 || x3 || ctx_lo_delta != 0 || ctx_hi2_delta != 0)
+            return fail(c, SGPT_ERR_INVALID, "sgpt_attention_ex: out_fp8 and the split-precision modes are causal only");
+        if (dtype != SGPT_F32 && dh != 64 && dh != 128) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_ex: 16-bit bidirectional attention serves head_dim 64 | 128");
+    }
     // every combination launch_attn_bf16 would abort() on is refused here, before anything is launched
     auto mis = [](const void* p, unsigned a) { return ((uintptr_t)p & (a - 1)) != 0; };
     if (!c || !q || !k || !v || !out || !seq_off || B <= 0 || T <= 0 || H <= 0 || window < 0 || !std::isfinite(scale))
@@ -229,10 +237,20 @@ sgpt_status sgpt_attention(sgpt_ctx* c, int32_t dtype, const void* q, const void
     at.out_fp8 = out_fp8 ? 1 : 0; at.out_scale = out_scale; at.range_flag = range_flag;
     at.x3 = x3 ? 1 : 0; at.qk_lo_delta = qk_lo_delta; at.v_lo_delta = v_lo_delta;
     at.ctx_lo_delta = ctx_lo_delta; at.ctx_hi2_delta = ctx_hi2_delta;
+    at.noncausal = causal ? 0 : 1; at.seq_len = seq_len;
     if (in16) launch_attn_bf16(at, (hipStream_t)stream);
     else launch_attn_f32(at, (hipStream_t)stream);
     HIPC(c, hipGetLastError());
     return SGPT_OK;
+}
+
+sgpt_status sgpt_attention(sgpt_ctx* c, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
+                           void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t dh,
+                           int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
+                           float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
+                           int64_t ctx_lo_delta, int64_t ctx_hi2_delta, void* stream) {
+    return sgpt_attention_ex(c, dtype, q, k, v, ldq, ldvt, out, ldo, seq_off, B, T, H, dh, window, scale, alibi, max_alloc_len, out_fp8,
+                             out_scale, range_flag, x3, qk_lo_delta, v_lo_delta, ctx_lo_delta, ctx_hi2_delta, 1, nullptr, stream);
 }
 
 // ---- the encoder's row kernels stand-alone (elementwise.hip; tests/test_gpu_rowops.py): every argument a launch would index or
@@ -270,6 +288,20 @@ sgpt_status sgpt_layernorm(sgpt_ctx* c, const float* x, const float* gamma, cons
     HIPC(c, hipSetDevice(c->device));
     if (split) launch_layernorm_split(x, gamma, beta, out, out_dtype, T, d, eps, (hipStream_t)stream, out_mul);
     else launch_layernorm(x, gamma, beta, out, out_dtype, T, d, eps, (hipStream_t)stream, out_mul);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_layernorm_writeback(sgpt_ctx* c, float* x, const float* gamma, const float* beta, int32_t T, int32_t d, float eps,
+                                     void* out16, int32_t out_dtype, void* stream) {
+    if (!c || !x || !gamma || !beta || !out16 || T <= 0 || !row_width_ok(d) || !(eps >= 0.f) || !std::isfinite(eps))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_layernorm_writeback: bad arguments (d % 4 == 0, d <= 4096)");
+    if (out_dtype != SGPT_BF16 && out_dtype != SGPT_F16) return fail(c, SGPT_ERR_INVALID, "sgpt_layernorm_writeback: out_dtype SGPT_BF16 | SGPT_F16");
+    if ((const void*)out16 == (const void*)x) return fail(c, SGPT_ERR_INVALID, "sgpt_layernorm_writeback: out16 is a buffer of its own");
+    if (mis(x, 16) || mis(gamma, 16) || mis(beta, 16) || mis(out16, 8))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_layernorm_writeback: 16-byte aligned x / gamma / beta, 8-byte aligned out16");
+    HIPC(c, hipSetDevice(c->device));
+    launch_layernorm_writeback(x, gamma, beta, out16, out_dtype, T, d, eps, out_dtype == SGPT_F16 ? c->range_flag : nullptr, (hipStream_t)stream);
     HIPC(c, hipGetLastError());
     return SGPT_OK;
 }

@@ -20,8 +20,8 @@ from typing import Dict, List, Optional
 import numpy as np
 
 _POOL_FLAGS = {"pooling_mode_mean_tokens": "mean", "pooling_mode_weightedmean_tokens": "weightedmean",
-               "pooling_mode_lasttoken": "lasttoken"}
-_UNSUPPORTED_POOL_FLAGS = ("pooling_mode_cls_token", "pooling_mode_max_tokens", "pooling_mode_mean_sqrt_len_tokens")
+               "pooling_mode_lasttoken": "lasttoken", "pooling_mode_cls_token": "cls"}   # cls: the BERT / SBERT baselines
+_UNSUPPORTED_POOL_FLAGS = ("pooling_mode_max_tokens", "pooling_mode_mean_sqrt_len_tokens")
 _SBERT_CONFIG_NAMES = ("sentence_bert_config.json", "sentence_roberta_config.json", "sentence_distilbert_config.json",
                        "sentence_camembert_config.json", "sentence_albert_config.json",
                        "sentence_xlm-roberta_config.json", "sentence_xlnet_config.json")   # Transformer.py:168

@@ -60,7 +60,7 @@ class SGPTConfig:
     window_size: int = 256
     attention_layers: Optional[List[str]] = None
     layer_norm_epsilon: float = 1e-5
-    model_type: str = "gpt_neo"          # "gpt_neo" (SGPT-125M/1.3B/2.7B) | "gptj" (SGPT-5.8B)
+    model_type: str = "gpt_neo"          # "gpt_neo" (SGPT-125M/1.3B/2.7B) | "gptj" (SGPT-5.8B) | "bloom" | "bert" (the BERT / SBERT baselines)
     rotary_dim: int = 0                   # GPT-J only (HF GPTJConfig.rotary_dim = 64)
 
     def __post_init__(self):
@@ -83,8 +83,19 @@ class SGPTConfig:
                        num_layers=c["n_layer"], num_heads=c["n_head"], intermediate_size=4 * c["hidden_size"],
                        layer_norm_epsilon=c.get("layer_norm_epsilon", 1e-5), model_type="bloom", window_size=0,
                        attention_layers=["global"] * c["n_layer"])
+        if mt == "bert":   # HF BertConfig (HF:bert/configuration_bert.py): the baseline of the reference's own scripts
+            if c.get("hidden_act", "gelu") != "gelu":
+                raise NotImplementedError(f"bert: hidden_act {c.get('hidden_act')!r} (only 'gelu', the erf form, is built)")
+            if c.get("position_embedding_type", "absolute") != "absolute":
+                raise NotImplementedError(f"bert: position_embedding_type {c.get('position_embedding_type')!r} (only 'absolute')")
+            if c.get("type_vocab_size", 2) < 1:
+                raise NotImplementedError("bert: type_vocab_size must be >= 1 (token type 0 is folded into the position table)")
+            return cls(vocab_size=c["vocab_size"], max_position_embeddings=c["max_position_embeddings"],
+                       hidden_size=c["hidden_size"], num_layers=c["num_hidden_layers"], num_heads=c["num_attention_heads"],
+                       intermediate_size=c["intermediate_size"], layer_norm_epsilon=c.get("layer_norm_eps", 1e-12),
+                       model_type="bert", window_size=0, attention_layers=["global"] * c["num_hidden_layers"])
         if mt != "gpt_neo":
-            raise NotImplementedError(f"model_type {mt!r}: GPT-Neo, GPT-J and BLOOM are the SGPT families")
+            raise NotImplementedError(f"model_type {mt!r}: GPT-Neo, GPT-J, BLOOM and BERT are the families built here")
         layers = c.get("attention_layers")
         if layers is None and c.get("attention_types"):
             layers = []
@@ -308,7 +319,7 @@ class SGPTModel:
         if dtype in ("fp16", "float16", "half"):
             dtype = "f16"
         if precision is None:
-            precision = "auto" if dtype == "f16" else "plain"
+            precision = "auto" if (dtype == "f16" and cfg.model_type != "bert") else "plain"   # (BERT: nothing to probe for)
         if precision not in ("plain", "x3", "auto", "auto-class"):
             raise ValueError("precision must be 'plain', 'x3', 'auto' or 'auto-class'")
         if precision != "plain" and dtype not in ("f16", "bf16"):
@@ -321,6 +332,13 @@ class SGPTModel:
             raise ValueError(f"precise_qk must be None, False, True or one of {sorted(PRECISE_QK_PLANS)}")
         if precise_qk and dtype not in ("f16", "bf16"):
             raise ValueError("precise_qk applies to dtype 'f16' / 'bf16'")
+        bert = cfg.model_type == "bert"
+        if bert:
+            # one arithmetic per operand format for this family (include/sgpt_hip.h, SGPT_ARCH_BERT): refused here, loudly
+            if dtype in ("fp8", "fp8mfma"):
+                raise ValueError(f"dtype {dtype!r} is not available for BERT models: use 'f16', 'bf16' or 'fp32'")
+            if precision != "plain" or precise_qk:
+                raise ValueError("split-precision operands (precision='x3' / 'auto' / 'auto-class', precise_qk) are not available for BERT models")
         if dtype not in ("f16", "bf16", "fp32", "fp8", "fp8mfma"):
             raise ValueError("dtype must be 'f16' (IEEE-half MFMA operands, range-guarded: the 1e-3-parity mode), "
                              "'bf16' (bf16 MFMA operands), 'fp32' (exact fp32 MFMA), "
@@ -339,11 +357,13 @@ class SGPTModel:
         gptj, bloom = cfg.model_type == "gptj", cfg.model_type == "bloom"
         dh = cfg.hidden_size // cfg.num_heads
         arch = _lib.SGPT_ARCH_GPTJ if gptj else (_lib.SGPT_ARCH_BLOOM if bloom else _lib.SGPT_ARCH_GPTNEO)
+        if bert:
+            arch = _lib.SGPT_ARCH_BERT
         desc = ModelDesc(arch=arch, n_layers=cfg.num_layers,
                          d_model=cfg.hidden_size, n_heads=cfg.num_heads, d_ffn=cfg.intermediate_size,
                          vocab=cfg.vocab_size, max_pos=cfg.max_position_embeddings, window=cfg.window_size,
                          ln_eps=cfg.layer_norm_epsilon,
-                         attn_scale=float(1.0 / np.sqrt(np.float32(dh))) if (gptj or bloom) else 1.0,   # HF:gptj:148, HF:bloom:186 / HF:gpt_neo:110
+                         attn_scale=float(1.0 / np.sqrt(np.float32(dh))) if (gptj or bloom or bert) else 1.0,   # HF:gptj:148, HF:bloom:186 / HF:gpt_neo:110
                          compute_dtype={"f16": SGPT_F16, "bf16": SGPT_BF16, "fp32": SGPT_F32, "fp8": SGPT_FP8W,
                                         "fp8mfma": SGPT_FP8M}[dtype],
                          layer_is_local=C.cast(local, C.POINTER(C.c_uint8)), rotary_dim=cfg.rotary_dim if gptj else 0,
@@ -361,6 +381,8 @@ class SGPTModel:
         if bloom:
             weights = dict(weights)
             weights["alibi.slopes"] = alibi_slopes(cfg.num_heads)
+        if bert:
+            weights = bert_state_dict(weights)
         names, keep = [], []
         for k, v in weights.items():
             k2 = k[len("transformer."):] if k.startswith("transformer.") else k
@@ -668,6 +690,8 @@ class SGPTModel:
     def _check_learnt(self, mode: str, pb: PackedBatch) -> None:
         if mode != "learntmean":
             return
+        if self.cfg.model_type == "bert":
+            raise ValueError("method 'learntmean' (trained position weights of the SGPT checkpoints) is not available for BERT models")
         if self.position_weights is None:
             raise ValueError("method 'learntmean' needs trained position weights (1_WeightedMeanPooling)")
         if pb.max_pos >= self.position_weights.numel():
@@ -693,6 +717,8 @@ class SGPTModel:
     def lm_logprobs(self, hidden: torch.Tensor, row_idx, targets, return_greedy: bool = False):
         """log P(targets[i] | prefix ending at token row row_idx[i]) from post-ln_f hidden states [T_pad, d]
         (the log_softmax + gather of crossencoder/beir/sgptce.py:233-255) -> fp32[n] on the GPU."""
+        if self.cfg.model_type == "bert":
+            raise ValueError("lm_logprobs: a BERT model carries no causal LM head")
         ri = torch.as_tensor(np.asarray(row_idx, dtype=np.int32)).to(self.device)
         tg = torch.as_tensor(np.asarray(targets, dtype=np.int32)).to(self.device)
         n = int(ri.numel())
@@ -836,7 +862,8 @@ class SGPTModel:
         flags = self.range_flags(reset=False)
         if not flags:
             return False
-        if flags & 1 and not flags & 6 and adapt and self.dtype == "f16" and self._adapt_range():
+        # (BERT models run without range shifts: nothing to adapt, the flag is final)
+        if flags & 1 and not flags & 6 and adapt and self.dtype == "f16" and self.cfg.model_type != "bert" and self._adapt_range():
             return True                      # (sgpt_model_range_adapt cleared bit 0 and the recorded magnitudes)
         self.range_flags(reset=True)
         if flags & 2:
@@ -1015,6 +1042,59 @@ def load_state_dict(root: str) -> Dict[str, torch.Tensor]:
                 sd.update(read(os.path.join(root, sh)))
             return sd
     raise FileNotFoundError(f"no model.safetensors / pytorch_model.bin (single or sharded) under {root}")
+
+
+def bert_state_dict(weights) -> dict:
+    """HF BertModel / BertFor* state dict -> the tensors include/sgpt_hip.h asks for under SGPT_ARCH_BERT: the `bert.` prefix and
+    the `pooler.*` / `cls.*` heads are dropped, `embeddings.position_ids` / `token_type_ids` buffers too, and -- token types are
+    all 0 on this path (single-segment inputs, biencoder/beir/beir_dense_retriever.py:128-136) -- row 0 of
+    `embeddings.token_type_embeddings.weight` is added to every row of the position table (one fp32 add per element, the order
+    HF sums them in: inputs + token_type, then + position, differs by one rounding from this one)."""
+    out = {}
+    for k, v in weights.items():
+        k2 = k[len("bert."):] if k.startswith("bert.") else k
+        if k2.startswith(("pooler.", "cls.", "classifier.")) or k2.endswith(("position_ids", "token_type_ids")) or k.startswith("cls."):
+            continue
+        out[k2] = v
+    tt = out.pop("embeddings.token_type_embeddings.weight", None)
+    if tt is not None:
+        pos = out["embeddings.position_embeddings.weight"]
+        as_t = lambda a: a.detach().to(torch.float32).cpu() if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a, dtype=np.float32))  # noqa: E731
+        out["embeddings.position_embeddings.weight"] = as_t(pos) + as_t(tt)[0][None, :]
+    return out
+
+
+def synthetic_bert_weights(cfg: SGPTConfig, seed: int = 0, std: float = 0.02) -> Dict[str, np.ndarray]:
+    """Seeded random-init weights under HF BertModel state-dict names (bench, tests: no checkpoints exist offline)."""
+    rng = np.random.default_rng(seed)
+    d, ffn = cfg.hidden_size, cfg.intermediate_size
+    f32 = np.float32
+
+    def nrm(*shape, s=std):
+        return (rng.standard_normal(shape, dtype=np.float32) * f32(s)).astype(f32)
+
+    def ln(name):
+        w[name + ".weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
+        w[name + ".bias"] = nrm(d, s=0.05)
+
+    w = {"embeddings.word_embeddings.weight": nrm(cfg.vocab_size, d),
+         "embeddings.position_embeddings.weight": nrm(cfg.max_position_embeddings, d, s=std / 2),
+         "embeddings.token_type_embeddings.weight": nrm(2, d, s=std / 2)}
+    ln("embeddings.LayerNorm")
+    for i in range(cfg.num_layers):
+        p = f"encoder.layer.{i}."
+        for n in ("query", "key", "value"):
+            w[p + f"attention.self.{n}.weight"] = nrm(d, d)
+            w[p + f"attention.self.{n}.bias"] = nrm(d, s=0.02)
+        w[p + "attention.output.dense.weight"] = nrm(d, d)
+        w[p + "attention.output.dense.bias"] = nrm(d, s=0.02)
+        ln(p + "attention.output.LayerNorm")
+        w[p + "intermediate.dense.weight"] = nrm(ffn, d)
+        w[p + "intermediate.dense.bias"] = nrm(ffn, s=0.02)
+        w[p + "output.dense.weight"] = nrm(d, ffn)
+        w[p + "output.dense.bias"] = nrm(d, s=0.02)
+        ln(p + "output.LayerNorm")
+    return w
 
 
 def alibi_slopes(n_head: int) -> np.ndarray:

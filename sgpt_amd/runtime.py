@@ -70,7 +70,8 @@ class Context:
     # ---- a4: stand-alone pooling ----
     def pool(self, hidden: torch.Tensor, mask: torch.Tensor, mode: str = "weightedmean",
              position_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """mode 'learntmean' takes `position_weights` (WeightedMeanPooling.py:21-39), indexed by the padded position."""
+        """mode 'learntmean' takes `position_weights` (WeightedMeanPooling.py:21-39), indexed by the padded position; 'cls' is
+        row 0 of every sequence, whatever the mask (Pooling.py:103-105)."""
         if mode not in POOL_MODES:
             raise ValueError(f"unknown pooling mode {mode}")
         hidden = hidden.to(self.device)
@@ -212,8 +213,9 @@ class Context:
     # ---- the projection GEMM with a fused epilogue (kernel-level tests, custom blocks) ----
     def linear(self, a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, epi: str = "store",
                resid: Optional[torch.Tensor] = None, out_dtype=None) -> torch.Tensor:
-        """epi: 'store' | 'gelu' (gelu_new(a.w^T + bias)) | 'resid' (resid + a.w^T + bias, fp32) | 'vt' (transposed)."""
-        code = {"store": 0, "gelu": 1, "resid": 2, "vt": 4}[epi]
+        """epi: 'store' | 'gelu' (gelu_new(a.w^T + bias)) | 'gelu_erf' (the BERT family's erf GELU) | 'resid' (resid + a.w^T + bias,
+        fp32) | 'vt' (transposed)."""
+        code = {"store": 0, "gelu": 1, "resid": 2, "vt": 4, "gelu_erf": 9}[epi]
         M, K = a.shape
         N = w.shape[0]
         if out_dtype is None:
@@ -269,10 +271,13 @@ class Context:
     def attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, seq_off: torch.Tensor,
                   H: int, dh: int, max_alloc_len: int, window: int = 0, scale: float = 1.0, alibi: Optional[torch.Tensor] = None,
                   out_scale: float = 0.0, range_flag: Optional[torch.Tensor] = None, x3: bool = False, qk_lo_delta: int = 0,
-                  v_lo_delta: int = 0, ctx_lo_delta: int = 0, ctx_hi2_delta: int = 0) -> torch.Tensor:
+                  v_lo_delta: int = 0, ctx_lo_delta: int = 0, ctx_hi2_delta: int = 0, causal: Optional[bool] = None,
+                  seq_len: Optional[torch.Tensor] = None) -> torch.Tensor:
         """include/sgpt_hip.h::sgpt_attention on caller-laid-out buffers (the over-read contract there is the caller's): q, k
         [T, >= H dh] row views of one leading dimension; v = V^T [H dh, >= T] (16-bit) or [T, ...] with q's leading dimension
-        (fp32); out [T, ...] in q's dtype, or uint8 (e4m3 codes of ctx / out_scale, bf16 operands).  Deltas in elements."""
+        (fp32); out [T, ...] in q's dtype, or uint8 (e4m3 codes of ctx / out_scale, bf16 operands).  Deltas in elements.
+        causal None: the sgpt_attention entry.  True / False: sgpt_attention_ex -- False is the bidirectional mode of the BERT family,
+        every query of a sequence sees its keys [0, seq_len[b]) (seq_len int32 [B]; None = the whole allocation)."""
         T = q.shape[0]
         out_fp8 = out.dtype == torch.uint8
         if q.dtype not in DT_CODE:
@@ -287,6 +292,14 @@ class Context:
             raise ValueError("attention: fp32 v rows share q's leading dimension (the fp32 kernel reads v with ldq)")
         so = seq_off.to(device=self.device, dtype=torch.int32).contiguous()
         al = None if alibi is None else alibi.to(device=self.device, dtype=torch.float32).contiguous()
+        if causal is not None:
+            sl = None if seq_len is None else seq_len.to(device=self.device, dtype=torch.int32).contiguous()
+            self._chk(self.lib.sgpt_attention_ex(self.handle, DT_CODE[q.dtype], _p(q), _p(k), _p(v), q.stride(0), v.stride(0), _p(out),
+                                                 out.stride(0), _p(so), so.numel() - 1, T, H, dh, window, scale, _p(al), max_alloc_len,
+                                                 1 if out_fp8 else 0, out_scale, _p(range_flag), 1 if x3 else 0, qk_lo_delta,
+                                                 v_lo_delta, ctx_lo_delta, ctx_hi2_delta, 1 if causal else 0, _p(sl),
+                                                 _stream_ptr(self.device)), "sgpt_attention_ex")
+            return out
         self._chk(self.lib.sgpt_attention(self.handle, DT_CODE[q.dtype], _p(q), _p(k), _p(v), q.stride(0), v.stride(0), _p(out),
                                           out.stride(0), _p(so), so.numel() - 1, T, H, dh, window, scale, _p(al), max_alloc_len,
                                           1 if out_fp8 else 0, out_scale, _p(range_flag), 1 if x3 else 0, qk_lo_delta,
@@ -325,6 +338,16 @@ class Context:
         self._chk(self.lib.sgpt_layernorm(self.handle, _p(x), _p(self._f32c(gamma)), _p(self._f32c(beta)), T, d, float(eps), _p(out),
                                           DT_CODE[out_dtype], float(out_mul), 1 if split else 0, _stream_ptr(self.device)),
                   "sgpt_layernorm")
+        return out
+
+    def layernorm_writeback(self, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-12,
+                            out_dtype=torch.float16) -> torch.Tensor:
+        """The LayerNorm of a post-LN block (include/sgpt_hip.h::sgpt_layernorm_writeback): x fp32 [T, d] is normalised IN PLACE and
+        the same values, rounded once, are returned as a [T, d] tensor of out_dtype (f16 | bf16)."""
+        T, d = x.shape
+        out = torch.empty((T, d), dtype=out_dtype, device=self.device)
+        self._chk(self.lib.sgpt_layernorm_writeback(self.handle, _p(x), _p(self._f32c(gamma)), _p(self._f32c(beta)), T, d, float(eps),
+                                                    _p(out), DT_CODE[out_dtype], _stream_ptr(self.device)), "sgpt_layernorm_writeback")
         return out
 
     def lnf_pool(self, x: torch.Tensor, seq_off: torch.Tensor, seq_len: torch.Tensor, pad_left: Optional[torch.Tensor] = None,

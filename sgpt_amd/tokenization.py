@@ -59,6 +59,11 @@ def load_tokenizer(model_name_or_path: str):
     return tok
 
 
+def is_bert(model) -> bool:
+    """Does this model object (SGPTModel, or a stand-in with a `cfg`) belong to the BERT family?"""
+    return getattr(getattr(model, "cfg", None), "model_type", None) == "bert"
+
+
 class TextPipeline:
     """text -> truncated id list (+ brackets).
 
@@ -68,15 +73,29 @@ class TextPipeline:
     st_path: the marker travels inside the text through the tokenizer call of Transformer.tokenize_bos_eos
            (Transformer.py:131-135, `max_length = max_seq_length - 2` INCLUDING the marker), so the content is cut to
            max_seq_length - 3 tokens; the raw-HF path (beir_dense_retriever.py:134-136,172-191) cuts the content to
-           max_seq_length - 2 and adds both brackets afterwards."""
+           max_seq_length - 2 and adds both brackets afterwards.
+    bert:  the model is a BERT encoder: the content is cut to max_token_len - 2 and framed `[CLS]` .. `[SEP]` with the
+           tokenizer's cls_token_id / sep_token_id (beir_dense_retriever.py:128-136); the reference brackets GPT inputs only, so
+           specb / speca are refused."""
 
-    def __init__(self, tokenizer, max_token_len: int, specb: bool = False, speca: bool = False, st_path: bool = False):
+    def __init__(self, tokenizer, max_token_len: int, specb: bool = False, speca: bool = False, st_path: bool = False,
+                 bert: bool = False):
         if speca and specb:
             raise ValueError("speca and specb are mutually exclusive")
+        self.frame = None
+        if bert:
+            if specb or speca:
+                raise ValueError("specb / speca brackets belong to the GPT models; a BERT model is framed [CLS] ... [SEP]")
+            cls_id, sep_id = getattr(tokenizer, "cls_token_id", None), getattr(tokenizer, "sep_token_id", None)
+            if cls_id is None or sep_id is None:
+                raise ValueError("a BERT model needs a tokenizer with cls_token_id and sep_token_id")
+            self.frame = ([int(cls_id)], [int(sep_id)])
         self.tok = tokenizer
         self.specb, self.speca, self.st_path = specb, speca, st_path
         bracketed = specb or speca
         self.max_token_len = max_token_len - (3 if st_path else 2) if bracketed else max_token_len   # :134-136
+        if self.frame:
+            self.max_token_len = max_token_len - 2                                                     # :128-136
         if specb:
             self.bos_q = list(tokenizer.encode(SPECB_QUE_BOS))
             self.eos_q = list(tokenizer.encode(SPECB_QUE_EOS))
@@ -104,6 +123,8 @@ class TextPipeline:
         tokens = list(tokens[: self.max_token_len])
         if self.specb or self.speca:                                            # :186-191
             tokens = (self.bos_q + tokens + self.eos_q) if is_query else (self.bos_d + tokens + self.eos_d)
+        if self.frame:                                                          # :131-132
+            tokens = self.frame[0] + tokens + self.frame[1]
         return tokens
 
     def batch(self, texts: Sequence[str], is_query: bool) -> List[List[int]]:
@@ -130,5 +151,7 @@ class TextPipeline:
                 raise ValueError("Empty items should be cleaned prior to running")  # :180-181
             if bracket:                                                             # :186-191
                 tokens = (self.bos_q + tokens + self.eos_q) if is_query else (self.bos_d + tokens + self.eos_d)
+            if self.frame:                                                          # :131-132
+                tokens = self.frame[0] + list(tokens) + self.frame[1]
             out.append(tokens)
         return out
