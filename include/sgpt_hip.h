@@ -571,7 +571,12 @@ sgpt_status sgpt_eval_pairs(sgpt_ctx* ctx, const float* score, const int32_t* la
  *   epi 9: out[M,N] = gelu(acc + bias), 0.5 u (1 + erf(u / sqrt 2))   out_dtype = dtype   (ABI v13; HF GELUActivation, the BERT family)
  * bias device fp32[N]; resid device fp32[M,N].  M % 256 == 0, N % 256 == 0, K % 64 == 0 with at least half a wave of
  * 256x256 tiles take the LDS-DMA throughput kernel, everything else the 128x128 / 64x64 register-staged one; both
- * feed every output element the same MFMA sequence, so the result does not depend on which one ran. */
+ * feed every output element the same MFMA sequence, so the result does not depend on which one ran.
+ * Accepted shapes: any M >= 1 (epi 4: M % 128 == 0); K % 8 == 0 for 16-bit operands, K % 4 == 0 for fp32 (rows of A and W
+ * are read in 16-byte chunks; a K that is no multiple of the kernel's k-step is zero-filled inside the kernel); N % 4 == 0
+ * for epi 1, 2, 4 and 9, any N >= 1 for epi 0 (the LM head, N = 50257) -- out is then a dense [M,N] array whose rows are
+ * not 8- / 16-byte aligned, which the vector stores of the epilogue allow.  fp32 operands give fp32 output and have no
+ * epi 4.  Anything else is SGPT_ERR_INVALID and leaves out untouched (tests/test_gpu_linear_edges.py). */
 sgpt_status sgpt_linear(sgpt_ctx* ctx, int32_t dtype, int32_t epi, int32_t out_dtype, const void* A, const void* W,
                         const float* bias, const float* resid, void* out, int32_t M, int32_t N, int32_t K, void* stream);
 

@@ -1,0 +1,232 @@
+"""Test infrastructure: the projection GEMM with its fused epilogues (include/sgpt_hip.h::sgpt_linear / sgpt_linear_split) in
+float64 numpy, a derived error bound for any fp32 accumulation of the same products, a Python mirror of the launch rule of
+csrc/gemm.hip, and the shape table of tests/test_gpu_linear_edges.py.  Checked without a GPU by tests/test_gemm_ref.py.
+
+Operands are the exact values of the already rounded inputs (16-bit x 16-bit and fp32 x fp32 products are taken as the float64
+product of the stored values), so the only error a kernel may show is that of its fp32 accumulation, of the epilogue function
+and of the one rounding to the output format."""
+import math
+from collections import namedtuple
+
+import numpy as np
+
+EPI_STORE, EPI_GELU, EPI_RESID, EPI_VT, EPI_GELU_ERF = 0, 1, 2, 4, 9
+U16 = {"bf16": 2.0 ** -8, "f16": 2.0 ** -11}
+GELU_SLOPE = 1.13                                     # max |gelu'| of both GELUs (1.1290 at u = 1.41): an error of the sum through the function
+
+
+def _erf(x):
+    """float64 erf, vectorised (torch's; tests/test_gemm_ref.py pins it to math.erf -- np.vectorize(math.erf) takes seconds on
+    the large cases)."""
+    import torch
+    return torch.erf(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))).numpy()
+
+
+def gelu_new(u):
+    """HF NewGELUActivation (gelu_new): 0.5 u (1 + tanh(sqrt(2 / pi) (u + 0.044715 u^3)))."""
+    u = np.asarray(u, np.float64)
+    return 0.5 * u * (1.0 + np.tanh(math.sqrt(2.0 / math.pi) * (u + 0.044715 * u ** 3)))
+
+
+def gelu_erf(u):
+    """HF GELUActivation ("gelu"): 0.5 u (1 + erf(u / sqrt 2))."""
+    u = np.asarray(u, np.float64)
+    return 0.5 * u * (1.0 + _erf(u / math.sqrt(2.0)))
+
+
+def product(a, w):
+    """a w^T in float64 (the part of linear_ref worth computing once per case)."""
+    return np.asarray(a, np.float64) @ np.asarray(w, np.float64).T
+
+
+def epilogue(u, bias, resid, epi):
+    """The epilogue of sgpt_linear on the float64 product u [M, N]."""
+    if bias is not None:
+        u = u + np.asarray(bias, np.float64)[None, :]
+    if epi == EPI_STORE:
+        return u
+    if epi == EPI_GELU:
+        return gelu_new(u)
+    if epi == EPI_GELU_ERF:
+        return gelu_erf(u)
+    if epi == EPI_RESID:
+        return np.asarray(resid, np.float64) + u
+    if epi == EPI_VT:
+        return np.ascontiguousarray(u.T)
+    raise ValueError(f"epi {epi}")
+
+
+def linear_ref(a, w, bias, resid, epi):
+    """float64 value of sgpt_linear: a [M, K], w [N, K], bias [N] or None, resid [M, N] or None.
+    epi 0: a w^T (+ bias); 1: gelu_new(a w^T + bias); 9: gelu_erf(a w^T + bias); 2: resid + a w^T + bias;
+    4: (a w^T (+ bias))^T, shape [N, M]."""
+    return epilogue(product(a, w), bias, resid, epi)
+
+
+def split_ref(a, w, bias, epi):
+    """sgpt_linear_split (epi 0 | 1 | 4): the float64 value v that hi = round16(v) and lo = round16(v - hi) reproduce together."""
+    if epi not in (EPI_STORE, EPI_GELU, EPI_VT):
+        raise ValueError(f"epi {epi}")
+    return linear_ref(a, w, bias, None, epi)
+
+
+def abs_product(a, w):
+    """|a| |w|^T in float64: the magnitude sum under the bound."""
+    return np.abs(np.asarray(a, np.float64)) @ np.abs(np.asarray(w, np.float64)).T
+
+
+def bound_from(s, bias, resid, K):
+    """bound() from a precomputed s = abs_product(a, w)."""
+    if bias is not None:
+        s = s + np.abs(np.asarray(bias, np.float64))[None, :]
+    if resid is not None:
+        s = s + np.abs(np.asarray(resid, np.float64))
+    return (K + 4) * 2.0 ** -23 * s
+
+
+def bound(a, w, bias, resid, K):
+    """Per-element bound [M, N] on |fp32 result - float64 value| of resid + a w^T + bias computed as an fp32 chain of ANY order:
+    (K + 4) 2^-23 S with S = |a| |w|^T + |bias| + |resid| -- the gamma_n bound of a sum of n = K products plus the bias, the
+    residual and the scale factors of the epilogue (4 more roundings).  Unit roundoff 2^-23, not 2^-24: the MFMA's internal
+    adds are not documented to round to nearest.  Derived, not measured: nothing of the kernel enters but fp32 accumulation."""
+    return bound_from(abs_product(a, w), bias, resid, K)
+
+
+def fp32_chain(a, w, group, reverse=False):
+    """a w^T the way an fp32 MFMA chain forms it, in numpy: float32 products, `group` of them summed in float32 per step (32 for
+    the 16x16x32 16-bit instruction, 4 for 16x16x4 fp32), the step added to a float32 accumulator; k ascending, or descending
+    with reverse=True.  Returns float32 [M, N].  For small shapes (a Python loop over K)."""
+    a32, w32 = np.asarray(a, np.float32), np.asarray(w, np.float32)
+    K = a32.shape[1]
+    ks = list(range(K))
+    if reverse:
+        ks.reverse()
+    acc = np.zeros((a32.shape[0], w32.shape[0]), np.float32)
+    for s0 in range(0, K, group):
+        part = np.zeros_like(acc)
+        for k in ks[s0:s0 + group]:
+            part = (part + a32[:, k, None] * w32[None, :, k]).astype(np.float32)
+        acc = (acc + part).astype(np.float32)
+    return acc
+
+
+# ---------------------------------------------------------------- the launch rule of csrc/gemm.hip, default build ----------------
+FEW_TILES, DEEP_TILES, KG16_MIN = 128, 512, 6        # SGPT_FEW_TILES, SGPT_DEEP_TILES, SGPT_KG16_MIN
+
+
+def linear_variant(dtype, epi, out16, M, N, K, tile_policy=0, low_latency=False):
+    """(kernel, block order) that sgpt_linear launches: a mirror of launch_gemm16<> and launch<> in csrc/gemm.hip.
+    dtype 'bf16' | 'f16' | 'fp32'; out16 is accepted for symmetry with the entry (no rule depends on it today).
+    kernel: '256d' (256x256 LDS-DMA tiles), 'rs128' (register-staged, 128x128, 64-element k-steps), 'rs64' (64x64, 64-element
+    k-steps), 'rs64-deep' (64x64, 128-element k-steps), 'rs64-kg2' (the same with two k-groups).  order: 'run' (at most 512
+    tiles: each XCD a contiguous run of the tile list), 'supertile' (8 x 8 supertiles per XCD), 'persistent' for 256d.
+    A change of the rule in gemm.hip must change this function and the shape table with it: test_gemm_ref.py fails until then."""
+    del out16
+    gelu = epi in (EPI_GELU, EPI_GELU_ERF)
+    if dtype != "fp32":
+        few = tile_policy != 1 and (M // 256) * (N // 256) <= (255 if gelu else FEW_TILES)
+        shape256 = M % 256 == 0 and N % 256 == 0 and K % 64 == 0 and K >= 128
+        if shape256 and not few:
+            return "256d", "persistent"
+    t128 = ((M + 127) // 128) * ((N + 127) // 128)
+    small = t128 < (600 if K <= 1024 else 300)
+    B = 64 if small else 128
+    MT, NT = (M + B - 1) // B, (N + B - 1) // B
+    order = "run" if MT * NT <= 512 else "supertile"
+    if not small:
+        return "rs128", order
+    if MT * NT > DEEP_TILES:
+        return "rs64", order
+    nk16 = -(-K // (16 * (4 if dtype == "fp32" else 8)))      # 128-element (fp32: 64-element) k-steps
+    if low_latency and nk16 % 2 == 0 and nk16 // 2 >= KG16_MIN:
+        return "rs64-kg2", order
+    return "rs64-deep", order
+
+
+def tile_of(kernel):
+    return {"rs128": 128, "rs64": 64, "rs64-deep": 64, "rs64-kg2": 64, "256d": 256}[kernel]
+
+
+def kstep_of(kernel, dtype):
+    """Elements of K per k-step of a register-staged kernel: 8 (deep: 16) chunks of 16 bytes."""
+    chunks = 16 if kernel in ("rs64-deep", "rs64-kg2") else 8
+    return chunks * (4 if dtype == "fp32" else 8)
+
+
+# ---------------------------------------------------------------- shapes of tests/test_gpu_linear_edges.py -----------------------
+# K16 / K32: the reduction length with 16-bit / fp32 operands.  edges: what the shape is listed for -- 'M' (M % tile != 0),
+# 'N' (N % tile != 0, a multiple of 4 left over unless N % 4 != 0), 'K' (K % k-step != 0), 'order' (MT % 8 != 0, NT % 8 != 0 or
+# MT == 1 under the supertile order).  ll: low-latency mode (k-groups) on.  tag: which test of the GPU file owns the case.
+Case = namedtuple("Case", "name M N K16 K32 kernel order edges ll tag")
+
+
+def _c(name, M, N, K16, K32, kernel, order, edges, ll=False, tag="epi"):
+    return Case(name, M, N, K16, K32, kernel, order, frozenset(edges.split()), ll, tag)
+
+
+CASES = [
+    # a single partial k-step: every M and N once, every (below / above one tile) x (below / above one tile) corner
+    _c("k1-1x4", 1, 4, 8, 4, "rs64-deep", "run", "M N K"),
+    _c("k1-63x132", 63, 132, 8, 4, "rs64-deep", "run", "M N K"),
+    _c("k1-65x60", 65, 60, 8, 4, "rs64-deep", "run", "M N K"),
+    _c("k1-130x68", 130, 68, 8, 4, "rs64-deep", "run", "M N K"),
+    _c("k1-1x132", 1, 132, 8, 4, "rs64-deep", "run", "M N K"),
+    _c("k1-130x4", 130, 4, 8, 4, "rs64-deep", "run", "M N K"),
+    _c("k1-63x60", 63, 60, 8, 4, "rs64-deep", "run", "M N K"),
+    _c("k1-65x68", 65, 68, 8, 4, "rs64-deep", "run", "M N K"),
+    # full 128-element (fp32: 64-element) steps and a tail
+    _c("kt-65x68", 65, 68, 136, 68, "rs64-deep", "run", "M N K"),
+    _c("kt-65x132", 65, 132, 200, 100, "rs64-deep", "run", "M N K"),
+    _c("kt-130x68", 130, 68, 200, 132, "rs64-deep", "run", "M N K"),
+    _c("kt-130x132", 130, 132, 136, 68, "rs64-deep", "run", "M N K"),
+    # M % 128 == 0: the same with the transposed store (epi 4) among the epilogues
+    _c("vt-128x60", 128, 60, 8, 4, "rs64-deep", "run", "N K"),
+    _c("vt-128x68", 128, 68, 200, 100, "rs64-deep", "run", "N K"),
+    _c("vt-256x132", 256, 132, 136, 68, "rs64-deep", "run", "N K"),
+    # 64-element steps, supertile order with MT = 25, NT = 23 (the last column tile 4 wide)
+    _c("st64-1540x1412", 1540, 1412, 72, 36, "rs64", "supertile", "M N K order"),
+    # 128x128 tiles: supertile order with 25 x 25 tiles; run order with a long k-loop and a tail (t128 = 320)
+    _c("st128-3100x3076", 3100, 3076, 72, 36, "rs128", "supertile", "M N K order"),
+    _c("run128-2500x1924", 2500, 1924, 1032, 1028, "rs128", "run", "M N K"),
+    # k-groups with a tail (group 1's last step is the partial one), and the control with an odd step count
+    _c("kg2-130x68", 130, 68, 1528, 764, "rs64-kg2", "run", "M N K", ll=True, tag="kgroup"),
+    _c("kg1-130x68", 130, 68, 1400, 700, "rs64-deep", "run", "M N K", ll=True, tag="kgroup"),
+    # the LM head: one row tile, N % 4 == 1 (epi 0 only)
+    _c("lmhead-37x50257", 37, 50257, 768, 768, "rs64", "supertile", "M N order", tag="oddn"),
+    # odd N with a 16-bit output: 8-byte vector stores that are not 8-byte aligned (the last test of the GPU file)
+    _c("odd-65x1001", 65, 1001, 136, 136, "rs64-deep", "run", "M N K", tag="last"),
+]
+
+# the block of the large cases that is also computed as a problem of its own (bit invariance across tile sizes and k-steps)
+BLOCK_M, BLOCK_N = 130, 68
+BLOCK_CASES = ("st128-3100x3076", "run128-2500x1924", "st64-1540x1412")
+
+
+def case(name):
+    return next(c for c in CASES if c.name == name)
+
+
+def case_k(c, dtype):
+    return c.K32 if dtype == "fp32" else c.K16
+
+
+def round_to(x, dtype):
+    """x (float64 / float32 numpy) rounded once to the operand format; returns (torch tensor of that format, float64 numpy of the
+    same values)."""
+    import torch
+    t = torch.from_numpy(np.asarray(x, np.float32)).to({"bf16": torch.bfloat16, "f16": torch.float16, "fp32": torch.float32}[dtype])
+    return t, t.double().numpy()
+
+
+def make_inputs(c, dtype, seed=0):
+    """Operands of case c: a ~ U(-2, 2), w ~ U(-0.4, 0.4) rounded to the operand format, bias ~ U(-1, 1) and resid ~ U(-2, 2) in
+    fp32.  Returns a dict of torch CPU tensors (a, w, bias, resid) and their float64 values (a64, w64, bias64, resid64).
+    The scales keep a dropped 16-byte k-chunk far above the bound and an fp32 chain far below it (tests/test_gemm_ref.py)."""
+    import torch
+    K = case_k(c, dtype)
+    rng = np.random.default_rng([seed, c.M, c.N, K])
+    a, a64 = round_to(rng.uniform(-2, 2, size=(c.M, K)), dtype)
+    w, w64 = round_to(rng.uniform(-0.4, 0.4, size=(c.N, K)), dtype)
+    bias = torch.from_numpy(rng.uniform(-1, 1, size=c.N).astype(np.float32))
+    resid = torch.from_numpy(rng.uniform(-2, 2, size=(c.M, c.N)).astype(np.float32))
+    return dict(a=a, w=w, bias=bias, resid=resid, a64=a64, w64=w64, bias64=bias.double().numpy(), resid64=resid.double().numpy(), K=K)

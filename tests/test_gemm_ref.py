@@ -1,0 +1,186 @@
+"""CPU: the infrastructure of tests/test_gpu_linear_edges.py (tests/gemm_ref.py) on its own -- the float64 reference against a
+triple loop, torch.float64 and torch's / HF's GELU formulas; the launch mirror against the shape table (every branch of the
+register-staged kernel reached, every case showing the edge it is listed for); the derived bound against an fp32 chain in numpy
+(room below it) and against a dropped 16-byte k-chunk (no room to hide one)."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import gemm_ref as G
+
+DTYPES = ["bf16", "f16", "fp32"]
+SMALL = [c for c in G.CASES if c.kernel == "rs64-deep"]          # the cases an fp32 chain in numpy can walk
+
+
+def _epis(c, dtype):
+    """(epi, out16) combinations sgpt_linear accepts for the case."""
+    out = [(0, False)] + ([(0, True)] if dtype != "fp32" else [])
+    if c.N % 4 == 0:
+        out += [(1, dtype != "fp32"), (9, dtype != "fp32"), (2, False)]
+        if c.M % 128 == 0 and dtype != "fp32":
+            out.append((4, True))
+    return out
+
+
+# ---------------------------------------------------------------- the launch mirror and the shape table --------------------------
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_cases_reach_every_branch_of_the_register_staged_kernel(dtype):
+    reached = {}
+    for c in G.CASES:
+        K = G.case_k(c, dtype)
+        for epi, out16 in _epis(c, dtype):
+            for policy in (0, 1):
+                got = G.linear_variant(dtype, epi, out16, c.M, c.N, K, tile_policy=policy, low_latency=c.ll)
+                assert got == (c.kernel, c.order), f"{c.name} {dtype} epi {epi} policy {policy}: {got}, listed as {(c.kernel, c.order)}"
+            reached.setdefault(got, set()).add(c.name)
+        if c.ll:        # mode off: one group
+            assert G.linear_variant(dtype, 0, False, c.M, c.N, K, low_latency=False) == ("rs64-deep", "run")
+    for k in sorted(reached):
+        print(f"{dtype} {k[0]:>9} / {k[1]:<9}: {' '.join(sorted(reached[k]))}")
+    assert set(reached) == {("rs64-deep", "run"), ("rs64", "supertile"), ("rs128", "run"), ("rs128", "supertile"), ("rs64-kg2", "run")}
+    # the blocks of the large cases as problems of their own: the other tile size, the other k-step
+    for name in G.BLOCK_CASES:
+        K = G.case_k(G.case(name), dtype)
+        for epi in (0, 1, 2, 9):
+            assert G.linear_variant(dtype, epi, False, G.BLOCK_M, G.BLOCK_N, K) == ("rs64-deep", "run")
+        assert G.kstep_of("rs64-deep", dtype) == 2 * G.kstep_of(G.case(name).kernel, dtype)
+
+
+def test_mirror_on_the_shapes_of_test_gpu_linear():
+    """The classification the shape list of tests/test_gpu_linear.py gets (aligned shapes: 256d or the 64x64 tile, never 128x128)."""
+    assert G.linear_variant("bf16", 0, True, 4096, 2304, 128)[0] == "256d"               # 144 tiles > 128
+    assert G.linear_variant("bf16", 1, True, 4096, 2304, 128) == ("rs64", "supertile")    # gelu: few; t128 = 576 < 600
+    assert G.linear_variant("f16", 2, False, 16384, 1536, 768)[0] == "256d"
+    assert G.linear_variant("f16", 0, True, 2048, 768, 3072) == ("rs64-deep", "run")      # t128 = 96
+    assert G.linear_variant("f16", 0, True, 1024, 768, 768, tile_policy=1)[0] == "256d"
+    assert G.linear_variant("f16", 2, False, 512, 768, 3072, low_latency=True) == ("rs64-kg2", "run")
+    assert G.linear_variant("f16", 2, False, 1024, 768, 2112, low_latency=True) == ("rs64-deep", "run")   # 17 steps
+    assert G.linear_variant("fp32", 9, False, 32, 512, 128) == ("rs64-deep", "run")
+    assert G.linear_variant("fp32", 0, False, 4096, 4096, 256) == ("rs128", "supertile")  # fp32 never takes 256d
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("c", G.CASES, ids=lambda c: c.name)
+def test_each_case_shows_the_edge_it_is_listed_for(c, dtype):
+    K = G.case_k(c, dtype)
+    kernel, order = G.linear_variant(dtype, 0, False, c.M, c.N, K, low_latency=c.ll)
+    assert kernel != "256d"
+    B, BK = G.tile_of(kernel), G.kstep_of(kernel, dtype)
+    assert BK in ((32, 64) if dtype == "fp32" else (64, 128))
+    MT, NT = -(-c.M // B), -(-c.N // B)
+    assert K % (4 if dtype == "fp32" else 8) == 0
+    assert ("M" in c.edges) == (c.M % B != 0)
+    assert ("N" in c.edges) == (c.N % B != 0)
+    if "N" in c.edges and c.N % 4 == 0:
+        assert c.N % B in (4, 60)                      # a last column tile one vector wide, or one vector short of full
+    assert ("K" in c.edges) == (K % BK != 0)
+    if "order" in c.edges:
+        assert order == "supertile" and (MT % 8 != 0 or NT % 8 != 0 or MT == 1)
+    assert (order == "supertile") == (MT * NT > 512)
+    if kernel == "rs64-kg2":                           # group 1's last step is the partial one
+        nk = -(-K // BK)
+        assert nk % 2 == 0 and K % BK != 0 and K > (nk - 1) * BK > (nk // 2) * BK
+
+
+def test_first_rows_take_every_value_and_every_corner():
+    first = [c for c in G.CASES if c.name.startswith("k1-")]
+    second = [c for c in G.CASES if c.name.startswith("kt-")]
+    assert {c.M for c in first} == {1, 63, 65, 130} and {c.N for c in first} == {4, 60, 68, 132}
+    assert {(c.M > 64, c.N > 64) for c in first} == {(False, False), (False, True), (True, False), (True, True)}
+    assert {(c.M, c.N) for c in second} == {(65, 68), (65, 132), (130, 68), (130, 132)}
+    assert {c.K16 for c in second} == {136, 200} and {c.K32 for c in second} == {68, 100, 132}
+    assert G.CASES[-1].tag == "last" and G.CASES[-1].N % 2 == 1
+
+
+# ---------------------------------------------------------------- linear_ref -------------------------------------------------
+
+def test_linear_ref_against_a_triple_loop():
+    rng = np.random.default_rng(1)
+    M, N, K = 3, 5, 4
+    a, w = rng.standard_normal((M, K)), rng.standard_normal((N, K))
+    bias, resid = rng.standard_normal(N), rng.standard_normal((M, N))
+    u = np.zeros((M, N))
+    for m in range(M):
+        for n in range(N):
+            for k in range(K):
+                u[m, n] += a[m, k] * w[n, k]
+            u[m, n] += bias[n]
+    assert np.abs(G.linear_ref(a, w, bias, None, 0) - u).max() < 1e-14
+    assert np.abs(G.linear_ref(a, w, None, None, 0) - (u - bias)).max() < 1e-14
+    assert np.abs(G.linear_ref(a, w, bias, resid, 2) - (u + resid)).max() < 1e-14
+    assert G.linear_ref(a, w, bias, None, 4).shape == (N, M) and np.abs(G.linear_ref(a, w, bias, None, 4) - u.T).max() < 1e-14
+    for m in range(M):
+        for n in range(N):
+            x = u[m, n]
+            assert abs(G.linear_ref(a, w, bias, None, 9)[m, n] - 0.5 * x * (1 + math.erf(x / math.sqrt(2)))) < 1e-14
+            t = math.tanh(math.sqrt(2 / math.pi) * (x + 0.044715 * x ** 3))
+            assert abs(G.linear_ref(a, w, bias, None, 1)[m, n] - 0.5 * x * (1 + t)) < 1e-14
+    assert np.array_equal(G.split_ref(a, w, bias, 1), G.linear_ref(a, w, bias, None, 1))
+    with pytest.raises(ValueError):
+        G.split_ref(a, w, bias, 2)
+
+
+@pytest.mark.parametrize("c", [c for c in G.CASES if c.M * c.N * c.K16 <= 2e8], ids=lambda c: c.name)
+def test_linear_ref_against_torch_float64(c):
+    x = G.make_inputs(c, "f16")
+    a, w, b, r = (torch.from_numpy(x[k]) for k in ("a64", "w64", "bias64", "resid64"))
+    u = a @ w.T + b
+    scale = float(u.abs().max()) + 1.0
+    assert np.abs(G.linear_ref(x["a64"], x["w64"], x["bias64"], None, 0) - u.numpy()).max() < 1e-13 * scale
+    assert np.abs(G.linear_ref(x["a64"], x["w64"], x["bias64"], x["resid64"], 2) - (u + r).numpy()).max() < 1e-13 * scale
+    want = torch.nn.functional.gelu(u)                                               # erf form
+    assert np.abs(G.linear_ref(x["a64"], x["w64"], x["bias64"], None, 9) - want.numpy()).max() < 1e-13 * scale
+    want = 0.5 * u * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (u + 0.044715 * torch.pow(u, 3.0))))   # HF NewGELUActivation
+    assert np.abs(G.linear_ref(x["a64"], x["w64"], x["bias64"], None, 1) - want.numpy()).max() < 1e-13 * scale
+    assert np.abs(G.linear_ref(x["a64"], x["w64"], x["bias64"], None, 1)
+                  - torch.nn.functional.gelu(u, approximate="tanh").numpy()).max() < 1e-13 * scale
+
+
+def test_gelu_slope_constant():
+    u = np.linspace(-8, 8, 160001)
+    for f in (G.gelu_new, G.gelu_erf):
+        assert np.abs(np.gradient(f(u), u)).max() < G.GELU_SLOPE
+    assert all(abs(float(G.gelu_erf(np.array([x]))[0]) - 0.5 * x * (1 + math.erf(x / math.sqrt(2)))) < 1e-15 for x in (-6.0, -1.3, 0.2, 3.0))
+
+
+# ---------------------------------------------------------------- the bound ---------------------------------------------------
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("c", SMALL, ids=lambda c: c.name)
+def test_fp32_chain_stays_under_a_quarter_of_the_bound(c, dtype):
+    """The inputs leave the bound room: an fp32 chain of the MFMA's shape, k ascending and k descending, is within bound / 4 of
+    the float64 value everywhere -- so an element beyond the bound on the GPU is the kernel's."""
+    x = G.make_inputs(c, dtype)
+    ref = G.linear_ref(x["a64"], x["w64"], None, None, 0)
+    bnd = G.bound(x["a64"], x["w64"], None, None, x["K"])
+    assert (bnd > 0).all()
+    group = 4 if dtype == "fp32" else 32
+    worst = 0.0
+    for rev in (False, True):
+        got = G.fp32_chain(x["a64"], x["w64"], group, reverse=rev).astype(np.float64)
+        worst = max(worst, float((np.abs(got - ref) / bnd).max()))
+    print(f"{c.name} {dtype}: fp32 chain error / bound = {worst:.4f}")
+    assert worst < 0.25
+    # with bias and residual added in fp32 (epi 2)
+    full = (G.fp32_chain(x["a64"], x["w64"], group) + (x["bias64"].astype(np.float32)[None, :] + x["resid64"].astype(np.float32))).astype(np.float32)
+    err = np.abs(full.astype(np.float64) - G.linear_ref(x["a64"], x["w64"], x["bias64"], x["resid64"], 2))
+    assert (err < 0.25 * G.bound(x["a64"], x["w64"], x["bias64"], x["resid64"], x["K"])).all()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("c", G.CASES, ids=lambda c: c.name)
+def test_a_dropped_k_chunk_is_detectable(c, dtype):
+    """One 16-byte chunk of one row of A zeroed (what a wrong tail guard or a skipped step does) moves some element of that row by
+    more than 4 x the bound -- with bias and residual in the bound, and for the first, a middle and the last chunk of K."""
+    x = G.make_inputs(c, dtype)
+    K, epc = x["K"], (4 if dtype == "fp32" else 8)
+    for m, k0 in ((0, 0), (c.M // 2, (K // epc // 2) * epc), (c.M - 1, K - epc)):
+        a_row, w = x["a64"][m:m + 1], x["w64"]
+        bnd = G.bound(a_row, w, x["bias64"], x["resid64"][m:m + 1], K)
+        cut = a_row.copy()
+        cut[:, k0:k0 + epc] = 0.0
+        moved = np.abs(a_row @ w.T - cut @ w.T)
+        assert (moved > 4.0 * bnd).any(), f"row {m}, chunk at k = {k0}: moved at most {float((moved / bnd).max()):.2f} x the bound"
