@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 13
+#define SGPT_ABI_VERSION 14
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -595,6 +595,18 @@ sgpt_status sgpt_linear(sgpt_ctx* ctx, int32_t dtype, int32_t epi, int32_t out_d
 sgpt_status sgpt_linear_query(sgpt_ctx* ctx, int32_t dtype, int32_t epi, const void* A, const float* x, const float* ln_gamma,
                               const float* ln_beta, float ln_eps, const void* W, const float* bias, const float* resid, void* out,
                               void* out_vt, int32_t n_split, int32_t M, int32_t N, int32_t K, void* stream);
+
+/* The bulk fused Q | K | V projection of sgpt_encode, stand-alone (ABI v14; kernel-level tests: tests/test_gpu_linear_256.py): ONE launch
+ * of the persistent 256x256 kernel over all N = 3 d columns -- the q_proj, k_proj and v_proj nn.Linear calls of GPTNeoSelfAttention.forward,
+ * HF:gpt_neo:141-143 -- the column tiles below n_split stored row-major, the V column tiles computed with swapped operand roles and stored
+ * transposed; the launch the 16-bit block of csrc/encode.hip makes for a bulk batch of a model without a QKV bias.
+ *   A device [M, K], W device [N, K], row-major, `dtype` SGPT_BF16 | SGPT_F16 (lda == ldw == K), no bias, fp32 accumulation
+ *   out     device [M, n_split]      (q | k)           out_vt  device [N - n_split, M]   (V^T), both in `dtype`
+ * Served: M, N and n_split multiples of 256, 0 < n_split < N, K % 64 == 0, K >= 128, and more than 128 q | k tiles
+ * ((M / 256) (n_split / 256) > 128) -- anything else is SGPT_ERR_INVALID and nothing is launched.
+ * Same bits as sgpt_linear epi 0 on W[0 : n_split] and epi 4 on W[n_split : N]. */
+sgpt_status sgpt_linear_qkv(sgpt_ctx* ctx, int32_t dtype, const void* A, const void* W, void* out, void* out_vt, int32_t n_split,
+                            int32_t M, int32_t N, int32_t K, void* stream);
 
 /* The attention kernels of sgpt_encode, stand-alone (ABI v9; kernel-level tests): causal (+ sliding-window) softmax attention
  * over packed variable-length sequences -- GPTNeoSelfAttention._attn (HF:gpt_neo:105-130) with BLOOM's ALiBi bias

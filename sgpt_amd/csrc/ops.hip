@@ -183,6 +183,23 @@ sgpt_status sgpt_linear_split(sgpt_ctx* c, int32_t dtype, int32_t epi, const voi
     return SGPT_OK;
 }
 
+sgpt_status sgpt_linear_qkv(sgpt_ctx* c, int32_t dtype, const void* A, const void* W, void* out, void* out_vt, int32_t n_split,
+                            int32_t M, int32_t N, int32_t K, void* stream) {
+    if (!c || !A || !W || !out || !out_vt || M <= 0 || N <= 0 || K <= 0 || n_split <= 0) return fail(c, SGPT_ERR_INVALID, "sgpt_linear_qkv: bad arguments");
+    if (dtype != SGPT_BF16 && dtype != SGPT_F16) return fail(c, SGPT_ERR_INVALID, "sgpt_linear_qkv: 16-bit operands (SGPT_BF16 | SGPT_F16)");
+    if (!gemm_qkv_bulk(M, N, K, n_split, c->force256 != 0))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_linear_qkv: not a bulk shape (M, N, n_split % 256; K % 64, K >= 128; 0 < n_split < N; more than "
+                                         "half a wave of q | k tiles)");
+    HIPC(c, hipSetDevice(c->device));
+    GemmArgs g{};
+    g.A = A; g.lda = K; g.W = W; g.ldw = K; g.M = M; g.m_valid = M; g.N = N; g.K = K;
+    g.out = out; g.ldo = n_split; g.out2 = out_vt; g.ldo2 = M; g.n_split = n_split;
+    g.range_flag = dtype == SGPT_F16 ? c->range_flag : nullptr;
+    gemm(c, dtype, EPI_QKV, dtype, g, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
 sgpt_status sgpt_attention_ex(sgpt_ctx* c, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
                               void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t dh,
                               int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,

@@ -248,6 +248,18 @@ class Context:
                                              _stream_ptr(self.device)), "sgpt_linear_query")
         return (out, vt) if epi == "qkv" else out
 
+    def linear_qkv(self, a: torch.Tensor, w: torch.Tensor, n_split: int):
+        """The bulk fused Q | K | V projection stand-alone (include/sgpt_hip.h::sgpt_linear_qkv): one launch of the persistent 256x256
+        kernel.  a: [M, K], w: [N, K], 16-bit.  Returns (q|k [M, n_split], V^T [N - n_split, M]); shapes the bulk launch does not
+        serve raise."""
+        M, K = a.shape
+        N = w.shape[0]
+        out = torch.empty((M, n_split), dtype=a.dtype, device=self.device)
+        vt = torch.empty((N - n_split, M), dtype=a.dtype, device=self.device)
+        self._chk(self.lib.sgpt_linear_qkv(self.handle, DT_CODE[a.dtype], _p(a.contiguous()), _p(w.contiguous()), _p(out), _p(vt),
+                                           int(n_split), M, N, K, _stream_ptr(self.device)), "sgpt_linear_qkv")
+        return out, vt
+
     def linear_split(self, a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, epi: str = "store",
                      triple: bool = False) -> torch.Tensor:
         """The split store epilogues (include/sgpt_hip.h::sgpt_linear_split): epi 'store' | 'gelu' -> [M, 2 N] = [hi | lo], or

@@ -1,10 +1,12 @@
 """Test infrastructure: the projection GEMM with its fused epilogues (include/sgpt_hip.h::sgpt_linear / sgpt_linear_split) in
 float64 numpy, a derived error bound for any fp32 accumulation of the same products, a Python mirror of the launch rule of
-csrc/gemm.hip, and the shape table of tests/test_gpu_linear_edges.py.  Checked without a GPU by tests/test_gemm_ref.py.
+csrc/gemm.hip and of the tile walk of its persistent 256x256 kernel, and the shape tables of tests/test_gpu_linear_edges.py and
+tests/test_gpu_linear_256.py.  Checked without a GPU by tests/test_gemm_ref.py.
 
 Operands are the exact values of the already rounded inputs (16-bit x 16-bit and fp32 x fp32 products are taken as the float64
 product of the stored values), so the only error a kernel may show is that of its fp32 accumulation, of the epilogue function
 and of the one rounding to the output format."""
+import functools
 import math
 from collections import namedtuple
 
@@ -202,11 +204,96 @@ BLOCK_M, BLOCK_N = 130, 68
 BLOCK_CASES = ("st128-3100x3076", "run128-2500x1924", "st64-1540x1412")
 
 
+# ---------------------------------------------------------------- the persistent 256x256 kernel: launch256d and tile_coords ------
+Launch256 = namedtuple("Launch256", "balanced m_major deep_a AT BT tiles_total grid skipped runs")
+
+
+@functools.lru_cache(maxsize=8)
+def _tile_list256(MT, NT, ncu, gm, gn):
+    """tile_coords of gemm256d_kernel for every tile index below tiles_total: (m0, n0), or None where it returns false."""
+    m_major = MT >= NT
+    AT, BT = (MT, NT) if m_major else (NT, MT)
+    GM, GN = (gm if gm > 0 else 4), (gn if gn > 0 else 8)
+    balanced = AT * BT <= 4 * ncu                              # launch256d
+    R = AT * BT
+    c0, rem = R >> 3, R & 7
+    tiles_total = 8 * ((R + 7) >> 3) if balanced else ((AT + 7) // 8 + GM - 1) // GM * GM * 8 * BT
+    per_band = GM * BT
+
+    def tile_coords(tile):
+        xcd = tile & 7
+        if balanced:
+            l = tile >> 3
+            if l >= c0 + (1 if xcd < rem else 0):
+                return None
+            gi = xcd * c0 + (xcd if xcd < rem else rem) + l
+            at = gi // BT
+            bt = gi - at * BT
+        else:
+            local = tile >> 3
+            band, inb = local // per_band, local % per_band
+            ng = inb // (GM * GN)
+            g = BT - ng * GN if BT - ng * GN < GN else GN
+            r = inb - ng * GM * GN
+            at, bt = xcd + 8 * (band * GM + r // g), ng * GN + r % g
+            if at >= AT:
+                return None
+        return ((at if m_major else bt) * 256, (bt if m_major else at) * 256)
+
+    return balanced, m_major, AT, BT, tuple(tile_coords(t) for t in range(tiles_total))
+
+
+def tiles256(M, N, ncu, cu_cap=0, gm=4, gn=8):
+    """A line-by-line mirror of launch256d<> and of tile_coords in gemm256d_kernel (csrc/gemm.hip): the launch of an M x N problem
+    (multiples of 256) on a device of ncu CUs under the per-ctx workgroup cap cu_cap.  runs[b] is the ordered list of (m0, n0)
+    workgroup b visits -- tile = b, b + grid, ... below tiles_total, the slots tile_coords refuses skipped (`skipped` of them in
+    all).  deep_a is what launch_gemm16 passes for sgpt_linear (M >= N; the EPI_QKV launch always passes true)."""
+    ncu = ncu // 8 * 8
+    balanced, m_major, AT, BT, coords = _tile_list256(M // 256, N // 256, ncu, gm, gn)
+    tiles_total = len(coords)
+    cus = cu_cap // 8 * 8 if 8 <= cu_cap < ncu else ncu
+    grid = tiles_total if tiles_total < cus else cus
+    runs = [[c for c in coords[b::grid] if c is not None] for b in range(grid)]
+    return Launch256(balanced, m_major, M >= N, AT, BT, tiles_total, grid, sum(c is None for c in coords), runs)
+
+
+# ---------------------------------------------------------------- shapes of tests/test_gpu_linear_256.py -------------------------
+# 16-bit operands only (fp32 never takes the 256x256 kernel); written for a device of NCU256 CUs.  policy: the tile policy of the
+# launch (1 = force 256x256 tiles).  tag: 'ring' (every epilogue; a run of several tiles at every nk % 6), 'small' (every
+# epilogue: single / uneven / two-tile), 'grid' and 'super' (in-place residual and transposed store only), 'cap' (bit invariance).
+NCU256 = 256
+Case256 = namedtuple("Case256", "name M N K policy cu_cap tag")
+RING_K = (128, 192, 256, 320, 384, 448)                # nk = 2 .. 7: every nk % 6
+CASES256 = (
+    [Case256(f"ringA-k{K}", 2048, 768, K, 1, 8, "ring") for K in RING_K]           # deep A: 24 tiles, 3 per workgroup
+    + [Case256(f"ringW-k{K}", 768, 2048, K, 1, 8, "ring") for K in RING_K]         # deep W (M < N)
+    + [
+        Case256("single", 256, 256, 128, 1, 0, "small"),                            # R = 1: seven of eight workgroups exit at once
+        Case256("uneven", 1280, 1024, 192, 1, 8, "small"),                          # R = 20: runs of 3 and 2 tiles
+        Case256("two-tile", 1024, 1024, 128, 1, 8, "small"),                        # the n2tile lookup runs past the end
+        Case256("grid-8448x2304", 8448, 2304, 192, 0, 0, "grid"),                   # 297 tiles on 256 workgroups: 2 and 1
+        Case256("super-m", 19200, 3584, 128, 0, 0, "super"),                        # AT 75 / BT 14: ragged bands, 294 skipped slots
+        Case256("super-n", 3584, 19200, 128, 0, 0, "super"),                        # m_major == false
+        Case256("super-3", 87552, 768, 128, 0, 0, "super"),                         # AT 342 / BT 3: BT < GN
+        Case256("cap24", 2048, 768, 320, 1, 24, "cap"),
+        Case256("cap100", 2048, 768, 320, 1, 100, "cap"),                           # 100 rounds down to 96
+    ]
+)
+SUPER_ROWS = ("super-m", "super-n", "super-3")
+
+
+def launch_of(c, ncu=NCU256, cu_cap=None):
+    return tiles256(c.M, c.N, ncu, c.cu_cap if cu_cap is None else cu_cap)
+
+
+
 def case(name):
-    return next(c for c in CASES if c.name == name)
+    return next(c for c in CASES + CASES256 if c.name == name)
 
 
 def case_k(c, dtype):
+    if isinstance(c, Case256):
+        return c.K
     return c.K32 if dtype == "fp32" else c.K16
 
 

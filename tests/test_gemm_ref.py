@@ -184,3 +184,125 @@ def test_a_dropped_k_chunk_is_detectable(c, dtype):
         cut[:, k0:k0 + epc] = 0.0
         moved = np.abs(a_row @ w.T - cut @ w.T)
         assert (moved > 4.0 * bnd).any(), f"row {m}, chunk at k = {k0}: moved at most {float((moved / bnd).max()):.2f} x the bound"
+
+
+# ---------------------------------------------------------------- the persistent 256x256 kernel: tile walk and case table --------
+
+def _all_tiles_once(M, N, cu_cap):
+    L = G.tiles256(M, N, G.NCU256, cu_cap)
+    seen = [t for run in L.runs for t in run]
+    n = (M // 256) * (N // 256)
+    assert len(seen) == n == len(set(seen)), f"{M} x {N}, cap {cu_cap}: {len(seen)} visits of {len(set(seen))} tiles, {n} exist"
+    assert all(0 <= m0 < M and 0 <= n0 < N and m0 % 256 == 0 and n0 % 256 == 0 for m0, n0 in seen)
+    assert L.skipped == L.tiles_total - n and len(L.runs) == L.grid
+    return L
+
+
+def test_tiles256_visits_every_tile_exactly_once():
+    """The arithmetic of launch256d / tile_coords: for every AT x BT in 1..90 x 1..20 and the tile counts of the case table, both
+    orientations, every workgroup cap: the union of the workgroups' runs is every tile exactly once.  A failure here is a finding
+    about tile_coords (this function mirrors it line by line), not about the mirror's caller."""
+    shapes = {(at, bt) for at in range(1, 91) for bt in range(1, 21)} | {(c.M // 256, c.N // 256) for c in G.CASES256}
+    shapes |= {(b, a) for a, b in shapes}
+    both = set()
+    for mt, nt in sorted(shapes):
+        for cap in (0, 8, 24, 96):
+            L = _all_tiles_once(mt * 256, nt * 256, cap)
+            both.add(L.balanced)
+            assert L.grid % 8 == 0 and L.grid <= (cap if cap else G.NCU256)      # the XCD interleave of the tile order
+    assert both == {True, False}
+
+
+def test_tiles256_pins():
+    """The mirror against values worked out by hand from launch256d."""
+    L = G.tiles256(19200, 3584, 256)
+    assert (L.balanced, L.m_major, L.AT, L.BT, L.tiles_total, L.grid, L.skipped) == (False, True, 75, 14, 1344, 256, 294)
+    # workgroup 0 of 256: tiles 0, 256, 512 = XCD 0, local 0 / 32 (band 0, the column group of 6: ng 1) / 64 (band 1, r = 8: A-tile 8 * 5)
+    assert L.runs[0][:3] == [(0, 0), (0, 8 * 256), (40 * 256, 0)]
+    # 8 workgroups: workgroup 0 walks XCD 0's local list -- 8 columns of A-tile 0, then A-tile 8
+    assert G.tiles256(19200, 3584, 256, 8).runs[0][:9] == [(0, 256 * j) for j in range(8)] + [(8 * 256, 0)]
+    L = G.tiles256(2048, 768, 256, 8)
+    assert L.balanced and L.grid == 8 and L.runs[1] == [(256, 0), (256, 256), (256, 512)]
+    L = G.tiles256(768, 2048, 256, 8)
+    assert not L.m_major and not L.deep_a and L.runs[1] == [(0, 256), (256, 256), (512, 256)]
+    assert G.tiles256(2048, 768, 256, 100).grid == 24 and G.tiles256(8448, 2304, 256, 100).grid == 96 and G.tiles256(8448, 2304, 256, 7).grid == 256
+    assert G.tiles256(256, 256, 256).grid == 8 and [len(r) for r in G.tiles256(256, 256, 256).runs] == [1] + [0] * 7
+    assert not G.tiles256(87552, 768, 256).balanced and G.tiles256(87296, 768, 256).balanced       # 1026 / 1023 tiles: 4 * ncu = 1024
+
+
+def test_cases256_reach_every_branch_of_the_tile_walk():
+    launches = {c.name: G.launch_of(c) for c in G.CASES256}
+    assert {L.balanced for L in launches.values()} == {True, False}
+    assert {L.m_major for L in launches.values()} == {True, False}
+    assert {(L.balanced, L.m_major) for L in launches.values()} == {(True, True), (True, False), (False, True), (False, False)}
+    sup = [launches[n] for n in G.SUPER_ROWS]
+    assert all(not L.balanced and L.skipped > 0 for L in sup) and launches["super-m"].skipped == 294
+    assert launches["super-3"].BT < 8 and launches["super-m"].BT % 8 == 6 and launches["super-m"].AT % 32 != 0
+    lens = {n: {len(r) for r in L.runs} for n, L in launches.items()}
+    assert 0 in lens["single"] and 1 in lens["single"]
+    assert lens["uneven"] == {2, 3} and lens["two-tile"] == {2} and lens["grid-8448x2304"] == {1, 2}
+    assert any(max(v) >= 3 for v in lens.values()) and any(len(v) > 1 and min(v) > 0 for v in lens.values())
+    for deep_a in (True, False):                       # every ring state: nk % 6 on a run of several tiles
+        res = {(c.K // 64) % 6 for c in G.CASES256 if c.tag == "ring" and launches[c.name].deep_a == deep_a
+               and min(len(r) for r in launches[c.name].runs) >= 3}
+        assert res == set(range(6)), (deep_a, res)
+    assert launches["cap24"].grid == launches["cap100"].grid == 24
+    for c in G.CASES256:
+        L = launches[c.name]
+        lens_ = sorted({len(r) for r in L.runs})
+        print(f"{c.name}: {L.AT} x {L.BT} tiles, {'balanced' if L.balanced else 'supertile'}, grid {L.grid}, "
+              f"tiles per workgroup {' / '.join(f'{n} ({sum(len(r) == n for r in L.runs)} wg)' for n in lens_)}, skipped slots {L.skipped}")
+
+
+@pytest.mark.parametrize("c", G.CASES256, ids=lambda c: c.name)
+def test_cases256_take_the_256_kernel_under_their_policy(c):
+    epis = [(2, False), (4, True)] + ([(0, True), (1, True), (9, True)] if c.tag in ("ring", "small", "cap") else [])
+    for dtype in ("bf16", "f16"):
+        for epi, out16 in epis:
+            assert G.linear_variant(dtype, epi, out16, c.M, c.N, c.K, tile_policy=c.policy) == ("256d", "persistent"), (c.name, epi)
+    if c.tag in ("ring", "cap") or c.name in ("uneven", "two-tile"):      # the bit-invariance partner: the register-staged kernel
+        assert G.linear_variant("f16", 0, True, c.M, c.N, c.K, tile_policy=0)[0] != "256d"
+    assert c.M % 256 == 0 and c.N % 256 == 0 and c.K % 64 == 0 and c.K >= 128
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "f16"])
+@pytest.mark.parametrize("name", ["ringA-k128", "ringA-k448", "ringW-k128", "ringW-k448"])
+def test_a_stale_slot_and_a_wrong_prefetch_are_detectable(name, dtype):
+    """What the carry-over between tiles can get wrong, in float64, on the second tile of workgroup 0's run (uniform inputs of
+    make_inputs, unchanged): (1) its k-step 1 reads the deep operand's ring slot as it was three steps earlier -- a k-step of the
+    PREVIOUS tile (a slot the run-ahead DMA did not refill); (2) its k-step 0, fetched during the previous tile's last steps, comes
+    from the previous tile's operand rows (s_nxt / d_nxt taken from the wrong tile).  Either moves at least a quarter of the tile's
+    elements by more than 4 x the tolerance of tests/test_gpu_linear_256.py (16-bit store with bias; bias + residual in fp32),
+    while an fp32 chain of the true inputs stays under a quarter of the accumulation bound alone."""
+    from gemm_gpu_util import tolerance
+    c = G.case(name)
+    x = G.make_inputs(c, dtype)
+    L = G.launch_of(c)
+    (pm0, pn0), (m0, n0) = L.runs[0][0], L.runs[0][1]
+    nk = c.K // 64
+    a, w = x["a64"], x["w64"]
+    A1, W1, A0, W0 = a[m0:m0 + 256], w[n0:n0 + 256], a[pm0:pm0 + 256], w[pn0:pn0 + 256]
+    true = G.product(A1, W1)
+    g_old = nk * 1 + 1 - 3                              # the global k-step whose data the deep slot of (tile 1, step 1) held before
+    assert g_old // nk == 0
+    ko = (g_old % nk) * 64
+    if L.deep_a:
+        stale = true + G.product(A0[:, ko:ko + 64] - A1[:, 64:128], W1[:, 64:128])
+    else:
+        stale = true + G.product(A1[:, 64:128], W0[:, ko:ko + 64] - W1[:, 64:128])
+    wrong = true - G.product(A1[:, :64], W1[:, :64]) + G.product(A0[:, :64], W0[:, :64])
+    bias, resid = x["bias64"][n0:n0 + 256], x["resid64"][m0:m0 + 256, n0:n0 + 256]
+    s = G.abs_product(A1, W1)
+    for epi, out16, r in ((0, True, None), (2, False, resid)):
+        ref = G.epilogue(true, bias, r, epi)
+        tol = tolerance(dtype, epi, out16, ref, G.bound_from(s, bias, r, c.K))
+        for what, bad in (("stale deep slot", stale), ("prefetch from the previous tile", wrong)):
+            frac = float((np.abs(bad - true) > 4.0 * tol).mean())
+            print(f"{name} {dtype} epi {epi} {what}: {frac:.3f} of the tile beyond 4 x the tolerance")
+            assert frac >= 0.25, f"{what}, epi {epi}: only {frac:.3f} of the tile's elements leave 4 x the tolerance"
+    bm, bn = G.BLOCK_M, G.BLOCK_N
+    bnd = G.bound(a[:bm], w[:bn], None, None, c.K)
+    ref = G.product(a[:bm], w[:bn])
+    worst = max(float((np.abs(G.fp32_chain(a[:bm], w[:bn], 32, reverse=rev).astype(np.float64) - ref) / bnd).max()) for rev in (False, True))
+    print(f"{name} {dtype}: fp32 chain error / bound = {worst:.4f}")
+    assert worst < 0.25

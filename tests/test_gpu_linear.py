@@ -3,7 +3,9 @@ against a plain PyTorch fp32 product of the SAME 16-bit operands (VERDICT r01 we
 kernels (16x16x32 and 32x32x16 MFMA), bf16 and f16, the ring parities K = 128 / 192 / 320 / 768 / 3072, M = 256
 (single tile row) and the register-staged kernel's 64x64 tile at ALIGNED shapes only (every M >= 128, N a multiple of 256, K a
 multiple of 64: no shape here reaches its 128x128 tile, its row / column / K-tail guards or fp32 operands -- those are
-tests/test_gpu_linear_edges.py, against the float64 reference and derived bound of tests/gemm_ref.py).  Tolerance: fp32 accumulation-order noise only,
+tests/test_gpu_linear_edges.py, against the float64 reference and derived bound of tests/gemm_ref.py; and every 256x256 shape here
+but one gives each workgroup a single tile -- runs of several tiles at every ring state, the supertile tile order, the workgroup
+cap and the bulk QKV launch of the 256x256 kernel are tests/test_gpu_linear_256.py, against the same reference).  Tolerance: fp32 accumulation-order noise only,
 1e-3 * sqrt(K / 64) relative to the output scale for fp32 outputs; one rounding to the 16-bit output format on top
 (2^-8 bf16 / 2^-11 f16 relative) for 16-bit outputs."""
 import math
