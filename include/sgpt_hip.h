@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 14
+#define SGPT_ABI_VERSION 15
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -49,7 +49,7 @@ typedef struct sgpt_ctx sgpt_ctx;
 typedef struct sgpt_model sgpt_model;
 
 enum { SGPT_F32 = 0, SGPT_BF16 = 1, SGPT_FP8W = 2, SGPT_F16 = 3, SGPT_FP8M = 4 };   /* element types; FP8W / FP8M: model compute_dtype only */
-enum { SGPT_ARCH_GPTNEO = 0, SGPT_ARCH_GPTJ = 1, SGPT_ARCH_BLOOM = 2, SGPT_ARCH_BERT = 3 };
+enum { SGPT_ARCH_GPTNEO = 0, SGPT_ARCH_GPTJ = 1, SGPT_ARCH_BLOOM = 2, SGPT_ARCH_BERT = 3, SGPT_ARCH_LLAMA = 4 };
 /* SGPT_ARCH_BERT (ABI v13): HF BertModel (HF:bert/modeling_bert.py) -- the baseline of the reference's own scripts
  * (biencoder/beir/beir_dense_retriever.py:36 defaults --modelname to bert-base-uncased; :131-132 frame [CLS] ... [SEP]).
  *   x = LN_emb(wte[id] + wpe'[pos]);  per layer: q | k | v = x W^T + b; ctx = softmax(q.k^T / sqrt(dh)) v over ALL keys of the
@@ -65,6 +65,20 @@ enum { SGPT_ARCH_GPTNEO = 0, SGPT_ARCH_GPTJ = 1, SGPT_ARCH_BLOOM = 2, SGPT_ARCH_
  *   records |v| >= 32768 in the model's guard word as for the other families, but sgpt_model_range_adapt and
  *   sgpt_model_set_range_shifts refuse -- a flagged model is reloaded as SGPT_BF16 / SGPT_F32.  16-bit head_dim 64 | 128.
  *   Every layout (T_pad % 32) runs the bulk projection kernels: the query-sized kernels' LayerNorm prologues assume pre-LN. */
+/* SGPT_ARCH_LLAMA (ABI v15): HF LlamaModel and MistralModel (HF:llama/modeling_llama.py, HF:mistral/modeling_mistral.py) -- the two differ
+ * only in the window.  Pre-norm causal decoder, no bias anywhere, x the fp32 residual stream:
+ *   a = RMSNorm_1(x);  q | k | v = a W^T with n_heads query heads and n_kv_heads key / value heads (grouped K / V: query head h reads
+ *   key / value head h / (n_heads / n_kv_heads));  q, k <- half-split rotary (rotate_half: x[i] pairs with x[i + head_dim / 2]);
+ *   x += softmax(q.k^T / sqrt(dh), causal, window) v Wo^T;  a = RMSNorm_2(x);  x += (silu(a Wgate^T) * (a Wup^T)) Wdown^T;
+ *   hidden state i of sgpt_encode_layers is the input of block i, state L the final RMSNorm of the last block's output.
+ *   RMSNorm(x) = x * rsqrt(mean(x^2) + ln_eps) * g (ln_eps = rms_norm_eps).  The MLP runs UNFUSED: one fc1 launch of N = 2 d_ffn
+ *   (gate rows, then up rows) into a workspace, then one row kernel for silu(gate) * up (sgpt_swiglu).
+ *   Descriptor: n_kv_heads (n_heads % n_kv_heads == 0; 0 = n_heads), attn_scale = 1 / sqrt(head_dim), window = the sliding window
+ *   (key j visible to query i iff i - window < j <= i; 0 = none) applied on the layers layer_is_local marks, rotary_dim = head_dim.
+ *   Tensors: see sgpt_tensor_view.  compute_dtype SGPT_F32 | SGPT_F16 | SGPT_BF16; SGPT_FP8W / SGPT_FP8M, qk_split, split_weights, any
+ *   non-zero precision plan, the precision probe, range shifts (sgpt_model_range_adapt / _set_range_shifts: a flagged f16 model is
+ *   reloaded as SGPT_BF16 / SGPT_F32), SGPT_POOL_LEARNTMEAN and sgpt_lm_logprobs are refused (SGPT_ERR_INVALID).  head_dim 64 | 128.
+ *   Every layout runs the bulk projection kernels (the query-sized kernels' prologues are LayerNorm). */
 enum { SGPT_POOL_WEIGHTEDMEAN = 0, SGPT_POOL_MEAN = 1, SGPT_POOL_LASTTOKEN = 2, SGPT_POOL_LEARNTMEAN = 3,
        SGPT_POOL_CLS = 4 };   /* ABI v13: the first token row of each sequence (Pooling.py:103-105 `pooling_mode_cls_token`); sgpt_encode*, sgpt_pool */
 enum { SGPT_COS = 0, SGPT_DOT = 1, SGPT_NEG_L2 = 2 };   /* SGPT_NEG_L2 (ABI v11): -||x - y||_2, sgpt_eval_groups only */
@@ -121,6 +135,7 @@ typedef struct {
     int32_t split_weights;   /* SGPT_F16 / SGPT_BF16 only.  1 = also keep [W_hi | W_hi | W_lo] copies of all four matmul weights of
                                 every block (3 x the 16-bit weight bytes on top of the plain copy) so that sgpt_model_set_precision
                                 can move any operand class of any block to split precision after load.  0 (default) = off */
+    int32_t n_kv_heads;      /* ABI v15, SGPT_ARCH_LLAMA only: key / value heads (grouped K / V), n_heads % n_kv_heads == 0; 0 = n_heads */
 } sgpt_model_desc;
 
 /* One named fp32 weight tensor under its HF state-dict name
@@ -132,6 +147,11 @@ typedef struct {
  *           caller), "embeddings.LayerNorm.{weight,bias}", "encoder.layer.0.attention.self.{query,key,value}.{weight,bias}" (fused
  *           to [3d, d] by the library), "encoder.layer.0.attention.output.{dense,LayerNorm}.*", "encoder.layer.0.intermediate.dense.*",
  *           "encoder.layer.0.output.{dense,LayerNorm}.*";
+ *  LLAMA:   "embed_tokens.weight", "layers.0.input_layernorm.weight", "layers.0.self_attn.qkv_proj.weight" (q_proj | k_proj | v_proj
+ *           rows fused by the caller, [d + 2 d_kv, d] with d_kv = n_kv_heads * head_dim), "layers.0.self_attn.o_proj.weight",
+ *           "layers.0.post_attention_layernorm.weight", "layers.0.mlp.gate_up_proj.weight" (gate_proj rows, then up_proj rows,
+ *           [2 d_ffn, d]), "layers.0.mlp.down_proj.weight", "norm.weight", plus "rotary.sin" / "rotary.cos" fp32[max_pos, head_dim/2]
+ *           (angle = pos * rope_theta^(-2i / head_dim), computed by the host); no biases;
  *  BLOOM:   "word_embeddings.weight", "word_embeddings_layernorm.*", "h.0.self_attention.query_key_value.{weight,bias}"
  *           (fused, head-interleaved [n_head, 3, head_dim] rows, HF:bloom:214 -- de-interleaved by the library),
  *           "h.0.self_attention.dense.*", "h.0.mlp.dense_h_to_4h.*", ..., plus "alibi.slopes" fp32[n_head]
@@ -647,6 +667,17 @@ sgpt_status sgpt_attention_ex(sgpt_ctx* ctx, int32_t dtype, const void* q, const
                               float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
                               int64_t ctx_lo_delta, int64_t ctx_hi2_delta, int32_t causal, const int32_t* seq_len, void* stream);
 
+/* sgpt_attention_gqa (ABI v15): causal sgpt_attention with grouped K / V (SGPT_ARCH_LLAMA): k holds n_kv_heads heads ([T, >= n_kv_heads *
+ *   head_dim] rows of leading dimension ldq), v = V^T [n_kv_heads * head_dim, ldvt] (16-bit) or [T, ...] rows (fp32); query head h
+ *   reads key / value head h / (H / n_kv_heads).  Only the addresses differ: the result is bit for bit that of sgpt_attention on
+ *   explicitly replicated K and V^T, and n_kv_heads == H is sgpt_attention itself.  window as sgpt_attention.  H % n_kv_heads != 0,
+ *   alibi, out_fp8, x3 and the split context are refused (SGPT_ERR_INVALID), as is 16-bit head_dim 256. */
+sgpt_status sgpt_attention_gqa(sgpt_ctx* ctx, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
+                               void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t n_kv_heads,
+                               int32_t dh, int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
+                               float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
+                               int64_t ctx_lo_delta, int64_t ctx_hi2_delta, void* stream);
+
 /* The encoder's row kernels, stand-alone (ABI v12; kernel-level tests: tests/test_gpu_rowops.py compares each with a float64
  * restatement of the same operation).  These are the launches sgpt_encode / sgpt_lm_logprobs make between their GEMMs, on
  * caller-owned device buffers.  Every entry returns SGPT_ERR_INVALID, with nothing launched, for a null pointer, a row width
@@ -665,6 +696,15 @@ sgpt_status sgpt_attention_ex(sgpt_ctx* ctx, int32_t dtype, const void* q, const
  * sgpt_layernorm_writeback (ABI v13): the LayerNorm of a post-LN block (SGPT_ARCH_BERT): x fp32[T, d] <- nn.LayerNorm(eps)(x) IN PLACE
  *   and, from the same registers, out16 [T, d] = the normalised row rounded once (RNE) to out_dtype SGPT_BF16 | SGPT_F16 -- the
  *   next projection's operand.  An f16 value of magnitude >= 32768 raises bit 0 of sgpt_range_check.
+ * sgpt_rmsnorm (ABI v15; SGPT_ARCH_LLAMA): out [T, d] = x * rsqrt(mean(x^2) + eps) * gamma in fp32, rounded once to out_dtype (SGPT_F32:
+ *   not at all; out may alias x).  An f16 value of magnitude >= 32768 raises bit 0 of sgpt_range_check.
+ * sgpt_swiglu (ABI v15): out [T, ffn] = silu(gu[:, :ffn]) * gu[:, ffn:] for gu [T, 2 ffn] of `dtype` (the fc1 output of the Llama MLP:
+ *   gate columns, then up columns), fp32 arithmetic, one rounding to `dtype`; ffn % 8 (16-bit) / 4 (fp32).  f16 range flag as above.
+ * sgpt_rope_half (ABI v15): HF rotate_half rotary embedding in place on buf [T, ld]: for the H query heads at column 0 and the H_kv key
+ *   heads at column k_off, i < head_dim / 2: (x[i], x[i + head_dim/2]) <- (x[i] c - x[i + head_dim/2] s, x[i + head_dim/2] c + x[i] s)
+ *   with s, c = sin_t / cos_t [max_pos, head_dim/2] at row pos[t] (clamped into the table, as sgpt_rope).  head_dim % 8.
+ * sgpt_lnf_pool_ex (ABI v15): sgpt_lnf_pool with a trailing norm_kind: 0 = LayerNorm (sgpt_lnf_pool exactly), 1 = RMSNorm(gamma)
+ *   (beta is not read).
  * sgpt_lnf_pool: the final LayerNorm fused with the pooling of a packed batch (layout of sgpt_encode: sequence i holds rows
  *   [seq_off[i], seq_off[i] + seq_len[i]) of x fp32[T_pad, d]; rows outside are never read).  apply_ln: ln_f (HF:gpt_neo:492)
  *   on every row first.  mode SGPT_POOL_*: weightedmean sum_t (P + t + 1) h_t / max(sum_t (P + t + 1), 1e-9) with P =
@@ -688,6 +728,15 @@ sgpt_status sgpt_layernorm(sgpt_ctx* ctx, const float* x, const float* gamma, co
                            void* out, int32_t out_dtype, float out_mul, int32_t split, void* stream);
 sgpt_status sgpt_layernorm_writeback(sgpt_ctx* ctx, float* x, const float* gamma, const float* beta, int32_t T, int32_t d, float eps,
                                      void* out16, int32_t out_dtype, void* stream);
+sgpt_status sgpt_rmsnorm(sgpt_ctx* ctx, const float* x, const float* gamma, int32_t T, int32_t d, float eps, void* out, int32_t out_dtype,
+                         void* stream);
+sgpt_status sgpt_swiglu(sgpt_ctx* ctx, const void* gu, int32_t dtype, int32_t T, int32_t ffn, void* out, void* stream);
+sgpt_status sgpt_rope_half(sgpt_ctx* ctx, void* buf, int32_t dtype, int64_t ld, int64_t k_off, const int32_t* pos, const float* sin_t,
+                           const float* cos_t, int32_t T, int32_t H, int32_t H_kv, int32_t head_dim, int32_t max_pos, void* stream);
+sgpt_status sgpt_lnf_pool_ex(sgpt_ctx* ctx, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
+                             const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
+                             int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,
+                             int32_t* nonfinite_flag, int32_t norm_kind, void* stream);
 sgpt_status sgpt_lnf_pool(sgpt_ctx* ctx, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
                           const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
                           int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,

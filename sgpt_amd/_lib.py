@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGPT_HIP_LIB") or os.path.join(HERE, "lib", "libsgpt_hip.so")   # env: A/B builds of the same ABI
 
 SGPT_F32, SGPT_BF16, SGPT_FP8W, SGPT_F16, SGPT_FP8M = 0, 1, 2, 3, 4
-SGPT_ABI_VERSION = 14
+SGPT_ABI_VERSION = 15
 SGPT_PREC_CLASSES = 5                      # precision-plan classes per block: LN1, ATT, CTX, LN2, H (include/sgpt_hip.h)
 PC_LN1, PC_ATT, PC_CTX, PC_LN2, PC_H = 0, 1, 2, 3, 4
 SGPT_ERR_RANGE = -5
@@ -18,7 +18,7 @@ SGPT_EVAL_MAX_CUTS = 16
 SGPT_EVAL_MAX_GROUP = 1024
 SGPT_EVAL_MAX_PAIRS = 1 << 24
 SGPT_COS, SGPT_DOT, SGPT_NEG_L2 = 0, 1, 2
-SGPT_ARCH_GPTNEO, SGPT_ARCH_GPTJ, SGPT_ARCH_BLOOM, SGPT_ARCH_BERT = 0, 1, 2, 3
+SGPT_ARCH_GPTNEO, SGPT_ARCH_GPTJ, SGPT_ARCH_BLOOM, SGPT_ARCH_BERT, SGPT_ARCH_LLAMA = 0, 1, 2, 3, 4
 POOL_MODES = {"weightedmean": 0, "mean": 1, "lasttoken": 2, "learntmean": 3, "cls": 4}
 EPI_BIAS_GELU_ERF = 9                      # sgpt_linear: bias + erf GELU (the BERT family)
 
@@ -28,7 +28,7 @@ class ModelDesc(C.Structure):
                 ("d_ffn", C.c_int32), ("vocab", C.c_int32), ("max_pos", C.c_int32), ("window", C.c_int32),
                 ("ln_eps", C.c_float), ("attn_scale", C.c_float), ("compute_dtype", C.c_int32),
                 ("layer_is_local", C.POINTER(C.c_uint8)), ("rotary_dim", C.c_int32), ("qk_split", C.c_int32),
-                ("split_weights", C.c_int32)]
+                ("split_weights", C.c_int32), ("n_kv_heads", C.c_int32)]
 
 
 class TensorView(C.Structure):
@@ -139,6 +139,18 @@ SIGNATURES = {
                                     C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_int32,
                                     C.c_float, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
                                     C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sgpt_attention_gqa": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_float, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
+                                     C.c_int64, C.c_int64, C.c_void_p]),
+    "sgpt_rmsnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
+    "sgpt_swiglu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sgpt_rope_half": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "sgpt_lnf_pool_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                   C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.c_int32, C.c_void_p]),
     "sgpt_layernorm_writeback": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
                                            C.c_int32, C.c_void_p]),
     "sgpt_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

@@ -160,8 +160,10 @@ void attn16_lds_kernel(const AttnArgs p) {
     const int q0 = qpos[0];
 
     const bf16_t* __restrict__ qb = static_cast<const bf16_t*>(p.q) + (long)head * DH;
-    const bf16_t* __restrict__ kb = static_cast<const bf16_t*>(p.k) + (long)head * DH;
-    const bf16_t* __restrict__ vt = static_cast<const bf16_t*>(p.v) + (long)head * DH * p.ldvt;
+    // grouped K / V (the Llama family): kv_group query heads share one key / value head; 1 = the head itself (the same addresses)
+    const int kvh = p.kv_group > 1 ? head / p.kv_group : head;
+    const bf16_t* __restrict__ kb = static_cast<const bf16_t*>(p.k) + (long)kvh * DH;
+    const bf16_t* __restrict__ vt = static_cast<const bf16_t*>(p.v) + (long)kvh * DH * p.ldvt;
 
     // (query rows past the allocation belong to the next sequence or to the padding of the token axis: loaded, never stored)
     uint4 qf[NQ][KS];
@@ -573,8 +575,9 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnArgs p) {
     if (qi >= alloc) return;
     const int dh = p.dh;
     const float* __restrict__ qb = static_cast<const float*>(p.q) + (long)head * dh;
-    const float* __restrict__ kb = static_cast<const float*>(p.k) + (long)head * dh;
-    const float* __restrict__ vb = static_cast<const float*>(p.v) + (long)head * dh;
+    const int kvh = p.kv_group > 1 ? head / p.kv_group : head;      // grouped K / V: see attn16_lds_kernel
+    const float* __restrict__ kb = static_cast<const float*>(p.k) + (long)kvh * dh;
+    const float* __restrict__ vb = static_cast<const float*>(p.v) + (long)kvh * dh;
     for (int c = lane; c < dh; c += 64) qs[wave][c] = qb[(long)(s0 + qi) * p.ldq + c];
     int lo = 0;
     if (p.window > 0) { lo = qi - p.window + 1; lo = lo < 0 ? 0 : lo; }

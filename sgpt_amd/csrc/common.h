@@ -369,6 +369,9 @@ struct AttnArgs {
     // 0 (every zero-initialised descriptor) = the causal kernels, unchanged.
     int noncausal;
     const int* seq_len;
+    // grouped K / V (SGPT_ARCH_LLAMA): query head h reads key / value head h / kv_group -- K from column (h / kv_group) * dh, V^T from
+    // row (h / kv_group) * dh.  1 (the default of every descriptor) = one K / V head per query head: today's addresses, today's bits.
+    int kv_group = 1;
 };
 inline bool attn_x3_supported(int dh) { return dh == 64 || dh == 128; }
 void launch_attn_bf16(const AttnArgs& a, hipStream_t s);   // 16-bit MFMA path (bf16 or f16 by a.dtype)
@@ -386,6 +389,11 @@ void launch_layernorm_writeback(float* x, const float* g, const float* b, void* 
                                 int* range_flag, hipStream_t s);
 void launch_layernorm_split(const float* x, const float* g, const float* b, void* out, int out_dtype, int T, int d,
                             float eps, hipStream_t s, float out_mul);
+// RMSNorm (SGPT_ARCH_LLAMA): out = x * rsqrt(mean(x^2) + eps) * g, fp32 arithmetic, one rounding to out_dtype (fp32: none; out may
+// alias x); range_flag (f16, or null): raised when a rounded magnitude reaches RANGE_LIMIT
+void launch_rmsnorm(const float* x, const float* g, void* out, int out_dtype, int T, int d, float eps, int* range_flag, hipStream_t s);
+// SwiGLU (SGPT_ARCH_LLAMA): h[t][j] = silu(gu[t][j]) * gu[t][ffn + j] in fp32, gu [T][2 ffn] and h [T][ffn] in `dtype`; range_flag as above
+void launch_swiglu(const void* gu, void* h, int dtype, int T, int ffn, int* range_flag, hipStream_t s);
 void launch_pack_split_rows(const float* src, long rows, long cols, void* dst, int out_dtype, hipStream_t s);
 // precision probe: max over rows of max|v| / rms(v) of a 16-bit operand [T][cols] (leading dim ld) folded into *out_bits
 void launch_crest16(const void* in, int T, int cols, long ld, int dtype, unsigned* out_bits, hipStream_t s);
@@ -398,7 +406,8 @@ void launch_absmax16(const void* in, long numel, int dtype, unsigned* out_bits, 
 void launch_lnf_pool(const float* x, const float* g, const float* b, const int* seq_off, const int* seq_len,
                      const int* pad_left, int B, int d, float eps, int apply_ln, int mode, int normalize,
                      const float* pos_weights, int pos_weights_n, float* out, hipStream_t s,
-                     int* nonfinite_flag = nullptr);   // f16 models: raised (bit 0) when a pooled row is not finite
+                     int* nonfinite_flag = nullptr,    // f16 models: raised (bit 0) when a pooled row is not finite
+                     int norm_kind = 0);               // apply_ln: 0 = LayerNorm(g, b), 1 = RMSNorm(g) (b is not read)
 void launch_pool(const void* hidden, int dtype, const int* mask, int B, int S, int d, int mode,
                  const float* pos_weights, float* out, hipStream_t s);
 // fp8 e4m3fn weight storage, one power-of-two scale per row (output channel)
@@ -421,6 +430,9 @@ void launch_fill_f32(float* p, long n, float v, hipStream_t s);
 // GPT-J rotary embedding, in place on the q / k columns of the projection buffer
 void launch_rope(void* qk, int dtype, long ld, long k_off, const int* pos, const float* sin_t, const float* cos_t, int T,
                  int H, int dh, int rotary_dim, int max_pos, hipStream_t s);
+// half-split rotary embedding (HF rotate_half: the Llama family), in place on q (H heads, column 0) and k (H_kv heads, column k_off)
+void launch_rope_half(void* qk, int dtype, long ld, long k_off, const int* pos, const float* sin_t, const float* cos_t, int T,
+                      int H, int H_kv, int dh, int max_pos, hipStream_t s);
 // BLOOM fused QKV rows [n_head, 3, head_dim] -> [q rows | k rows | v rows] (row_len floats per row; 1 for the bias)
 void launch_qkv_deinterleave(const float* src, float* dst, int H, int dh, long row_len, hipStream_t s);
 void launch_fill_rand(void* p, long n, int dtype, unsigned seed, float scale, hipStream_t s);

@@ -87,6 +87,93 @@ __global__ __launch_bounds__(256) void layernorm_writeback_kernel(float* __restr
     range.finish(range_flag);
 }
 
+// RMSNorm of the Llama family (HF:llama/modeling_llama.py LlamaRMSNorm): out = x * rsqrt(mean(x^2) + eps) * g -- no mean subtraction,
+// no bias.  The row in registers with layernorm_kernel's load pattern (RowLN::load), the square sum through the same butterfly;
+// HF's order of operations: (x * rstd) first, then * g.  Columns past d hold zeros and add nothing to the sum.
+template <int NV, bool FAST = false>
+__device__ __forceinline__ void rms_normalize(RowLN<NV>& r, const float* __restrict__ g, int d, float eps, int lane) {
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) q += (r.v[i].x * r.v[i].x + r.v[i].y * r.v[i].y) + (r.v[i].z * r.v[i].z + r.v[i].w * r.v[i].w);
+    const float rstd = 1.0f / sqrtf((FAST ? wave_sum_valu(q) : wave_sum(q)) / (float)d + eps);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (i * 64 + lane) * 4;
+        if (c < d) {
+            const float4 gg = *reinterpret_cast<const float4*>(g + c);
+            r.v[i].x = r.v[i].x * rstd * gg.x; r.v[i].y = r.v[i].y * rstd * gg.y;
+            r.v[i].z = r.v[i].z * rstd * gg.z; r.v[i].w = r.v[i].w * rstd * gg.w;
+        }
+    }
+}
+
+// One wave per row; the output is rounded once to OutT (fp32: stored as it is, out may alias x -- a wave owns its row and all of
+// its loads precede its stores).  f16: every rounded value passes the range tracker (no load-time bound on the gain is relied upon).
+template <typename OutT, int NV>
+__global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ x, const float* __restrict__ g, OutT* __restrict__ out,
+                                                      int T, int d, float eps, int* __restrict__ range_flag) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= T) return;
+    const int lane = threadIdx.x & 63;
+    RowLN<NV> r;
+    r.load(x + (long)row * d, d, lane);
+    rms_normalize<NV>(r, g, d, eps, lane);
+    RangeTrack<OutT> range;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (i * 64 + lane) * 4;
+        if (c < d) {
+            if constexpr (sizeof(OutT) == 4) {
+                *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + (long)row * d + c) = r.v[i];
+            } else {
+                range.note(r.v[i].x, r.v[i].y); range.note(r.v[i].z, r.v[i].w);
+                *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(out) + (long)row * d + c) =
+                    make_uint2(Half<OutT>::pack2(r.v[i].x, r.v[i].y), Half<OutT>::pack2(r.v[i].z, r.v[i].w));
+            }
+        }
+    }
+    if constexpr (sizeof(OutT) != 4) range.finish(range_flag);
+}
+
+// SwiGLU of the Llama family (HF:llama/modeling_llama.py LlamaMLP: down(silu(gate(x)) * up(x))): gu [T][2 ffn] holds the gate
+// columns, then the up columns, of ONE fc1 launch; h[t][j] = silu(gu[t][j]) * gu[t][ffn + j] with silu(u) = u / (1 + exp(-u)) in
+// fp32 (expf and the IEEE divide: the kernel moves 3 values per 4 flops + one exp, it waits on memory), rounded once to T.  One
+// thread per 16 bytes of h: 8 (16-bit) or 4 (fp32) consecutive columns, two 16-byte loads.  f16: the product passes the range tracker.
+__device__ __forceinline__ float silu_mul(float u, float v) { return u / (1.0f + expf(-u)) * v; }
+template <typename T>
+__global__ __launch_bounds__(256) void swiglu_kernel(const T* __restrict__ gu, T* __restrict__ h, long n_vec, int ffn,
+                                                     int* __restrict__ range_flag) {
+    constexpr int VW = 16 / sizeof(T);
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    RangeTrack<T> range;
+    if (idx < n_vec) {
+        const int vpr = ffn / VW;                        // vectors per row
+        const long t = idx / vpr;
+        const int j = (int)(idx - t * vpr) * VW;
+        const T* grow = gu + t * 2 * (long)ffn + j;
+        const uint4 a = *reinterpret_cast<const uint4*>(grow), b = *reinterpret_cast<const uint4*>(grow + ffn);
+        uint4 o;
+        if constexpr (sizeof(T) == 4) {
+            o.x = __float_as_uint(silu_mul(__uint_as_float(a.x), __uint_as_float(b.x)));
+            o.y = __float_as_uint(silu_mul(__uint_as_float(a.y), __uint_as_float(b.y)));
+            o.z = __float_as_uint(silu_mul(__uint_as_float(a.z), __uint_as_float(b.z)));
+            o.w = __float_as_uint(silu_mul(__uint_as_float(a.w), __uint_as_float(b.w)));
+        } else {
+            const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
+            uint32_t ow[4];
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const float p0 = silu_mul(Half<T>::lo(aw[w]), Half<T>::lo(bw[w])), p1 = silu_mul(Half<T>::hi(aw[w]), Half<T>::hi(bw[w]));
+                range.note(p0, p1);
+                ow[w] = Half<T>::pack2(p0, p1);
+            }
+            o = make_uint4(ow[0], ow[1], ow[2], ow[3]);
+        }
+        *reinterpret_cast<uint4*>(h + t * (long)ffn + j) = o;
+    }
+    if constexpr (sizeof(T) != 4) range.finish(range_flag);
+}
+
 // LayerNorm for the split-precision Q / K projection (sgpt_model_desc.qk_split): the normalised row a is written as
 // [hi | lo | hi] with hi = round16(a), lo = round16(a - hi) -- three K blocks of a [T, 3d] operand.  Against weights packed as
 // [W_hi | W_hi | W_lo] (pack_split_rows_kernel) one ordinary GEMM over K' = 3d computes a_hi.W_hi + a_lo.W_hi + a_hi.W_lo:
@@ -184,7 +271,9 @@ __global__ __launch_bounds__(256) void layernorm_q8_kernel(const float* __restri
 //   (Pooling.py:99-125; beir_dense_retriever.py:258-270; weights follow the PADDED index)
 // mean: Pooling.py:117-125 / beir_dense_retriever.py:238-242;  lasttoken: :271-282 (index len-1)
 // learntmean (mode 3): w_t = position_weights[P+t], clamp 1e-9 (WeightedMeanPooling.py:21-39)
-template <int NV>
+// RMS = true (the Llama family): the final norm is the RMSNorm of rms_normalize (g alone; b is not read).  The LayerNorm
+// instantiations do not see it (if constexpr).
+template <int NV, bool RMS = false>
 __global__ __launch_bounds__(256) void lnf_pool_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                        const float* __restrict__ b, const int* __restrict__ seq_off,
                                                        const int* __restrict__ seq_len,
@@ -216,7 +305,8 @@ __global__ __launch_bounds__(256) void lnf_pool_kernel(const float* __restrict__
         for (int u = 0; u < LPB; ++u) {
             const int tt = t + 4 * u;
             if (tt >= t_hi) break;
-            if (apply_ln) r[u].template normalize<true>(g, b, d, eps, lane);
+            if constexpr (RMS) { if (apply_ln) rms_normalize<NV, true>(r[u], g, d, eps, lane); }
+            else if (apply_ln) r[u].template normalize<true>(g, b, d, eps, lane);
             // mode 3 (learntmean): trained per-position weights, indexed like the padded position
             // (WeightedMeanPooling.py:21-39; useb_dense_retriever.py:253-270)
             const float w = mode == 0 ? (float)(P + tt + 1) : (mode == 3 ? pw[P + tt < pw_n ? P + tt : pw_n - 1] : 1.0f);   // index clamped: no OOB read
@@ -381,6 +471,44 @@ __global__ __launch_bounds__(256) void rope_kernel(T* __restrict__ buf, long ld,
             const float x0 = Half<T>::lo(u), x1 = Half<T>::hi(u);   // f16: |rotated| <= sqrt(2) * RANGE_LIMIT < 65504
             *reinterpret_cast<uint32_t*>(ptr) = Half<T>::pack2(x0 * cs - x1 * sn, x1 * cs + x0 * sn);
         }
+    }
+}
+
+// ---- half-split rotary position embedding of the Llama family (HF:llama/modeling_llama.py rotate_half / apply_rotary_pos_emb) ----
+// For every token, head and i < dh/2:  (x[i], x[i + dh/2]) <- (x[i] cos - x[i + dh/2] sin, x[i + dh/2] cos + x[i] sin), angle =
+// pos * inv_freq[i] -- the two halves of a head pair up, not GPT-J's neighbours.  In place on the H query heads at column 0 and the
+// H_kv key heads at column k_off of [T][ld].  One thread per four consecutive i of one head: two 16- / 8-byte words of the row and
+// one float4 of each table; fp32 arithmetic, one rounding.  f16: |rotated| <= sqrt(2) * RANGE_LIMIT < 65504, as rope_kernel.
+template <typename T>
+__global__ __launch_bounds__(256) void rope_half_kernel(T* __restrict__ buf, long ld, long k_off, const int* __restrict__ pos,
+                                                        const float* __restrict__ sin_t, const float* __restrict__ cos_t,
+                                                        int Tn, int H, int H_kv, int dh, int max_pos) {
+    const int half = dh / 2, qpt = half / 4;             // quads per head
+    const long per_tok = (long)(H + H_kv) * qpt;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)Tn * per_tok) return;
+    const int tkn = (int)(idx / per_tok);
+    const int rem = (int)(idx - (long)tkn * per_tok);
+    const int h = rem / qpt, i = (rem - h * qpt) * 4;
+    // the position is clamped into the tables, as rope_kernel does
+    int ps = pos[tkn]; ps = ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps);
+    const float4 sn = *reinterpret_cast<const float4*>(sin_t + (long)ps * half + i);
+    const float4 cs = *reinterpret_cast<const float4*>(cos_t + (long)ps * half + i);
+    // heads [0, H): q at column h * dh; heads [H, H + H_kv): k at column k_off + (h - H) * dh
+    T* lo = buf + (long)tkn * ld + (h < H ? (long)h * dh : k_off + (long)(h - H) * dh) + i;
+    T* hi = lo + half;
+    if constexpr (sizeof(T) == 4) {
+        const float4 a = *reinterpret_cast<const float4*>(lo), b = *reinterpret_cast<const float4*>(hi);
+        *reinterpret_cast<float4*>(lo) = make_float4(a.x * cs.x - b.x * sn.x, a.y * cs.y - b.y * sn.y, a.z * cs.z - b.z * sn.z, a.w * cs.w - b.w * sn.w);
+        *reinterpret_cast<float4*>(hi) = make_float4(b.x * cs.x + a.x * sn.x, b.y * cs.y + a.y * sn.y, b.z * cs.z + a.z * sn.z, b.w * cs.w + a.w * sn.w);
+    } else {
+        const uint2 ua = *reinterpret_cast<const uint2*>(lo), ub = *reinterpret_cast<const uint2*>(hi);
+        const float a0 = Half<T>::lo(ua.x), a1 = Half<T>::hi(ua.x), a2 = Half<T>::lo(ua.y), a3 = Half<T>::hi(ua.y);
+        const float b0 = Half<T>::lo(ub.x), b1 = Half<T>::hi(ub.x), b2 = Half<T>::lo(ub.y), b3 = Half<T>::hi(ub.y);
+        *reinterpret_cast<uint2*>(lo) = make_uint2(Half<T>::pack2(a0 * cs.x - b0 * sn.x, a1 * cs.y - b1 * sn.y),
+                                                   Half<T>::pack2(a2 * cs.z - b2 * sn.z, a3 * cs.w - b3 * sn.w));
+        *reinterpret_cast<uint2*>(hi) = make_uint2(Half<T>::pack2(b0 * cs.x + a0 * sn.x, b1 * cs.y + a1 * sn.y),
+                                                   Half<T>::pack2(b2 * cs.z + a2 * sn.z, b3 * cs.w + a3 * sn.w));
     }
 }
 
@@ -662,6 +790,29 @@ void launch_layernorm_writeback(float* x, const float* g, const float* b, void* 
 #undef LW_CASE
 }
 
+void launch_rmsnorm(const float* x, const float* g, void* out, int out_dtype, int T, int d, float eps, int* range_flag, hipStream_t s) {
+#define RN_CASE(NV)                                                                                                              \
+    if (out_dtype == DT_BF16)                                                                                                    \
+        hipLaunchKernelGGL((rmsnorm_kernel<bf16_t, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, (bf16_t*)out, T, d, eps, range_flag); \
+    else if (out_dtype == DT_F16)                                                                                                \
+        hipLaunchKernelGGL((rmsnorm_kernel<f16_t, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, (f16_t*)out, T, d, eps, range_flag);   \
+    else                                                                                                                         \
+        hipLaunchKernelGGL((rmsnorm_kernel<float, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, (float*)out, T, d, eps, range_flag);
+    const int nv = (d + 255) / 256;
+    if (nv <= 1) { RN_CASE(1) } else if (nv <= 2) { RN_CASE(2) } else if (nv <= 3) { RN_CASE(3) }
+    else if (nv <= 4) { RN_CASE(4) } else if (nv <= 8) { RN_CASE(8) } else if (nv <= 10) { RN_CASE(10) }
+    else { RN_CASE(16) }
+#undef RN_CASE
+}
+
+void launch_swiglu(const void* gu, void* h, int dtype, int T, int ffn, int* range_flag, hipStream_t s) {
+    const long n_vec = (long)T * ffn / (dtype == DT_F32 ? 4 : 8);
+    const unsigned grid = (unsigned)((n_vec + 255) / 256);
+    if (dtype == DT_BF16) hipLaunchKernelGGL(swiglu_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)gu, (bf16_t*)h, n_vec, ffn, range_flag);
+    else if (dtype == DT_F16) hipLaunchKernelGGL(swiglu_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (const f16_t*)gu, (f16_t*)h, n_vec, ffn, range_flag);
+    else hipLaunchKernelGGL(swiglu_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)gu, (float*)h, n_vec, ffn, range_flag);
+}
+
 void launch_layernorm_split(const float* x, const float* g, const float* b, void* out, int out_dtype, int T, int d,
                             float eps, hipStream_t s, float out_mul) {
 #define LS_CASE(NV)                                                                                              \
@@ -719,9 +870,13 @@ void launch_absmax16(const void* in, long numel, int dtype, unsigned* out_bits, 
 
 void launch_lnf_pool(const float* x, const float* g, const float* b, const int* seq_off, const int* seq_len,
                      const int* pad_left, int B, int d, float eps, int apply_ln, int mode, int normalize,
-                     const float* pos_weights, int pos_weights_n, float* out, hipStream_t s, int* nonfinite_flag) {
+                     const float* pos_weights, int pos_weights_n, float* out, hipStream_t s, int* nonfinite_flag, int norm_kind) {
     const size_t sm = (size_t)(4 * d + 8) * sizeof(float);
 #define LP_CASE(NV)                                                                                              \
+    if (norm_kind == 1)                                                                                          \
+        hipLaunchKernelGGL((lnf_pool_kernel<NV, true>), dim3(B), dim3(256), sm, s, x, g, b, seq_off, seq_len, pad_left, d, \
+                           eps, apply_ln, mode, normalize, pos_weights, pos_weights_n, out, nonfinite_flag);     \
+    else                                                                                                         \
     hipLaunchKernelGGL((lnf_pool_kernel<NV>), dim3(B), dim3(256), sm, s, x, g, b, seq_off, seq_len, pad_left, d, \
                        eps, apply_ln, mode, normalize, pos_weights, pos_weights_n, out, nonfinite_flag);
     const int nv = (d + 255) / 256;
@@ -819,6 +974,18 @@ void launch_rope(void* qk, int dtype, long ld, long k_off, const int* pos, const
         hipLaunchKernelGGL(rope_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (f16_t*)qk, ld, k_off, pos, sin_t, cos_t, T, H, dh, half, max_pos);
     else
         hipLaunchKernelGGL(rope_kernel<float>, dim3(grid), dim3(256), 0, s, (float*)qk, ld, k_off, pos, sin_t, cos_t, T, H, dh, half, max_pos);
+}
+
+void launch_rope_half(void* qk, int dtype, long ld, long k_off, const int* pos, const float* sin_t, const float* cos_t, int T,
+                      int H, int H_kv, int dh, int max_pos, hipStream_t s) {
+    const long n = (long)T * (H + H_kv) * (dh / 8);
+    const int grid = (int)((n + 255) / 256);
+    if (dtype == DT_BF16)
+        hipLaunchKernelGGL(rope_half_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (bf16_t*)qk, ld, k_off, pos, sin_t, cos_t, T, H, H_kv, dh, max_pos);
+    else if (dtype == DT_F16)
+        hipLaunchKernelGGL(rope_half_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (f16_t*)qk, ld, k_off, pos, sin_t, cos_t, T, H, H_kv, dh, max_pos);
+    else
+        hipLaunchKernelGGL(rope_half_kernel<float>, dim3(grid), dim3(256), 0, s, (float*)qk, ld, k_off, pos, sin_t, cos_t, T, H, H_kv, dh, max_pos);
 }
 
 void launch_qkv_deinterleave(const float* src, float* dst, int H, int dh, long row_len, hipStream_t s) {

@@ -17,6 +17,7 @@ struct Fwd {
     // LayerNorm output; attention context; 16-bit: [T][2d] q | k + V^T [d][T] (x3 attention: the lo halves att_lo elements behind),
     // fp32: [T][3d]; MLP hidden
     void *a, *ctx, *qkv, *vt, *h;
+    void* gu;             // SGPT_ARCH_LLAMA: fc1 output [T][2 ffn] = gate | up columns, the input of the SwiGLU row kernel
     void* a8; float* sa;  // fp8-MFMA block: LayerNorm output as e4m3 codes + one scale per row
     long att_lo;
 };
@@ -94,6 +95,52 @@ void block_bert16(const Fwd& f, const LayerW& l) {
     gemm(f.c, dt, EPI_BIAS_GELU_ERF, dt, proj(f, f.a, dm, l.w_fc, ffn, dm, f.h, ffn, l.b_fc), f.s);
     gemm(f.c, dt, EPI_BIAS_RESID, SGPT_F32, proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x), f.s);
     launch_layernorm_writeback(f.x, l.ln2_g, l.ln2_b, f.a, dt, T, dm, d.ln_eps, f.range_flag, f.s);
+}
+
+// ---- the Llama / Mistral family (SGPT_ARCH_LLAMA; HF:llama/modeling_llama.py LlamaDecoderLayer): pre-RMSNorm, grouped K / V, half-split
+// rotary, SwiGLU, no bias ----
+//   a = RMS1(x) ; q | k | v = a W^T (d + 2 d_kv columns) ; rope_half(q, k) ; x += attention(kv_group) Wo^T ;
+//   a = RMS2(x) ; gu = a [Wgate | Wup]^T ; h = silu(gate) * up ; x += h Wdown^T
+// No range shifts (every f16 store is tracked), no precision plan, bulk kernels at every layout.  l.b_o / l.b_proj are the model's
+// zero vector (the residual epilogue reads a bias).
+AttnArgs attn_llama(const Fwd& f, const LayerW& l, int dkv) {
+    const sgpt_model_desc& d = f.m->d;
+    const int dm = d.d_model;
+    AttnArgs at = attn_base(f, l, 0);
+    at.alibi = nullptr; at.kv_group = d.n_heads / d.n_kv_heads;
+    if (f.vt) { at.k = (bf16_t*)f.qkv + dm; at.ldq = dm + dkv; }                                        // [T][d + d_kv] q | k, V^T [d_kv][T]
+    else { at.k = (float*)f.qkv + dm; at.v = (float*)f.qkv + dm + dkv; at.ldq = dm + 2 * dkv; }      // [T][d + 2 d_kv] q | k | v
+    return at;
+}
+
+void block_llama_f32(const Fwd& f, const LayerW& l) {
+    const sgpt_model_desc& d = f.m->d;
+    const int dm = d.d_model, ffn = d.d_ffn, T = f.T, dh = dm / d.n_heads, dkv = d.n_kv_heads * dh;
+    launch_rmsnorm(f.x, l.ln1_g, f.a, SGPT_F32, T, dm, d.ln_eps, nullptr, f.s);
+    gemm(f.c, SGPT_F32, EPI_STORE, SGPT_F32, proj(f, f.a, dm, l.w_qkv, dm + 2 * dkv, dm, f.qkv, dm + 2 * dkv, nullptr), f.s);
+    launch_rope_half(f.qkv, SGPT_F32, dm + 2 * dkv, dm, f.pos, f.m->rot_sin, f.m->rot_cos, T, d.n_heads, d.n_kv_heads, dh, d.max_pos, f.s);
+    launch_attn_f32(attn_llama(f, l, dkv), f.s);
+    gemm(f.c, SGPT_F32, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dm, l.w_o, dm, dm, f.x, dm, l.b_o, f.x), f.s);
+    launch_rmsnorm(f.x, l.ln2_g, f.a, SGPT_F32, T, dm, d.ln_eps, nullptr, f.s);
+    gemm(f.c, SGPT_F32, EPI_STORE, SGPT_F32, proj(f, f.a, dm, l.w_fc, 2 * ffn, dm, f.gu, 2 * ffn, nullptr), f.s);
+    launch_swiglu(f.gu, f.h, SGPT_F32, T, ffn, nullptr, f.s);
+    gemm(f.c, SGPT_F32, EPI_BIAS_RESID, SGPT_F32, proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x), f.s);
+}
+
+// 16-bit: the context shares a's buffer (a is consumed by the Q | K and V projections before the attention writes)
+void block_llama16(const Fwd& f, const LayerW& l) {
+    const sgpt_model_desc& d = f.m->d;
+    const int dm = d.d_model, ffn = d.d_ffn, T = f.T, dt = f.dt, dh = dm / d.n_heads, dkv = d.n_kv_heads * dh;
+    launch_rmsnorm(f.x, l.ln1_g, f.a, dt, T, dm, d.ln_eps, f.range_flag, f.s);
+    gemm(f.c, dt, EPI_STORE, dt, proj(f, f.a, dm, l.w_qkv, dm + dkv, dm, f.qkv, dm + dkv, nullptr), f.s);                       // q | k
+    gemm(f.c, dt, EPI_VT, dt, proj(f, f.a, dm, (bf16_t*)l.w_qkv + (size_t)(dm + dkv) * dm, dkv, dm, f.vt, T, nullptr), f.s);     // V^T
+    launch_rope_half(f.qkv, dt, dm + dkv, dm, f.pos, f.m->rot_sin, f.m->rot_cos, T, d.n_heads, d.n_kv_heads, dh, d.max_pos, f.s);
+    launch_attn_bf16(attn_llama(f, l, dkv), f.s);
+    gemm(f.c, dt, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dm, l.w_o, dm, dm, f.x, dm, l.b_o, f.x), f.s);
+    launch_rmsnorm(f.x, l.ln2_g, f.a, dt, T, dm, d.ln_eps, f.range_flag, f.s);
+    gemm(f.c, dt, EPI_STORE, dt, proj(f, f.a, dm, l.w_fc, 2 * ffn, dm, f.gu, 2 * ffn, nullptr), f.s);
+    launch_swiglu(f.gu, f.h, dt, T, ffn, f.range_flag, f.s);
+    gemm(f.c, dt, EPI_BIAS_RESID, SGPT_F32, proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x), f.s);
 }
 
 // ---- fp32 block (SGPT_F32): plain operands, q | k | v rows in one buffer ----
@@ -266,6 +313,12 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
     if (bert && pool_mode == SGPT_POOL_LEARNTMEAN)
         return fail(c, SGPT_ERR_INVALID, "sgpt_encode: learntmean pooling (trained position weights of the SGPT checkpoints) is not available for SGPT_ARCH_BERT");
     if (bert) apply_final_ln = 0;      // no ln_f in this family: the last block's LayerNorm output is hidden_states[-1]
+    const bool llama = m->d.arch == SGPT_ARCH_LLAMA;
+    if (llama && pool_mode == SGPT_POOL_LEARNTMEAN)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_encode: learntmean pooling (trained position weights of the SGPT checkpoints) is not available for SGPT_ARCH_LLAMA");
+    if (llama && pool_mode == SGPT_POOL_CLS)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_encode: cls pooling belongs to SGPT_ARCH_BERT");
+    const int norm_kind = llama ? 1 : 0;       // the final norm inside the pool: RMSNorm for this family
     if (pool_mode == SGPT_POOL_LEARNTMEAN && (out || layer_out || layer_mean)) {
         if (!m->pool_w) return fail(c, SGPT_ERR_MISSING, "sgpt_encode: learntmean needs sgpt_model_set_pool_weights first");
         // with pad_left on the device the longest padded position is not known here: the kernel clamps the table index,
@@ -307,6 +360,7 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
     const size_t qkv_bytes = ((size_t)T + SLACK) * 3 * dm * esz;
     const size_t o_qkv = carve(qkv_bytes * (any_att ? 2 : 1));           // bf16: [T][2d] qk + V^T [d][T] (x3 attention: the lo halves behind); fp32: [T][3d]
     const size_t o_h = carve((size_t)T * ffn * esz * (any_h ? 3 : 1));                     // MLP hidden (FP8M: e4m3 codes in the same region)
+    const size_t o_gu = llama ? carve((size_t)T * 2 * ffn * esz) : 0;                      // SGPT_ARCH_LLAMA: fc1 output, gate | up columns
     // FP8M: fp8 MFMA on all four projections when the shapes fit the 256x256x128 kernel and the activation scales are
     // calibrated; otherwise (and while calibrating) the block runs the SGPT_FP8W arithmetic (weights de-quantised to bf16)
     const bool shapes8 = gemm_fp8_shape_ok(T, ffn, dm) && gemm_fp8_shape_ok(T, dm, ffn) && gemm_fp8_shape_ok(T, 2 * dm, dm);
@@ -319,7 +373,7 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
     // pass riding on the forward.  Every projection takes the register-staged deep-prefetch kernel; at d = 512 / 768 / 1024 the two
     // LayerNorms of a sequential block (GPT-Neo, BLOOM) run inside the prologues of the projections they feed: five launches per block
     // instead of seven.  Same arithmetic per element as the bulk path (identical bits); sgpt_ctx_set_tile_policy(1 | 2) keeps the bulk kernels.
-    const bool qpath = bf && !fp8 && !split && !bert && !(m->probing && m->crest_dev) && !m->calibrating && !c->force256 && !c->no_qpath && T <= QGEMM_MAX_ROWS &&
+    const bool qpath = bf && !fp8 && !split && !bert && !llama && !(m->probing && m->crest_dev) && !m->calibrating && !c->force256 && !c->no_qpath && T <= QGEMM_MAX_ROWS &&
                        qgemm_shape_ok(T, 3 * dm, dm, EPI_QKV, 2 * dm) && qgemm_shape_ok(T, dm, dm, EPI_BIAS_RESID, 0) &&
                        qgemm_shape_ok(T, ffn, dm, EPI_BIAS_GELU, 0) && qgemm_shape_ok(T, dm, ffn, EPI_BIAS_RESID, 0);
     const bool qln = qpath && !gptj && qgemm_ln_ok(T, 3 * dm, dm, EPI_QKV, 2 * dm) && qgemm_ln_ok(T, ffn, dm, EPI_BIAS_GELU, 0);
@@ -335,6 +389,7 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
     f.dt = dt; f.range_flag = (mlp8 || dt == SGPT_F16) ? (int*)m->range_dev : nullptr;
     f.can_split = can_split; f.qpath = qpath; f.qln = qln;
     f.x = (float*)(base + o_x); f.a = base + o_a; f.ctx = base + o_c; f.qkv = base + o_qkv; f.h = base + o_h;
+    f.gu = llama ? base + o_gu : nullptr;
     f.vt = bf ? (void*)((bf16_t*)f.qkv + ((size_t)T + SLACK) * 2 * dm) : nullptr;
     if (mlp8) { f.a8 = base + o_a8; f.sa = (float*)(base + o_sa); }
     f.att_lo = (long)(qkv_bytes / 2);      // element distance of the lo halves of q | k and of V^T (x3 attention)
@@ -344,7 +399,13 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
     // (a masked key contributes p = 0, and 0 * NaN = NaN): the slack behind the q/k/v buffers, and -- when
     // the attention context has its own buffer (GPT-J) -- the filler rows past the last sequence.  The
     // workspace is reused across calls / dtypes, so stale bytes there can decode to NaN.
-    if (bf) {
+    if (llama) {          // q | k rows of d + d_kv columns, V^T of d_kv rows (fp32: the kernel reads no key past its query)
+        const size_t dkv = (size_t)m->d.n_kv_heads * (dm / m->d.n_heads);
+        if (bf) {
+            HIPC(c, hipMemsetAsync((bf16_t*)f.qkv + (size_t)T * (dm + dkv), 0, SLACK * (dm + dkv) * esz, s));
+            HIPC(c, hipMemsetAsync((bf16_t*)f.vt + (size_t)T * dkv, 0, SLACK * dkv * esz, s));
+        }
+    } else if (bf) {
         HIPC(c, hipMemsetAsync((bf16_t*)f.qkv + (size_t)T * 2 * dm, 0, SLACK * 2 * dm * esz, s));
         HIPC(c, hipMemsetAsync((bf16_t*)f.vt + (size_t)T * dm, 0, SLACK * dm * esz, s));
         if (any_att) {
@@ -364,7 +425,7 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
         LayerW l = m->L[li];
         if (layer_out)   // hidden_states[li] = input of block li (HF:gpt_neo:475-478)
             launch_lnf_pool(x, m->lnf_g, m->lnf_b, seq_off, seq_len, pad_left, B, dm, m->d.ln_eps, 0, pool_mode,
-                            normalize, m->pool_w, m->pool_w_n, layer_out + (size_t)li * B * dm, s);
+                            normalize, m->pool_w, m->pool_w_n, layer_out + (size_t)li * B * dm, s, nullptr, norm_kind);
         if (fp8 && !mlp8) {  // this block's weights: e4m3fn codes * 2^k -> bf16, exact; <1 % of the block's time at T >= 16k
             launch_fp8_dequant_rows(l.w_qkv, l.s_qkv, (long)3 * dm, dm, m->dq[0], SGPT_BF16, s);
             launch_fp8_dequant_rows(l.w_o, l.s_o, dm, dm, m->dq[1], SGPT_BF16, s);
@@ -373,21 +434,23 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
             l.w_qkv = m->dq[0]; l.w_o = m->dq[1]; l.w_fc = m->dq[2]; l.w_proj = m->dq[3];
         }
         if (bert) { if (bf) block_bert16(f, l); else block_bert_f32(f, l); }
+        else if (llama) { if (bf) block_llama16(f, l); else block_llama_f32(f, l); }
         else if (mlp8) block_fp8(f, l, li);
         else if (!bf) block_f32(f, l);
         else if ((st = block_16(f, l, li)) != SGPT_OK) return st;
     }
     if (hidden_out) {
-        if (apply_final_ln) launch_layernorm(x, m->lnf_g, m->lnf_b, hidden_out, SGPT_F32, T, dm, m->d.ln_eps, s);
+        if (apply_final_ln && llama) launch_rmsnorm(x, m->lnf_g, hidden_out, SGPT_F32, T, dm, m->d.ln_eps, nullptr, s);
+        else if (apply_final_ln) launch_layernorm(x, m->lnf_g, m->lnf_b, hidden_out, SGPT_F32, T, dm, m->d.ln_eps, s);
         else HIPC(c, hipMemcpyAsync(hidden_out, x, (size_t)T * dm * 4, hipMemcpyDeviceToDevice, s));
     }
     if (out)
         launch_lnf_pool(x, m->lnf_g, m->lnf_b, seq_off, seq_len, pad_left, B, dm, m->d.ln_eps, apply_final_ln,
                         pool_mode, normalize, m->pool_w, m->pool_w_n, out, s,
-                        m->d.compute_dtype == SGPT_F16 ? (int*)m->range_dev : nullptr);
+                        m->d.compute_dtype == SGPT_F16 ? (int*)m->range_dev : nullptr, norm_kind);
     if (layer_out)
         launch_lnf_pool(x, m->lnf_g, m->lnf_b, seq_off, seq_len, pad_left, B, dm, m->d.ln_eps, apply_final_ln,
-                        pool_mode, normalize, m->pool_w, m->pool_w_n, layer_out + (size_t)n_layers_run * B * dm, s);
+                        pool_mode, normalize, m->pool_w, m->pool_w_n, layer_out + (size_t)n_layers_run * B * dm, s, nullptr, norm_kind);
     if (layer_mean) launch_mean_over_axis0(layer_out, n_layers_run + 1, (long)B * dm, layer_mean, s);
     HIPC(c, hipGetLastError());
     return SGPT_OK;
@@ -418,6 +481,7 @@ sgpt_status sgpt_lm_logprobs(sgpt_model* m, const float* hidden, const int32_t* 
     sgpt_ctx* c = m->ctx;
     if (!hidden || !row_idx || !targets || !out_logprob || n <= 0) return fail(c, SGPT_ERR_INVALID, "sgpt_lm_logprobs: bad arguments");
     if (m->d.arch == SGPT_ARCH_BERT) return fail(c, SGPT_ERR_INVALID, "sgpt_lm_logprobs: SGPT_ARCH_BERT carries no causal LM head");
+    if (m->d.arch == SGPT_ARCH_LLAMA) return fail(c, SGPT_ERR_INVALID, "sgpt_lm_logprobs: not built for SGPT_ARCH_LLAMA (the LM head of this family is not loaded)");
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int dm = m->d.d_model, V = m->d.vocab;

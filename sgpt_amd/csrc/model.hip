@@ -11,9 +11,11 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
     if (!c || !d || !tv || !out) return SGPT_ERR_INVALID;
     *out = nullptr;
     HIPC(c, hipSetDevice(c->device));
-    if (d->arch != SGPT_ARCH_GPTNEO && d->arch != SGPT_ARCH_GPTJ && d->arch != SGPT_ARCH_BLOOM && d->arch != SGPT_ARCH_BERT)
-        return fail(c, SGPT_ERR_INVALID, "arch must be SGPT_ARCH_GPTNEO, SGPT_ARCH_GPTJ, SGPT_ARCH_BLOOM or SGPT_ARCH_BERT");
+    if (d->arch != SGPT_ARCH_GPTNEO && d->arch != SGPT_ARCH_GPTJ && d->arch != SGPT_ARCH_BLOOM && d->arch != SGPT_ARCH_BERT &&
+        d->arch != SGPT_ARCH_LLAMA)
+        return fail(c, SGPT_ERR_INVALID, "arch must be SGPT_ARCH_GPTNEO, SGPT_ARCH_GPTJ, SGPT_ARCH_BLOOM, SGPT_ARCH_BERT or SGPT_ARCH_LLAMA");
     const bool gptj = d->arch == SGPT_ARCH_GPTJ, bloom = d->arch == SGPT_ARCH_BLOOM, bert = d->arch == SGPT_ARCH_BERT;
+    const bool llama = d->arch == SGPT_ARCH_LLAMA;
     const int dm = d->d_model, ffn = d->d_ffn, H = d->n_heads;
     if (dm % 128 || ffn % 128 || H <= 0 || dm % H) return fail(c, SGPT_ERR_INVALID, "d_model and d_ffn must be multiples of 128");
     const int dh = dm / H;
@@ -40,12 +42,27 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
         if (d->window != 0) return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_BERT: window must be 0");
     }
 
+    if (llama) {
+        // one arithmetic per operand format, as for SGPT_ARCH_BERT
+        if (d->compute_dtype == SGPT_FP8W || d->compute_dtype == SGPT_FP8M)
+            return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_LLAMA: compute_dtype SGPT_F32, SGPT_F16 or SGPT_BF16 (no fp8 mode for this family)");
+        if (d->qk_split != 0 || d->split_weights != 0)
+            return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_LLAMA: qk_split / split_weights (split-precision operands) are not available for this family");
+        if (dh != 64 && dh != 128) return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_LLAMA: head_dim 64 or 128");
+        if (d->n_kv_heads < 0 || (d->n_kv_heads > 0 && H % d->n_kv_heads))
+            return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_LLAMA: n_heads % n_kv_heads == 0 (0 = n_heads)");
+        if (d->window < 0) return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_LLAMA: window >= 0");
+    } else if (d->n_kv_heads != 0 && d->n_kv_heads != H) {
+        return fail(c, SGPT_ERR_INVALID, "n_kv_heads (grouped K / V) belongs to SGPT_ARCH_LLAMA");
+    }
+
     std::unordered_map<std::string, const sgpt_tensor_view*> byname;
     for (size_t i = 0; i < nt; ++i) byname[tv[i].name] = &tv[i];
     sgpt_model* m = new sgpt_model();
     m->ctx = c;
     m->d = *d;
     m->d.layer_is_local = nullptr;
+    if (m->d.n_kv_heads == 0) m->d.n_kv_heads = H;
     const bool fp8 = d->compute_dtype == SGPT_FP8W || d->compute_dtype == SGPT_FP8M;
     const bool f16 = d->compute_dtype == SGPT_F16;
     const bool bf = d->compute_dtype == SGPT_BF16 || f16;          // 16-bit packed weights
@@ -100,8 +117,12 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
         if (src) pack_rows(src, rows, cols, dst, row_off, scale);
     };
 
-    m->wte = copy_f32(bert ? "embeddings.word_embeddings.weight" : (bloom ? "word_embeddings.weight" : "wte.weight"), (int64_t)d->vocab * dm);
-    if (bert) {
+    m->wte = copy_f32(llama ? "embed_tokens.weight" : (bert ? "embeddings.word_embeddings.weight" : (bloom ? "word_embeddings.weight" : "wte.weight")),
+                      (int64_t)d->vocab * dm);
+    if (llama) {        // no position table: half-split rotary on q / k (tables from the host, include/sgpt_hip.h)
+        m->rot_sin = copy_f32("rotary.sin", (int64_t)d->max_pos * (dh / 2));
+        m->rot_cos = copy_f32("rotary.cos", (int64_t)d->max_pos * (dh / 2));
+    } else if (bert) {
         // position table with token_type_embeddings[0] already added by the caller (single-segment inputs; include/sgpt_hip.h)
         m->wpe = copy_f32("embeddings.position_embeddings.weight", (int64_t)d->max_pos * dm);
         copy_ln("embeddings.LayerNorm", &m->emb_ln_g, &m->emb_ln_b);
@@ -122,7 +143,9 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
         m->lm_w = copy_f32("lm_head.weight", (int64_t)d->vocab * dm);
         if (byname.count("lm_head.bias")) m->lm_b = copy_f32("lm_head.bias", d->vocab);
     }
-    if (!bert) {        // (BERT has no final LayerNorm: every block ends in one)
+    if (llama) {        // final RMSNorm: a gain, no bias
+        m->lnf_g = copy_f32("norm.weight", dm);
+    } else if (!bert) { // (BERT has no final LayerNorm: every block ends in one)
         m->lnf_g = copy_f32("ln_f.weight", dm);
         m->lnf_b = copy_f32("ln_f.bias", dm);
     }
@@ -170,7 +193,30 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
         pack_w(p + "intermediate.dense.weight", ffn, dm, l.w_fc, 0, nullptr);
         pack_w(p + "output.dense.weight", dm, ffn, l.w_proj, 0, nullptr);
     }
-    for (int i = 0; !bert && i < d->n_layers && st == SGPT_OK; ++i) {
+    // LLAMA layers.N.input_layernorm / self_attn.{qkv_proj (q | k | v rows fused by the caller), o_proj} / post_attention_layernorm /
+    //       mlp.{gate_up_proj (gate rows, then up rows), down_proj}; no biases      (HF:llama/modeling_llama.py LlamaDecoderLayer)
+    // The RMSNorm gains carry no load-time bound (the f16 stores of rmsnorm_kernel are range-tracked at run time): shifts stay 0.
+    for (int i = 0; llama && i < d->n_layers && st == SGPT_OK; ++i) {
+        const std::string p = "layers." + std::to_string(i) + ".";
+        const int64_t dkv = (int64_t)m->d.n_kv_heads * dh;
+        LayerW& l = m->L[i];
+        l.is_local = d->layer_is_local ? d->layer_is_local[i] : (d->window > 0 ? 1 : 0);
+        l.ln1_g = copy_f32(p + "input_layernorm.weight", dm);
+        l.ln2_g = copy_f32(p + "post_attention_layernorm.weight", dm);
+        l.ln1_b = l.ln2_b = nullptr;
+        l.b_o = l.b_proj = m->zero_bias;       // the residual epilogue reads a bias vector: zeros
+        l.b_fc = nullptr;
+        l.w_qkv = dalloc((size_t)(dm + 2 * dkv) * dm * esz);
+        l.w_o = dalloc((size_t)dm * dm * esz);
+        l.w_fc = dalloc((size_t)2 * ffn * dm * esz);
+        l.w_proj = dalloc((size_t)dm * ffn * esz);
+        if (st != SGPT_OK) break;
+        pack_w(p + "self_attn.qkv_proj.weight", dm + 2 * dkv, dm, l.w_qkv, 0, nullptr);
+        pack_w(p + "self_attn.o_proj.weight", dm, dm, l.w_o, 0, nullptr);
+        pack_w(p + "mlp.gate_up_proj.weight", (int64_t)2 * ffn, dm, l.w_fc, 0, nullptr);
+        pack_w(p + "mlp.down_proj.weight", dm, ffn, l.w_proj, 0, nullptr);
+    }
+    for (int i = 0; !bert && !llama && i < d->n_layers && st == SGPT_OK; ++i) {
         const std::string p = "h." + std::to_string(i) + ".";
         LayerW& l = m->L[i];
         l.is_local = (gptj || bloom) ? 0 : (d->layer_is_local ? d->layer_is_local[i] : (i & 1));
@@ -272,7 +318,7 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
         if (st == SGPT_OK && (!(wmax < 65504.f) || !std::isfinite(bound)))
             st = fail(c, SGPT_ERR_RANGE, "SGPT_F16: a matmul weight exceeds the f16 range (or a LayerNorm parameter is not finite); load with SGPT_BF16");
         // (BERT: shifts stay 0 -- its write-back LayerNorm carries a run-time range tracker instead of relying on this bound)
-        if (st == SGPT_OK && !(bound < 32768.f) && !bert) {
+        if (st == SGPT_OK && !(bound < 32768.f) && !bert && !llama) {
             int k = (int)std::ceil(std::log2(bound / 16384.f));
             k = k < 1 ? 1 : k;
             if (k > RS_MAX_SHIFT) st = fail(c, SGPT_ERR_RANGE, "SGPT_F16: LayerNorm parameters beyond any usable range shift; load with SGPT_BF16");
@@ -378,8 +424,8 @@ sgpt_status sgpt_model_range_adapt(sgpt_model* m, int32_t* n_raised, void* strea
     sgpt_ctx* c = m->ctx;
     *n_raised = 0;
     if (m->d.compute_dtype != SGPT_F16) return fail(c, SGPT_ERR_INVALID, "sgpt_model_range_adapt applies to SGPT_F16 models");
-    if (m->d.arch == SGPT_ARCH_BERT)
-        return fail(c, SGPT_ERR_INVALID, "sgpt_model_range_adapt: SGPT_ARCH_BERT runs without range shifts; a flagged f16 model must be loaded with SGPT_BF16 or SGPT_F32");
+    if (m->d.arch == SGPT_ARCH_BERT || m->d.arch == SGPT_ARCH_LLAMA)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_model_range_adapt: SGPT_ARCH_BERT / SGPT_ARCH_LLAMA run without range shifts; a flagged f16 model must be loaded with SGPT_BF16 or SGPT_F32");
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int n = m->d.n_layers * RS_N;
@@ -422,7 +468,8 @@ sgpt_status sgpt_model_set_range_shifts(sgpt_model* m, const int32_t* shifts, in
     sgpt_ctx* c = m->ctx;
     if (m->d.compute_dtype != SGPT_F16 || !shifts || n != m->d.n_layers * RS_N)
         return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_range_shifts: SGPT_F16 models, n = 4 * n_layers");
-    if (m->d.arch == SGPT_ARCH_BERT) return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_range_shifts: SGPT_ARCH_BERT runs without range shifts");
+    if (m->d.arch == SGPT_ARCH_BERT || m->d.arch == SGPT_ARCH_LLAMA)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_range_shifts: SGPT_ARCH_BERT / SGPT_ARCH_LLAMA run without range shifts");
     for (int i = 0; i < n; ++i)
         if (shifts[i] < 0 || shifts[i] > RS_MAX_SHIFT) return fail(c, SGPT_ERR_INVALID, "range shifts must lie in [0, 40]");
     // the LayerNorm kernels have no run-time range tracker: their shifts may not go below the bound sgpt_model_load derived
@@ -458,7 +505,8 @@ sgpt_status sgpt_model_set_precision(sgpt_model* m, const int32_t* plan, int32_t
         if (cls == PC_LN2 && m->d.arch == SGPT_ARCH_GPTJ && v != 0 && plan[i - PC_LN2 + PC_LN1] == 0)
             return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision: GPT-J's MLP reads ln_1's output: a split fc1 needs a split LayerNorm-1 entry");
     }
-    if (any && m->d.arch == SGPT_ARCH_BERT) return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision: no split-precision operands for SGPT_ARCH_BERT");
+    if (any && (m->d.arch == SGPT_ARCH_BERT || m->d.arch == SGPT_ARCH_LLAMA))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision: no split-precision operands for SGPT_ARCH_BERT / SGPT_ARCH_LLAMA");
     if (any && cd != SGPT_F16 && cd != SGPT_BF16) return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision applies to SGPT_F16 / SGPT_BF16 models");
     for (int i = 0; i < n; ++i) m->prec[i] = plan[i];
     c->generation++;                                      // captured graphs carry the old launch sequence
@@ -515,7 +563,7 @@ sgpt_status sgpt_model_release_split_weights(sgpt_model* m, int64_t* bytes_freed
 sgpt_status sgpt_model_precision_probe_begin(sgpt_model* m) {
     if (!m) return SGPT_ERR_INVALID;
     sgpt_ctx* c = m->ctx;
-    if (!m->crest_dev || m->d.arch == SGPT_ARCH_BERT) return fail(c, SGPT_ERR_INVALID, "the precision probe applies to SGPT_F16 / SGPT_BF16 models of the decoder families");
+    if (!m->crest_dev || m->d.arch == SGPT_ARCH_BERT || m->d.arch == SGPT_ARCH_LLAMA) return fail(c, SGPT_ERR_INVALID, "the precision probe applies to SGPT_F16 / SGPT_BF16 models of the decoder families");
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipDeviceSynchronize());
     HIPC(c, hipMemset(m->crest_dev, 0, (size_t)m->d.n_layers * RS_N * 4));

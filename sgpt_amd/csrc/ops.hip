@@ -200,50 +200,54 @@ sgpt_status sgpt_linear_qkv(sgpt_ctx* c, int32_t dtype, const void* A, const voi
     return SGPT_OK;
 }
 
-sgpt_status sgpt_attention_ex(sgpt_ctx* c, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
+}  // extern "C"
+
+// sgpt_attention / sgpt_attention_ex / sgpt_attention_gqa: one argument check, one descriptor.  kv_group = query heads per key / value head.
+static sgpt_status attention_impl(sgpt_ctx* c, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
                               void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t dh,
                               int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
                               float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
-                              int64_t ctx_lo_delta, int64_t ctx_hi2_delta, int32_t causal, const int32_t* seq_len, void* stream) {
-    if (causal != 0 && causal != 1) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_ex: causal 0 | 1");
-    if (causal && seq_len) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_ex: seq_len belongs to the bidirectional mode (causal = 0)");
+                              int64_t ctx_lo_delta, int64_t ctx_hi2_delta, int32_t causal, const int32_t* seq_len, int32_t kv_group, const char* who, void* stream) {
+    const std::string w = std::string(who) + ": ";   // the entry the caller used: its name leads every refusal
+    if (causal != 0 && causal != 1) return fail(c, SGPT_ERR_INVALID, w + "causal 0 | 1");
+    if (causal && seq_len) return fail(c, SGPT_ERR_INVALID, w + "seq_len belongs to the bidirectional mode (causal = 0)");
     if (!causal) {
-        if (window != 0 || alibi != nullptr) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_ex: bidirectional attention takes no window and no ALiBi");
+        if (window != 0 || alibi != nullptr) return fail(c, SGPT_ERR_INVALID, w + "bidirectional attention takes no window and no ALiBi");
         if (out_fp8 || x3 || ctx_lo_delta != 0 || ctx_hi2_delta != 0)
-            return fail(c, SGPT_ERR_INVALID, "sgpt_attention_ex: out_fp8 and the split-precision modes are causal only");
-        if (dtype != SGPT_F32 && dh != 64 && dh != 128) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_ex: 16-bit bidirectional attention serves head_dim 64 | 128");
+            return fail(c, SGPT_ERR_INVALID, w + "out_fp8 and the split-precision modes are causal only");
+        if (dtype != SGPT_F32 && dh != 64 && dh != 128) return fail(c, SGPT_ERR_INVALID, w + "16-bit bidirectional attention serves head_dim 64 | 128");
     }
     // every combination launch_attn_bf16 would abort() on is refused here, before anything is launched
     auto mis = [](const void* p, unsigned a) { return ((uintptr_t)p & (a - 1)) != 0; };
     if (!c || !q || !k || !v || !out || !seq_off || B <= 0 || T <= 0 || H <= 0 || window < 0 || !std::isfinite(scale))
-        return fail(c, SGPT_ERR_INVALID, "sgpt_attention: bad arguments");
+        return fail(c, SGPT_ERR_INVALID, w + "bad arguments");
     const bool in16 = dtype == SGPT_BF16 || dtype == SGPT_F16;
-    if (!in16 && dtype != SGPT_F32) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: dtype SGPT_F32 | SGPT_BF16 | SGPT_F16");
-    if (dh != 64 && dh != 128 && dh != 256) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: head_dim 64, 128 or 256");
-    if (T % 32) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: T % 32 == 0");
+    if (!in16 && dtype != SGPT_F32) return fail(c, SGPT_ERR_INVALID, w + "dtype SGPT_F32 | SGPT_BF16 | SGPT_F16");
+    if (dh != 64 && dh != 128 && dh != 256) return fail(c, SGPT_ERR_INVALID, w + "head_dim 64, 128 or 256");
+    if (T % 32) return fail(c, SGPT_ERR_INVALID, w + "T % 32 == 0");
     if (max_alloc_len <= 0 || max_alloc_len > 2048 || max_alloc_len % 2)
-        return fail(c, SGPT_ERR_INVALID, "sgpt_attention: max_alloc_len even, in [2, 2048]");
+        return fail(c, SGPT_ERR_INVALID, w + "max_alloc_len even, in [2, 2048]");
     const long d = (long)H * dh;
-    if (ldq < d || ldo < d) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: ldq, ldo >= H * head_dim");
+    if (ldq < d || ldo < d) return fail(c, SGPT_ERR_INVALID, w + "ldq, ldo >= H * head_dim");
     const bool split_ctx = ctx_lo_delta != 0;
     if (!in16 && (out_fp8 || x3 || split_ctx || ctx_hi2_delta))
-        return fail(c, SGPT_ERR_INVALID, "sgpt_attention: out_fp8 / x3 / split context are 16-bit modes");
-    if (ctx_hi2_delta != 0 && !split_ctx) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: ctx_hi2_delta needs ctx_lo_delta");
+        return fail(c, SGPT_ERR_INVALID, w + "out_fp8 / x3 / split context are 16-bit modes");
+    if (ctx_hi2_delta != 0 && !split_ctx) return fail(c, SGPT_ERR_INVALID, w + "ctx_hi2_delta needs ctx_lo_delta");
     if (out_fp8) {
-        if (dtype != SGPT_BF16) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: out_fp8 takes bf16 operands");
-        if (x3 || split_ctx) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: out_fp8 with a split-precision mode");
-        if (!(out_scale > 0.f) || !std::isfinite(out_scale)) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: out_scale > 0");
+        if (dtype != SGPT_BF16) return fail(c, SGPT_ERR_INVALID, w + "out_fp8 takes bf16 operands");
+        if (x3 || split_ctx) return fail(c, SGPT_ERR_INVALID, w + "out_fp8 with a split-precision mode");
+        if (!(out_scale > 0.f) || !std::isfinite(out_scale)) return fail(c, SGPT_ERR_INVALID, w + "out_scale > 0");
     }
-    if (x3 && !attn_x3_supported(dh)) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: x3 needs head_dim 64 | 128");
-    if (x3 && (qk_lo_delta == 0 || v_lo_delta == 0)) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: x3 needs non-zero lo deltas");
+    if (x3 && !attn_x3_supported(dh)) return fail(c, SGPT_ERR_INVALID, w + "x3 needs head_dim 64 | 128");
+    if (x3 && (qk_lo_delta == 0 || v_lo_delta == 0)) return fail(c, SGPT_ERR_INVALID, w + "x3 needs non-zero lo deltas");
     if (in16) {
         if (mis(q, 16) || mis(k, 16) || mis(v, 4) || mis(out, 16))
-            return fail(c, SGPT_ERR_INVALID, "sgpt_attention: 16-byte aligned q / k / out, 4-byte aligned V^T");
+            return fail(c, SGPT_ERR_INVALID, w + "16-byte aligned q / k / out, 4-byte aligned V^T");
         if (ldq % 8 || ldo % (out_fp8 ? 16 : 8) || qk_lo_delta % 8 || ctx_lo_delta % 8 || ctx_hi2_delta % 8 || ldvt % 2 || v_lo_delta % 2)
-            return fail(c, SGPT_ERR_INVALID, "sgpt_attention: ldq, ldo, qk / ctx deltas % 8 (out_fp8: ldo % 16); ldvt, v_lo_delta even");
-        if (ldvt < T) return fail(c, SGPT_ERR_INVALID, "sgpt_attention: ldvt >= T");
+            return fail(c, SGPT_ERR_INVALID, w + "ldq, ldo, qk / ctx deltas % 8 (out_fp8: ldo % 16); ldvt, v_lo_delta even");
+        if (ldvt < T) return fail(c, SGPT_ERR_INVALID, w + "ldvt >= T");
     } else if (mis(q, 16) || mis(k, 16) || mis(v, 16) || mis(out, 4) || ldq % 4) {
-        return fail(c, SGPT_ERR_INVALID, "sgpt_attention: fp32 q / k / v 16-byte aligned, ldq % 4");
+        return fail(c, SGPT_ERR_INVALID, w + "fp32 q / k / v 16-byte aligned, ldq % 4");
     }
     HIPC(c, hipSetDevice(c->device));
     AttnArgs at{};
@@ -254,11 +258,36 @@ sgpt_status sgpt_attention_ex(sgpt_ctx* c, int32_t dtype, const void* q, const v
     at.out_fp8 = out_fp8 ? 1 : 0; at.out_scale = out_scale; at.range_flag = range_flag;
     at.x3 = x3 ? 1 : 0; at.qk_lo_delta = qk_lo_delta; at.v_lo_delta = v_lo_delta;
     at.ctx_lo_delta = ctx_lo_delta; at.ctx_hi2_delta = ctx_hi2_delta;
-    at.noncausal = causal ? 0 : 1; at.seq_len = seq_len;
+    at.noncausal = causal ? 0 : 1; at.seq_len = seq_len; at.kv_group = kv_group;
     if (in16) launch_attn_bf16(at, (hipStream_t)stream);
     else launch_attn_f32(at, (hipStream_t)stream);
     HIPC(c, hipGetLastError());
     return SGPT_OK;
+}
+
+extern "C" {
+
+sgpt_status sgpt_attention_ex(sgpt_ctx* c, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
+                              void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t dh,
+                              int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
+                              float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
+                              int64_t ctx_lo_delta, int64_t ctx_hi2_delta, int32_t causal, const int32_t* seq_len, void* stream) {
+    return attention_impl(c, dtype, q, k, v, ldq, ldvt, out, ldo, seq_off, B, T, H, dh, window, scale, alibi, max_alloc_len, out_fp8,
+                          out_scale, range_flag, x3, qk_lo_delta, v_lo_delta, ctx_lo_delta, ctx_hi2_delta, causal, seq_len, 1, "sgpt_attention_ex", stream);
+}
+
+sgpt_status sgpt_attention_gqa(sgpt_ctx* c, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
+                               void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t n_kv_heads,
+                               int32_t dh, int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
+                               float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
+                               int64_t ctx_lo_delta, int64_t ctx_hi2_delta, void* stream) {
+    if (H <= 0 || n_kv_heads <= 0 || H % n_kv_heads) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_gqa: n_heads % n_kv_heads == 0, both > 0");
+    if (alibi != nullptr) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_gqa: no ALiBi with grouped K / V");
+    if (out_fp8 || x3 || ctx_lo_delta != 0 || ctx_hi2_delta != 0)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_attention_gqa: out_fp8 and the split-precision modes are not available with grouped K / V");
+    if (dtype != SGPT_F32 && dh != 64 && dh != 128) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_gqa: 16-bit grouped attention serves head_dim 64 | 128");
+    return attention_impl(c, dtype, q, k, v, ldq, ldvt, out, ldo, seq_off, B, T, H, dh, window, scale, nullptr, max_alloc_len, 0,
+                          out_scale, range_flag, 0, qk_lo_delta, v_lo_delta, 0, 0, 1, nullptr, H / n_kv_heads, "sgpt_attention_gqa", stream);
 }
 
 sgpt_status sgpt_attention(sgpt_ctx* c, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
@@ -266,8 +295,8 @@ sgpt_status sgpt_attention(sgpt_ctx* c, int32_t dtype, const void* q, const void
                            int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
                            float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
                            int64_t ctx_lo_delta, int64_t ctx_hi2_delta, void* stream) {
-    return sgpt_attention_ex(c, dtype, q, k, v, ldq, ldvt, out, ldo, seq_off, B, T, H, dh, window, scale, alibi, max_alloc_len, out_fp8,
-                             out_scale, range_flag, x3, qk_lo_delta, v_lo_delta, ctx_lo_delta, ctx_hi2_delta, 1, nullptr, stream);
+    return attention_impl(c, dtype, q, k, v, ldq, ldvt, out, ldo, seq_off, B, T, H, dh, window, scale, alibi, max_alloc_len, out_fp8,
+                          out_scale, range_flag, x3, qk_lo_delta, v_lo_delta, ctx_lo_delta, ctx_hi2_delta, 1, nullptr, 1, "sgpt_attention", stream);
 }
 
 // ---- the encoder's row kernels stand-alone (elementwise.hip; tests/test_gpu_rowops.py): every argument a launch would index or
@@ -323,21 +352,70 @@ sgpt_status sgpt_layernorm_writeback(sgpt_ctx* c, float* x, const float* gamma, 
     return SGPT_OK;
 }
 
+sgpt_status sgpt_rmsnorm(sgpt_ctx* c, const float* x, const float* gamma, int32_t T, int32_t d, float eps, void* out, int32_t out_dtype,
+                         void* stream) {
+    if (!c || !x || !gamma || !out || T <= 0 || !row_width_ok(d) || !(eps >= 0.f) || !std::isfinite(eps))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_rmsnorm: bad arguments (d % 4 == 0, d <= 4096)");
+    const bool o16 = out_dtype == SGPT_BF16 || out_dtype == SGPT_F16;
+    if (!o16 && out_dtype != SGPT_F32) return fail(c, SGPT_ERR_INVALID, "sgpt_rmsnorm: out_dtype SGPT_F32 | SGPT_BF16 | SGPT_F16");
+    if ((const void*)out == (const void*)x && o16) return fail(c, SGPT_ERR_INVALID, "sgpt_rmsnorm: in place is fp32 only");
+    if (mis(x, 16) || mis(gamma, 16) || mis(out, o16 ? 8 : 16))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_rmsnorm: 16-byte aligned x / gamma / fp32 out, 8-byte aligned 16-bit out");
+    HIPC(c, hipSetDevice(c->device));
+    launch_rmsnorm(x, gamma, out, out_dtype, T, d, eps, out_dtype == SGPT_F16 ? c->range_flag : nullptr, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_swiglu(sgpt_ctx* c, const void* gu, int32_t dtype, int32_t T, int32_t ffn, void* out, void* stream) {
+    if (!c || !gu || !out || T <= 0 || ffn <= 0) return fail(c, SGPT_ERR_INVALID, "sgpt_swiglu: bad arguments");
+    if (dtype != SGPT_F32 && dtype != SGPT_BF16 && dtype != SGPT_F16) return fail(c, SGPT_ERR_INVALID, "sgpt_swiglu: dtype SGPT_F32 | SGPT_BF16 | SGPT_F16");
+    // a thread moves 16 bytes of a row: 4 fp32 / 8 16-bit columns, the up half ffn elements behind the gate half
+    if (ffn % (dtype == SGPT_F32 ? 4 : 8) || mis(gu, 16) || mis(out, 16) || gu == (const void*)out)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_swiglu: ffn % 8 (16-bit) / 4 (fp32); 16-byte aligned buffers; out is a buffer of its own");
+    HIPC(c, hipSetDevice(c->device));
+    launch_swiglu(gu, out, dtype, T, ffn, dtype == SGPT_F16 ? c->range_flag : nullptr, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+static sgpt_status lnf_pool_impl(sgpt_ctx* c, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
+                                 const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
+                                 int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,
+                                 int32_t* nonfinite_flag, int32_t norm_kind, void* stream);
+
 sgpt_status sgpt_lnf_pool(sgpt_ctx* c, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
                           const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
                           int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,
                           int32_t* nonfinite_flag, void* stream) {
+    return lnf_pool_impl(c, x, gamma, beta, seq_off, seq_len, pad_left, B, d, eps, apply_ln, mode, normalize, pos_weights, n_weights, out,
+                         nonfinite_flag, 0, stream);
+}
+
+sgpt_status sgpt_lnf_pool_ex(sgpt_ctx* c, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
+                             const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
+                             int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,
+                             int32_t* nonfinite_flag, int32_t norm_kind, void* stream) {
+    if (norm_kind != 0 && norm_kind != 1) return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool_ex: norm_kind 0 (LayerNorm) | 1 (RMSNorm)");
+    return lnf_pool_impl(c, x, gamma, beta, seq_off, seq_len, pad_left, B, d, eps, apply_ln, mode, normalize, pos_weights, n_weights, out,
+                         nonfinite_flag, norm_kind, stream);
+}
+
+static sgpt_status lnf_pool_impl(sgpt_ctx* c, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
+                                 const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
+                                 int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,
+                                 int32_t* nonfinite_flag, int32_t norm_kind, void* stream) {
     if (!c || !x || !seq_off || !seq_len || !out || B <= 0 || !row_width_ok(d))
         return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool: bad arguments (d % 4 == 0, d <= 4096)");
     if (mode < SGPT_POOL_WEIGHTEDMEAN || mode > SGPT_POOL_LEARNTMEAN) return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool: mode 0 .. 3");
-    if (apply_ln && (!gamma || !beta || !(eps >= 0.f) || !std::isfinite(eps)))
-        return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool: apply_ln needs gamma, beta and eps >= 0");
+    if (apply_ln && (!gamma || (!beta && norm_kind == 0) || !(eps >= 0.f) || !std::isfinite(eps)))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool: apply_ln needs gamma, beta (LayerNorm) and eps >= 0");
     if (mode == SGPT_POOL_LEARNTMEAN && (!pos_weights || n_weights <= 0))
         return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool: learntmean needs pos_weights and n_weights > 0");
     if (mis(x, 16) || mis(gamma, 16) || mis(beta, 16)) return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool: 16-byte aligned x / gamma / beta");
     HIPC(c, hipSetDevice(c->device));
     launch_lnf_pool(x, gamma, beta, seq_off, seq_len, pad_left, B, d, eps, apply_ln ? 1 : 0, mode, normalize ? 1 : 0, pos_weights,
-                    n_weights, out, (hipStream_t)stream, nonfinite_flag);
+                    n_weights, out, (hipStream_t)stream, nonfinite_flag, norm_kind);
     HIPC(c, hipGetLastError());
     return SGPT_OK;
 }
@@ -355,6 +433,22 @@ sgpt_status sgpt_rope(sgpt_ctx* c, void* buf, int32_t dtype, int64_t ld, int64_t
         return fail(c, SGPT_ERR_INVALID, "sgpt_rope: head_dim, ld, k_off even; k_off >= H * head_dim; ld >= k_off + H * head_dim; buf aligned to a pair");
     HIPC(c, hipSetDevice(c->device));
     launch_rope(buf, dtype, ld, k_off, pos, sin_t, cos_t, T, H, head_dim, rotary_dim, max_pos, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_rope_half(sgpt_ctx* c, void* buf, int32_t dtype, int64_t ld, int64_t k_off, const int32_t* pos, const float* sin_t,
+                           const float* cos_t, int32_t T, int32_t H, int32_t H_kv, int32_t head_dim, int32_t max_pos, void* stream) {
+    if (!c || !buf || !pos || !sin_t || !cos_t || T <= 0 || H <= 0 || H_kv <= 0 || head_dim <= 0 || max_pos <= 0)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_rope_half: bad arguments");
+    if (dtype != SGPT_F32 && dtype != SGPT_BF16 && dtype != SGPT_F16) return fail(c, SGPT_ERR_INVALID, "sgpt_rope_half: dtype SGPT_F32 | SGPT_BF16 | SGPT_F16");
+    // a thread moves four consecutive x[i] and their partners x[i + dh/2] as 16- / 8-byte words, with one float4 of each table
+    const int64_t dq = (int64_t)H * head_dim, dk = (int64_t)H_kv * head_dim;
+    if (head_dim % 8 || ld % 4 || k_off % 4 || k_off < dq || ld < k_off + dk || mis(buf, dtype == SGPT_F32 ? 16 : 8) || mis(sin_t, 16) || mis(cos_t, 16))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_rope_half: head_dim % 8; ld, k_off % 4; k_off >= H * head_dim; ld >= k_off + H_kv * head_dim; "
+                                         "buf aligned to four elements, tables to 16 bytes");
+    HIPC(c, hipSetDevice(c->device));
+    launch_rope_half(buf, dtype, ld, k_off, pos, sin_t, cos_t, T, H, H_kv, head_dim, max_pos, (hipStream_t)stream);
     HIPC(c, hipGetLastError());
     return SGPT_OK;
 }

@@ -38,6 +38,7 @@ TOKEN_TILE = 256   # GEMM M tile (256x256 LDS-DMA kernel)
 # only -- its projections run on 32-row tiles, and one 18-token query no longer pays for 256 rows.
 QUERY_ROWS = 512
 QUERY_TILE = 32
+MAX_SEQ_LEN = 2048   # tokens per sequence sgpt_encode takes (include/sgpt_hip.h)
 
 
 def pad_rows(total: int, row_tile: Optional[int] = None) -> int:
@@ -62,8 +63,12 @@ class SGPTConfig:
     layer_norm_epsilon: float = 1e-5
     model_type: str = "gpt_neo"          # "gpt_neo" (SGPT-125M/1.3B/2.7B) | "gptj" (SGPT-5.8B) | "bloom" | "bert" (the BERT / SBERT baselines)
     rotary_dim: int = 0                   # GPT-J only (HF GPTJConfig.rotary_dim = 64)
+    num_kv_heads: Optional[int] = None    # "llama" only: key / value heads (grouped K / V); None = num_heads
+    rope_theta: float = 10000.0           # "llama" only: base of the rotary frequencies
 
     def __post_init__(self):
+        if self.num_kv_heads is None:
+            self.num_kv_heads = self.num_heads
         if self.intermediate_size is None:
             self.intermediate_size = 4 * self.hidden_size
         if self.attention_layers is None:
@@ -94,8 +99,39 @@ class SGPTConfig:
                        hidden_size=c["hidden_size"], num_layers=c["num_hidden_layers"], num_heads=c["num_attention_heads"],
                        intermediate_size=c["intermediate_size"], layer_norm_epsilon=c.get("layer_norm_eps", 1e-12),
                        model_type="bert", window_size=0, attention_layers=["global"] * c["num_hidden_layers"])
+        if mt in ("llama", "mistral"):   # HF LlamaConfig / MistralConfig: one family here (model_type "llama"), Mistral adds the window
+            L, H, d = c["num_hidden_layers"], c["num_attention_heads"], c["hidden_size"]
+            if c.get("hidden_act", "silu") != "silu":
+                raise NotImplementedError(f"{mt}: hidden_act {c.get('hidden_act')!r} (only 'silu', the SwiGLU MLP, is built)")
+            for key in ("attention_bias", "mlp_bias"):
+                if c.get(key):
+                    raise NotImplementedError(f"{mt}: {key} = true (the biased variants are not built)")
+            rs = c.get("rope_scaling")
+            if rs is None and isinstance(c.get("rope_parameters"), dict) and c["rope_parameters"].get("rope_type", "default") != "default":
+                rs = c["rope_parameters"]
+            if rs is not None and rs.get("rope_type", rs.get("type", "default")) != "default":
+                raise NotImplementedError(f"{mt}: rope_scaling {rs!r} (only the default rotary frequencies are built)")
+            if c.get("head_dim") is not None and c["head_dim"] * H != d:
+                raise NotImplementedError(f"{mt}: head_dim {c['head_dim']} with head_dim * num_attention_heads != hidden_size {d}")
+            if d > 4096:
+                raise NotImplementedError(f"{mt}: hidden_size {d} > 4096 (the row kernels hold one row of at most 4096 columns per wave)")
+            theta = c.get("rope_theta")
+            if theta is None and isinstance(c.get("rope_parameters"), dict):
+                theta = c["rope_parameters"].get("rope_theta")
+            # Mistral: key j is visible to query i iff j > i - sliding_window (HF sliding_window_overlay) -- the window rule of the
+            # GPT-Neo local layers, on every layer.  A window that no sequence here can reach is no window: the longest sequence is
+            # min(max_position_embeddings, MAX_SEQ_LEN) tokens (Mistral-7B-v0.1's 4096 folds to 0: the no-window kernels).  A missing
+            # key is HF MistralConfig's default, 4096
+            sw = c.get("sliding_window", 4096) if mt == "mistral" else None
+            window = 0 if (sw is None or sw >= min(c["max_position_embeddings"], MAX_SEQ_LEN)) else int(sw)
+            if window < 0:
+                raise NotImplementedError(f"{mt}: sliding_window {sw!r}")
+            return cls(vocab_size=c["vocab_size"], max_position_embeddings=c["max_position_embeddings"], hidden_size=d, num_layers=L,
+                       num_heads=H, intermediate_size=c["intermediate_size"], layer_norm_epsilon=c.get("rms_norm_eps", 1e-6),
+                       model_type="llama", window_size=window, attention_layers=["local" if window else "global"] * L,
+                       num_kv_heads=c.get("num_key_value_heads") or H, rope_theta=float(theta if theta is not None else 10000.0))
         if mt != "gpt_neo":
-            raise NotImplementedError(f"model_type {mt!r}: GPT-Neo, GPT-J, BLOOM and BERT are the families built here")
+            raise NotImplementedError(f"model_type {mt!r}: GPT-Neo, GPT-J, BLOOM, BERT and Llama / Mistral are the families built here")
         layers = c.get("attention_layers")
         if layers is None and c.get("attention_types"):
             layers = []
@@ -319,7 +355,7 @@ class SGPTModel:
         if dtype in ("fp16", "float16", "half"):
             dtype = "f16"
         if precision is None:
-            precision = "auto" if (dtype == "f16" and cfg.model_type != "bert") else "plain"   # (BERT: nothing to probe for)
+            precision = "auto" if (dtype == "f16" and cfg.model_type not in ("bert", "llama")) else "plain"   # (BERT, Llama: nothing to probe for)
         if precision not in ("plain", "x3", "auto", "auto-class"):
             raise ValueError("precision must be 'plain', 'x3', 'auto' or 'auto-class'")
         if precision != "plain" and dtype not in ("f16", "bf16"):
@@ -339,6 +375,16 @@ class SGPTModel:
                 raise ValueError(f"dtype {dtype!r} is not available for BERT models: use 'f16', 'bf16' or 'fp32'")
             if precision != "plain" or precise_qk:
                 raise ValueError("split-precision operands (precision='x3' / 'auto' / 'auto-class', precise_qk) are not available for BERT models")
+        llama = cfg.model_type == "llama"
+        if llama:
+            # one arithmetic per operand format for this family too (include/sgpt_hip.h, SGPT_ARCH_LLAMA)
+            if dtype in ("fp8", "fp8mfma"):
+                raise ValueError(f"dtype {dtype!r} is not available for Llama / Mistral models: use 'bf16', 'f16' or 'fp32'")
+            if precision != "plain" or precise_qk:
+                raise ValueError("split-precision operands (precision='x3' / 'auto' / 'auto-class', precise_qk) are not available for "
+                                 "Llama / Mistral models")
+            if cfg.num_heads % cfg.num_kv_heads:
+                raise ValueError("num_heads must be a multiple of num_kv_heads")
         if dtype not in ("f16", "bf16", "fp32", "fp8", "fp8mfma"):
             raise ValueError("dtype must be 'f16' (IEEE-half MFMA operands, range-guarded: the 1e-3-parity mode), "
                              "'bf16' (bf16 MFMA operands), 'fp32' (exact fp32 MFMA), "
@@ -359,14 +405,17 @@ class SGPTModel:
         arch = _lib.SGPT_ARCH_GPTJ if gptj else (_lib.SGPT_ARCH_BLOOM if bloom else _lib.SGPT_ARCH_GPTNEO)
         if bert:
             arch = _lib.SGPT_ARCH_BERT
+        if llama:
+            arch = _lib.SGPT_ARCH_LLAMA
         desc = ModelDesc(arch=arch, n_layers=cfg.num_layers,
                          d_model=cfg.hidden_size, n_heads=cfg.num_heads, d_ffn=cfg.intermediate_size,
                          vocab=cfg.vocab_size, max_pos=cfg.max_position_embeddings, window=cfg.window_size,
                          ln_eps=cfg.layer_norm_epsilon,
-                         attn_scale=float(1.0 / np.sqrt(np.float32(dh))) if (gptj or bloom or bert) else 1.0,   # HF:gptj:148, HF:bloom:186 / HF:gpt_neo:110
+                         attn_scale=float(1.0 / np.sqrt(np.float32(dh))) if (gptj or bloom or bert or llama) else 1.0,   # HF:gptj:148, HF:bloom:186 / HF:gpt_neo:110
                          compute_dtype={"f16": SGPT_F16, "bf16": SGPT_BF16, "fp32": SGPT_F32, "fp8": SGPT_FP8W,
                                         "fp8mfma": SGPT_FP8M}[dtype],
-                         layer_is_local=C.cast(local, C.POINTER(C.c_uint8)), rotary_dim=cfg.rotary_dim if gptj else 0,
+                         layer_is_local=C.cast(local, C.POINTER(C.c_uint8)), rotary_dim=cfg.rotary_dim if gptj else (dh if llama else 0),
+                         n_kv_heads=cfg.num_kv_heads if llama else 0,
                          qk_split=1 if (precise_qk and PRECISE_QK_PLANS[precise_qk][0] in (1, 3)) else 0,
                          split_weights=1 if (precision != "plain" or (precise_qk and (PRECISE_QK_PLANS[precise_qk][0] == 2 or
                                                                                         PRECISE_QK_PLANS[precise_qk][2]))) else 0)
@@ -383,6 +432,9 @@ class SGPTModel:
             weights["alibi.slopes"] = alibi_slopes(cfg.num_heads)
         if bert:
             weights = bert_state_dict(weights)
+        if llama:
+            weights = llama_state_dict(weights)
+            weights["rotary.sin"], weights["rotary.cos"] = rotary_tables_half(cfg.max_position_embeddings, dh, cfg.rope_theta)
         names, keep = [], []
         for k, v in weights.items():
             k2 = k[len("transformer."):] if k.startswith("transformer.") else k
@@ -690,8 +742,8 @@ class SGPTModel:
     def _check_learnt(self, mode: str, pb: PackedBatch) -> None:
         if mode != "learntmean":
             return
-        if self.cfg.model_type == "bert":
-            raise ValueError("method 'learntmean' (trained position weights of the SGPT checkpoints) is not available for BERT models")
+        if self.cfg.model_type in ("bert", "llama"):
+            raise ValueError("method 'learntmean' (trained position weights of the SGPT checkpoints) is not available for BERT / Llama models")
         if self.position_weights is None:
             raise ValueError("method 'learntmean' needs trained position weights (1_WeightedMeanPooling)")
         if pb.max_pos >= self.position_weights.numel():
@@ -719,6 +771,8 @@ class SGPTModel:
         (the log_softmax + gather of crossencoder/beir/sgptce.py:233-255) -> fp32[n] on the GPU."""
         if self.cfg.model_type == "bert":
             raise ValueError("lm_logprobs: a BERT model carries no causal LM head")
+        if self.cfg.model_type == "llama":
+            raise ValueError("lm_logprobs is not built for Llama / Mistral models (their LM head is not loaded)")
         ri = torch.as_tensor(np.asarray(row_idx, dtype=np.int32)).to(self.device)
         tg = torch.as_tensor(np.asarray(targets, dtype=np.int32)).to(self.device)
         n = int(ri.numel())
@@ -863,7 +917,7 @@ class SGPTModel:
         if not flags:
             return False
         # (BERT models run without range shifts: nothing to adapt, the flag is final)
-        if flags & 1 and not flags & 6 and adapt and self.dtype == "f16" and self.cfg.model_type != "bert" and self._adapt_range():
+        if flags & 1 and not flags & 6 and adapt and self.dtype == "f16" and self.cfg.model_type not in ("bert", "llama") and self._adapt_range():
             return True                      # (sgpt_model_range_adapt cleared bit 0 and the recorded magnitudes)
         self.range_flags(reset=True)
         if flags & 2:
@@ -1062,6 +1116,67 @@ def bert_state_dict(weights) -> dict:
         as_t = lambda a: a.detach().to(torch.float32).cpu() if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a, dtype=np.float32))  # noqa: E731
         out["embeddings.position_embeddings.weight"] = as_t(pos) + as_t(tt)[0][None, :]
     return out
+
+
+def llama_state_dict(weights) -> dict:
+    """HF LlamaModel / LlamaForCausalLM / Mistral* state dict -> the tensors include/sgpt_hip.h asks for under SGPT_ARCH_LLAMA: the
+    `model.` prefix and `lm_head.*` are dropped (as are `rotary_emb.inv_freq` buffers of older checkpoints), q_proj | k_proj | v_proj
+    are stacked into `self_attn.qkv_proj.weight` [d + 2 d_kv, d] and gate_proj | up_proj into `mlp.gate_up_proj.weight` [2 ffn, d]
+    (gate rows first).  A bias tensor of a projection means a biased variant, which is not built."""
+    as_t = lambda a: a.detach().to(torch.float32).cpu() if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a, dtype=np.float32))  # noqa: E731
+    flat = {}
+    for k, v in weights.items():
+        k2 = k[len("model."):] if k.startswith("model.") else k
+        if k.startswith("lm_head.") or k2.endswith("rotary_emb.inv_freq"):
+            continue
+        if k2.endswith("_proj.bias"):
+            raise NotImplementedError(f"llama: {k} (the biased variants are not built)")
+        flat[k2] = v
+    out, fuse = {}, (("self_attn.", ("q_proj", "k_proj", "v_proj"), "qkv_proj"), ("mlp.", ("gate_proj", "up_proj"), "gate_up_proj"))
+    for k, v in flat.items():
+        for mod, parts, fused in fuse:
+            if k.endswith(mod + parts[0] + ".weight"):
+                base = k[: -len(parts[0] + ".weight")]
+                out[base + fused + ".weight"] = torch.cat([as_t(flat[base + n + ".weight"]) for n in parts], dim=0)
+                break
+        else:
+            if not any(k.endswith(mod + n + ".weight") for mod, parts, _ in fuse for n in parts):
+                out[k] = v
+    return out
+
+
+def rotary_tables_half(max_pos: int, head_dim: int, theta: float = 10000.0):
+    """sin, cos fp32 [max_pos, head_dim / 2] of HF LlamaRotaryEmbedding (default rope): inv_freq[i] = theta^(-2i / head_dim) as
+    `1.0 / (base ** (arange(0, dim, 2, int64).float() / dim))`, angle = position * inv_freq in float32."""
+    inv_freq = 1.0 / (theta ** (torch.arange(0, head_dim, 2, dtype=torch.int64).to(dtype=torch.float) / head_dim))
+    ang = torch.arange(max_pos, dtype=torch.float32)[:, None] * inv_freq[None, :].to(torch.float32)
+    return ang.sin().numpy().astype(np.float32), ang.cos().numpy().astype(np.float32)
+
+
+def synthetic_llama_weights(cfg: SGPTConfig, seed: int = 0, std: float = 0.02) -> Dict[str, np.ndarray]:
+    """Seeded random-init weights under HF LlamaModel state-dict names (fixtures, benches: no checkpoints exist offline)."""
+    rng = np.random.default_rng(seed)
+    d, ffn = cfg.hidden_size, cfg.intermediate_size
+    dkv = cfg.num_kv_heads * (d // cfg.num_heads)
+    f32 = np.float32
+
+    def nrm(*shape, s=std):
+        return (rng.standard_normal(shape, dtype=np.float32) * f32(s)).astype(f32)
+
+    w = {"embed_tokens.weight": nrm(cfg.vocab_size, d)}
+    for i in range(cfg.num_layers):
+        p = f"layers.{i}."
+        w[p + "input_layernorm.weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
+        w[p + "self_attn.q_proj.weight"] = nrm(d, d)
+        w[p + "self_attn.k_proj.weight"] = nrm(dkv, d)
+        w[p + "self_attn.v_proj.weight"] = nrm(dkv, d)
+        w[p + "self_attn.o_proj.weight"] = nrm(d, d)
+        w[p + "post_attention_layernorm.weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
+        w[p + "mlp.gate_proj.weight"] = nrm(ffn, d)
+        w[p + "mlp.up_proj.weight"] = nrm(ffn, d)
+        w[p + "mlp.down_proj.weight"] = nrm(d, ffn)
+    w["norm.weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
+    return w
 
 
 def synthetic_bert_weights(cfg: SGPTConfig, seed: int = 0, std: float = 0.02) -> Dict[str, np.ndarray]:

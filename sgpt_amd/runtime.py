@@ -284,12 +284,13 @@ class Context:
                   H: int, dh: int, max_alloc_len: int, window: int = 0, scale: float = 1.0, alibi: Optional[torch.Tensor] = None,
                   out_scale: float = 0.0, range_flag: Optional[torch.Tensor] = None, x3: bool = False, qk_lo_delta: int = 0,
                   v_lo_delta: int = 0, ctx_lo_delta: int = 0, ctx_hi2_delta: int = 0, causal: Optional[bool] = None,
-                  seq_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  seq_len: Optional[torch.Tensor] = None, n_kv_heads: Optional[int] = None) -> torch.Tensor:
         """include/sgpt_hip.h::sgpt_attention on caller-laid-out buffers (the over-read contract there is the caller's): q, k
         [T, >= H dh] row views of one leading dimension; v = V^T [H dh, >= T] (16-bit) or [T, ...] with q's leading dimension
         (fp32); out [T, ...] in q's dtype, or uint8 (e4m3 codes of ctx / out_scale, bf16 operands).  Deltas in elements.
         causal None: the sgpt_attention entry.  True / False: sgpt_attention_ex -- False is the bidirectional mode of the BERT family,
-        every query of a sequence sees its keys [0, seq_len[b]) (seq_len int32 [B]; None = the whole allocation)."""
+        every query of a sequence sees its keys [0, seq_len[b]) (seq_len int32 [B]; None = the whole allocation).
+        n_kv_heads: sgpt_attention_gqa -- k and v hold n_kv_heads heads, query head h reads head h // (H // n_kv_heads) (causal)."""
         T = q.shape[0]
         out_fp8 = out.dtype == torch.uint8
         if q.dtype not in DT_CODE:
@@ -304,6 +305,15 @@ class Context:
             raise ValueError("attention: fp32 v rows share q's leading dimension (the fp32 kernel reads v with ldq)")
         so = seq_off.to(device=self.device, dtype=torch.int32).contiguous()
         al = None if alibi is None else alibi.to(device=self.device, dtype=torch.float32).contiguous()
+        if n_kv_heads is not None:
+            if causal is False or seq_len is not None:
+                raise ValueError("attention: grouped K / V is causal")
+            self._chk(self.lib.sgpt_attention_gqa(self.handle, DT_CODE[q.dtype], _p(q), _p(k), _p(v), q.stride(0), v.stride(0), _p(out),
+                                                  out.stride(0), _p(so), so.numel() - 1, T, H, int(n_kv_heads), dh, window, scale, _p(al),
+                                                  max_alloc_len, 1 if out_fp8 else 0, out_scale, _p(range_flag), 1 if x3 else 0,
+                                                  qk_lo_delta, v_lo_delta, ctx_lo_delta, ctx_hi2_delta, _stream_ptr(self.device)),
+                      "sgpt_attention_gqa")
+            return out
         if causal is not None:
             sl = None if seq_len is None else seq_len.to(device=self.device, dtype=torch.int32).contiguous()
             self._chk(self.lib.sgpt_attention_ex(self.handle, DT_CODE[q.dtype], _p(q), _p(k), _p(v), q.stride(0), v.stride(0), _p(out),
@@ -362,11 +372,59 @@ class Context:
                                                     _p(out), DT_CODE[out_dtype], _stream_ptr(self.device)), "sgpt_layernorm_writeback")
         return out
 
+    def rmsnorm(self, x: torch.Tensor, gamma: torch.Tensor, eps: float = 1e-6, out_dtype=torch.float32,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """RMSNorm over the rows of x fp32 [T, d] (include/sgpt_hip.h::sgpt_rmsnorm): x * rsqrt(mean(x^2) + eps) * gamma -> [T, d] in
+        out_dtype, rounded once.  out: written in place of a new tensor (x itself for fp32)."""
+        T, d = x.shape
+        if out is None:
+            out = torch.empty((T, d), dtype=out_dtype, device=self.device)
+        self._chk(self.lib.sgpt_rmsnorm(self.handle, _p(x), _p(self._f32c(gamma)), T, d, float(eps), _p(out), DT_CODE[out_dtype],
+                                        _stream_ptr(self.device)), "sgpt_rmsnorm")
+        return out
+
+    def swiglu(self, gu: torch.Tensor) -> torch.Tensor:
+        """silu(gu[:, :ffn]) * gu[:, ffn:] for gu [T, 2 ffn] (fp32, bf16 or f16, contiguous) -> [T, ffn] of the same dtype
+        (include/sgpt_hip.h::sgpt_swiglu)."""
+        if gu.dtype not in DT_CODE or not gu.is_contiguous() or gu.shape[1] % 2:
+            raise ValueError("swiglu: gu is a contiguous fp32 / bf16 / f16 [T, 2 ffn] tensor")
+        T, ffn = gu.shape[0], gu.shape[1] // 2
+        out = torch.empty((T, ffn), dtype=gu.dtype, device=self.device)
+        self._chk(self.lib.sgpt_swiglu(self.handle, _p(gu), DT_CODE[gu.dtype], T, ffn, _p(out), _stream_ptr(self.device)), "sgpt_swiglu")
+        return out
+
+    def rope_half(self, buf: torch.Tensor, pos: torch.Tensor, sin: torch.Tensor, cos: torch.Tensor, H: int, H_kv: int, head_dim: int,
+                  k_off: int, T: Optional[int] = None, max_pos: Optional[int] = None) -> torch.Tensor:
+        """HF rotate_half rotary embedding in place on the H query heads (column 0) and the H_kv key heads (column k_off) of the
+        first T rows of buf [rows, ld]; sin / cos fp32 [max_pos, head_dim / 2] (include/sgpt_hip.h::sgpt_rope_half)."""
+        if buf.dtype not in DT_CODE or buf.stride(1) != 1:
+            raise ValueError("rope_half: buf is fp32, bf16 or f16 with a unit column stride")
+        if sin.stride() != (head_dim // 2, 1) or cos.stride() != (head_dim // 2, 1):
+            raise ValueError("rope_half: sin / cos are row-contiguous [max_pos, head_dim / 2]")
+        self._chk(self.lib.sgpt_rope_half(self.handle, _p(buf), DT_CODE[buf.dtype], buf.stride(0), int(k_off), _p(pos), _p(sin), _p(cos),
+                                          buf.shape[0] if T is None else int(T), H, H_kv, head_dim,
+                                          sin.shape[0] if max_pos is None else int(max_pos), _stream_ptr(self.device)), "sgpt_rope_half")
+        return buf
+
     def lnf_pool(self, x: torch.Tensor, seq_off: torch.Tensor, seq_len: torch.Tensor, pad_left: Optional[torch.Tensor] = None,
                  ln=None, mode: str = "weightedmean", normalize: bool = False, position_weights: Optional[torch.Tensor] = None,
-                 n_weights: Optional[int] = None, nonfinite_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 n_weights: Optional[int] = None, nonfinite_flag: Optional[torch.Tensor] = None, rms=None) -> torch.Tensor:
         """The fused final LayerNorm + pooling of a packed batch (include/sgpt_hip.h::sgpt_lnf_pool): x fp32 [T_pad, d], int32
-        seq_off / seq_len / pad_left on the device; ln = (gamma, beta, eps) or None (pool x as it is) -> fp32 [B, d]."""
+        seq_off / seq_len / pad_left on the device; ln = (gamma, beta, eps) or None (pool x as it is) -> fp32 [B, d].
+        rms = (gamma, eps): the final RMSNorm of the Llama family instead (sgpt_lnf_pool_ex, norm_kind 1)."""
+        if rms is not None:
+            if ln is not None:
+                raise ValueError("lnf_pool: ln or rms, not both")
+            if mode not in POOL_MODES:
+                raise ValueError(f"unknown pooling mode {mode}")
+            B, d = seq_len.numel(), x.shape[1]
+            pw = self._f32c(position_weights)
+            n_w = (0 if pw is None else pw.numel()) if n_weights is None else int(n_weights)
+            out = torch.empty((B, d), dtype=torch.float32, device=self.device)
+            self._chk(self.lib.sgpt_lnf_pool_ex(self.handle, _p(x), _p(self._f32c(rms[0])), None, _p(seq_off), _p(seq_len), _p(pad_left), B, d,
+                                                float(rms[1]), 1, POOL_MODES[mode], 1 if normalize else 0, _p(pw), n_w, _p(out),
+                                                _p(nonfinite_flag), 1, _stream_ptr(self.device)), "sgpt_lnf_pool_ex")
+            return out
         if mode not in POOL_MODES:
             raise ValueError(f"unknown pooling mode {mode}")
         B, d = seq_len.numel(), x.shape[1]

@@ -64,6 +64,11 @@ def is_bert(model) -> bool:
     return getattr(getattr(model, "cfg", None), "model_type", None) == "bert"
 
 
+def is_llama(model) -> bool:
+    """Does this model object belong to the Llama / Mistral family?"""
+    return getattr(getattr(model, "cfg", None), "model_type", None) == "llama"
+
+
 class TextPipeline:
     """text -> truncated id list (+ brackets).
 
@@ -76,10 +81,13 @@ class TextPipeline:
            max_seq_length - 2 and adds both brackets afterwards.
     bert:  the model is a BERT encoder: the content is cut to max_token_len - 2 and framed `[CLS]` .. `[SEP]` with the
            tokenizer's cls_token_id / sep_token_id (beir_dense_retriever.py:128-136); the reference brackets GPT inputs only, so
-           specb / speca are refused."""
+           specb / speca are refused.
+    llama: the model is a Llama / Mistral decoder: the tokenizer's own framing is applied after truncation -- bos_token_id in front
+           when its `add_bos_token` is set (the HF default of these tokenizers), eos_token_id behind when `add_eos_token` is (off by
+           default) -- and the content is cut to max_token_len minus what is added; specb / speca are refused."""
 
     def __init__(self, tokenizer, max_token_len: int, specb: bool = False, speca: bool = False, st_path: bool = False,
-                 bert: bool = False):
+                 bert: bool = False, llama: bool = False):
         if speca and specb:
             raise ValueError("speca and specb are mutually exclusive")
         self.frame = None
@@ -90,12 +98,25 @@ class TextPipeline:
             if cls_id is None or sep_id is None:
                 raise ValueError("a BERT model needs a tokenizer with cls_token_id and sep_token_id")
             self.frame = ([int(cls_id)], [int(sep_id)])
+        if llama:
+            if specb or speca:
+                raise ValueError("specb / speca brackets belong to the GPT models; a Llama / Mistral model takes its tokenizer's BOS / EOS")
+            front, back = [], []
+            if getattr(tokenizer, "add_bos_token", True):
+                if getattr(tokenizer, "bos_token_id", None) is None:
+                    raise ValueError("add_bos_token is set but the tokenizer has no bos_token_id")
+                front = [int(tokenizer.bos_token_id)]
+            if getattr(tokenizer, "add_eos_token", False):
+                if getattr(tokenizer, "eos_token_id", None) is None:
+                    raise ValueError("add_eos_token is set but the tokenizer has no eos_token_id")
+                back = [int(tokenizer.eos_token_id)]
+            self.frame = (front, back)
         self.tok = tokenizer
         self.specb, self.speca, self.st_path = specb, speca, st_path
         bracketed = specb or speca
         self.max_token_len = max_token_len - (3 if st_path else 2) if bracketed else max_token_len   # :134-136
         if self.frame:
-            self.max_token_len = max_token_len - 2                                                     # :128-136
+            self.max_token_len = max_token_len - len(self.frame[0]) - len(self.frame[1])               # :128-136
         if specb:
             self.bos_q = list(tokenizer.encode(SPECB_QUE_BOS))
             self.eos_q = list(tokenizer.encode(SPECB_QUE_EOS))
