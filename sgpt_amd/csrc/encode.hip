@@ -7,15 +7,19 @@ namespace {
 // What the block functions of one forward share: the call's token layout, the operand format, the launch path and the workspace.
 struct Fwd {
     sgpt_model* m; sgpt_ctx* c; hipStream_t s;
+    const Family* F;      // the model's family row (host.h)
     const int32_t *pos, *seq_off, *seq_len;
     int B, T, max_alloc;
+    int d_kv;             // key / value width n_kv_heads * head_dim: d_model unless the family groups K / V
     int dt;               // operand format of the projections: SGPT_F32 | SGPT_BF16 | SGPT_F16
     int* range_flag;      // the model's range words (SGPT_F16 stores, e4m3 codes of the fp8-MFMA block) or null
-    bool can_split;       // the format takes a precision plan (prec[])
-    bool qpath, qln;      // query-sized kernels (qgemm.hip); with the LayerNorms of a block inside their prologues
+    // can_split: the format takes a precision plan (prec[]); any_*: a block of this call splits that class; split: any of them.
+    // fp8: fp8 weight codes, mlp8: with the fp8-MFMA block (block_fp8) rather than weights de-quantised per block.
+    // qpath: query-sized kernels (qgemm.hip), qln: with the LayerNorms of a block inside their prologues.
+    bool can_split, any_ln, any_att, any_ctx, any_h, split, fp8, mlp8, qpath, qln;
     float* x;             // residual stream fp32
-    // LayerNorm output; attention context; 16-bit: [T][2d] q | k + V^T [d][T] (x3 attention: the lo halves att_lo elements behind),
-    // fp32: [T][3d]; MLP hidden
+    // LayerNorm output; attention context; 16-bit: [T][d + d_kv] q | k + V^T [d_kv][T] (x3 attention: the lo halves att_lo elements
+    // behind), fp32: [T][d + 2 d_kv]; MLP hidden
     void *a, *ctx, *qkv, *vt, *h;
     void* gu;             // SGPT_ARCH_LLAMA: fc1 output [T][2 ffn] = gate | up columns, the input of the SwiGLU row kernel
     void* a8; float* sa;  // fp8-MFMA block: LayerNorm output as e4m3 codes + one scale per row
@@ -36,6 +40,22 @@ GemmArgs proj(const Fwd& f, const void* A, long lda, const void* W, int N, int K
 // a_hi.W_hi + a_lo.W_hi + a_hi.W_lo  (nblk = 2: the activation alone is split -- the first TWO blocks of both layouts)
 void split_w(GemmArgs& g, const void* W3, int k, int nblk = 3) { g.W = W3; g.K = nblk * k; g.ldw = 3 * k; g.k_algo = k; }
 
+// The Q | K and V projections of a 16-bit block as two launches over the fused weight (and bias) rows: q | k -> out[T][n_qk] row-major from
+// rows [0, n_qk), then V^T[n_v][T] from the n_v rows behind them.  `g` carries what both share (A, K, bias base, shifts).  Split-precision
+// operands, by the block's plan for the LayerNorm-1 class p_ln1 (block_16): 0 plain | 1, 2: Q | K contract over all three blocks of W3's
+// [W_hi | W_hi | W_lo] rows | 3: over the first two (the activation alone is split); 2: V too, over the rows behind them.
+void proj_qk_vt(const Fwd& f, const GemmArgs& g, int n_qk, int n_v, const void* W3 = nullptr, int p_ln1 = 0) {
+    GemmArgs qk = g, v = g;
+    if (p_ln1) split_w(qk, W3, g.K, p_ln1 == 3 ? 2 : 3);
+    qk.N = n_qk;
+    gemm(f.c, f.dt, EPI_STORE, f.dt, qk, f.s);
+    if (p_ln1 == 2) split_w(v, (const bf16_t*)W3 + (size_t)n_qk * 3 * g.K, g.K);
+    else v.W = (const bf16_t*)g.W + (size_t)n_qk * g.K;
+    v.N = n_v; v.out = f.vt; v.ldo = f.T; v.bias = g.bias ? g.bias + n_qk : nullptr;
+    gemm(f.c, f.dt, EPI_VT, f.dt, v, f.s);
+}
+
+// q | k | v of every family: q rows of d columns, k and v of d_kv (= d unless the family groups K / V: then kv_group query heads share one)
 AttnArgs attn_base(const Fwd& f, const LayerW& l, int k_qkv) {
     const sgpt_model_desc& d = f.m->d;
     const int dm = d.d_model;
@@ -44,9 +64,9 @@ AttnArgs attn_base(const Fwd& f, const LayerW& l, int k_qkv) {
     at.seq_off = f.seq_off; at.B = f.B; at.H = d.n_heads; at.dh = dm / d.n_heads; at.window = l.is_local ? d.window : 0;
     at.scale = d.attn_scale * pow2f(2 * k_qkv);      // q and k are both stored down-shifted
     at.max_alloc_len = f.max_alloc; at.ctx = f.ctx; at.ldo = dm; at.alibi = f.m->alibi;
-    at.q = f.qkv;
-    if (f.vt) { at.k = (bf16_t*)f.qkv + dm; at.v = f.vt; at.ldq = 2 * dm; at.ldvt = f.T; }
-    else { at.k = (float*)f.qkv + dm; at.v = (float*)f.qkv + 2 * dm; at.ldq = 3 * dm; }
+    at.q = f.qkv; at.kv_group = d.n_heads / d.n_kv_heads;
+    if (f.vt) { at.k = (bf16_t*)f.qkv + dm; at.v = f.vt; at.ldq = dm + f.d_kv; at.ldvt = f.T; }
+    else { at.k = (float*)f.qkv + dm; at.v = (float*)f.qkv + dm + f.d_kv; at.ldq = dm + 2 * f.d_kv; }
     return at;
 }
 
@@ -56,12 +76,12 @@ AttnArgs attn_base(const Fwd& f, const LayerW& l, int k_qkv) {
 // plan, bulk kernels at every layout (the LayerNorm prologues of the query-sized projections assume pre-LN).
 AttnArgs attn_bidir(const Fwd& f, const LayerW& l) {
     AttnArgs at = attn_base(f, l, 0);
-    at.noncausal = 1; at.seq_len = f.seq_len; at.window = 0; at.alibi = nullptr;
+    at.noncausal = 1; at.seq_len = f.seq_len;        // (window and alibi are 0 already: no local layer, no slopes in this family)
     return at;
 }
 
 // fp32: the projections read the residual stream itself
-void block_bert_f32(const Fwd& f, const LayerW& l) {
+sgpt_status block_bert_f32(const Fwd& f, const LayerW& l, int) {
     const sgpt_model_desc& d = f.m->d;
     const int dm = d.d_model, ffn = d.d_ffn, T = f.T;
     gemm(f.c, SGPT_F32, EPI_STORE, SGPT_F32, proj(f, f.x, dm, l.w_qkv, 3 * dm, dm, f.qkv, 3 * dm, l.b_qkv), f.s);
@@ -71,30 +91,26 @@ void block_bert_f32(const Fwd& f, const LayerW& l) {
     gemm(f.c, SGPT_F32, EPI_BIAS_GELU_ERF, SGPT_F32, proj(f, f.x, dm, l.w_fc, ffn, dm, f.h, ffn, l.b_fc), f.s);
     gemm(f.c, SGPT_F32, EPI_BIAS_RESID, SGPT_F32, proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x), f.s);
     launch_layernorm(f.x, l.ln2_g, l.ln2_b, f.x, SGPT_F32, T, dm, d.ln_eps, f.s);
+    return SGPT_OK;
 }
 
 // 16-bit: `a` holds the 16-bit copy of x the previous write-back LayerNorm (or the embedding LayerNorm) left; the context shares
 // its buffer (a is consumed by the Q | K | V projection before the attention writes)
-void block_bert16(const Fwd& f, const LayerW& l) {
+sgpt_status block_bert16(const Fwd& f, const LayerW& l, int) {
     const sgpt_model_desc& d = f.m->d;
     const int dm = d.d_model, ffn = d.d_ffn, T = f.T, dt = f.dt;
     GemmArgs q = proj(f, f.a, dm, l.w_qkv, 3 * dm, dm, f.qkv, 2 * dm, l.b_qkv);
     if (gemm_qkv_one_launch(T, 2 * dm, f.c->force256 != 0)) {        // query-sized batch: q | k and V^T from one launch
         q.n_split = 2 * dm; q.out2 = f.vt; q.ldo2 = T;
         gemm(f.c, dt, EPI_QKV, dt, q, f.s);
-    } else {
-        GemmArgs qk = q, v = q;
-        qk.N = 2 * dm;
-        gemm(f.c, dt, EPI_STORE, dt, qk, f.s);
-        v.W = (bf16_t*)l.w_qkv + (size_t)2 * dm * dm; v.N = dm; v.out = f.vt; v.ldo = T; v.bias = l.b_qkv + 2 * dm;
-        gemm(f.c, dt, EPI_VT, dt, v, f.s);
-    }
+    } else proj_qk_vt(f, q, 2 * dm, dm);
     launch_attn_bf16(attn_bidir(f, l), f.s);
     gemm(f.c, dt, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dm, l.w_o, dm, dm, f.x, dm, l.b_o, f.x), f.s);
     launch_layernorm_writeback(f.x, l.ln1_g, l.ln1_b, f.a, dt, T, dm, d.ln_eps, f.range_flag, f.s);
     gemm(f.c, dt, EPI_BIAS_GELU_ERF, dt, proj(f, f.a, dm, l.w_fc, ffn, dm, f.h, ffn, l.b_fc), f.s);
     gemm(f.c, dt, EPI_BIAS_RESID, SGPT_F32, proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x), f.s);
     launch_layernorm_writeback(f.x, l.ln2_g, l.ln2_b, f.a, dt, T, dm, d.ln_eps, f.range_flag, f.s);
+    return SGPT_OK;
 }
 
 // ---- the Llama / Mistral family (SGPT_ARCH_LLAMA; HF:llama/modeling_llama.py LlamaDecoderLayer): pre-RMSNorm, grouped K / V, half-split
@@ -103,48 +119,39 @@ void block_bert16(const Fwd& f, const LayerW& l) {
 //   a = RMS2(x) ; gu = a [Wgate | Wup]^T ; h = silu(gate) * up ; x += h Wdown^T
 // No range shifts (every f16 store is tracked), no precision plan, bulk kernels at every layout.  l.b_o / l.b_proj are the model's
 // zero vector (the residual epilogue reads a bias).
-AttnArgs attn_llama(const Fwd& f, const LayerW& l, int dkv) {
+sgpt_status block_llama_f32(const Fwd& f, const LayerW& l, int) {
     const sgpt_model_desc& d = f.m->d;
-    const int dm = d.d_model;
-    AttnArgs at = attn_base(f, l, 0);
-    at.alibi = nullptr; at.kv_group = d.n_heads / d.n_kv_heads;
-    if (f.vt) { at.k = (bf16_t*)f.qkv + dm; at.ldq = dm + dkv; }                                        // [T][d + d_kv] q | k, V^T [d_kv][T]
-    else { at.k = (float*)f.qkv + dm; at.v = (float*)f.qkv + dm + dkv; at.ldq = dm + 2 * dkv; }      // [T][d + 2 d_kv] q | k | v
-    return at;
-}
-
-void block_llama_f32(const Fwd& f, const LayerW& l) {
-    const sgpt_model_desc& d = f.m->d;
-    const int dm = d.d_model, ffn = d.d_ffn, T = f.T, dh = dm / d.n_heads, dkv = d.n_kv_heads * dh;
+    const int dm = d.d_model, ffn = d.d_ffn, T = f.T, dh = dm / d.n_heads, dkv = f.d_kv;
     launch_rmsnorm(f.x, l.ln1_g, f.a, SGPT_F32, T, dm, d.ln_eps, nullptr, f.s);
     gemm(f.c, SGPT_F32, EPI_STORE, SGPT_F32, proj(f, f.a, dm, l.w_qkv, dm + 2 * dkv, dm, f.qkv, dm + 2 * dkv, nullptr), f.s);
     launch_rope_half(f.qkv, SGPT_F32, dm + 2 * dkv, dm, f.pos, f.m->rot_sin, f.m->rot_cos, T, d.n_heads, d.n_kv_heads, dh, d.max_pos, f.s);
-    launch_attn_f32(attn_llama(f, l, dkv), f.s);
+    launch_attn_f32(attn_base(f, l, 0), f.s);
     gemm(f.c, SGPT_F32, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dm, l.w_o, dm, dm, f.x, dm, l.b_o, f.x), f.s);
     launch_rmsnorm(f.x, l.ln2_g, f.a, SGPT_F32, T, dm, d.ln_eps, nullptr, f.s);
     gemm(f.c, SGPT_F32, EPI_STORE, SGPT_F32, proj(f, f.a, dm, l.w_fc, 2 * ffn, dm, f.gu, 2 * ffn, nullptr), f.s);
     launch_swiglu(f.gu, f.h, SGPT_F32, T, ffn, nullptr, f.s);
     gemm(f.c, SGPT_F32, EPI_BIAS_RESID, SGPT_F32, proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x), f.s);
+    return SGPT_OK;
 }
 
 // 16-bit: the context shares a's buffer (a is consumed by the Q | K and V projections before the attention writes)
-void block_llama16(const Fwd& f, const LayerW& l) {
+sgpt_status block_llama16(const Fwd& f, const LayerW& l, int) {
     const sgpt_model_desc& d = f.m->d;
-    const int dm = d.d_model, ffn = d.d_ffn, T = f.T, dt = f.dt, dh = dm / d.n_heads, dkv = d.n_kv_heads * dh;
+    const int dm = d.d_model, ffn = d.d_ffn, T = f.T, dt = f.dt, dh = dm / d.n_heads, dkv = f.d_kv;
     launch_rmsnorm(f.x, l.ln1_g, f.a, dt, T, dm, d.ln_eps, f.range_flag, f.s);
-    gemm(f.c, dt, EPI_STORE, dt, proj(f, f.a, dm, l.w_qkv, dm + dkv, dm, f.qkv, dm + dkv, nullptr), f.s);                       // q | k
-    gemm(f.c, dt, EPI_VT, dt, proj(f, f.a, dm, (bf16_t*)l.w_qkv + (size_t)(dm + dkv) * dm, dkv, dm, f.vt, T, nullptr), f.s);     // V^T
+    proj_qk_vt(f, proj(f, f.a, dm, l.w_qkv, dm + dkv, dm, f.qkv, dm + dkv, nullptr), dm + dkv, dkv);
     launch_rope_half(f.qkv, dt, dm + dkv, dm, f.pos, f.m->rot_sin, f.m->rot_cos, T, d.n_heads, d.n_kv_heads, dh, d.max_pos, f.s);
-    launch_attn_bf16(attn_llama(f, l, dkv), f.s);
+    launch_attn_bf16(attn_base(f, l, 0), f.s);
     gemm(f.c, dt, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dm, l.w_o, dm, dm, f.x, dm, l.b_o, f.x), f.s);
     launch_rmsnorm(f.x, l.ln2_g, f.a, dt, T, dm, d.ln_eps, f.range_flag, f.s);
     gemm(f.c, dt, EPI_STORE, dt, proj(f, f.a, dm, l.w_fc, 2 * ffn, dm, f.gu, 2 * ffn, nullptr), f.s);
     launch_swiglu(f.gu, f.h, dt, T, ffn, f.range_flag, f.s);
     gemm(f.c, dt, EPI_BIAS_RESID, SGPT_F32, proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x), f.s);
+    return SGPT_OK;
 }
 
 // ---- fp32 block (SGPT_F32): plain operands, q | k | v rows in one buffer ----
-void block_f32(const Fwd& f, const LayerW& l) {
+sgpt_status block_f32(const Fwd& f, const LayerW& l, int) {
     const sgpt_model_desc& d = f.m->d;
     const int dm = d.d_model, ffn = d.d_ffn, T = f.T;
     const bool gptj = d.arch == SGPT_ARCH_GPTJ;
@@ -157,10 +164,11 @@ void block_f32(const Fwd& f, const LayerW& l) {
     if (!gptj) launch_layernorm(f.x, l.ln2_g, l.ln2_b, f.a, SGPT_F32, T, dm, d.ln_eps, f.s);
     gemm(f.c, SGPT_F32, EPI_BIAS_GELU, SGPT_F32, proj(f, f.a, dm, l.w_fc, ffn, dm, f.h, ffn, l.b_fc), f.s);
     gemm(f.c, SGPT_F32, EPI_BIAS_RESID, SGPT_F32, proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x), f.s);
+    return SGPT_OK;
 }
 
 // ---- fp8-MFMA block (SGPT_FP8M with calibrated activation scales): the e4m3 weight codes feed the MFMA directly ----
-void block_fp8(const Fwd& f, const LayerW& l, int li) {
+sgpt_status block_fp8(const Fwd& f, const LayerW& l, int li) {
     const sgpt_model_desc& d = f.m->d;
     const int dm = d.d_model, ffn = d.d_ffn, T = f.T;
     const bool gptj = d.arch == SGPT_ARCH_GPTJ;
@@ -190,6 +198,7 @@ void block_fp8(const Fwd& f, const LayerW& l, int li) {
     GemmArgs p = proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x);
     p.a_scalar = s_h; p.w_scale = l.s_proj;
     launch(EPI_BIAS_RESID, 0, p);
+    return SGPT_OK;
 }
 
 // A LayerNorm of the residual stream in front of the projection `q` that reads it: inside that projection's prologue (qln), or
@@ -214,9 +223,7 @@ sgpt_status launch16(const Fwd& f, int epi, int out_dtype, const QGemmArgs& q, c
 // ---- 16-bit block (bf16 / f16 operands; FP8W and un-calibrated FP8M with l's weights de-quantised to bf16) ----
 // [LN1 +] QKV -> (rope) -> attention -> out-proj + residual -> [LN2 +] fc1 + GELU -> fc2 + residual
 sgpt_status block_16(const Fwd& f, const LayerW& l, int li) {
-    sgpt_model* m = f.m;
-    sgpt_ctx* c = f.c;
-    hipStream_t s = f.s;
+    sgpt_model* m = f.m; sgpt_ctx* c = f.c; hipStream_t s = f.s;
     const int dm = m->d.d_model, ffn = m->d.d_ffn, T = f.T, dt = f.dt;
     const bool gptj = m->d.arch == SGPT_ARCH_GPTJ;
     // SGPT_F16 range shifts of this block (all 0 unless the checkpoint needed them): class stored as value * 2^-k
@@ -251,14 +258,7 @@ sgpt_status block_16(const Fwd& f, const LayerW& l, int li) {
             if ((st = launch16(f, EPI_QKV, dt, q, "QKV projection")) != SGPT_OK) return st;
         } else {
             // Q | K (split: K' = 3d, or 2d for p_ln1 == 3), then V from the hi block alone unless the plan splits it too (p_ln1 == 2)
-            GemmArgs qk = q.g, v = q.g;
-            if (p_ln1) split_w(qk, l.w_qkv3, dm, p_ln1 == 3 ? 2 : 3);
-            qk.N = 2 * dm;
-            gemm(c, dt, EPI_STORE, dt, qk, s);
-            if (p_ln1 == 2) split_w(v, (bf16_t*)l.w_qkv3 + (size_t)2 * dm * 3 * dm, dm);
-            else v.W = (bf16_t*)l.w_qkv + (size_t)2 * dm * dm;
-            v.N = dm; v.out = f.vt; v.ldo = T; v.bias = l.b_qkv ? l.b_qkv + 2 * dm : nullptr;
-            gemm(c, dt, EPI_VT, dt, v, s);
+            proj_qk_vt(f, q.g, 2 * dm, dm, l.w_qkv3, p_ln1);
         }
     }
     if (gptj) launch_rope(f.qkv, dt, 2 * dm, dm, f.pos, m->rot_sin, m->rot_cos, T, m->d.n_heads, dm / m->d.n_heads, m->d.rotary_dim, m->d.max_pos, s);
@@ -294,6 +294,124 @@ sgpt_status block_16(const Fwd& f, const LayerW& l, int li) {
     return launch16(f, EPI_BIAS_RESID, SGPT_F32, q, "fc2");
 }
 
+using BlockFn = sgpt_status (*)(const Fwd&, const LayerW&, int);
+// the block function of this forward: per family, then per arithmetic
+BlockFn pick_block(const Fwd& f) {
+    const bool bf = f.dt != SGPT_F32;
+    if (f.m->d.arch == SGPT_ARCH_BERT) return bf ? block_bert16 : block_bert_f32;
+    if (f.m->d.arch == SGPT_ARCH_LLAMA) return bf ? block_llama16 : block_llama_f32;
+    return f.mlp8 ? block_fp8 : (bf ? block_16 : block_f32);
+}
+
+// The argument and pooling refusals of a forward.  layout: ids, pos, seq_off, seq_len; pooled: the outputs that go through the pool
+// (out, layer_out, layer_mean).
+sgpt_status check_call(sgpt_model* m, const int32_t* const (&layout)[4], const int32_t* pad_left, int B, int T, int max_alloc, int pool_mode,
+                       int n_layers_run, bool pooled, const float* hidden_out) {
+    sgpt_ctx* c = m->ctx;
+    const Family& F = family(m->d.arch);
+    if (!layout[0] || !layout[1] || !layout[2] || !layout[3] || B <= 0 || T <= 0 || T % 32 != 0 || max_alloc <= 0 || max_alloc % 2 != 0)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_encode: bad token layout (T_pad % 32, max_alloc_len % 2)");
+    if (n_layers_run < 0 || n_layers_run > m->d.n_layers) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: n_layers_run out of range");
+    if (pool_mode < 0 || pool_mode > SGPT_POOL_CLS) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: bad pool_mode");
+    if (pool_mode == SGPT_POOL_LEARNTMEAN && !F.learntmean)
+        return fail(c, SGPT_ERR_INVALID, std::string("sgpt_encode: learntmean pooling (trained position weights of the SGPT checkpoints) is not available for ") + F.name);
+    if (pool_mode == SGPT_POOL_CLS && !F.cls) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: cls pooling belongs to SGPT_ARCH_BERT");
+    if (pool_mode == SGPT_POOL_LEARNTMEAN && pooled) {
+        if (!m->pool_w) return fail(c, SGPT_ERR_MISSING, "sgpt_encode: learntmean needs sgpt_model_set_pool_weights first");
+        // with pad_left on the device the longest padded position is not known here: the kernel clamps the table index,
+        // and the Python host checks max(pad_left + len) before the call (model.py::_check_learnt)
+        // (allocations are 8-row aligned: the longest sequence has at least max_alloc - 7 tokens)
+        if (!pad_left && max_alloc - 7 > m->pool_w_n)
+            return fail(c, SGPT_ERR_INVALID, "sgpt_encode: fewer learnt position weights than the longest sequence");
+    }
+    if (max_alloc > 2048) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: sequence longer than 2048 tokens");
+    if (!pooled && !hidden_out) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: no output requested");
+    return SGPT_OK;
+}
+
+constexpr size_t SLACK = 64;  // rows of zeroed slack behind buffers the attention key tiles may over-read
+
+// Fills what the blocks of this call share (the caller has set m, c, s, F, the token layout): the precision-plan scan, the launch path
+// (mlp8 / qpath / qln), the workspace carve and the pointers into it.  lp: receives scratch for the per-layer pooled vectors, or null.
+sgpt_status plan(Fwd& f, int n_layers_run, float** lp) {
+    sgpt_model* m = f.m; sgpt_ctx* c = f.c;
+    const int T = f.T, dm = m->d.d_model, ffn = m->d.d_ffn;
+    const bool gptj = m->d.arch == SGPT_ARCH_GPTJ, fp8m = m->d.compute_dtype == SGPT_FP8M;
+    const bool bf = m->d.compute_dtype != SGPT_F32;                 // 16-bit MFMA operands (bf16 or f16)
+    const size_t esz = bf ? 2 : 4;
+    f.fp8 = m->d.compute_dtype == SGPT_FP8W || fp8m;
+    f.dt = !bf ? SGPT_F32 : (m->d.compute_dtype == SGPT_F16 ? SGPT_F16 : SGPT_BF16);
+    f.d_kv = m->d.n_kv_heads * (dm / m->d.n_heads);
+    // Precision plan (prec[]): a split class is stored as [hi | lo | hi] rows of 3 x its width (the consuming GEMM contracts over
+    // all three blocks against [W_hi | W_hi | W_lo]; a consumer that is not split reads the first block alone).  Any split at
+    // all: the attention context gets its own buffer (the LayerNorm buffer has 3 d rows then).
+    f.can_split = bf && !f.fp8;
+    for (int li = 0; f.can_split && li < n_layers_run; ++li) {
+        const int* pc = &m->prec[(size_t)li * PC_N];
+        f.any_ln |= pc[PC_LN1] != 0 || pc[PC_LN2] != 0; f.any_att |= pc[PC_ATT] != 0; f.any_ctx |= pc[PC_CTX] != 0; f.any_h |= pc[PC_H] != 0;
+    }
+    f.split = f.any_ln || f.any_att || f.any_ctx || f.any_h;
+    // FP8M: fp8 MFMA on all four projections when the shapes fit the 256x256x128 kernel and the activation scales are
+    // calibrated; otherwise (and while calibrating) the block runs the SGPT_FP8W arithmetic (weights de-quantised to bf16)
+    const bool shapes8 = gemm_fp8_shape_ok(T, ffn, dm) && gemm_fp8_shape_ok(T, dm, ffn) && gemm_fp8_shape_ok(T, 2 * dm, dm);
+    f.mlp8 = fp8m && !m->calibrating && shapes8;
+    if (f.mlp8)
+        for (int li = 0; li < n_layers_run; ++li)
+            if (!(m->act_scale[li] > 0.f) || !(m->act_scale[m->d.n_layers + li] > 0.f))
+                return fail(c, SGPT_ERR_INVALID, "SGPT_FP8M: activation scales are not set (sgpt_model_calibrate_begin / _end, or sgpt_model_set_act_scales)");
+    // Query-sized batches (round 6; qgemm.hip): at most QGEMM_MAX_ROWS token rows, plain 16-bit operands, no probe / calibration
+    // pass riding on the forward.  Every projection takes the register-staged deep-prefetch kernel; at d = 512 / 768 / 1024 the two
+    // LayerNorms of a sequential block (GPT-Neo, BLOOM) run inside the prologues of the projections they feed: five launches per block
+    // instead of seven.  Same arithmetic per element as the bulk path (identical bits); sgpt_ctx_set_tile_policy(1 | 2) keeps the bulk kernels.
+    f.qpath = bf && !f.fp8 && !f.split && f.F->qpath && !(m->probing && m->crest_dev) && !m->calibrating && !c->force256 && !c->no_qpath && T <= QGEMM_MAX_ROWS &&
+              qgemm_shape_ok(T, 3 * dm, dm, EPI_QKV, 2 * dm) && qgemm_shape_ok(T, dm, dm, EPI_BIAS_RESID, 0) &&
+              qgemm_shape_ok(T, ffn, dm, EPI_BIAS_GELU, 0) && qgemm_shape_ok(T, dm, ffn, EPI_BIAS_RESID, 0);
+    f.qln = f.qpath && !gptj && qgemm_ln_ok(T, 3 * dm, dm, EPI_QKV, 2 * dm) && qgemm_ln_ok(T, ffn, dm, EPI_BIAS_GELU, 0);
+    // workspace carve (all offsets 256-B aligned)
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    const size_t o_x = carve((size_t)T * dm * 4);                        // residual stream fp32
+    const size_t o_a = carve((size_t)T * dm * esz * (f.any_ln ? 3 : 1));    // LN output (GPT-Neo: also attention ctx)
+    const size_t o_c = (gptj || f.split) ? carve((size_t)T * dm * esz * (f.any_ctx ? 3 : 1)) : o_a;   // GPT-J: ctx separate (ln_1 output feeds the MLP too)
+    const size_t qkv_bytes = ((size_t)T + SLACK) * 3 * dm * esz;
+    const size_t o_qkv = carve(qkv_bytes * (f.any_att ? 2 : 1));         // 16-bit: q | k rows + V^T (x3 attention: the lo halves behind); fp32: q | k | v rows
+    const size_t o_h = carve((size_t)T * ffn * esz * (f.any_h ? 3 : 1));                   // MLP hidden (FP8M: e4m3 codes in the same region)
+    const size_t o_gu = f.F->swiglu ? carve((size_t)T * 2 * ffn * esz) : 0;                     // SGPT_ARCH_LLAMA: fc1 output, gate | up columns
+    const size_t o_a8 = f.mlp8 ? carve((size_t)T * dm) : 0;              // FP8M: LayerNorm output as e4m3 codes
+    const size_t o_sa = f.mlp8 ? carve((size_t)T * 4) : 0;               //       + one scale per row
+    const size_t o_lp = lp ? carve((size_t)(m->d.n_layers + 1) * f.B * dm * 4) : 0;
+    sgpt_status st = ensure(c, &c->ws, &c->ws_bytes, off);
+    if (st != SGPT_OK) return st;
+    char* base = (char*)c->ws;
+    f.range_flag = (f.mlp8 || f.dt == SGPT_F16) ? (int*)m->range_dev : nullptr;
+    f.x = (float*)(base + o_x); f.a = base + o_a; f.ctx = base + o_c; f.qkv = base + o_qkv; f.h = base + o_h;
+    if (f.F->swiglu) f.gu = base + o_gu;
+    f.vt = bf ? (void*)((bf16_t*)f.qkv + ((size_t)T + SLACK) * 2 * dm) : nullptr;
+    if (f.mlp8) { f.a8 = base + o_a8; f.sa = (float*)(base + o_sa); }
+    if (lp) *lp = (float*)(base + o_lp);
+    f.att_lo = (long)(qkv_bytes / 2);      // element distance of the lo halves of q | k and of V^T (x3 attention)
+    return SGPT_OK;
+}
+
+// Rows that are over-read by the attention key tiles but never written in this call must be finite
+// (a masked key contributes p = 0, and 0 * NaN = NaN): the slack behind the q/k/v buffers, and -- when
+// the attention context has its own buffer (GPT-J) -- the filler rows past the last sequence.  The
+// workspace is reused across calls / dtypes, so stale bytes there can decode to NaN.
+sgpt_status zero_overread(const Fwd& f) {
+    sgpt_ctx* c = f.c; const size_t T = f.T, dm = f.m->d.d_model, dkv = f.d_kv, esz = f.vt ? 2 : 4;
+    if (f.vt)            // q | k rows of d + d_kv columns, V^T of d_kv rows; x3 attention: their lo halves too
+        for (long lo = 0; lo <= (f.any_att ? f.att_lo : 0); lo += f.att_lo) {
+            HIPC(c, hipMemsetAsync((bf16_t*)f.qkv + lo + T * (dm + dkv), 0, SLACK * (dm + dkv) * esz, f.s));
+            HIPC(c, hipMemsetAsync((bf16_t*)f.vt + lo + T * dkv, 0, SLACK * dkv * esz, f.s));
+        }
+    else if (f.F->slack_f32) HIPC(c, hipMemsetAsync((float*)f.qkv + T * (dm + 2 * dkv), 0, SLACK * (dm + 2 * dkv) * esz, f.s));
+    // (query path with the LayerNorm inside the projections: no LayerNorm launch fills the buffer the context shares with it)
+    // (post-LN family in fp32: no LayerNorm ever writes the buffer the context lives in)
+    if (f.m->d.arch == SGPT_ARCH_GPTJ || f.mlp8 || f.split || f.qln || (f.F->post_ln && !f.vt))
+        HIPC(c, hipMemsetAsync(f.ctx, 0, T * dm * esz * (f.any_ctx ? 3 : 1), f.s));   // (fp8: stale bytes would decode to NaN codes)
+    return SGPT_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -305,152 +423,44 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
                                float* out, float* hidden_out, float* layer_out, float* layer_mean, void* stream) {
     if (!m) return SGPT_ERR_INVALID;
     sgpt_ctx* c = m->ctx;
-    if (!ids || !pos || !seq_off || !seq_len || B <= 0 || T <= 0 || T % 32 || max_alloc <= 0 || max_alloc % 2)
-        return fail(c, SGPT_ERR_INVALID, "sgpt_encode: bad token layout (T_pad % 32, max_alloc_len % 2)");
-    if (n_layers_run < 0 || n_layers_run > m->d.n_layers) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: n_layers_run out of range");
-    if (pool_mode < 0 || pool_mode > SGPT_POOL_CLS) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: bad pool_mode");
-    const bool bert = m->d.arch == SGPT_ARCH_BERT;
-    if (bert && pool_mode == SGPT_POOL_LEARNTMEAN)
-        return fail(c, SGPT_ERR_INVALID, "sgpt_encode: learntmean pooling (trained position weights of the SGPT checkpoints) is not available for SGPT_ARCH_BERT");
-    if (bert) apply_final_ln = 0;      // no ln_f in this family: the last block's LayerNorm output is hidden_states[-1]
-    const bool llama = m->d.arch == SGPT_ARCH_LLAMA;
-    if (llama && pool_mode == SGPT_POOL_LEARNTMEAN)
-        return fail(c, SGPT_ERR_INVALID, "sgpt_encode: learntmean pooling (trained position weights of the SGPT checkpoints) is not available for SGPT_ARCH_LLAMA");
-    if (llama && pool_mode == SGPT_POOL_CLS)
-        return fail(c, SGPT_ERR_INVALID, "sgpt_encode: cls pooling belongs to SGPT_ARCH_BERT");
-    const int norm_kind = llama ? 1 : 0;       // the final norm inside the pool: RMSNorm for this family
-    if (pool_mode == SGPT_POOL_LEARNTMEAN && (out || layer_out || layer_mean)) {
-        if (!m->pool_w) return fail(c, SGPT_ERR_MISSING, "sgpt_encode: learntmean needs sgpt_model_set_pool_weights first");
-        // with pad_left on the device the longest padded position is not known here: the kernel clamps the table index,
-        // and the Python host checks max(pad_left + len) before the call (model.py::_check_learnt)
-        // (allocations are 8-row aligned: the longest sequence has at least max_alloc - 7 tokens)
-        if (!pad_left && max_alloc - 7 > m->pool_w_n)
-            return fail(c, SGPT_ERR_INVALID, "sgpt_encode: fewer learnt position weights than the longest sequence");
-    }
-    if (max_alloc > 2048) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: sequence longer than 2048 tokens");
-    if (!out && !hidden_out && !layer_out && !layer_mean) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: no output requested");
+    const Family& F = family(m->d.arch);
+    sgpt_status st = check_call(m, {ids, pos, seq_off, seq_len}, pad_left, B, T, max_alloc, pool_mode, n_layers_run, out || layer_out || layer_mean, hidden_out);
+    if (st != SGPT_OK) return st;
+    if (!F.lnf) apply_final_ln = 0;    // no final norm in this family: the last block's LayerNorm output is hidden_states[-1]
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    const int dm = m->d.d_model, ffn = m->d.d_ffn;
-    const bool fp8m = m->d.compute_dtype == SGPT_FP8M;
-    const bool fp8 = m->d.compute_dtype == SGPT_FP8W || fp8m;
-    const bool bf = m->d.compute_dtype != SGPT_F32;                 // 16-bit MFMA operands (bf16 or f16)
-    const int dt = !bf ? SGPT_F32 : (m->d.compute_dtype == SGPT_F16 ? SGPT_F16 : SGPT_BF16);
-    const size_t esz = bf ? 2 : 4;
-    const size_t SLACK = 64;  // rows of zeroed slack behind buffers the attention key tiles may over-read
-
-    const bool gptj = m->d.arch == SGPT_ARCH_GPTJ;
-    // workspace carve (all offsets 256-B aligned)
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_x = carve((size_t)T * dm * 4);                        // residual stream fp32
-    // Precision plan (prec[]): a split class is stored as [hi | lo | hi] rows of 3 x its width (the consuming GEMM contracts over
-    // all three blocks against [W_hi | W_hi | W_lo]; a consumer that is not split reads the first block alone).  Any split at
-    // all: the attention context gets its own buffer (the LayerNorm buffer has 3 d rows then).
-    const bool can_split = bf && !fp8;
-    bool any_ln = false, any_att = false, any_ctx = false, any_h = false;
-    if (can_split)
-        for (int li = 0; li < n_layers_run; ++li) {
-            const int* pc = &m->prec[(size_t)li * PC_N];
-            any_ln |= pc[PC_LN1] != 0 || pc[PC_LN2] != 0; any_att |= pc[PC_ATT] != 0; any_ctx |= pc[PC_CTX] != 0; any_h |= pc[PC_H] != 0;
-        }
-    const bool split = any_ln || any_att || any_ctx || any_h;
-    const size_t o_a = carve((size_t)T * dm * esz * (any_ln ? 3 : 1));    // LN output (GPT-Neo: also attention ctx)
-    const size_t o_c = (gptj || split) ? carve((size_t)T * dm * esz * (any_ctx ? 3 : 1)) : o_a;   // GPT-J: ctx separate (ln_1 output feeds the MLP too)
-    const size_t qkv_bytes = ((size_t)T + SLACK) * 3 * dm * esz;
-    const size_t o_qkv = carve(qkv_bytes * (any_att ? 2 : 1));           // bf16: [T][2d] qk + V^T [d][T] (x3 attention: the lo halves behind); fp32: [T][3d]
-    const size_t o_h = carve((size_t)T * ffn * esz * (any_h ? 3 : 1));                     // MLP hidden (FP8M: e4m3 codes in the same region)
-    const size_t o_gu = llama ? carve((size_t)T * 2 * ffn * esz) : 0;                      // SGPT_ARCH_LLAMA: fc1 output, gate | up columns
-    // FP8M: fp8 MFMA on all four projections when the shapes fit the 256x256x128 kernel and the activation scales are
-    // calibrated; otherwise (and while calibrating) the block runs the SGPT_FP8W arithmetic (weights de-quantised to bf16)
-    const bool shapes8 = gemm_fp8_shape_ok(T, ffn, dm) && gemm_fp8_shape_ok(T, dm, ffn) && gemm_fp8_shape_ok(T, 2 * dm, dm);
-    const bool mlp8 = fp8m && !m->calibrating && shapes8;
-    if (mlp8)
-        for (int li = 0; li < n_layers_run; ++li)
-            if (!(m->act_scale[li] > 0.f) || !(m->act_scale[m->d.n_layers + li] > 0.f))
-                return fail(c, SGPT_ERR_INVALID, "SGPT_FP8M: activation scales are not set (sgpt_model_calibrate_begin / _end, or sgpt_model_set_act_scales)");
-    // Query-sized batches (round 6; qgemm.hip): at most QGEMM_MAX_ROWS token rows, plain 16-bit operands, no probe / calibration
-    // pass riding on the forward.  Every projection takes the register-staged deep-prefetch kernel; at d = 512 / 768 / 1024 the two
-    // LayerNorms of a sequential block (GPT-Neo, BLOOM) run inside the prologues of the projections they feed: five launches per block
-    // instead of seven.  Same arithmetic per element as the bulk path (identical bits); sgpt_ctx_set_tile_policy(1 | 2) keeps the bulk kernels.
-    const bool qpath = bf && !fp8 && !split && !bert && !llama && !(m->probing && m->crest_dev) && !m->calibrating && !c->force256 && !c->no_qpath && T <= QGEMM_MAX_ROWS &&
-                       qgemm_shape_ok(T, 3 * dm, dm, EPI_QKV, 2 * dm) && qgemm_shape_ok(T, dm, dm, EPI_BIAS_RESID, 0) &&
-                       qgemm_shape_ok(T, ffn, dm, EPI_BIAS_GELU, 0) && qgemm_shape_ok(T, dm, ffn, EPI_BIAS_RESID, 0);
-    const bool qln = qpath && !gptj && qgemm_ln_ok(T, 3 * dm, dm, EPI_QKV, 2 * dm) && qgemm_ln_ok(T, ffn, dm, EPI_BIAS_GELU, 0);
-    const size_t o_a8 = mlp8 ? carve((size_t)T * dm) : 0;                // FP8M: LayerNorm output as e4m3 codes
-    const size_t o_sa = mlp8 ? carve((size_t)T * 4) : 0;                 //       + one scale per row
-    const size_t o_lp = (layer_mean && !layer_out) ? carve((size_t)(m->d.n_layers + 1) * B * dm * 4) : 0;
-    sgpt_status st = ensure(c, &c->ws, &c->ws_bytes, off);
-    if (st != SGPT_OK) return st;
-    char* base = (char*)c->ws;
-    if (layer_mean && !layer_out) layer_out = (float*)(base + o_lp);     // per-layer pooled vectors, scratch
     Fwd f{};
-    f.m = m; f.c = c; f.s = s; f.pos = pos; f.seq_off = seq_off; f.seq_len = seq_len; f.B = B; f.T = T; f.max_alloc = max_alloc;
-    f.dt = dt; f.range_flag = (mlp8 || dt == SGPT_F16) ? (int*)m->range_dev : nullptr;
-    f.can_split = can_split; f.qpath = qpath; f.qln = qln;
-    f.x = (float*)(base + o_x); f.a = base + o_a; f.ctx = base + o_c; f.qkv = base + o_qkv; f.h = base + o_h;
-    f.gu = llama ? base + o_gu : nullptr;
-    f.vt = bf ? (void*)((bf16_t*)f.qkv + ((size_t)T + SLACK) * 2 * dm) : nullptr;
-    if (mlp8) { f.a8 = base + o_a8; f.sa = (float*)(base + o_sa); }
-    f.att_lo = (long)(qkv_bytes / 2);      // element distance of the lo halves of q | k and of V^T (x3 attention)
-    float* x = f.x;
-
-    // Rows that are over-read by the attention key tiles but never written in this call must be finite
-    // (a masked key contributes p = 0, and 0 * NaN = NaN): the slack behind the q/k/v buffers, and -- when
-    // the attention context has its own buffer (GPT-J) -- the filler rows past the last sequence.  The
-    // workspace is reused across calls / dtypes, so stale bytes there can decode to NaN.
-    if (llama) {          // q | k rows of d + d_kv columns, V^T of d_kv rows (fp32: the kernel reads no key past its query)
-        const size_t dkv = (size_t)m->d.n_kv_heads * (dm / m->d.n_heads);
-        if (bf) {
-            HIPC(c, hipMemsetAsync((bf16_t*)f.qkv + (size_t)T * (dm + dkv), 0, SLACK * (dm + dkv) * esz, s));
-            HIPC(c, hipMemsetAsync((bf16_t*)f.vt + (size_t)T * dkv, 0, SLACK * dkv * esz, s));
-        }
-    } else if (bf) {
-        HIPC(c, hipMemsetAsync((bf16_t*)f.qkv + (size_t)T * 2 * dm, 0, SLACK * 2 * dm * esz, s));
-        HIPC(c, hipMemsetAsync((bf16_t*)f.vt + (size_t)T * dm, 0, SLACK * dm * esz, s));
-        if (any_att) {
-            HIPC(c, hipMemsetAsync((bf16_t*)f.qkv + f.att_lo + (size_t)T * 2 * dm, 0, SLACK * 2 * dm * esz, s));
-            HIPC(c, hipMemsetAsync((bf16_t*)f.vt + f.att_lo + (size_t)T * dm, 0, SLACK * dm * esz, s));
-        }
-    } else {
-        HIPC(c, hipMemsetAsync((float*)f.qkv + (size_t)T * 3 * dm, 0, SLACK * 3 * dm * esz, s));
-    }
-    // (query path with the LayerNorm inside the projections: no LayerNorm launch fills the buffer the context shares with it)
-    // (BERT fp32: no LayerNorm ever writes the buffer the context lives in)
-    if (gptj || mlp8 || split || qln || (bert && !bf)) HIPC(c, hipMemsetAsync(f.ctx, 0, (size_t)T * dm * esz * (any_ctx ? 3 : 1), s));   // (fp8: stale bytes would decode to NaN codes)
+    f.m = m; f.c = c; f.s = s; f.F = &F; f.pos = pos; f.seq_off = seq_off; f.seq_len = seq_len; f.B = B; f.T = T; f.max_alloc = max_alloc;
+    if ((st = plan(f, n_layers_run, layer_mean && !layer_out ? &layer_out : nullptr)) != SGPT_OK) return st;   // (their mean alone: scratch)
+    if ((st = zero_overread(f)) != SGPT_OK) return st;
+    const int dm = m->d.d_model, ffn = m->d.d_ffn, dt = f.dt; float* x = f.x;
+    auto pool = [&](int final_ln, float* dst, int* range_flag) {
+        launch_lnf_pool(x, m->lnf_g, m->lnf_b, seq_off, seq_len, pad_left, B, dm, m->d.ln_eps, final_ln, pool_mode, normalize, m->pool_w,
+                        m->pool_w_n, dst, s, range_flag, F.norm_kind);
+    };
     launch_embed(ids, pos, m->wte, m->wpe, x, T, dm, m->d.vocab, m->d.max_pos, s);
-    if (bert && bf) launch_layernorm_writeback(x, m->emb_ln_g, m->emb_ln_b, f.a, dt, T, dm, m->d.ln_eps, f.range_flag, s);   // x and its 16-bit copy
+    if (F.post_ln && f.vt) launch_layernorm_writeback(x, m->emb_ln_g, m->emb_ln_b, f.a, dt, T, dm, m->d.ln_eps, f.range_flag, s);   // x and its 16-bit copy
     else if (m->emb_ln_g) launch_layernorm(x, m->emb_ln_g, m->emb_ln_b, x, SGPT_F32, T, dm, m->d.ln_eps, s);   // BLOOM :499
+    const BlockFn block = pick_block(f);
     for (int li = 0; li < n_layers_run; ++li) {
         LayerW l = m->L[li];
-        if (layer_out)   // hidden_states[li] = input of block li (HF:gpt_neo:475-478)
-            launch_lnf_pool(x, m->lnf_g, m->lnf_b, seq_off, seq_len, pad_left, B, dm, m->d.ln_eps, 0, pool_mode,
-                            normalize, m->pool_w, m->pool_w_n, layer_out + (size_t)li * B * dm, s, nullptr, norm_kind);
-        if (fp8 && !mlp8) {  // this block's weights: e4m3fn codes * 2^k -> bf16, exact; <1 % of the block's time at T >= 16k
+        if (layer_out) pool(0, layer_out + (size_t)li * B * dm, nullptr);   // hidden_states[li] = input of block li (HF:gpt_neo:475-478)
+        if (f.fp8 && !f.mlp8) {  // this block's weights: e4m3fn codes * 2^k -> bf16, exact; <1 % of the block's time at T >= 16k
             launch_fp8_dequant_rows(l.w_qkv, l.s_qkv, (long)3 * dm, dm, m->dq[0], SGPT_BF16, s);
             launch_fp8_dequant_rows(l.w_o, l.s_o, dm, dm, m->dq[1], SGPT_BF16, s);
             launch_fp8_dequant_rows(l.w_fc, l.s_fc, ffn, dm, m->dq[2], SGPT_BF16, s);
             launch_fp8_dequant_rows(l.w_proj, l.s_proj, dm, ffn, m->dq[3], SGPT_BF16, s);
             l.w_qkv = m->dq[0]; l.w_o = m->dq[1]; l.w_fc = m->dq[2]; l.w_proj = m->dq[3];
         }
-        if (bert) { if (bf) block_bert16(f, l); else block_bert_f32(f, l); }
-        else if (llama) { if (bf) block_llama16(f, l); else block_llama_f32(f, l); }
-        else if (mlp8) block_fp8(f, l, li);
-        else if (!bf) block_f32(f, l);
-        else if ((st = block_16(f, l, li)) != SGPT_OK) return st;
+        if ((st = block(f, l, li)) != SGPT_OK) return st;
     }
     if (hidden_out) {
-        if (apply_final_ln && llama) launch_rmsnorm(x, m->lnf_g, hidden_out, SGPT_F32, T, dm, m->d.ln_eps, nullptr, s);
+        if (apply_final_ln && F.norm_kind == 1) launch_rmsnorm(x, m->lnf_g, hidden_out, SGPT_F32, T, dm, m->d.ln_eps, nullptr, s);
         else if (apply_final_ln) launch_layernorm(x, m->lnf_g, m->lnf_b, hidden_out, SGPT_F32, T, dm, m->d.ln_eps, s);
         else HIPC(c, hipMemcpyAsync(hidden_out, x, (size_t)T * dm * 4, hipMemcpyDeviceToDevice, s));
     }
-    if (out)
-        launch_lnf_pool(x, m->lnf_g, m->lnf_b, seq_off, seq_len, pad_left, B, dm, m->d.ln_eps, apply_final_ln,
-                        pool_mode, normalize, m->pool_w, m->pool_w_n, out, s,
-                        m->d.compute_dtype == SGPT_F16 ? (int*)m->range_dev : nullptr, norm_kind);
-    if (layer_out)
-        launch_lnf_pool(x, m->lnf_g, m->lnf_b, seq_off, seq_len, pad_left, B, dm, m->d.ln_eps, apply_final_ln,
-                        pool_mode, normalize, m->pool_w, m->pool_w_n, layer_out + (size_t)n_layers_run * B * dm, s, nullptr, norm_kind);
+    if (out) pool(apply_final_ln, out, m->d.compute_dtype == SGPT_F16 ? (int*)m->range_dev : nullptr);
+    if (layer_out) pool(apply_final_ln, layer_out + (size_t)n_layers_run * B * dm, nullptr);
     if (layer_mean) launch_mean_over_axis0(layer_out, n_layers_run + 1, (long)B * dm, layer_mean, s);
     HIPC(c, hipGetLastError());
     return SGPT_OK;
@@ -480,8 +490,7 @@ sgpt_status sgpt_lm_logprobs(sgpt_model* m, const float* hidden, const int32_t* 
     if (!m) return SGPT_ERR_INVALID;
     sgpt_ctx* c = m->ctx;
     if (!hidden || !row_idx || !targets || !out_logprob || n <= 0) return fail(c, SGPT_ERR_INVALID, "sgpt_lm_logprobs: bad arguments");
-    if (m->d.arch == SGPT_ARCH_BERT) return fail(c, SGPT_ERR_INVALID, "sgpt_lm_logprobs: SGPT_ARCH_BERT carries no causal LM head");
-    if (m->d.arch == SGPT_ARCH_LLAMA) return fail(c, SGPT_ERR_INVALID, "sgpt_lm_logprobs: not built for SGPT_ARCH_LLAMA (the LM head of this family is not loaded)");
+    if (family(m->d.arch).no_lm) return fail(c, SGPT_ERR_INVALID, std::string("sgpt_lm_logprobs: ") + family(m->d.arch).no_lm);
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int dm = m->d.d_model, V = m->d.vocab;

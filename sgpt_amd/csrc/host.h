@@ -100,6 +100,39 @@ inline const char* exp_env(const char* name) { return getenv(name); }
 inline const char* exp_env(const char*) { return nullptr; }
 #endif
 
+// ---- what a model family is: one row per SGPT_ARCH_* value ("What a family consists of") ----
+// A family that does not build a feature says so in its row and nowhere else: every refusal of model.hip / encode.hip reads this table,
+// and outside it only the loader dispatch (model.hip) and the block dispatch (encode.hip) look at `arch` for these families.
+enum { WIN_ANY, WIN_ZERO, WIN_NONNEG };            // sgpt_model_desc.window: any value | must be 0 | >= 0
+struct Family {
+    const char *name, *prefix, *wte, *lnf;   // name in messages; state dict: layer prefix, embedding tensor, final norm (null: it has none)
+    int norm_kind;                     // final norm inside the pool (launch_lnf_pool): 0 LayerNorm | 1 RMSNorm
+    // post_ln: every block ends in the LayerNorm that writes the residual stream (the fp32 blocks never write `a`).  swiglu: fc1 yields
+    // gate | up columns ([T][2 ffn] scratch).  slack_f32: the fp32 forward zeroes the slack rows behind q | k | v -- the Llama fp32 forward
+    // has never issued that memset ("the kernel reads no key past its query") and keeps not issuing it: to be settled on its own.
+    bool post_ln, swiglu, slack_f32;
+    // what the family builds: fp8 modes, split-precision operands, f16 range shifts, the precision probe, the query path, pooling modes
+    bool fp8, split, shifts, probe, qpath, learntmean, cls;
+    const char* no_lm;                 // sgpt_lm_logprobs: why it is refused (null: the LM head is built)
+    // head dims its 16-bit attention serves: 64 and 128, with dh256 also 256 (the library-wide rule of check_desc); without it dh_rule
+    // is the family's refusal of anything else, and dh_all: it holds for SGPT_F32 models too.  window: WIN_*.  gqa: n_kv_heads may
+    // differ from n_heads.
+    bool dh256; const char* dh_rule; bool dh_all; int window; bool gqa;
+};
+constexpr Family FAMILIES[] = {
+    // name, prefix, wte, lnf, norm_kind | post_ln, swiglu, slack_f32 | fp8, split, shifts, probe, qpath, learntmean, cls | no_lm |
+    // dh256, dh_rule, dh_all, window, gqa          (the bools of a row are grouped as in this line: 3, then 7, then dh256)
+    {"SGPT_ARCH_GPTNEO", "h.", "wte.weight", "ln_f", 0, false, false, true,  true, true, true, true, true, true, true,  nullptr, true, nullptr, false, WIN_ANY, false},
+    {"SGPT_ARCH_GPTJ", "h.", "wte.weight", "ln_f", 0, false, false, true,  true, true, true, true, true, true, true,  nullptr, true, nullptr, false, WIN_ANY, false},
+    {"SGPT_ARCH_BLOOM", "h.", "word_embeddings.weight", "ln_f", 0, false, false, true,  true, true, true, true, true, true, true,  nullptr, true, nullptr, false, WIN_ANY, false},
+    {"SGPT_ARCH_BERT", "encoder.layer.", "embeddings.word_embeddings.weight", nullptr, 0, true, false, true,  false, false, false, false, false, false, true,
+     "SGPT_ARCH_BERT carries no causal LM head", false, "16-bit bidirectional attention supports head_dim 64 or 128", false, WIN_ZERO, false},
+    {"SGPT_ARCH_LLAMA", "layers.", "embed_tokens.weight", "norm", 1, false, true, false,  false, false, false, false, false, false, false,
+     "not built for SGPT_ARCH_LLAMA (the LM head of this family is not loaded)", false, "head_dim 64 or 128", true, WIN_NONNEG, true},
+};
+constexpr int N_FAMILIES = sizeof(FAMILIES) / sizeof(FAMILIES[0]);
+static_assert(SGPT_ARCH_GPTNEO == 0 && SGPT_ARCH_GPTJ == 1 && SGPT_ARCH_BLOOM == 2 && SGPT_ARCH_BERT == 3 && SGPT_ARCH_LLAMA == 4 && N_FAMILIES == 5, "FAMILIES is indexed by SGPT_ARCH_*");
+inline const Family& family(int arch) { return FAMILIES[arch]; }
 // grow-only workspace (ctx.hip)
 sgpt_status ensure(sgpt_ctx* c, void** p, size_t* have, size_t need);
 

@@ -3,106 +3,71 @@
 // Host-side C++ only -- every device op is one of the hand-written kernels in this directory.
 #include "host.h"
 
-extern "C" {
+namespace {
 
-// ------------------------------------------------------------------------------------------
-sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_tensor_view* tv, size_t nt,
-                            sgpt_model** out) {
-    if (!c || !d || !tv || !out) return SGPT_ERR_INVALID;
-    *out = nullptr;
-    HIPC(c, hipSetDevice(c->device));
-    if (d->arch != SGPT_ARCH_GPTNEO && d->arch != SGPT_ARCH_GPTJ && d->arch != SGPT_ARCH_BLOOM && d->arch != SGPT_ARCH_BERT &&
-        d->arch != SGPT_ARCH_LLAMA)
-        return fail(c, SGPT_ERR_INVALID, "arch must be SGPT_ARCH_GPTNEO, SGPT_ARCH_GPTJ, SGPT_ARCH_BLOOM, SGPT_ARCH_BERT or SGPT_ARCH_LLAMA");
-    const bool gptj = d->arch == SGPT_ARCH_GPTJ, bloom = d->arch == SGPT_ARCH_BLOOM, bert = d->arch == SGPT_ARCH_BERT;
-    const bool llama = d->arch == SGPT_ARCH_LLAMA;
-    const int dm = d->d_model, ffn = d->d_ffn, H = d->n_heads;
+// Every refusal sgpt_model_load makes on the descriptor alone.  The order is part of the ABI's behaviour: where a descriptor breaks
+// several rules, the first one here answers.  The family rules come from the family's row (host.h).
+sgpt_status check_desc(sgpt_ctx* c, const sgpt_model_desc* d) {
+    if (d->arch < 0 || d->arch >= N_FAMILIES) return fail(c, SGPT_ERR_INVALID, "arch must be SGPT_ARCH_GPTNEO, SGPT_ARCH_GPTJ, SGPT_ARCH_BLOOM, SGPT_ARCH_BERT or SGPT_ARCH_LLAMA");
+    const Family& F = family(d->arch); const std::string fam = std::string(F.name) + ": ";
+    const int dm = d->d_model, ffn = d->d_ffn, H = d->n_heads, cd = d->compute_dtype;
     if (dm % 128 || ffn % 128 || H <= 0 || dm % H) return fail(c, SGPT_ERR_INVALID, "d_model and d_ffn must be multiples of 128");
     const int dh = dm / H;
-    if (d->compute_dtype != SGPT_F32 && dh != 64 && dh != 128 && dh != 256)
-        return fail(c, SGPT_ERR_INVALID, "16-bit attention supports head_dim 64, 128 or 256");
+    const bool fp8 = cd == SGPT_FP8W || cd == SGPT_FP8M, split = d->qk_split != 0 || d->split_weights != 0;
+    if (cd != SGPT_F32 && dh != 64 && dh != 128 && dh != 256) return fail(c, SGPT_ERR_INVALID, "16-bit attention supports head_dim 64, 128 or 256");
     if (dh > 256 || dh % 4) return fail(c, SGPT_ERR_INVALID, "head_dim must be <= 256 and a multiple of 4");
     if (dm > 4096) return fail(c, SGPT_ERR_INVALID, "d_model > 4096 not supported");
-    if (d->compute_dtype != SGPT_BF16 && d->compute_dtype != SGPT_F32 && d->compute_dtype != SGPT_FP8W &&
-        d->compute_dtype != SGPT_F16 && d->compute_dtype != SGPT_FP8M)
-        return fail(c, SGPT_ERR_INVALID, "bad compute_dtype");
-    if (gptj && (d->rotary_dim <= 0 || d->rotary_dim > dh || d->rotary_dim % 2))
-        return fail(c, SGPT_ERR_INVALID, "GPT-J needs an even rotary_dim in (0, head_dim]");
-    if ((d->qk_split != 0 || d->split_weights != 0) && d->compute_dtype != SGPT_F16 && d->compute_dtype != SGPT_BF16)
-        return fail(c, SGPT_ERR_INVALID, "qk_split / split_weights apply to SGPT_F16 / SGPT_BF16 models");
+    if (cd != SGPT_BF16 && cd != SGPT_F32 && cd != SGPT_F16 && !fp8) return fail(c, SGPT_ERR_INVALID, "bad compute_dtype");
+    if (d->arch == SGPT_ARCH_GPTJ && (d->rotary_dim <= 0 || d->rotary_dim > dh || d->rotary_dim % 2)) return fail(c, SGPT_ERR_INVALID, "GPT-J needs an even rotary_dim in (0, head_dim]");
+    if (split && cd != SGPT_F16 && cd != SGPT_BF16) return fail(c, SGPT_ERR_INVALID, "qk_split / split_weights apply to SGPT_F16 / SGPT_BF16 models");
+    // (a family without them has one arithmetic per operand format: no fp8 storage / MFMA, no split-precision operands)
+    if (fp8 && !F.fp8) return fail(c, SGPT_ERR_INVALID, fam + "compute_dtype SGPT_F32, SGPT_F16 or SGPT_BF16 (no fp8 mode for this family)");
+    if (split && !F.split) return fail(c, SGPT_ERR_INVALID, fam + "qk_split / split_weights (split-precision operands) are not available for this family");
+    if (!F.dh256 && (F.dh_all || cd != SGPT_F32) && dh != 64 && dh != 128) return fail(c, SGPT_ERR_INVALID, fam + F.dh_rule);
+    if (F.gqa && (d->n_kv_heads < 0 || (d->n_kv_heads > 0 && H % d->n_kv_heads))) return fail(c, SGPT_ERR_INVALID, fam + "n_heads % n_kv_heads == 0 (0 = n_heads)");
+    if (F.window == WIN_ZERO && d->window != 0) return fail(c, SGPT_ERR_INVALID, fam + "window must be 0");
+    if (F.window == WIN_NONNEG && d->window < 0) return fail(c, SGPT_ERR_INVALID, fam + "window >= 0");
+    if (!F.gqa && d->n_kv_heads != 0 && d->n_kv_heads != H) return fail(c, SGPT_ERR_INVALID, "n_kv_heads (grouped K / V) belongs to SGPT_ARCH_LLAMA");
+    return SGPT_OK;
+}
 
-    if (bert) {
-        // the post-LayerNorm block has one arithmetic per operand format: no fp8 storage / MFMA, no split-precision operands
-        if (d->compute_dtype == SGPT_FP8W || d->compute_dtype == SGPT_FP8M)
-            return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_BERT: compute_dtype SGPT_F32, SGPT_F16 or SGPT_BF16 (no fp8 mode for this family)");
-        if (d->qk_split != 0 || d->split_weights != 0)
-            return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_BERT: qk_split / split_weights (split-precision operands) are not available for this family");
-        if (d->compute_dtype != SGPT_F32 && dh != 64 && dh != 128)
-            return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_BERT: 16-bit bidirectional attention supports head_dim 64 or 128");
-        if (d->window != 0) return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_BERT: window must be 0");
-    }
-
-    if (llama) {
-        // one arithmetic per operand format, as for SGPT_ARCH_BERT
-        if (d->compute_dtype == SGPT_FP8W || d->compute_dtype == SGPT_FP8M)
-            return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_LLAMA: compute_dtype SGPT_F32, SGPT_F16 or SGPT_BF16 (no fp8 mode for this family)");
-        if (d->qk_split != 0 || d->split_weights != 0)
-            return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_LLAMA: qk_split / split_weights (split-precision operands) are not available for this family");
-        if (dh != 64 && dh != 128) return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_LLAMA: head_dim 64 or 128");
-        if (d->n_kv_heads < 0 || (d->n_kv_heads > 0 && H % d->n_kv_heads))
-            return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_LLAMA: n_heads % n_kv_heads == 0 (0 = n_heads)");
-        if (d->window < 0) return fail(c, SGPT_ERR_INVALID, "SGPT_ARCH_LLAMA: window >= 0");
-    } else if (d->n_kv_heads != 0 && d->n_kv_heads != H) {
-        return fail(c, SGPT_ERR_INVALID, "n_kv_heads (grouped K / V) belongs to SGPT_ARCH_LLAMA");
-    }
-
+// One sgpt_model_load at work: the caller's tensors by name, the model being filled, the packed format and the running status.  A
+// failure is recorded in `st` (the last one answers) and ends the layer loop of the family's loader.
+struct Loader {
+    sgpt_ctx* c; const sgpt_model_desc* d; sgpt_model* m;
     std::unordered_map<std::string, const sgpt_tensor_view*> byname;
-    for (size_t i = 0; i < nt; ++i) byname[tv[i].name] = &tv[i];
-    sgpt_model* m = new sgpt_model();
-    m->ctx = c;
-    m->d = *d;
-    m->d.layer_is_local = nullptr;
-    if (m->d.n_kv_heads == 0) m->d.n_kv_heads = H;
-    const bool fp8 = d->compute_dtype == SGPT_FP8W || d->compute_dtype == SGPT_FP8M;
-    const bool f16 = d->compute_dtype == SGPT_F16;
-    const bool bf = d->compute_dtype == SGPT_BF16 || f16;          // 16-bit packed weights
-    const size_t esz = fp8 ? 1 : (bf ? 2 : 4);
-    sgpt_status st = SGPT_OK;
-    // SGPT_F16 range audit: stats[0] = max|matmul weight|, [1] = max|LayerNorm gamma|, [2] = max|LayerNorm beta|
-    unsigned* stats = nullptr;
-    if (f16) {
-        if (hipMalloc((void**)&stats, 16) != hipSuccess) { delete m; return fail(c, SGPT_ERR_OOM, "hipMalloc failed"); }
-        (void)hipMemsetAsync(stats, 0, 16, 0);
-    }
+    unsigned* stats;           // SGPT_F16 range audit: [0] = max|matmul weight|, [1] = max|LayerNorm gamma|, [2] = max|LayerNorm beta|
+    bool fp8, f16, bf;         // bf: 16-bit packed weights (bf16 or f16)
+    size_t esz; int dm, ffn, H, dh; sgpt_status st;
 
-    auto find = [&](const std::string& name, int64_t numel) -> const float* {
+    const float* find(const std::string& name, int64_t numel) {
         auto it = byname.find(name);
         if (it == byname.end()) { st = fail(c, SGPT_ERR_MISSING, "missing weight tensor: " + name); return nullptr; }
         if (it->second->numel != numel) { st = fail(c, SGPT_ERR_INVALID, "wrong numel for " + name); return nullptr; }
         return it->second->ptr;
-    };
-    auto dalloc = [&](size_t bytes) -> void* {
+    }
+    void* dalloc(size_t bytes) {
         void* p = nullptr;
         if (hipMalloc(&p, bytes) != hipSuccess) { st = fail(c, SGPT_ERR_OOM, "hipMalloc weights failed"); return nullptr; }
         m->allocs.push_back(p);
         return p;
-    };
-    auto copy_f32 = [&](const std::string& name, int64_t numel) -> float* {
+    }
+    float* copy_f32(const std::string& name, int64_t numel) {
         const float* src = find(name, numel);
         if (!src) return nullptr;
         float* dst = (float*)dalloc(numel * 4);
         if (!dst) return nullptr;
         if (hipMemcpyAsync(dst, src, numel * 4, hipMemcpyDeviceToDevice, 0) != hipSuccess) st = fail(c, SGPT_ERR_HIP, "memcpy " + name);
         return dst;
-    };
+    }
     // LayerNorm parameters whose output is rounded to the 16-bit GEMM operand format
-    auto copy_ln = [&](const std::string& base, float** g, float** b) {
+    void copy_ln(const std::string& base, float** g, float** b) {
         *g = copy_f32(base + ".weight", dm);
         *b = copy_f32(base + ".bias", dm);
         if (f16 && *g && *b) { launch_absmax(*g, dm, stats + 1, 0); launch_absmax(*b, dm, stats + 2, 0); }
-    };
+    }
     // matmul weight [rows, cols] -> packed dtype at row `row_off` of dst (fp8: codes + one scale per row)
-    auto pack_rows = [&](const float* src, int64_t rows, int64_t cols, void* dst, int64_t row_off, float* scale) {
+    void pack_rows(const float* src, int64_t rows, int64_t cols, void* dst, int64_t row_off, float* scale) {
         const int64_t off = row_off * cols, numel = rows * cols;
         if (fp8) launch_fp8_quant_rows(src, rows, cols, (uint8_t*)dst + off, scale + row_off, 0);
         else if (bf) {
@@ -111,181 +76,195 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
         }
         else if (hipMemcpyAsync((float*)dst + off, src, numel * 4, hipMemcpyDeviceToDevice, 0) != hipSuccess)
             st = fail(c, SGPT_ERR_HIP, "memcpy weight");
-    };
-    auto pack_w = [&](const std::string& name, int64_t rows, int64_t cols, void* dst, int64_t row_off, float* scale) {
+    }
+    void pack_w(const std::string& name, int64_t rows, int64_t cols, void* dst, int64_t row_off, float* scale) {
         const float* src = find(name, rows * cols);
         if (src) pack_rows(src, rows, cols, dst, row_off, scale);
-    };
+    }
+    // the split-precision copy [W_hi | W_hi | W_lo] of a whole matrix
+    void pack3(const std::string& name, int64_t rows, int64_t cols, void* dst3) {
+        const float* src = find(name, rows * cols);
+        if (src) launch_pack_split_rows(src, rows, cols, dst3, f16 ? DT_F16 : DT_BF16, 0);
+    }
+    // the four packed matrices of a block: w_qkv [qkv_rows, d], w_o [d, d], w_fc [fc_rows, d], w_proj [d, ffn]
+    void alloc_w(LayerW& l, size_t qkv_rows, size_t fc_rows) {
+        l.w_qkv = dalloc(qkv_rows * dm * esz); l.w_o = dalloc((size_t)dm * dm * esz);
+        l.w_fc = dalloc(fc_rows * dm * esz); l.w_proj = dalloc((size_t)dm * ffn * esz);
+    }
+    // What follows a family's own embedding tensors, in the order the tensors have always been read: the LM head, the final norm the
+    // family's row names, the zero bias vector.
+    void head() {
+        const Family& F = family(d->arch);
+        // LM head of the cross-encoder scorer (crossencoder/beir/sgptce.py): GPT-Neo / BLOOM tie it to the embedding
+        // (HF tie_word_embeddings), GPT-J carries lm_head.weight / lm_head.bias
+        m->lm_w = m->wte;
+        if (byname.count("lm_head.weight")) {
+            m->lm_w = copy_f32("lm_head.weight", (int64_t)d->vocab * dm);
+            if (byname.count("lm_head.bias")) m->lm_b = copy_f32("lm_head.bias", d->vocab);
+        }
+        if (F.lnf) m->lnf_g = copy_f32(std::string(F.lnf) + ".weight", dm);
+        if (F.lnf && F.norm_kind == 0) m->lnf_b = copy_f32(std::string(F.lnf) + ".bias", dm);       // (an RMSNorm is a gain, no bias)
+        m->zero_bias = (float*)dalloc((size_t)(ffn > dm ? ffn : dm) * 4);
+        if (m->zero_bias && hipMemsetAsync(m->zero_bias, 0, (size_t)(ffn > dm ? ffn : dm) * 4, 0) != hipSuccess)
+            st = fail(c, SGPT_ERR_HIP, "memset zero_bias");
+        m->L.resize(d->n_layers);
+    }
+};
 
-    m->wte = copy_f32(llama ? "embed_tokens.weight" : (bert ? "embeddings.word_embeddings.weight" : (bloom ? "word_embeddings.weight" : "wte.weight")),
-                      (int64_t)d->vocab * dm);
-    if (llama) {        // no position table: half-split rotary on q / k (tables from the host, include/sgpt_hip.h)
-        m->rot_sin = copy_f32("rotary.sin", (int64_t)d->max_pos * (dh / 2));
-        m->rot_cos = copy_f32("rotary.cos", (int64_t)d->max_pos * (dh / 2));
-    } else if (bert) {
-        // position table with token_type_embeddings[0] already added by the caller (single-segment inputs; include/sgpt_hip.h)
-        m->wpe = copy_f32("embeddings.position_embeddings.weight", (int64_t)d->max_pos * dm);
-        copy_ln("embeddings.LayerNorm", &m->emb_ln_g, &m->emb_ln_b);
-    } else if (gptj) {
-        m->rot_sin = copy_f32("rotary.sin", (int64_t)d->max_pos * (d->rotary_dim / 2));
-        m->rot_cos = copy_f32("rotary.cos", (int64_t)d->max_pos * (d->rotary_dim / 2));
+// GPT-Neo / GPT-J / BLOOM.  HF state-dict names:
+//   GPT-Neo h.N.attn.attention.{q,k,v,out}_proj / mlp.c_fc / mlp.c_proj          (HF:gpt_neo:84-87,302-303)
+//   GPT-J   h.N.attn.{q,k,v,out}_proj (no biases) / mlp.fc_in / mlp.fc_out          (HF:gptj:98-101,368-369)
+//   BLOOM   h.N.self_attention.{query_key_value,dense} / mlp.dense_h_to_4h / mlp.dense_4h_to_h,
+//           input_layernorm / post_attention_layernorm                               (HF:bloom:197-198,320-322,351-354)
+void load_decoder(Loader& L) {
+    sgpt_model* m = L.m; const sgpt_model_desc* d = L.d;
+    const int dm = L.dm, ffn = L.ffn, H = L.H, dh = L.dh;
+    const bool gptj = d->arch == SGPT_ARCH_GPTJ, bloom = d->arch == SGPT_ARCH_BLOOM, fp8 = L.fp8;
+    if (gptj) {
+        m->rot_sin = L.copy_f32("rotary.sin", (int64_t)d->max_pos * (d->rotary_dim / 2));
+        m->rot_cos = L.copy_f32("rotary.cos", (int64_t)d->max_pos * (d->rotary_dim / 2));
     } else if (bloom) {
-        m->emb_ln_g = copy_f32("word_embeddings_layernorm.weight", dm);
-        m->emb_ln_b = copy_f32("word_embeddings_layernorm.bias", dm);
-        m->alibi = copy_f32("alibi.slopes", H);
+        m->emb_ln_g = L.copy_f32("word_embeddings_layernorm.weight", dm);
+        m->emb_ln_b = L.copy_f32("word_embeddings_layernorm.bias", dm);
+        m->alibi = L.copy_f32("alibi.slopes", H);
     } else {
-        m->wpe = copy_f32("wpe.weight", (int64_t)d->max_pos * dm);
+        m->wpe = L.copy_f32("wpe.weight", (int64_t)d->max_pos * dm);
     }
-    // LM head of the cross-encoder scorer (crossencoder/beir/sgptce.py): GPT-Neo / BLOOM tie it to the embedding
-    // (HF tie_word_embeddings), GPT-J carries lm_head.weight / lm_head.bias
-    m->lm_w = m->wte;
-    if (byname.count("lm_head.weight")) {
-        m->lm_w = copy_f32("lm_head.weight", (int64_t)d->vocab * dm);
-        if (byname.count("lm_head.bias")) m->lm_b = copy_f32("lm_head.bias", d->vocab);
-    }
-    if (llama) {        // final RMSNorm: a gain, no bias
-        m->lnf_g = copy_f32("norm.weight", dm);
-    } else if (!bert) { // (BERT has no final LayerNorm: every block ends in one)
-        m->lnf_g = copy_f32("ln_f.weight", dm);
-        m->lnf_b = copy_f32("ln_f.bias", dm);
-    }
-    m->zero_bias = (float*)dalloc((size_t)(ffn > dm ? ffn : dm) * 4);
-    if (m->zero_bias && hipMemsetAsync(m->zero_bias, 0, (size_t)(ffn > dm ? ffn : dm) * 4, 0) != hipSuccess)
-        st = fail(c, SGPT_ERR_HIP, "memset zero_bias");
-    m->L.resize(d->n_layers);
-    // HF state-dict names
-    //   GPT-Neo h.N.attn.attention.{q,k,v,out}_proj / mlp.c_fc / mlp.c_proj          (HF:gpt_neo:84-87,302-303)
-    //   GPT-J   h.N.attn.{q,k,v,out}_proj (no biases) / mlp.fc_in / mlp.fc_out          (HF:gptj:98-101,368-369)
-    //   BLOOM   h.N.self_attention.{query_key_value,dense} / mlp.dense_h_to_4h / mlp.dense_4h_to_h,
-    //           input_layernorm / post_attention_layernorm                               (HF:bloom:197-198,320-322,351-354)
+    L.head();
     const std::string attn = gptj ? "attn." : "attn.attention.";
     const std::string fc1 = bloom ? "mlp.dense_h_to_4h" : (gptj ? "mlp.fc_in" : "mlp.c_fc");
     const std::string fc2 = bloom ? "mlp.dense_4h_to_h" : (gptj ? "mlp.fc_out" : "mlp.c_proj");
     const std::string ln1 = bloom ? "input_layernorm" : "ln_1", ln2 = bloom ? "post_attention_layernorm" : "ln_2";
-    float* stage = nullptr;   // BLOOM: fp32 staging for the de-interleaved fused QKV weight
-    if (bloom) stage = (float*)dalloc((size_t)3 * dm * dm * 4);
-    // BERT  encoder.layer.N.attention.self.{query,key,value} / attention.output.{dense,LayerNorm} / intermediate.dense /
-    //       output.{dense,LayerNorm}; `pooler.*` is not read                         (HF:bert/modeling_bert.py BertLayer)
-    // ln1 = the LayerNorm behind the attention (attention.output.LayerNorm), ln2 = the one behind the MLP (output.LayerNorm)
-    for (int i = 0; bert && i < d->n_layers && st == SGPT_OK; ++i) {
-        const std::string p = "encoder.layer." + std::to_string(i) + ".";
-        LayerW& l = m->L[i];
-        l.is_local = 0;
-        copy_ln(p + "attention.output.LayerNorm", &l.ln1_g, &l.ln1_b);
-        copy_ln(p + "output.LayerNorm", &l.ln2_g, &l.ln2_b);
-        l.b_o = copy_f32(p + "attention.output.dense.bias", dm);
-        l.b_fc = copy_f32(p + "intermediate.dense.bias", ffn);
-        l.b_proj = copy_f32(p + "output.dense.bias", dm);
-        l.b_qkv = (float*)dalloc((size_t)3 * dm * 4);
-        l.w_qkv = dalloc((size_t)3 * dm * dm * esz);
-        l.w_o = dalloc((size_t)dm * dm * esz);
-        l.w_fc = dalloc((size_t)ffn * dm * esz);
-        l.w_proj = dalloc((size_t)dm * ffn * esz);
-        if (st != SGPT_OK) break;
-        const char* qkv[3] = {"query", "key", "value"};
-        for (int j = 0; j < 3 && st == SGPT_OK; ++j) {          // fused [q rows | k rows | v rows], biases alike
-            pack_w(p + "attention.self." + qkv[j] + ".weight", dm, dm, l.w_qkv, (int64_t)j * dm, nullptr);
-            const float* bj = find(p + "attention.self." + qkv[j] + ".bias", dm);
-            if (bj && hipMemcpyAsync(l.b_qkv + (size_t)j * dm, bj, (size_t)dm * 4, hipMemcpyDeviceToDevice, 0) != hipSuccess)
-                st = fail(c, SGPT_ERR_HIP, "memcpy qkv bias");
-        }
-        pack_w(p + "attention.output.dense.weight", dm, dm, l.w_o, 0, nullptr);
-        pack_w(p + "intermediate.dense.weight", ffn, dm, l.w_fc, 0, nullptr);
-        pack_w(p + "output.dense.weight", dm, ffn, l.w_proj, 0, nullptr);
-    }
-    // LLAMA layers.N.input_layernorm / self_attn.{qkv_proj (q | k | v rows fused by the caller), o_proj} / post_attention_layernorm /
-    //       mlp.{gate_up_proj (gate rows, then up rows), down_proj}; no biases      (HF:llama/modeling_llama.py LlamaDecoderLayer)
-    // The RMSNorm gains carry no load-time bound (the f16 stores of rmsnorm_kernel are range-tracked at run time): shifts stay 0.
-    for (int i = 0; llama && i < d->n_layers && st == SGPT_OK; ++i) {
-        const std::string p = "layers." + std::to_string(i) + ".";
-        const int64_t dkv = (int64_t)m->d.n_kv_heads * dh;
-        LayerW& l = m->L[i];
-        l.is_local = d->layer_is_local ? d->layer_is_local[i] : (d->window > 0 ? 1 : 0);
-        l.ln1_g = copy_f32(p + "input_layernorm.weight", dm);
-        l.ln2_g = copy_f32(p + "post_attention_layernorm.weight", dm);
-        l.ln1_b = l.ln2_b = nullptr;
-        l.b_o = l.b_proj = m->zero_bias;       // the residual epilogue reads a bias vector: zeros
-        l.b_fc = nullptr;
-        l.w_qkv = dalloc((size_t)(dm + 2 * dkv) * dm * esz);
-        l.w_o = dalloc((size_t)dm * dm * esz);
-        l.w_fc = dalloc((size_t)2 * ffn * dm * esz);
-        l.w_proj = dalloc((size_t)dm * ffn * esz);
-        if (st != SGPT_OK) break;
-        pack_w(p + "self_attn.qkv_proj.weight", dm + 2 * dkv, dm, l.w_qkv, 0, nullptr);
-        pack_w(p + "self_attn.o_proj.weight", dm, dm, l.w_o, 0, nullptr);
-        pack_w(p + "mlp.gate_up_proj.weight", (int64_t)2 * ffn, dm, l.w_fc, 0, nullptr);
-        pack_w(p + "mlp.down_proj.weight", dm, ffn, l.w_proj, 0, nullptr);
-    }
-    for (int i = 0; !bert && !llama && i < d->n_layers && st == SGPT_OK; ++i) {
-        const std::string p = "h." + std::to_string(i) + ".";
+    float* stage = bloom ? (float*)L.dalloc((size_t)3 * dm * dm * 4) : nullptr;   // BLOOM: fp32 staging for the de-interleaved fused QKV weight
+    const bool split_all = m->d.split_weights != 0, split = m->d.qk_split != 0 || split_all;
+    const int dt16 = L.f16 ? DT_F16 : DT_BF16;
+    for (int i = 0; i < d->n_layers && L.st == SGPT_OK; ++i) {
+        const std::string p = family(d->arch).prefix + std::to_string(i) + ".";
         LayerW& l = m->L[i];
         l.is_local = (gptj || bloom) ? 0 : (d->layer_is_local ? d->layer_is_local[i] : (i & 1));
-        copy_ln(p + ln1, &l.ln1_g, &l.ln1_b);
-        if (!gptj) copy_ln(p + ln2, &l.ln2_g, &l.ln2_b);
+        L.copy_ln(p + ln1, &l.ln1_g, &l.ln1_b);
+        if (!gptj) L.copy_ln(p + ln2, &l.ln2_g, &l.ln2_b);
         else l.ln2_g = l.ln2_b = nullptr;
-        if (gptj) l.b_o = m->zero_bias;
-        else l.b_o = copy_f32(p + (bloom ? std::string("self_attention.dense.bias") : attn + "out_proj.bias"), dm);
-        l.b_fc = copy_f32(p + fc1 + ".bias", ffn);
-        l.b_proj = copy_f32(p + fc2 + ".bias", dm);
-        l.w_qkv = dalloc((size_t)3 * dm * dm * esz);
-        l.w_o = dalloc((size_t)dm * dm * esz);
-        l.w_fc = dalloc((size_t)ffn * dm * esz);
-        l.w_proj = dalloc((size_t)dm * ffn * esz);
+        const std::string wo = p + (bloom ? std::string("self_attention.dense") : attn + "out_proj");
+        l.b_o = gptj ? m->zero_bias : L.copy_f32(wo + ".bias", dm);
+        l.b_fc = L.copy_f32(p + fc1 + ".bias", ffn);
+        l.b_proj = L.copy_f32(p + fc2 + ".bias", dm);
+        L.alloc_w(l, (size_t)3 * dm, ffn);
         if (fp8) {
-            l.s_qkv = (float*)dalloc((size_t)3 * dm * 4); l.s_o = (float*)dalloc((size_t)dm * 4);
-            l.s_fc = (float*)dalloc((size_t)ffn * 4); l.s_proj = (float*)dalloc((size_t)dm * 4);
+            l.s_qkv = (float*)L.dalloc((size_t)3 * dm * 4); l.s_o = (float*)L.dalloc((size_t)dm * 4);
+            l.s_fc = (float*)L.dalloc((size_t)ffn * 4); l.s_proj = (float*)L.dalloc((size_t)dm * 4);
         }
-        if (st != SGPT_OK) break;
-        const bool split_all = m->d.split_weights != 0;
-        const bool split = m->d.qk_split != 0 || split_all;
-        if (split) { l.w_qkv3 = dalloc((size_t)(split_all ? 3 : 2) * dm * 3 * dm * 2); if (!l.w_qkv3) break; }
+        if (L.st != SGPT_OK) break;
+        if (split) { l.w_qkv3 = L.dalloc((size_t)(split_all ? 3 : 2) * dm * 3 * dm * 2); if (!l.w_qkv3) break; }
         if (split_all) {
-            l.w_o3 = dalloc((size_t)dm * 3 * dm * 2); l.w_fc3 = dalloc((size_t)ffn * 3 * dm * 2); l.w_proj3 = dalloc((size_t)dm * 3 * ffn * 2);
+            l.w_o3 = L.dalloc((size_t)dm * 3 * dm * 2); l.w_fc3 = L.dalloc((size_t)ffn * 3 * dm * 2); l.w_proj3 = L.dalloc((size_t)dm * 3 * ffn * 2);
             if (!l.w_o3 || !l.w_fc3 || !l.w_proj3) break;
         }
-        const int dt16 = f16 ? DT_F16 : DT_BF16;
-        auto pack3 = [&](const std::string& name, int64_t rows, int64_t cols, void* dst3) {
-            const float* src = find(name, rows * cols);
-            if (src) launch_pack_split_rows(src, rows, cols, dst3, dt16, 0);
-        };
         if (bloom) {
-            const float* wq = find(p + "self_attention.query_key_value.weight", (int64_t)3 * dm * dm);
-            const float* bq = find(p + "self_attention.query_key_value.bias", (int64_t)3 * dm);
-            l.b_qkv = (float*)dalloc((size_t)3 * dm * 4);
+            const float* wq = L.find(p + "self_attention.query_key_value.weight", (int64_t)3 * dm * dm);
+            const float* bq = L.find(p + "self_attention.query_key_value.bias", (int64_t)3 * dm);
+            l.b_qkv = (float*)L.dalloc((size_t)3 * dm * 4);
             if (!wq || !bq || !l.b_qkv || !stage) break;
             launch_qkv_deinterleave(wq, stage, H, dh, dm, 0);          // rows [h,3,dh] -> [q | k | v]
             launch_qkv_deinterleave(bq, l.b_qkv, H, dh, 1, 0);
-            pack_rows(stage, (int64_t)3 * dm, dm, l.w_qkv, 0, l.s_qkv);
+            L.pack_rows(stage, (int64_t)3 * dm, dm, l.w_qkv, 0, l.s_qkv);
             if (split) launch_pack_split_rows(stage, (long)(split_all ? 3 : 2) * dm, dm, l.w_qkv3, dt16, 0);      // q and k (and v) rows
-            pack_w(p + "self_attention.dense.weight", dm, dm, l.w_o, 0, l.s_o);
-            if (split_all) pack3(p + "self_attention.dense.weight", dm, dm, l.w_o3);
         } else {
-            if (split) {
-                const float* wq = find(p + attn + "q_proj.weight", (int64_t)dm * dm);
-                const float* wk = find(p + attn + "k_proj.weight", (int64_t)dm * dm);
-                if (!wq || !wk) break;
-                launch_pack_split_rows(wq, dm, dm, l.w_qkv3, dt16, 0);
-                launch_pack_split_rows(wk, dm, dm, (bf16_t*)l.w_qkv3 + (size_t)dm * 3 * dm, dt16, 0);
-                if (split_all) pack3(p + attn + "v_proj.weight", dm, dm, (bf16_t*)l.w_qkv3 + (size_t)2 * dm * 3 * dm);
-            }
-            pack_w(p + attn + "q_proj.weight", dm, dm, l.w_qkv, 0, l.s_qkv);
-            pack_w(p + attn + "k_proj.weight", dm, dm, l.w_qkv, dm, l.s_qkv);
-            pack_w(p + attn + "v_proj.weight", dm, dm, l.w_qkv, (int64_t)2 * dm, l.s_qkv);
-            pack_w(p + attn + "out_proj.weight", dm, dm, l.w_o, 0, l.s_o);
-            if (split_all) pack3(p + attn + "out_proj.weight", dm, dm, l.w_o3);
+            if (split) L.pack3(p + attn + "q_proj.weight", dm, dm, l.w_qkv3);
+            if (split) L.pack3(p + attn + "k_proj.weight", dm, dm, (bf16_t*)l.w_qkv3 + (size_t)dm * 3 * dm);
+            if (L.st != SGPT_OK) break;
+            if (split_all) L.pack3(p + attn + "v_proj.weight", dm, dm, (bf16_t*)l.w_qkv3 + (size_t)2 * dm * 3 * dm);
+            L.pack_w(p + attn + "q_proj.weight", dm, dm, l.w_qkv, 0, l.s_qkv);
+            L.pack_w(p + attn + "k_proj.weight", dm, dm, l.w_qkv, dm, l.s_qkv);
+            L.pack_w(p + attn + "v_proj.weight", dm, dm, l.w_qkv, (int64_t)2 * dm, l.s_qkv);
         }
-        pack_w(p + fc1 + ".weight", ffn, dm, l.w_fc, 0, l.s_fc);
-        pack_w(p + fc2 + ".weight", dm, ffn, l.w_proj, 0, l.s_proj);
-        if (split_all) { pack3(p + fc1 + ".weight", ffn, dm, l.w_fc3); pack3(p + fc2 + ".weight", dm, ffn, l.w_proj3); }
+        L.pack_w(wo + ".weight", dm, dm, l.w_o, 0, l.s_o);
+        if (split_all) L.pack3(wo + ".weight", dm, dm, l.w_o3);
+        L.pack_w(p + fc1 + ".weight", ffn, dm, l.w_fc, 0, l.s_fc);
+        L.pack_w(p + fc2 + ".weight", dm, ffn, l.w_proj, 0, l.s_proj);
+        if (split_all) { L.pack3(p + fc1 + ".weight", ffn, dm, l.w_fc3); L.pack3(p + fc2 + ".weight", dm, ffn, l.w_proj3); }
     }
-    if (fp8 && st == SGPT_OK) {
-        m->dq[0] = dalloc((size_t)3 * dm * dm * 2); m->dq[1] = dalloc((size_t)dm * dm * 2);
-        m->dq[2] = dalloc((size_t)ffn * dm * 2); m->dq[3] = dalloc((size_t)dm * ffn * 2);
+}
+
+// BERT  encoder.layer.N.attention.self.{query,key,value} / attention.output.{dense,LayerNorm} / intermediate.dense /
+//       output.{dense,LayerNorm}; `pooler.*` is not read                         (HF:bert/modeling_bert.py BertLayer)
+// ln1 = the LayerNorm behind the attention (attention.output.LayerNorm), ln2 = the one behind the MLP (output.LayerNorm)
+void load_bert(Loader& L) {
+    sgpt_model* m = L.m; const sgpt_model_desc* d = L.d;
+    const int dm = L.dm, ffn = L.ffn;
+    // position table with token_type_embeddings[0] already added by the caller (single-segment inputs; include/sgpt_hip.h)
+    m->wpe = L.copy_f32("embeddings.position_embeddings.weight", (int64_t)d->max_pos * dm);
+    L.copy_ln("embeddings.LayerNorm", &m->emb_ln_g, &m->emb_ln_b);
+    L.head();
+    for (int i = 0; i < d->n_layers && L.st == SGPT_OK; ++i) {
+        const std::string p = family(d->arch).prefix + std::to_string(i) + ".";
+        LayerW& l = m->L[i];
+        l.is_local = 0;
+        L.copy_ln(p + "attention.output.LayerNorm", &l.ln1_g, &l.ln1_b);
+        L.copy_ln(p + "output.LayerNorm", &l.ln2_g, &l.ln2_b);
+        l.b_o = L.copy_f32(p + "attention.output.dense.bias", dm);
+        l.b_fc = L.copy_f32(p + "intermediate.dense.bias", ffn);
+        l.b_proj = L.copy_f32(p + "output.dense.bias", dm);
+        l.b_qkv = (float*)L.dalloc((size_t)3 * dm * 4);
+        L.alloc_w(l, (size_t)3 * dm, ffn);
+        if (L.st != SGPT_OK) break;
+        const char* qkv[3] = {"query", "key", "value"};
+        for (int j = 0; j < 3 && L.st == SGPT_OK; ++j) {          // fused [q rows | k rows | v rows], biases alike
+            L.pack_w(p + "attention.self." + qkv[j] + ".weight", dm, dm, l.w_qkv, (int64_t)j * dm, nullptr);
+            const float* bj = L.find(p + "attention.self." + qkv[j] + ".bias", dm);
+            if (bj && hipMemcpyAsync(l.b_qkv + (size_t)j * dm, bj, (size_t)dm * 4, hipMemcpyDeviceToDevice, 0) != hipSuccess)
+                L.st = fail(L.c, SGPT_ERR_HIP, "memcpy qkv bias");
+        }
+        L.pack_w(p + "attention.output.dense.weight", dm, dm, l.w_o, 0, nullptr);
+        L.pack_w(p + "intermediate.dense.weight", ffn, dm, l.w_fc, 0, nullptr);
+        L.pack_w(p + "output.dense.weight", dm, ffn, l.w_proj, 0, nullptr);
     }
-    if (d->compute_dtype == SGPT_FP8M && st == SGPT_OK) {
+}
+
+// LLAMA layers.N.input_layernorm / self_attn.{qkv_proj (q | k | v rows fused by the caller), o_proj} / post_attention_layernorm /
+//       mlp.{gate_up_proj (gate rows, then up rows), down_proj}; no biases      (HF:llama/modeling_llama.py LlamaDecoderLayer)
+// The RMSNorm gains carry no load-time bound (the f16 stores of rmsnorm_kernel are range-tracked at run time): shifts stay 0.
+void load_llama(Loader& L) {
+    sgpt_model* m = L.m; const sgpt_model_desc* d = L.d;
+    const int dm = L.dm, ffn = L.ffn; const int64_t dkv = (int64_t)m->d.n_kv_heads * L.dh;
+    // no position table: half-split rotary on q / k (tables from the host, include/sgpt_hip.h)
+    m->rot_sin = L.copy_f32("rotary.sin", (int64_t)d->max_pos * (L.dh / 2));
+    m->rot_cos = L.copy_f32("rotary.cos", (int64_t)d->max_pos * (L.dh / 2));
+    L.head();
+    for (int i = 0; i < d->n_layers && L.st == SGPT_OK; ++i) {
+        const std::string p = family(d->arch).prefix + std::to_string(i) + ".";
+        LayerW& l = m->L[i];
+        l.is_local = d->layer_is_local ? d->layer_is_local[i] : (d->window > 0 ? 1 : 0);
+        l.ln1_g = L.copy_f32(p + "input_layernorm.weight", dm);
+        l.ln2_g = L.copy_f32(p + "post_attention_layernorm.weight", dm);
+        l.ln1_b = l.ln2_b = l.b_fc = nullptr;
+        l.b_o = l.b_proj = m->zero_bias;       // the residual epilogue reads a bias vector: zeros
+        L.alloc_w(l, dm + 2 * dkv, (size_t)2 * ffn);
+        if (L.st != SGPT_OK) break;
+        L.pack_w(p + "self_attn.qkv_proj.weight", dm + 2 * dkv, dm, l.w_qkv, 0, nullptr);
+        L.pack_w(p + "self_attn.o_proj.weight", dm, dm, l.w_o, 0, nullptr);
+        L.pack_w(p + "mlp.gate_up_proj.weight", (int64_t)2 * ffn, dm, l.w_fc, 0, nullptr);
+        L.pack_w(p + "mlp.down_proj.weight", dm, ffn, l.w_proj, 0, nullptr);
+    }
+}
+
+// What every model has behind its layers: fp8 de-quantisation scratch, FP8M activation scales, range shifts, the precision plan, the
+// crest and range words.
+void load_tail(Loader& L) {
+    sgpt_model* m = L.m; const sgpt_model_desc* d = L.d;
+    const int dm = L.dm, ffn = L.ffn;
+    auto zeroed = [&](size_t bytes) {
+        void* p = L.dalloc(bytes);
+        if (p && hipMemsetAsync(p, 0, bytes, 0) != hipSuccess) L.st = fail(L.c, SGPT_ERR_HIP, "memset");
+        return (unsigned*)p;
+    };
+    if (L.fp8 && L.st == SGPT_OK) {
+        m->dq[0] = L.dalloc((size_t)3 * dm * dm * 2); m->dq[1] = L.dalloc((size_t)dm * dm * 2);
+        m->dq[2] = L.dalloc((size_t)ffn * dm * 2); m->dq[3] = L.dalloc((size_t)dm * ffn * 2);
+    }
+    if (d->compute_dtype == SGPT_FP8M && L.st == SGPT_OK) {
         m->act_scale.assign(2 * (size_t)d->n_layers, 0.0f);   // 0 = not calibrated
-        m->h_amax = (unsigned*)dalloc((size_t)d->n_layers * 8);
-        if (m->h_amax && hipMemsetAsync(m->h_amax, 0, (size_t)d->n_layers * 8, 0) != hipSuccess) st = fail(c, SGPT_ERR_HIP, "memset");
+        m->h_amax = zeroed((size_t)d->n_layers * 8);
     }
     m->shift.assign((size_t)d->n_layers * RS_N, 0);
     m->ln_floor.assign((size_t)d->n_layers, 0);
@@ -294,41 +273,63 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
     m->qkv3_rows = d->split_weights != 0 ? 3 : (d->qk_split != 0 ? 2 : 0);
     if (d->qk_split != 0)              // the round-3 switch: the Q / K projection of every block contracts over hi + lo pairs
         for (int i = 0; i < d->n_layers; ++i) m->prec[(size_t)i * PC_N + PC_LN1] = 1;
-    if (st == SGPT_OK && bf && !fp8) {
-        m->crest_dev = (unsigned*)dalloc((size_t)d->n_layers * RS_N * 4);
-        if (m->crest_dev && hipMemsetAsync(m->crest_dev, 0, (size_t)d->n_layers * RS_N * 4, 0) != hipSuccess) st = fail(c, SGPT_ERR_HIP, "memset");
+    if (L.st == SGPT_OK && L.bf && !L.fp8) m->crest_dev = zeroed((size_t)d->n_layers * RS_N * 4);
+    if (L.st == SGPT_OK) m->range_dev = zeroed((size_t)(1 + d->n_layers * RS_N) * 4);
+}
+
+// SGPT_F16, after the weights are packed.  f16 has 5 exponent bits.  A LayerNorm output is bounded by max|gamma| * sqrt(d) + max|beta|
+// (|x_hat| <= sqrt(d-1)): when that bound can leave the format the LayerNorm outputs are stored under a power-of-two down-shift that
+// the consuming GEMMs undo on their fp32 accumulators (exact; sgpt_model.shift).  Activations behind the GEMMs are range-checked on the
+// device at run time (RangeTrack in the store epilogues -> sgpt_model_range_check / sgpt_model_range_adapt).  Only a weight outside
+// the format is refused.
+void audit_f16_range(Loader& L) {
+    unsigned h[4] = {0, 0, 0, 0};
+    if (L.st == SGPT_OK && hipMemcpy(h, L.stats, 12, hipMemcpyDeviceToHost) != hipSuccess) L.st = fail(L.c, SGPT_ERR_HIP, "range audit");
+    (void)hipFree(L.stats);
+    float wmax, gmax, bmax;
+    memcpy(&wmax, &h[0], 4); memcpy(&gmax, &h[1], 4); memcpy(&bmax, &h[2], 4);
+    const float bound = gmax * sqrtf((float)L.dm) + bmax;
+    if (L.st == SGPT_OK && (!(wmax < 65504.f) || !std::isfinite(bound)))
+        L.st = fail(L.c, SGPT_ERR_RANGE, "SGPT_F16: a matmul weight exceeds the f16 range (or a LayerNorm parameter is not finite); load with SGPT_BF16");
+    // (a family without range shifts keeps 0: its norm kernels carry a run-time range tracker instead of relying on this bound)
+    if (L.st != SGPT_OK || bound < 32768.f || !family(L.d->arch).shifts) return;
+    int k = (int)std::ceil(std::log2(bound / 16384.f));
+    k = k < 1 ? 1 : k;
+    if (k > RS_MAX_SHIFT) L.st = fail(L.c, SGPT_ERR_RANGE, "SGPT_F16: LayerNorm parameters beyond any usable range shift; load with SGPT_BF16");
+    for (int i = 0; i < L.d->n_layers && L.st == SGPT_OK; ++i) {
+        L.m->shift[(size_t)i * RS_N + RS_LN1] = L.m->shift[(size_t)i * RS_N + RS_LN2] = k;
+        L.m->ln_floor[i] = k;
     }
-    if (st == SGPT_OK) {
-        m->range_dev = (unsigned*)dalloc((size_t)(1 + d->n_layers * RS_N) * 4);
-        if (m->range_dev && hipMemsetAsync(m->range_dev, 0, (size_t)(1 + d->n_layers * RS_N) * 4, 0) != hipSuccess) st = fail(c, SGPT_ERR_HIP, "memset");
-    }
-    if (st == SGPT_OK && hipDeviceSynchronize() != hipSuccess) st = fail(c, SGPT_ERR_HIP, "sync after weight pack");
-    if (f16) {
-        // f16 has 5 exponent bits.  A LayerNorm output is bounded by max|gamma| * sqrt(d) + max|beta| (|x_hat| <= sqrt(d-1)):
-        // when that bound can leave the format the LayerNorm outputs are stored under a power-of-two down-shift that the
-        // consuming GEMMs undo on their fp32 accumulators (exact; shift[] above).  Activations behind the GEMMs are
-        // range-checked on the device at run time (RangeTrack in the store epilogues -> sgpt_model_range_check /
-        // sgpt_model_range_adapt).  Only a weight outside the format is refused.
-        unsigned h[4] = {0, 0, 0, 0};
-        if (st == SGPT_OK && hipMemcpy(h, stats, 12, hipMemcpyDeviceToHost) != hipSuccess) st = fail(c, SGPT_ERR_HIP, "range audit");
-        (void)hipFree(stats);
-        float wmax, gmax, bmax;
-        memcpy(&wmax, &h[0], 4); memcpy(&gmax, &h[1], 4); memcpy(&bmax, &h[2], 4);
-        const float bound = gmax * sqrtf((float)dm) + bmax;
-        if (st == SGPT_OK && (!(wmax < 65504.f) || !std::isfinite(bound)))
-            st = fail(c, SGPT_ERR_RANGE, "SGPT_F16: a matmul weight exceeds the f16 range (or a LayerNorm parameter is not finite); load with SGPT_BF16");
-        // (BERT: shifts stay 0 -- its write-back LayerNorm carries a run-time range tracker instead of relying on this bound)
-        if (st == SGPT_OK && !(bound < 32768.f) && !bert && !llama) {
-            int k = (int)std::ceil(std::log2(bound / 16384.f));
-            k = k < 1 ? 1 : k;
-            if (k > RS_MAX_SHIFT) st = fail(c, SGPT_ERR_RANGE, "SGPT_F16: LayerNorm parameters beyond any usable range shift; load with SGPT_BF16");
-            for (int i = 0; i < d->n_layers && st == SGPT_OK; ++i) {
-                m->shift[(size_t)i * RS_N + RS_LN1] = m->shift[(size_t)i * RS_N + RS_LN2] = k;
-                m->ln_floor[i] = k;
-            }
-        }
-    }
-    if (st != SGPT_OK) { sgpt_model_free(m); return st; }
+}
+
+}  // namespace
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------------
+sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_tensor_view* tv, size_t nt, sgpt_model** out) {
+    if (!c || !d || !tv || !out) return SGPT_ERR_INVALID;
+    *out = nullptr;
+    HIPC(c, hipSetDevice(c->device));
+    if (sgpt_status st = check_desc(c, d)) return st;
+    const int cd = d->compute_dtype;
+    Loader L{};                // (st = SGPT_OK)
+    L.c = c; L.d = d; L.dm = d->d_model; L.ffn = d->d_ffn; L.H = d->n_heads; L.dh = L.dm / L.H;
+    L.fp8 = cd == SGPT_FP8W || cd == SGPT_FP8M; L.f16 = cd == SGPT_F16; L.bf = cd == SGPT_BF16 || L.f16;
+    L.esz = L.fp8 ? 1 : (L.bf ? 2 : 4);
+    if (L.f16 && hipMalloc((void**)&L.stats, 16) != hipSuccess) return fail(c, SGPT_ERR_OOM, "hipMalloc failed");
+    if (L.f16) (void)hipMemsetAsync(L.stats, 0, 16, 0);
+    for (size_t i = 0; i < nt; ++i) L.byname[tv[i].name] = &tv[i];
+    sgpt_model* m = L.m = new sgpt_model();
+    m->ctx = c; m->d = *d; m->d.layer_is_local = nullptr;
+    if (m->d.n_kv_heads == 0) m->d.n_kv_heads = L.H;
+    m->wte = L.copy_f32(family(d->arch).wte, (int64_t)d->vocab * L.dm);
+    // the family's own embedding tensors, L.head(), its layers
+    (d->arch == SGPT_ARCH_BERT ? load_bert : d->arch == SGPT_ARCH_LLAMA ? load_llama : load_decoder)(L);
+    load_tail(L);
+    if (L.st == SGPT_OK && hipDeviceSynchronize() != hipSuccess) L.st = fail(c, SGPT_ERR_HIP, "sync after weight pack");
+    if (L.f16) audit_f16_range(L);
+    if (L.st != SGPT_OK) { sgpt_model_free(m); return L.st; }
     *out = m;
     return SGPT_OK;
 }
@@ -424,7 +425,7 @@ sgpt_status sgpt_model_range_adapt(sgpt_model* m, int32_t* n_raised, void* strea
     sgpt_ctx* c = m->ctx;
     *n_raised = 0;
     if (m->d.compute_dtype != SGPT_F16) return fail(c, SGPT_ERR_INVALID, "sgpt_model_range_adapt applies to SGPT_F16 models");
-    if (m->d.arch == SGPT_ARCH_BERT || m->d.arch == SGPT_ARCH_LLAMA)
+    if (!family(m->d.arch).shifts)
         return fail(c, SGPT_ERR_INVALID, "sgpt_model_range_adapt: SGPT_ARCH_BERT / SGPT_ARCH_LLAMA run without range shifts; a flagged f16 model must be loaded with SGPT_BF16 or SGPT_F32");
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
@@ -468,7 +469,7 @@ sgpt_status sgpt_model_set_range_shifts(sgpt_model* m, const int32_t* shifts, in
     sgpt_ctx* c = m->ctx;
     if (m->d.compute_dtype != SGPT_F16 || !shifts || n != m->d.n_layers * RS_N)
         return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_range_shifts: SGPT_F16 models, n = 4 * n_layers");
-    if (m->d.arch == SGPT_ARCH_BERT || m->d.arch == SGPT_ARCH_LLAMA)
+    if (!family(m->d.arch).shifts)
         return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_range_shifts: SGPT_ARCH_BERT / SGPT_ARCH_LLAMA run without range shifts");
     for (int i = 0; i < n; ++i)
         if (shifts[i] < 0 || shifts[i] > RS_MAX_SHIFT) return fail(c, SGPT_ERR_INVALID, "range shifts must lie in [0, 40]");
@@ -505,7 +506,7 @@ sgpt_status sgpt_model_set_precision(sgpt_model* m, const int32_t* plan, int32_t
         if (cls == PC_LN2 && m->d.arch == SGPT_ARCH_GPTJ && v != 0 && plan[i - PC_LN2 + PC_LN1] == 0)
             return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision: GPT-J's MLP reads ln_1's output: a split fc1 needs a split LayerNorm-1 entry");
     }
-    if (any && (m->d.arch == SGPT_ARCH_BERT || m->d.arch == SGPT_ARCH_LLAMA))
+    if (any && !family(m->d.arch).split)
         return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision: no split-precision operands for SGPT_ARCH_BERT / SGPT_ARCH_LLAMA");
     if (any && cd != SGPT_F16 && cd != SGPT_BF16) return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_precision applies to SGPT_F16 / SGPT_BF16 models");
     for (int i = 0; i < n; ++i) m->prec[i] = plan[i];
@@ -563,7 +564,7 @@ sgpt_status sgpt_model_release_split_weights(sgpt_model* m, int64_t* bytes_freed
 sgpt_status sgpt_model_precision_probe_begin(sgpt_model* m) {
     if (!m) return SGPT_ERR_INVALID;
     sgpt_ctx* c = m->ctx;
-    if (!m->crest_dev || m->d.arch == SGPT_ARCH_BERT || m->d.arch == SGPT_ARCH_LLAMA) return fail(c, SGPT_ERR_INVALID, "the precision probe applies to SGPT_F16 / SGPT_BF16 models of the decoder families");
+    if (!m->crest_dev || !family(m->d.arch).probe) return fail(c, SGPT_ERR_INVALID, "the precision probe applies to SGPT_F16 / SGPT_BF16 models of the decoder families");
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipDeviceSynchronize());
     HIPC(c, hipMemset(m->crest_dev, 0, (size_t)m->d.n_layers * RS_N * 4));
