@@ -19,7 +19,8 @@ import torch
 
 from .model import SGPTModel
 from .runtime import get_context
-from .tokenization import TextPipeline, is_bert, is_llama, load_tokenizer
+from .families import family_of
+from .tokenization import TextPipeline, load_tokenizer
 
 logger = logging.getLogger(__name__)
 
@@ -42,7 +43,7 @@ class CustomEmbedder:
         self.model = model if model is not None else SGPTModel.from_pretrained(model_name, device=device, dtype=dtype)
         self.tokenizer = tokenizer if tokenizer is not None else load_tokenizer(model_name)
         self.max_token_len = maxseqlen if maxseqlen else self.model.cfg.max_position_embeddings   # :128
-        self.pipe = TextPipeline(self.tokenizer, self.max_token_len, specb=specb, bert=is_bert(self.model), llama=is_llama(self.model))
+        self.pipe = TextPipeline(self.tokenizer, self.max_token_len, specb=specb, family=family_of(self.model))
         self.max_token_len = self.pipe.max_token_len
         self.batch_size = batch_size
         self.save_emb = save_emb
@@ -423,7 +424,7 @@ class SentenceBERTBOSEOS:
         self.model = model if model is not None else SGPTModel.from_pretrained(model_path, device=device, dtype=dtype)
         tok = tokenizer if tokenizer is not None else load_tokenizer(model_path)
         self.pipe = TextPipeline(tok, max_seq_length, specb=specb and not speca, speca=speca, st_path=True,
-                                 bert=is_bert(self.model), llama=is_llama(self.model))
+                                 family=family_of(self.model))
         if speca and max(self.pipe.bos_q + self.pipe.eos_q + self.pipe.bos_d + self.pipe.eos_d) >= self.model.cfg.vocab_size:
             raise ValueError("speca: the checkpoint's embedding table has no rows for the added [SOS]/[EOS]/{SOS}/{EOS} ids")
         self.method = method

@@ -8,7 +8,7 @@ import ctypes as C
 import itertools
 import json
 import os
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -17,6 +17,8 @@ import torch
 from . import _lib
 from ._lib import (ModelDesc, TensorView, POOL_MODES, SGPT_BF16, SGPT_F16, SGPT_F32, SGPT_FP8M, SGPT_FP8W, SgptRangeError,
                    SGPT_PREC_CLASSES, PC_LN1, PC_ATT, PC_CTX, PC_LN2, PC_H)
+from .families import (MAX_SEQ_LEN, SGPTConfig, alibi_slopes, bert_state_dict, family, llama_state_dict, rotary_tables,  # noqa: F401
+                       rotary_tables_half, synthetic_bert_weights, synthetic_llama_weights, synthetic_weights)
 from .runtime import Context, get_context, _p, _stream_ptr
 
 # Precision probe thresholds: crest factor max|v| / rms(v) of an operand row above which 11-bit operands are not trusted.
@@ -38,7 +40,6 @@ TOKEN_TILE = 256   # GEMM M tile (256x256 LDS-DMA kernel)
 # only -- its projections run on 32-row tiles, and one 18-token query no longer pays for 256 rows.
 QUERY_ROWS = 512
 QUERY_TILE = 32
-MAX_SEQ_LEN = 2048   # tokens per sequence sgpt_encode takes (include/sgpt_hip.h)
 
 
 def pad_rows(total: int, row_tile: Optional[int] = None) -> int:
@@ -47,101 +48,6 @@ def pad_rows(total: int, row_tile: Optional[int] = None) -> int:
     fit would silently run the fp8-storage arithmetic)."""
     tile = row_tile or (QUERY_TILE if total <= QUERY_ROWS else TOKEN_TILE)
     return (int(total) + tile - 1) // tile * tile
-
-
-@dataclass
-class SGPTConfig:
-    """The fields of HF GPTNeoConfig the forward reads (HF:gpt_neo/configuration_gpt_neo.py)."""
-    vocab_size: int = 50257
-    max_position_embeddings: int = 2048
-    hidden_size: int = 768
-    num_layers: int = 12
-    num_heads: int = 12
-    intermediate_size: Optional[int] = None
-    window_size: int = 256
-    attention_layers: Optional[List[str]] = None
-    layer_norm_epsilon: float = 1e-5
-    model_type: str = "gpt_neo"          # "gpt_neo" (SGPT-125M/1.3B/2.7B) | "gptj" (SGPT-5.8B) | "bloom" | "bert" (the BERT / SBERT baselines)
-    rotary_dim: int = 0                   # GPT-J only (HF GPTJConfig.rotary_dim = 64)
-    num_kv_heads: Optional[int] = None    # "llama" only: key / value heads (grouped K / V); None = num_heads
-    rope_theta: float = 10000.0           # "llama" only: base of the rotary frequencies
-
-    def __post_init__(self):
-        if self.num_kv_heads is None:
-            self.num_kv_heads = self.num_heads
-        if self.intermediate_size is None:
-            self.intermediate_size = 4 * self.hidden_size
-        if self.attention_layers is None:
-            self.attention_layers = ["global" if i % 2 == 0 else "local" for i in range(self.num_layers)]
-
-    @classmethod
-    def from_hf_dict(cls, c: dict) -> "SGPTConfig":
-        mt = c.get("model_type", "gpt_neo")
-        if mt == "gptj":   # HF GPTJConfig field names (HF:gptj/configuration_gptj.py)
-            return cls(vocab_size=c["vocab_size"], max_position_embeddings=c["n_positions"], hidden_size=c["n_embd"],
-                       num_layers=c["n_layer"], num_heads=c["n_head"], intermediate_size=c.get("n_inner"),
-                       layer_norm_epsilon=c.get("layer_norm_epsilon", 1e-5), model_type="gptj",
-                       rotary_dim=c.get("rotary_dim") or c["n_embd"] // c["n_head"], window_size=0,
-                       attention_layers=["global"] * c["n_layer"])
-        if mt == "bloom":  # HF BloomConfig (HF:bloom/configuration_bloom.py): ALiBi, no position table
-            return cls(vocab_size=c["vocab_size"], max_position_embeddings=2048, hidden_size=c["hidden_size"],
-                       num_layers=c["n_layer"], num_heads=c["n_head"], intermediate_size=4 * c["hidden_size"],
-                       layer_norm_epsilon=c.get("layer_norm_epsilon", 1e-5), model_type="bloom", window_size=0,
-                       attention_layers=["global"] * c["n_layer"])
-        if mt == "bert":   # HF BertConfig (HF:bert/configuration_bert.py): the baseline of the reference's own scripts
-            if c.get("hidden_act", "gelu") != "gelu":
-                raise NotImplementedError(f"bert: hidden_act {c.get('hidden_act')!r} (only 'gelu', the erf form, is built)")
-            if c.get("position_embedding_type", "absolute") != "absolute":
-                raise NotImplementedError(f"bert: position_embedding_type {c.get('position_embedding_type')!r} (only 'absolute')")
-            if c.get("type_vocab_size", 2) < 1:
-                raise NotImplementedError("bert: type_vocab_size must be >= 1 (token type 0 is folded into the position table)")
-            return cls(vocab_size=c["vocab_size"], max_position_embeddings=c["max_position_embeddings"],
-                       hidden_size=c["hidden_size"], num_layers=c["num_hidden_layers"], num_heads=c["num_attention_heads"],
-                       intermediate_size=c["intermediate_size"], layer_norm_epsilon=c.get("layer_norm_eps", 1e-12),
-                       model_type="bert", window_size=0, attention_layers=["global"] * c["num_hidden_layers"])
-        if mt in ("llama", "mistral"):   # HF LlamaConfig / MistralConfig: one family here (model_type "llama"), Mistral adds the window
-            L, H, d = c["num_hidden_layers"], c["num_attention_heads"], c["hidden_size"]
-            if c.get("hidden_act", "silu") != "silu":
-                raise NotImplementedError(f"{mt}: hidden_act {c.get('hidden_act')!r} (only 'silu', the SwiGLU MLP, is built)")
-            for key in ("attention_bias", "mlp_bias"):
-                if c.get(key):
-                    raise NotImplementedError(f"{mt}: {key} = true (the biased variants are not built)")
-            rs = c.get("rope_scaling")
-            if rs is None and isinstance(c.get("rope_parameters"), dict) and c["rope_parameters"].get("rope_type", "default") != "default":
-                rs = c["rope_parameters"]
-            if rs is not None and rs.get("rope_type", rs.get("type", "default")) != "default":
-                raise NotImplementedError(f"{mt}: rope_scaling {rs!r} (only the default rotary frequencies are built)")
-            if c.get("head_dim") is not None and c["head_dim"] * H != d:
-                raise NotImplementedError(f"{mt}: head_dim {c['head_dim']} with head_dim * num_attention_heads != hidden_size {d}")
-            if d > 4096:
-                raise NotImplementedError(f"{mt}: hidden_size {d} > 4096 (the row kernels hold one row of at most 4096 columns per wave)")
-            theta = c.get("rope_theta")
-            if theta is None and isinstance(c.get("rope_parameters"), dict):
-                theta = c["rope_parameters"].get("rope_theta")
-            # Mistral: key j is visible to query i iff j > i - sliding_window (HF sliding_window_overlay) -- the window rule of the
-            # GPT-Neo local layers, on every layer.  A window that no sequence here can reach is no window: the longest sequence is
-            # min(max_position_embeddings, MAX_SEQ_LEN) tokens (Mistral-7B-v0.1's 4096 folds to 0: the no-window kernels).  A missing
-            # key is HF MistralConfig's default, 4096
-            sw = c.get("sliding_window", 4096) if mt == "mistral" else None
-            window = 0 if (sw is None or sw >= min(c["max_position_embeddings"], MAX_SEQ_LEN)) else int(sw)
-            if window < 0:
-                raise NotImplementedError(f"{mt}: sliding_window {sw!r}")
-            return cls(vocab_size=c["vocab_size"], max_position_embeddings=c["max_position_embeddings"], hidden_size=d, num_layers=L,
-                       num_heads=H, intermediate_size=c["intermediate_size"], layer_norm_epsilon=c.get("rms_norm_eps", 1e-6),
-                       model_type="llama", window_size=window, attention_layers=["local" if window else "global"] * L,
-                       num_kv_heads=c.get("num_key_value_heads") or H, rope_theta=float(theta if theta is not None else 10000.0))
-        if mt != "gpt_neo":
-            raise NotImplementedError(f"model_type {mt!r}: GPT-Neo, GPT-J, BLOOM, BERT and Llama / Mistral are the families built here")
-        layers = c.get("attention_layers")
-        if layers is None and c.get("attention_types"):
-            layers = []
-            for pattern, rep in c["attention_types"]:
-                for _ in range(rep):
-                    layers.extend(pattern)
-        return cls(vocab_size=c["vocab_size"], max_position_embeddings=c["max_position_embeddings"],
-                   hidden_size=c["hidden_size"], num_layers=c["num_layers"], num_heads=c["num_heads"],
-                   intermediate_size=c.get("intermediate_size"), window_size=c.get("window_size", 256),
-                   attention_layers=layers, layer_norm_epsilon=c.get("layer_norm_epsilon", 1e-5))
 
 
 @dataclass
@@ -296,7 +202,6 @@ PRECISE_QK_PLANS = {"full": (1, 0, 0), "logits": (0, 1, 0), "act+logits": (3, 1,
                     "qkv+logits": (2, 1, 0), "attn": (2, 1, 1)}
 
 
-
 def default_precise_qk(cfg: "SGPTConfig", dtype: str):
     """precise_qk=None: the cheapest variant that holds BOTH reference fixtures of the model's shape inside the 1e-3 bar with
     >= 25 % of margin, measured on MI355X (max |cos - ref| / max |normalised emb - ref|; first fixture, second seed;
@@ -315,11 +220,74 @@ def default_precise_qk(cfg: "SGPTConfig", dtype: str):
                                             'attn'       3.4e-4 / 5.0e-4    3.3e-4 / 5.9e-4    @ 1100
     GPT-Neo only (no 1/sqrt(dh) in its attention, HF:gpt_neo:110: the logits grow with the width); GPT-J / BLOOM sit at 6e-5
     and SGPT-125M at 3.2e-4 without any of it."""
-    if dtype != "f16" or cfg.model_type != "gpt_neo" or cfg.hidden_size < 2048:
+    if dtype != "f16" or family(cfg.model_type).scaled_logits or cfg.hidden_size < 2048:
         return False
     if cfg.hidden_size // cfg.num_heads not in (64, 128):
         return "full"      # the split-precision attention exists for head_dim 64 / 128: the split Q / K projection alone (round 3's default)
     return "act+logits" if cfg.hidden_size < 2560 else "qkv+logits"
+
+
+def check_args(cfg: SGPTConfig, dtype: str, precise_qk, precision):
+    """SGPTModel's dtype / precise_qk / precision, defaults filled in -- or the refusal, before anything touches the device."""
+    fam = family(cfg.model_type)
+    if dtype in ("fp16", "float16", "half"):
+        dtype = "f16"
+    if precision is None:
+        precision = "auto" if (dtype == "f16" and fam.sgpt_modes) else "plain"
+    if precision not in ("plain", "x3", "auto", "auto-class"):
+        raise ValueError("precision must be 'plain', 'x3', 'auto' or 'auto-class'")
+    if precision != "plain" and dtype not in ("f16", "bf16"):
+        raise ValueError("precision applies to dtype 'f16' / 'bf16'")
+    if precise_qk is None:
+        precise_qk = default_precise_qk(cfg, dtype)
+    if precise_qk is True:
+        precise_qk = "full"
+    if precise_qk not in (False,) + tuple(PRECISE_QK_PLANS):
+        raise ValueError(f"precise_qk must be None, False, True or one of {sorted(PRECISE_QK_PLANS)}")
+    if precise_qk and dtype not in ("f16", "bf16"):
+        raise ValueError("precise_qk applies to dtype 'f16' / 'bf16'")
+    # one arithmetic per operand format for a family that says so in its row (include/sgpt_hip.h): refused here, loudly
+    if not fam.sgpt_modes and dtype in ("fp8", "fp8mfma"):
+        raise ValueError(f"dtype {dtype!r} is not available for {fam.name} models: use {fam.dtype_advice}")
+    if not fam.sgpt_modes and (precision != "plain" or precise_qk):
+        raise ValueError(f"split-precision operands (precision='x3' / 'auto' / 'auto-class', precise_qk) are not available for {fam.name} models")
+    if fam.grouped_kv and cfg.num_heads % cfg.num_kv_heads:
+        raise ValueError("num_heads must be a multiple of num_kv_heads")
+    if dtype not in ("f16", "bf16", "fp32", "fp8", "fp8mfma"):
+        raise ValueError("dtype must be 'f16' (IEEE-half MFMA operands, range-guarded: the 1e-3-parity mode), "
+                         "'bf16' (bf16 MFMA operands), 'fp32' (exact fp32 MFMA), "
+                         "'fp8' (e4m3fn weight storage, bf16 arithmetic) or 'fp8mfma' (fp8 storage + fp8 MFMA on the MLP)")
+    return dtype, precise_qk, precision
+
+
+def model_desc(cfg: SGPTConfig, dtype: str, precise_qk, precision: str):
+    """The sgpt_model_desc of a model (arguments as check_args returns them) and the layer_is_local array it points to: keep both."""
+    fam = family(cfg.model_type)
+    local = (C.c_uint8 * cfg.num_layers)(*[1 if a == "local" else 0 for a in cfg.attention_layers])
+    dh = cfg.hidden_size // cfg.num_heads
+    ln1, _, ctx = PRECISE_QK_PLANS[precise_qk] if precise_qk else (0, 0, 0)
+    return ModelDesc(arch=fam.arch, n_layers=cfg.num_layers, d_model=cfg.hidden_size, n_heads=cfg.num_heads, d_ffn=cfg.intermediate_size,
+                     vocab=cfg.vocab_size, max_pos=cfg.max_position_embeddings, window=cfg.window_size, ln_eps=cfg.layer_norm_epsilon,
+                     attn_scale=float(1.0 / np.sqrt(np.float32(dh))) if fam.scaled_logits else 1.0,
+                     compute_dtype={"f16": SGPT_F16, "bf16": SGPT_BF16, "fp32": SGPT_F32, "fp8": SGPT_FP8W, "fp8mfma": SGPT_FP8M}[dtype],
+                     layer_is_local=C.cast(local, C.POINTER(C.c_uint8)),
+                     rotary_dim={"none": 0, "config": cfg.rotary_dim, "head_dim": dh}[fam.rotary_dim],
+                     n_kv_heads=cfg.num_kv_heads if fam.grouped_kv else 0, qk_split=1 if ln1 in (1, 3) else 0,
+                     split_weights=1 if (precision != "plain" or ln1 == 2 or ctx) else 0), local
+
+
+def load_tensors(cfg: SGPTConfig, weights) -> List[Tuple[str, torch.Tensor]]:
+    """A state dict -> the (name, tensor) list sgpt_model_load takes, in the dict's order and after Family.prepare_weights: the
+    `transformer.` prefix stripped, what the library does not load dropped.  Tensors stay on their device and keep their dtype."""
+    fam, out = family(cfg.model_type), []
+    for k, v in fam.prepare_weights(cfg, weights).items():
+        k2 = k[len("transformer."):] if k.startswith("transformer.") else k
+        # dropped: the learntmean table riding along with the weights, HF's buffers, an LM head tied to the embedding
+        if (k2 == "position_weights" or k2.endswith(("attn.attention.bias", "attn.bias", "masked_bias", "embed_positions"))
+                or (k.startswith("lm_head") and not fam.keeps_lm_head)):
+            continue
+        out.append((k2, v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))))
+    return out
 
 
 class SGPTModel:
@@ -352,43 +320,7 @@ class SGPTModel:
         'logits' = q / k / v / p as hi + lo pairs inside the attention only (no extra GEMM FLOPs); 'act+logits' = that plus the
         LayerNorm-1 output split against plain weights (+17 % FLOPs); 'full+logits'; 'qkv+logits' (the V projection split as
         well); 'attn' (the whole attention sub-block: Q / K / V projection, attention, out-projection)."""
-        if dtype in ("fp16", "float16", "half"):
-            dtype = "f16"
-        if precision is None:
-            precision = "auto" if (dtype == "f16" and cfg.model_type not in ("bert", "llama")) else "plain"   # (BERT, Llama: nothing to probe for)
-        if precision not in ("plain", "x3", "auto", "auto-class"):
-            raise ValueError("precision must be 'plain', 'x3', 'auto' or 'auto-class'")
-        if precision != "plain" and dtype not in ("f16", "bf16"):
-            raise ValueError("precision applies to dtype 'f16' / 'bf16'")
-        if precise_qk is None:
-            precise_qk = default_precise_qk(cfg, dtype)
-        if precise_qk is True:
-            precise_qk = "full"
-        if precise_qk not in (False,) + tuple(PRECISE_QK_PLANS):
-            raise ValueError(f"precise_qk must be None, False, True or one of {sorted(PRECISE_QK_PLANS)}")
-        if precise_qk and dtype not in ("f16", "bf16"):
-            raise ValueError("precise_qk applies to dtype 'f16' / 'bf16'")
-        bert = cfg.model_type == "bert"
-        if bert:
-            # one arithmetic per operand format for this family (include/sgpt_hip.h, SGPT_ARCH_BERT): refused here, loudly
-            if dtype in ("fp8", "fp8mfma"):
-                raise ValueError(f"dtype {dtype!r} is not available for BERT models: use 'f16', 'bf16' or 'fp32'")
-            if precision != "plain" or precise_qk:
-                raise ValueError("split-precision operands (precision='x3' / 'auto' / 'auto-class', precise_qk) are not available for BERT models")
-        llama = cfg.model_type == "llama"
-        if llama:
-            # one arithmetic per operand format for this family too (include/sgpt_hip.h, SGPT_ARCH_LLAMA)
-            if dtype in ("fp8", "fp8mfma"):
-                raise ValueError(f"dtype {dtype!r} is not available for Llama / Mistral models: use 'bf16', 'f16' or 'fp32'")
-            if precision != "plain" or precise_qk:
-                raise ValueError("split-precision operands (precision='x3' / 'auto' / 'auto-class', precise_qk) are not available for "
-                                 "Llama / Mistral models")
-            if cfg.num_heads % cfg.num_kv_heads:
-                raise ValueError("num_heads must be a multiple of num_kv_heads")
-        if dtype not in ("f16", "bf16", "fp32", "fp8", "fp8mfma"):
-            raise ValueError("dtype must be 'f16' (IEEE-half MFMA operands, range-guarded: the 1e-3-parity mode), "
-                             "'bf16' (bf16 MFMA operands), 'fp32' (exact fp32 MFMA), "
-                             "'fp8' (e4m3fn weight storage, bf16 arithmetic) or 'fp8mfma' (fp8 storage + fp8 MFMA on the MLP)")
+        dtype, precise_qk, precision = check_args(cfg, dtype, precise_qk, precision)
         self.cfg = cfg
         self.ctx = ctx or get_context(device)
         self.device = self.ctx.device
@@ -398,63 +330,17 @@ class SGPTModel:
         # projections (measured: 1000 TFLOP/s there, 864-890 at 49 k rows, 754 at 25 k); activations ~2.5 GB (125M) to
         # ~13 GB (bloom-7b1) of the 288 GB
         self.max_tokens_per_call = max_tokens_per_call
-        lib = self.ctx.lib
-        local = (C.c_uint8 * cfg.num_layers)(*[1 if a == "local" else 0 for a in cfg.attention_layers])
-        gptj, bloom = cfg.model_type == "gptj", cfg.model_type == "bloom"
-        dh = cfg.hidden_size // cfg.num_heads
-        arch = _lib.SGPT_ARCH_GPTJ if gptj else (_lib.SGPT_ARCH_BLOOM if bloom else _lib.SGPT_ARCH_GPTNEO)
-        if bert:
-            arch = _lib.SGPT_ARCH_BERT
-        if llama:
-            arch = _lib.SGPT_ARCH_LLAMA
-        desc = ModelDesc(arch=arch, n_layers=cfg.num_layers,
-                         d_model=cfg.hidden_size, n_heads=cfg.num_heads, d_ffn=cfg.intermediate_size,
-                         vocab=cfg.vocab_size, max_pos=cfg.max_position_embeddings, window=cfg.window_size,
-                         ln_eps=cfg.layer_norm_epsilon,
-                         attn_scale=float(1.0 / np.sqrt(np.float32(dh))) if (gptj or bloom or bert or llama) else 1.0,   # HF:gptj:148, HF:bloom:186 / HF:gpt_neo:110
-                         compute_dtype={"f16": SGPT_F16, "bf16": SGPT_BF16, "fp32": SGPT_F32, "fp8": SGPT_FP8W,
-                                        "fp8mfma": SGPT_FP8M}[dtype],
-                         layer_is_local=C.cast(local, C.POINTER(C.c_uint8)), rotary_dim=cfg.rotary_dim if gptj else (dh if llama else 0),
-                         n_kv_heads=cfg.num_kv_heads if llama else 0,
-                         qk_split=1 if (precise_qk and PRECISE_QK_PLANS[precise_qk][0] in (1, 3)) else 0,
-                         split_weights=1 if (precision != "plain" or (precise_qk and (PRECISE_QK_PLANS[precise_qk][0] == 2 or
-                                                                                        PRECISE_QK_PLANS[precise_qk][2]))) else 0)
-        self.precise_qk = precise_qk
-        self.precision = precision
+        desc, _local = model_desc(cfg, dtype, precise_qk, precision)     # (_local: the array desc.layer_is_local points to)
+        self.precise_qk, self.precision = precise_qk, precision
         self.precision_report = None      # filled by the probe: crest factors [num_layers, 4] and what was decided
-        self._att_ok = (not gptj) and dh in (64, 128)          # split-precision attention: head_dim 64 / 128, no rotary
+        self._att_ok = family(cfg.model_type).rotary_dim == "none" and cfg.hidden_size // cfg.num_heads in (64, 128)   # split-precision attention: head_dim 64 / 128, no rotary
         self._plan_pending = precision in ("auto", "auto-class")
-        if gptj:
-            weights = dict(weights)
-            weights["rotary.sin"], weights["rotary.cos"] = rotary_tables(cfg.max_position_embeddings, cfg.rotary_dim)
-        if bloom:
-            weights = dict(weights)
-            weights["alibi.slopes"] = alibi_slopes(cfg.num_heads)
-        if bert:
-            weights = bert_state_dict(weights)
-        if llama:
-            weights = llama_state_dict(weights)
-            weights["rotary.sin"], weights["rotary.cos"] = rotary_tables_half(cfg.max_position_embeddings, dh, cfg.rope_theta)
-        names, keep = [], []
-        for k, v in weights.items():
-            k2 = k[len("transformer."):] if k.startswith("transformer.") else k
-            if k2 == "position_weights":          # learntmean table riding along with the weights
-                continue
-            if (k2.endswith("attn.attention.bias") or k2.endswith("attn.bias") or k2.endswith("masked_bias")
-                    or k2.endswith("embed_positions")):
-                continue
-            if k.startswith("lm_head") and not gptj:     # GPT-Neo / BLOOM tie the LM head to the embedding
-                continue
-            t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))
-            t = t.to(device=self.device, dtype=torch.float32).contiguous()   # H2D staging only
-            names.append(k2.encode())
-            keep.append(t)
-        views = (TensorView * len(keep))(*[TensorView(n, t.data_ptr(), t.numel()) for n, t in zip(names, keep)])
-        h = C.c_void_p()
+        keep = [(n.encode(), t.to(device=self.device, dtype=torch.float32).contiguous()) for n, t in load_tensors(cfg, weights)]   # H2D staging only
+        views = (TensorView * len(keep))(*[TensorView(n, t.data_ptr(), t.numel()) for n, t in keep])
+        self.handle = C.c_void_p()
         torch.cuda.synchronize(self.device)
-        _lib.check(self.ctx.handle, lib.sgpt_model_load(self.ctx.handle, C.byref(desc), views, len(keep), C.byref(h)),
+        _lib.check(self.ctx.handle, self.ctx.lib.sgpt_model_load(self.ctx.handle, C.byref(desc), views, len(keep), C.byref(self.handle)),
                    "sgpt_model_load")
-        self.handle = h
         del keep  # the library now owns packed copies
         self._staging = _Staging(self.device)
         self.act_scales = None
@@ -472,6 +358,10 @@ class SGPTModel:
             if self._plan_pending:
                 S = min(64, cfg.max_position_embeddings)
                 self._auto_precision(np.random.default_rng(4321).integers(0, cfg.vocab_size, size=(64, S), dtype=np.int64), None, final=False)
+
+    def _call(self, fn: str, *args) -> None:
+        """sgpt_model_<fn>(this model, *args); a failure raises with the library's message."""
+        _lib.check(self.ctx.handle, getattr(self.ctx.lib, "sgpt_model_" + fn)(self.handle, *args), "sgpt_model_" + fn)
 
     # ---- precision plan (split-precision operand classes per block) ----
     def _base_plan(self) -> np.ndarray:
@@ -495,16 +385,14 @@ class SGPTModel:
         """int32[num_layers, 5]: per block (LayerNorm-1 -> Q/K/V: 0 | 1 q,k | 2 q,k,v | 3 q,k activation-only; attention; context ->
         out-projection; LayerNorm-2 -> fc1; GELU output -> fc2); non-zero = that operand class enters its MFMAs as hi + lo pairs."""
         out = np.zeros(self.cfg.num_layers * SGPT_PREC_CLASSES, dtype=np.int32)
-        _lib.check(self.ctx.handle, self.ctx.lib.sgpt_model_get_precision(self.handle, out.ctypes.data_as(C.c_void_p), out.size),
-                   "sgpt_model_get_precision")
+        self._call("get_precision", out.ctypes.data_as(C.c_void_p), out.size)
         return out.reshape(self.cfg.num_layers, SGPT_PREC_CLASSES)
 
     def set_precision_plan(self, plan, _keep_pending: bool = False) -> None:
         """Install a plan (e.g. the one an earlier run's probe chose: reproducible embeddings across processes).  Ends the
         'auto' probe: the plan is the caller's now."""
         a = np.ascontiguousarray(np.asarray(plan, dtype=np.int32).reshape(-1))
-        _lib.check(self.ctx.handle, self.ctx.lib.sgpt_model_set_precision(self.handle, a.ctypes.data_as(C.c_void_p), a.size),
-                   "sgpt_model_set_precision")
+        self._call("set_precision", a.ctypes.data_as(C.c_void_p), a.size)
         if not _keep_pending:
             self._plan_pending = False
 
@@ -518,15 +406,14 @@ class SGPTModel:
         n = max(1, int(np.searchsorted(alloc, PROBE_MAX_ROWS, side="right")))
         sub = [seqs[i][:PROBE_MAX_ROWS] for i in range(n)]
         pl = None if pad_left is None else [pad_left[i] for i in range(n)]
-        lib = self.ctx.lib
         out = (C.c_float * (4 * self.cfg.num_layers))()
 
         def once():
-            _lib.check(self.ctx.handle, lib.sgpt_model_precision_probe_begin(self.handle), "sgpt_model_precision_probe_begin")
+            self._call("precision_probe_begin")
             try:
                 self.encode_packed(self.pack(sub, pl))
             finally:
-                _lib.check(self.ctx.handle, lib.sgpt_model_precision_probe_end(self.handle, out), "sgpt_model_precision_probe_end")
+                self._call("precision_probe_end", out)
         self.guarded(once)          # (an f16 range overflow inside the probe forward: shifts raised, probed again)
         return np.array(list(out), dtype=np.float32).reshape(self.cfg.num_layers, 4)
 
@@ -546,8 +433,7 @@ class SGPTModel:
         if plan[:, [PC_CTX, PC_LN2, PC_H]].any():
             return 0                       # (a LayerNorm-1 entry only reads the Q / K / V copy, which then stays)
         freed = C.c_int64(0)
-        _lib.check(self.ctx.handle, self.ctx.lib.sgpt_model_release_split_weights(self.handle, C.byref(freed)),
-                   "sgpt_model_release_split_weights")
+        self._call("release_split_weights", C.byref(freed))
         return int(freed.value)
 
     def sync_precision(self, seqs, reduce, pad_left=None) -> None:
@@ -601,7 +487,7 @@ class SGPTModel:
                 plan[hot[:, 1], PC_CTX] = 1
                 plan[hot[:, 2], PC_LN2] = 1
                 plan[hot[:, 3], PC_H] = 1
-                if self.cfg.model_type == "gptj":
+                if family(self.cfg.model_type).parallel_block:
                     plan[:, PC_LN2] = (plan[:, PC_LN1] != 0).astype(np.int32)
             self.set_precision_plan(plan)          # (ends the probing: an ill-conditioned checkpoint stays escalated)
         freed = 0
@@ -639,20 +525,18 @@ class SGPTModel:
                           stacklevel=2)
             S = min(64, self.cfg.max_position_embeddings)
             seqs = np.random.default_rng(1234).integers(0, self.cfg.vocab_size, size=(64, S), dtype=np.int64)
-        lib = self.ctx.lib
-        _lib.check(self.ctx.handle, lib.sgpt_model_calibrate_begin(self.handle), "sgpt_model_calibrate_begin")
+        self._call("calibrate_begin")
         try:
             self.encode_ids(seqs)
         finally:
             out = (C.c_float * (2 * self.cfg.num_layers))()
-            _lib.check(self.ctx.handle, lib.sgpt_model_calibrate_end(self.handle, float(margin), out), "sgpt_model_calibrate_end")
+            self._call("calibrate_end", float(margin), out)
         self.act_scales = np.array(list(out), dtype=np.float32)
         return self.act_scales
 
     def set_act_scales(self, scales) -> None:
         a = np.ascontiguousarray(scales, dtype=np.float32)
-        _lib.check(self.ctx.handle, self.ctx.lib.sgpt_model_set_act_scales(self.handle, a.ctypes.data_as(C.c_void_p), a.size),
-                   "sgpt_model_set_act_scales")
+        self._call("set_act_scales", a.ctypes.data_as(C.c_void_p), a.size)
         self.act_scales = a
 
     def set_position_weights(self, w) -> None:
@@ -660,8 +544,7 @@ class SGPTModel:
         (the reference reads 1_WeightedMeanPooling/pytorch_model.bin, useb_dense_retriever.py:253-257)."""
         t = w if isinstance(w, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(w))
         t = t.detach().to(device=self.device, dtype=torch.float32).contiguous().reshape(-1)
-        _lib.check(self.ctx.handle, self.ctx.lib.sgpt_model_set_pool_weights(self.handle, _p(t), t.numel()),
-                   "sgpt_model_set_pool_weights")
+        self._call("set_pool_weights", _p(t), t.numel())
         self.position_weights = t
 
     def close(self):
@@ -742,7 +625,7 @@ class SGPTModel:
     def _check_learnt(self, mode: str, pb: PackedBatch) -> None:
         if mode != "learntmean":
             return
-        if self.cfg.model_type in ("bert", "llama"):
+        if not family(self.cfg.model_type).sgpt_modes:
             raise ValueError("method 'learntmean' (trained position weights of the SGPT checkpoints) is not available for BERT / Llama models")
         if self.position_weights is None:
             raise ValueError("method 'learntmean' needs trained position weights (1_WeightedMeanPooling)")
@@ -769,10 +652,8 @@ class SGPTModel:
     def lm_logprobs(self, hidden: torch.Tensor, row_idx, targets, return_greedy: bool = False):
         """log P(targets[i] | prefix ending at token row row_idx[i]) from post-ln_f hidden states [T_pad, d]
         (the log_softmax + gather of crossencoder/beir/sgptce.py:233-255) -> fp32[n] on the GPU."""
-        if self.cfg.model_type == "bert":
-            raise ValueError("lm_logprobs: a BERT model carries no causal LM head")
-        if self.cfg.model_type == "llama":
-            raise ValueError("lm_logprobs is not built for Llama / Mistral models (their LM head is not loaded)")
+        if refusal := family(self.cfg.model_type).no_lm_head:
+            raise ValueError(refusal)
         ri = torch.as_tensor(np.asarray(row_idx, dtype=np.int32)).to(self.device)
         tg = torch.as_tensor(np.asarray(targets, dtype=np.int32)).to(self.device)
         n = int(ri.numel())
@@ -827,7 +708,6 @@ class SGPTModel:
             rem = mt_tot - fixed * mt_max
             if rem <= 0:
                 continue
-            import itertools
             for combo in itertools.combinations_with_replacement(good, n_free - 1):
                 last = rem - sum(combo)
                 if last <= 0 or last > mt_max:
@@ -882,29 +762,25 @@ class SGPTModel:
         """The model's guard word since the last reset (syncs the stream; include/sgpt_hip.h::sgpt_model_range_check):
         bit 0 = an f16 activation reached |v| >= 32768, bit 1 / 2 = an fp8mfma GELU output / attention context saturated."""
         flagged = C.c_int32(0)
-        _lib.check(self.ctx.handle, self.ctx.lib.sgpt_model_range_check(self.handle, C.byref(flagged), 1 if reset else 0,
-                                                                        _stream_ptr(self.device)), "sgpt_model_range_check")
+        self._call("range_check", C.byref(flagged), 1 if reset else 0, _stream_ptr(self.device))
         return int(flagged.value)
 
     def range_shifts(self) -> np.ndarray:
         """dtype='f16': the power-of-two down-shifts per block, int32[num_layers, 4] = (LayerNorm-1 output, q | k | v,
         LayerNorm-2 output, GELU output).  All zero for a checkpoint whose activations stay inside the half range."""
         out = np.zeros(self.cfg.num_layers * 4, dtype=np.int32)
-        _lib.check(self.ctx.handle, self.ctx.lib.sgpt_model_get_range_shifts(self.handle, out.ctypes.data_as(C.c_void_p), out.size),
-                   "sgpt_model_get_range_shifts")
+        self._call("get_range_shifts", out.ctypes.data_as(C.c_void_p), out.size)
         return out.reshape(self.cfg.num_layers, 4)
 
     def set_range_shifts(self, shifts) -> None:
         """Pin the shifts found on an earlier run (reproducible embeddings across processes)."""
         a = np.ascontiguousarray(np.asarray(shifts, dtype=np.int32).reshape(-1))
-        _lib.check(self.ctx.handle, self.ctx.lib.sgpt_model_set_range_shifts(self.handle, a.ctypes.data_as(C.c_void_p), a.size),
-                   "sgpt_model_set_range_shifts")
+        self._call("set_range_shifts", a.ctypes.data_as(C.c_void_p), a.size)
 
     def _adapt_range(self) -> bool:
         """dtype='f16', after a flagged call: raise the shifts of the classes that overflowed.  True = re-run the call."""
         n = C.c_int32(0)
-        _lib.check(self.ctx.handle, self.ctx.lib.sgpt_model_range_adapt(self.handle, C.byref(n), _stream_ptr(self.device)),
-                   "sgpt_model_range_adapt")
+        self._call("range_adapt", C.byref(n), _stream_ptr(self.device))
         return n.value > 0
 
     def check_range(self, adapt: bool = False) -> bool:
@@ -917,7 +793,7 @@ class SGPTModel:
         if not flags:
             return False
         # (BERT models run without range shifts: nothing to adapt, the flag is final)
-        if flags & 1 and not flags & 6 and adapt and self.dtype == "f16" and self.cfg.model_type not in ("bert", "llama") and self._adapt_range():
+        if flags & 1 and not flags & 6 and adapt and self.dtype == "f16" and family(self.cfg.model_type).sgpt_modes and self._adapt_range():
             return True                      # (sgpt_model_range_adapt cleared bit 0 and the recorded magnitudes)
         self.range_flags(reset=True)
         if flags & 2:
@@ -951,8 +827,7 @@ class SGPTModel:
         lens = np.fromiter(map(len, seqs), dtype=np.int64, count=n)
         if (lens <= 0).any():
             raise ValueError("Empty items should be cleaned prior to running")
-        if self._plan_pending:
-            self._auto_precision(seqs, pad_left)
+        self.ensure_precision_plan(seqs, pad_left)
         return self.guarded(lambda: self._batched_once(seqs, pad_left, run, lens))
 
     def _batched_once(self, seqs, pad_left, run, lens) -> torch.Tensor:
@@ -1096,171 +971,3 @@ def load_state_dict(root: str) -> Dict[str, torch.Tensor]:
                 sd.update(read(os.path.join(root, sh)))
             return sd
     raise FileNotFoundError(f"no model.safetensors / pytorch_model.bin (single or sharded) under {root}")
-
-
-def bert_state_dict(weights) -> dict:
-    """HF BertModel / BertFor* state dict -> the tensors include/sgpt_hip.h asks for under SGPT_ARCH_BERT: the `bert.` prefix and
-    the `pooler.*` / `cls.*` heads are dropped, `embeddings.position_ids` / `token_type_ids` buffers too, and -- token types are
-    all 0 on this path (single-segment inputs, biencoder/beir/beir_dense_retriever.py:128-136) -- row 0 of
-    `embeddings.token_type_embeddings.weight` is added to every row of the position table (one fp32 add per element, the order
-    HF sums them in: inputs + token_type, then + position, differs by one rounding from this one)."""
-    out = {}
-    for k, v in weights.items():
-        k2 = k[len("bert."):] if k.startswith("bert.") else k
-        if k2.startswith(("pooler.", "cls.", "classifier.")) or k2.endswith(("position_ids", "token_type_ids")) or k.startswith("cls."):
-            continue
-        out[k2] = v
-    tt = out.pop("embeddings.token_type_embeddings.weight", None)
-    if tt is not None:
-        pos = out["embeddings.position_embeddings.weight"]
-        as_t = lambda a: a.detach().to(torch.float32).cpu() if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a, dtype=np.float32))  # noqa: E731
-        out["embeddings.position_embeddings.weight"] = as_t(pos) + as_t(tt)[0][None, :]
-    return out
-
-
-def llama_state_dict(weights) -> dict:
-    """HF LlamaModel / LlamaForCausalLM / Mistral* state dict -> the tensors include/sgpt_hip.h asks for under SGPT_ARCH_LLAMA: the
-    `model.` prefix and `lm_head.*` are dropped (as are `rotary_emb.inv_freq` buffers of older checkpoints), q_proj | k_proj | v_proj
-    are stacked into `self_attn.qkv_proj.weight` [d + 2 d_kv, d] and gate_proj | up_proj into `mlp.gate_up_proj.weight` [2 ffn, d]
-    (gate rows first).  A bias tensor of a projection means a biased variant, which is not built."""
-    as_t = lambda a: a.detach().to(torch.float32).cpu() if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a, dtype=np.float32))  # noqa: E731
-    flat = {}
-    for k, v in weights.items():
-        k2 = k[len("model."):] if k.startswith("model.") else k
-        if k.startswith("lm_head.") or k2.endswith("rotary_emb.inv_freq"):
-            continue
-        if k2.endswith("_proj.bias"):
-            raise NotImplementedError(f"llama: {k} (the biased variants are not built)")
-        flat[k2] = v
-    out, fuse = {}, (("self_attn.", ("q_proj", "k_proj", "v_proj"), "qkv_proj"), ("mlp.", ("gate_proj", "up_proj"), "gate_up_proj"))
-    for k, v in flat.items():
-        for mod, parts, fused in fuse:
-            if k.endswith(mod + parts[0] + ".weight"):
-                base = k[: -len(parts[0] + ".weight")]
-                out[base + fused + ".weight"] = torch.cat([as_t(flat[base + n + ".weight"]) for n in parts], dim=0)
-                break
-        else:
-            if not any(k.endswith(mod + n + ".weight") for mod, parts, _ in fuse for n in parts):
-                out[k] = v
-    return out
-
-
-def rotary_tables_half(max_pos: int, head_dim: int, theta: float = 10000.0):
-    """sin, cos fp32 [max_pos, head_dim / 2] of HF LlamaRotaryEmbedding (default rope): inv_freq[i] = theta^(-2i / head_dim) as
-    `1.0 / (base ** (arange(0, dim, 2, int64).float() / dim))`, angle = position * inv_freq in float32."""
-    inv_freq = 1.0 / (theta ** (torch.arange(0, head_dim, 2, dtype=torch.int64).to(dtype=torch.float) / head_dim))
-    ang = torch.arange(max_pos, dtype=torch.float32)[:, None] * inv_freq[None, :].to(torch.float32)
-    return ang.sin().numpy().astype(np.float32), ang.cos().numpy().astype(np.float32)
-
-
-def synthetic_llama_weights(cfg: SGPTConfig, seed: int = 0, std: float = 0.02) -> Dict[str, np.ndarray]:
-    """Seeded random-init weights under HF LlamaModel state-dict names (fixtures, benches: no checkpoints exist offline)."""
-    rng = np.random.default_rng(seed)
-    d, ffn = cfg.hidden_size, cfg.intermediate_size
-    dkv = cfg.num_kv_heads * (d // cfg.num_heads)
-    f32 = np.float32
-
-    def nrm(*shape, s=std):
-        return (rng.standard_normal(shape, dtype=np.float32) * f32(s)).astype(f32)
-
-    w = {"embed_tokens.weight": nrm(cfg.vocab_size, d)}
-    for i in range(cfg.num_layers):
-        p = f"layers.{i}."
-        w[p + "input_layernorm.weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
-        w[p + "self_attn.q_proj.weight"] = nrm(d, d)
-        w[p + "self_attn.k_proj.weight"] = nrm(dkv, d)
-        w[p + "self_attn.v_proj.weight"] = nrm(dkv, d)
-        w[p + "self_attn.o_proj.weight"] = nrm(d, d)
-        w[p + "post_attention_layernorm.weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
-        w[p + "mlp.gate_proj.weight"] = nrm(ffn, d)
-        w[p + "mlp.up_proj.weight"] = nrm(ffn, d)
-        w[p + "mlp.down_proj.weight"] = nrm(d, ffn)
-    w["norm.weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
-    return w
-
-
-def synthetic_bert_weights(cfg: SGPTConfig, seed: int = 0, std: float = 0.02) -> Dict[str, np.ndarray]:
-    """Seeded random-init weights under HF BertModel state-dict names (bench, tests: no checkpoints exist offline)."""
-    rng = np.random.default_rng(seed)
-    d, ffn = cfg.hidden_size, cfg.intermediate_size
-    f32 = np.float32
-
-    def nrm(*shape, s=std):
-        return (rng.standard_normal(shape, dtype=np.float32) * f32(s)).astype(f32)
-
-    def ln(name):
-        w[name + ".weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
-        w[name + ".bias"] = nrm(d, s=0.05)
-
-    w = {"embeddings.word_embeddings.weight": nrm(cfg.vocab_size, d),
-         "embeddings.position_embeddings.weight": nrm(cfg.max_position_embeddings, d, s=std / 2),
-         "embeddings.token_type_embeddings.weight": nrm(2, d, s=std / 2)}
-    ln("embeddings.LayerNorm")
-    for i in range(cfg.num_layers):
-        p = f"encoder.layer.{i}."
-        for n in ("query", "key", "value"):
-            w[p + f"attention.self.{n}.weight"] = nrm(d, d)
-            w[p + f"attention.self.{n}.bias"] = nrm(d, s=0.02)
-        w[p + "attention.output.dense.weight"] = nrm(d, d)
-        w[p + "attention.output.dense.bias"] = nrm(d, s=0.02)
-        ln(p + "attention.output.LayerNorm")
-        w[p + "intermediate.dense.weight"] = nrm(ffn, d)
-        w[p + "intermediate.dense.bias"] = nrm(ffn, s=0.02)
-        w[p + "output.dense.weight"] = nrm(d, ffn)
-        w[p + "output.dense.bias"] = nrm(d, s=0.02)
-        ln(p + "output.LayerNorm")
-    return w
-
-
-def alibi_slopes(n_head: int) -> np.ndarray:
-    """HF build_alibi_tensor slopes (HF:bloom/modeling_bloom.py:62-79) in float32."""
-    import math
-    f32 = np.float32
-    cp2 = 2 ** math.floor(math.log2(n_head))
-    base = f32(2 ** (-(2 ** -(math.log2(cp2) - 3))))
-    slopes = np.power(base, np.arange(1, 1 + cp2, dtype=np.int32).astype(f32)).astype(f32)
-    if cp2 != n_head:
-        extra_base = f32(2 ** (-(2 ** -(math.log2(2 * cp2) - 3))))
-        nrem = min(cp2, n_head - cp2)
-        slopes = np.concatenate([slopes, np.power(extra_base, np.arange(1, 1 + 2 * nrem, 2, dtype=np.int32).astype(f32)).astype(f32)])
-    return slopes.astype(f32)
-
-
-def rotary_tables(max_pos: int, dim: int):
-    """HF create_sinusoidal_positions (HF:gptj/modeling_gptj.py:47-50) in float32: sin, cos [max_pos, dim/2]."""
-    f32 = np.float32
-    inv_freq = (f32(1.0) / (f32(10000.0) ** (np.arange(0, dim, 2).astype(f32) / f32(dim)))).astype(f32)
-    ang = (np.arange(max_pos).astype(f32)[:, None] * inv_freq[None, :]).astype(f32)
-    return np.sin(ang).astype(f32), np.cos(ang).astype(f32)
-
-
-def synthetic_weights(cfg: SGPTConfig, seed: int = 0, std: float = 0.02) -> Dict[str, np.ndarray]:
-    """Seeded random-init weights under HF GPT-Neo state-dict names (no checkpoints exist offline).
-    Same generator stream as oracle/sgpt_oracle.py::synth_weights so the CPU oracle and the GPU read
-    identical bytes; duplicated here because product code must not import the oracle."""
-    rng = np.random.default_rng(seed)
-    d, ffn = cfg.hidden_size, cfg.intermediate_size
-    f32 = np.float32
-
-    def nrm(*shape, s=std):
-        return (rng.standard_normal(shape, dtype=np.float32) * f32(s)).astype(f32)
-
-    w = {"wte.weight": nrm(cfg.vocab_size, d), "wpe.weight": nrm(cfg.max_position_embeddings, d, s=std / 2)}
-    for i in range(cfg.num_layers):
-        p = f"h.{i}."
-        w[p + "ln_1.weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
-        w[p + "ln_1.bias"] = nrm(d, s=0.05)
-        w[p + "attn.attention.q_proj.weight"] = nrm(d, d)
-        w[p + "attn.attention.k_proj.weight"] = nrm(d, d)
-        w[p + "attn.attention.v_proj.weight"] = nrm(d, d)
-        w[p + "attn.attention.out_proj.weight"] = nrm(d, d)
-        w[p + "attn.attention.out_proj.bias"] = nrm(d, s=0.02)
-        w[p + "ln_2.weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
-        w[p + "ln_2.bias"] = nrm(d, s=0.05)
-        w[p + "mlp.c_fc.weight"] = nrm(ffn, d)
-        w[p + "mlp.c_fc.bias"] = nrm(ffn, s=0.02)
-        w[p + "mlp.c_proj.weight"] = nrm(d, ffn)
-        w[p + "mlp.c_proj.bias"] = nrm(d, s=0.02)
-    w["ln_f.weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
-    w["ln_f.bias"] = nrm(d, s=0.05)
-    return w

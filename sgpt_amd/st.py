@@ -11,7 +11,8 @@ import torch
 from .dist import balanced_cuts, get_comm, is_distributed, shard_sizes  # noqa: F401  (shard_sizes: re-exported)
 from .model import ALIGN, SGPTModel
 from .runtime import get_context  # noqa: F401
-from .tokenization import TextPipeline, is_bert, is_llama
+from .families import family_of
+from .tokenization import TextPipeline
 
 
 class SentenceTransformerSGPT:
@@ -26,7 +27,7 @@ class SentenceTransformerSGPT:
         self.pooling_mode = pooling_mode
         self.specb = specb
         self.normalize = normalize          # a Normalize module in modules.json (models/Normalize.py)
-        self.pipe = TextPipeline(tokenizer, max_seq_length, specb=specb, bert=is_bert(model), llama=is_llama(model))
+        self.pipe = TextPipeline(tokenizer, max_seq_length, specb=specb, family=family_of(model))
 
     @classmethod
     def from_pretrained(cls, path: str, tokenizer=None, device=None, dtype: str = "f16", specb: bool = False,

@@ -5,10 +5,13 @@ Restates CustomEmbedder.embed's per-text loop (biencoder/beir/beir_dense_retriev
 and Transformer.tokenize_bos_eos (sentence_transformers/models/Transformer.py:131-153)."""
 import re
 import zlib
-from typing import List, Optional, Sequence
+from typing import List, Sequence
+
+from .families import FAMILIES, FRAMED, Family, family as family_row
 
 SPECB_QUE_BOS, SPECB_QUE_EOS = "[", "]"     # beir_dense_retriever.py:100-104
 SPECB_DOC_BOS, SPECB_DOC_EOS = "{", "}"
+SPECB_TOKENS = [SPECB_QUE_BOS, SPECB_QUE_EOS, SPECB_DOC_BOS, SPECB_DOC_EOS]
 SPECA_TOKENS = ["[SOS]", "[EOS]", "{SOS}", "{EOS}"]   # sentence_bert_asym.py:52-53: added vocabulary rows
 
 
@@ -59,16 +62,6 @@ def load_tokenizer(model_name_or_path: str):
     return tok
 
 
-def is_bert(model) -> bool:
-    """Does this model object (SGPTModel, or a stand-in with a `cfg`) belong to the BERT family?"""
-    return getattr(getattr(model, "cfg", None), "model_type", None) == "bert"
-
-
-def is_llama(model) -> bool:
-    """Does this model object belong to the Llama / Mistral family?"""
-    return getattr(getattr(model, "cfg", None), "model_type", None) == "llama"
-
-
 class TextPipeline:
     """text -> truncated id list (+ brackets).
 
@@ -79,28 +72,24 @@ class TextPipeline:
            (Transformer.py:131-135, `max_length = max_seq_length - 2` INCLUDING the marker), so the content is cut to
            max_seq_length - 3 tokens; the raw-HF path (beir_dense_retriever.py:134-136,172-191) cuts the content to
            max_seq_length - 2 and adds both brackets afterwards.
-    bert:  the model is a BERT encoder: the content is cut to max_token_len - 2 and framed `[CLS]` .. `[SEP]` with the
-           tokenizer's cls_token_id / sep_token_id (beir_dense_retriever.py:128-136); the reference brackets GPT inputs only, so
-           specb / speca are refused.
-    llama: the model is a Llama / Mistral decoder: the tokenizer's own framing is applied after truncation -- bos_token_id in front
-           when its `add_bos_token` is set (the HF default of these tokenizers), eos_token_id behind when `add_eos_token` is (off by
-           default) -- and the content is cut to max_token_len minus what is added; specb / speca are refused."""
+    family: the model's row of sgpt_amd/families.py (or its model_type; None = a GPT model).  Its `framing` says what goes around the
+           content, which is cut to max_token_len minus that; any but "brackets" refuses specb / speca (the reference brackets GPT inputs
+           only).  "cls_sep": the tokenizer's cls_token_id .. sep_token_id (beir_dense_retriever.py:128-136).  "bos_eos": bos_token_id in
+           front if the tokenizer's `add_bos_token` is set (the HF default), eos_token_id behind if `add_eos_token` is (off by default)."""
 
-    def __init__(self, tokenizer, max_token_len: int, specb: bool = False, speca: bool = False, st_path: bool = False,
-                 bert: bool = False, llama: bool = False):
+    def __init__(self, tokenizer, max_token_len: int, specb: bool = False, speca: bool = False, st_path: bool = False, family=None):
         if speca and specb:
             raise ValueError("speca and specb are mutually exclusive")
+        fam = family if isinstance(family, Family) else (FAMILIES[0] if family is None else family_row(family))
         self.frame = None
-        if bert:
-            if specb or speca:
-                raise ValueError("specb / speca brackets belong to the GPT models; a BERT model is framed [CLS] ... [SEP]")
+        if fam.framing != "brackets" and (specb or speca):
+            raise ValueError(f"specb / speca brackets belong to the GPT models; a {fam.name} model {FRAMED[fam.framing]}")
+        if fam.framing == "cls_sep":
             cls_id, sep_id = getattr(tokenizer, "cls_token_id", None), getattr(tokenizer, "sep_token_id", None)
             if cls_id is None or sep_id is None:
-                raise ValueError("a BERT model needs a tokenizer with cls_token_id and sep_token_id")
+                raise ValueError(f"a {fam.name} model needs a tokenizer with cls_token_id and sep_token_id")
             self.frame = ([int(cls_id)], [int(sep_id)])
-        if llama:
-            if specb or speca:
-                raise ValueError("specb / speca brackets belong to the GPT models; a Llama / Mistral model takes its tokenizer's BOS / EOS")
+        if fam.framing == "bos_eos":
             front, back = [], []
             if getattr(tokenizer, "add_bos_token", True):
                 if getattr(tokenizer, "bos_token_id", None) is None:
@@ -113,23 +102,18 @@ class TextPipeline:
             self.frame = (front, back)
         self.tok = tokenizer
         self.specb, self.speca, self.st_path = specb, speca, st_path
-        bracketed = specb or speca
-        self.max_token_len = max_token_len - (3 if st_path else 2) if bracketed else max_token_len   # :134-136
+        self.max_token_len = max_token_len - (3 if st_path else 2) if (specb or speca) else max_token_len   # :134-136
         if self.frame:
             self.max_token_len = max_token_len - len(self.frame[0]) - len(self.frame[1])               # :128-136
         if specb:
-            self.bos_q = list(tokenizer.encode(SPECB_QUE_BOS))
-            self.eos_q = list(tokenizer.encode(SPECB_QUE_EOS))
-            self.bos_d = list(tokenizer.encode(SPECB_DOC_BOS))
-            self.eos_d = list(tokenizer.encode(SPECB_DOC_EOS))
+            self.bos_q, self.eos_q, self.bos_d, self.eos_d = (list(tokenizer.encode(t)) for t in SPECB_TOKENS)
         if speca:
             tokenizer.add_tokens(SPECA_TOKENS, special_tokens=True)             # sentence_bert_asym.py:52-54
             enc = [list(tokenizer.encode(t, add_special_tokens=False)) for t in SPECA_TOKENS]
             if any(len(e) != 1 for e in enc):
                 raise ValueError("speca markers must be single added tokens of the tokenizer")
             self.bos_q, self.eos_q, self.bos_d, self.eos_d = enc
-        self.docs_truncated = 0
-        self.toks_truncated = 0
+        self.docs_truncated = self.toks_truncated = 0
 
     def ids(self, txt: str, is_query: bool) -> List[int]:
         if not self.st_path:                                                    # the ST path hands the text to the

@@ -7,7 +7,8 @@ import torch
 
 from .beir import ALL_LAYER_METHODS, SINGLE_LAYER_METHODS
 from .model import SGPTModel
-from .tokenization import TextPipeline, is_bert, is_llama
+from .families import family_of
+from .tokenization import TextPipeline
 
 
 class CustomEmbedder:
@@ -23,7 +24,7 @@ class CustomEmbedder:
         self.layeridx = layeridx
         self.method = method
         self.pipe = TextPipeline(tokenizer, maxseqlen or model.cfg.max_position_embeddings, specb=specb,
-                                 bert=is_bert(model), llama=is_llama(model))
+                                 family=family_of(model))
 
     def encode_device(self, sentences: List[str], is_query: bool = True) -> torch.Tensor:
         seqs = self.pipe.batch(sentences, is_query)

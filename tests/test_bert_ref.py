@@ -128,7 +128,7 @@ def test_text_pipeline_frames_bert_inputs_and_truncates_first():
     words = [f"w{i}" for i in range(20)]
     tok = _bert_tokenizer(words)
     assert tok.cls_token_id == 2 and tok.sep_token_id == 3 and tok.is_fast
-    pipe = TextPipeline(tok, 8, bert=True)
+    pipe = TextPipeline(tok, 8, family="bert")
     assert pipe.max_token_len == 6
     short, long_ = "w0 w1 w2", " ".join(words[:12])
     for got in (pipe.batch([short, long_], True), [pipe.ids(short, False), pipe.ids(long_, False)]):   # batched and per-text paths
@@ -139,10 +139,10 @@ def test_text_pipeline_frames_bert_inputs_and_truncates_first():
     assert plain.ids(short, True) == [4, 5, 6]
     for kw in (dict(specb=True), dict(speca=True)):
         with pytest.raises(ValueError, match="BERT"):
-            TextPipeline(tok, 8, bert=True, **kw)
+            TextPipeline(tok, 8, family="bert", **kw)
     from sgpt_amd.tokenization import SyntheticTokenizer
     with pytest.raises(ValueError, match="cls_token_id"):
-        TextPipeline(SyntheticTokenizer(100), 8, bert=True)
+        TextPipeline(SyntheticTokenizer(100), 8, family="bert")
 
 
 def test_st_folder_cls_flag_round_trip(tmp_path):

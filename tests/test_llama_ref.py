@@ -192,22 +192,22 @@ class _Tok:
 def test_text_pipeline_frames_llama_inputs_after_truncation():
     from sgpt_amd.tokenization import TextPipeline
     short, long_ = "w0 w1 w2", " ".join(f"w{i}" for i in range(12))
-    pipe = TextPipeline(_Tok(), 8, llama=True)                     # HF default: BOS, no EOS
+    pipe = TextPipeline(_Tok(), 8, family="llama")                     # HF default: BOS, no EOS
     assert pipe.max_token_len == 7
     assert pipe.ids(short, True) == [1, 3, 4, 5] and pipe.batch([long_], False) == [[1] + list(range(3, 10))]
     assert pipe.docs_truncated == 1 and pipe.toks_truncated == 5
-    both = TextPipeline(_Tok(add_eos=True), 8, llama=True)
+    both = TextPipeline(_Tok(add_eos=True), 8, family="llama")
     assert both.max_token_len == 6 and both.ids(long_, True) == [1] + list(range(3, 9)) + [2] and len(both.ids(long_, True)) == 8
-    none = TextPipeline(_Tok(add_bos=False), 8, llama=True)
+    none = TextPipeline(_Tok(add_bos=False), 8, family="llama")
     assert none.max_token_len == 8 and none.ids(short, True) == [3, 4, 5]
     assert TextPipeline(_Tok(), 8).ids(short, True) == [3, 4, 5]                              # not a Llama model: untouched
     for kw in (dict(specb=True), dict(speca=True)):
         with pytest.raises(ValueError, match="Llama"):
-            TextPipeline(_Tok(), 8, llama=True, **kw)
+            TextPipeline(_Tok(), 8, family="llama", **kw)
     t = _Tok()
     t.bos_token_id = None
     with pytest.raises(ValueError, match="bos_token_id"):
-        TextPipeline(t, 8, llama=True)
+        TextPipeline(t, 8, family="llama")
 
 
 def test_abi_constants_and_st_folder_round_trip(tmp_path):
