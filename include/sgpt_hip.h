@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 15
+#define SGPT_ABI_VERSION 16
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -78,7 +78,18 @@ enum { SGPT_ARCH_GPTNEO = 0, SGPT_ARCH_GPTJ = 1, SGPT_ARCH_BLOOM = 2, SGPT_ARCH_
  *   Tensors: see sgpt_tensor_view.  compute_dtype SGPT_F32 | SGPT_F16 | SGPT_BF16; SGPT_FP8W / SGPT_FP8M, qk_split, split_weights, any
  *   non-zero precision plan, the precision probe, range shifts (sgpt_model_range_adapt / _set_range_shifts: a flagged f16 model is
  *   reloaded as SGPT_BF16 / SGPT_F32), SGPT_POOL_LEARNTMEAN and sgpt_lm_logprobs are refused (SGPT_ERR_INVALID).  head_dim 64 | 128.
- *   Every layout runs the bulk projection kernels (the query-sized kernels' prologues are LayerNorm). */
+ *   Every layout runs the bulk projection kernels (the query-sized kernels' prologues are LayerNorm).
+ *   ABI v16 -- HF Qwen2Model and Qwen3Model (HF:qwen2/modeling_qwen2.py, HF:qwen3/modeling_qwen3.py) are this family with three facts
+ *   more, none of them a descriptor field of its own:
+ *   head_dim: for this arch rotary_dim > 0 IS the head dim and rotary_dim == 0 means d_model / n_heads.  n_heads * head_dim (the query
+ *   width d_q) need not equal d_model: q has d_q columns, k and v d_kv = n_kv_heads * head_dim, the fused weight is [d_q + 2 d_kv, d]
+ *   and o_proj [d, d_q].  d_q % 128 == 0 and d_q <= 4096, head_dim 64 | 128 as before.
+ *   QKV bias (Qwen2): when "layers.N.self_attn.qkv_proj.bias" fp32 [d_q + 2 d_kv] (q | k | v, fused by the caller) is given, it is
+ *   added to the projection; o_proj and the MLP carry none.
+ *   q / k norm (Qwen3): when "layers.N.self_attn.q_norm.weight" and "layers.N.self_attn.k_norm.weight" fp32 [head_dim] are given, every
+ *   query and key head is RMS-normalised over head_dim (ln_eps, the gain shared by the heads) before the rotary -- one fused row
+ *   kernel, sgpt_qknorm_rope_half.  Presence is decided on layer 0 and holds for every layer; one gain without the other, or a layer
+ *   that disagrees with layer 0, is SGPT_ERR_MISSING by name. */
 enum { SGPT_POOL_WEIGHTEDMEAN = 0, SGPT_POOL_MEAN = 1, SGPT_POOL_LASTTOKEN = 2, SGPT_POOL_LEARNTMEAN = 3,
        SGPT_POOL_CLS = 4 };   /* ABI v13: the first token row of each sequence (Pooling.py:103-105 `pooling_mode_cls_token`); sgpt_encode*, sgpt_pool */
 enum { SGPT_COS = 0, SGPT_DOT = 1, SGPT_NEG_L2 = 2 };   /* SGPT_NEG_L2 (ABI v11): -||x - y||_2, sgpt_eval_groups only */
@@ -123,7 +134,8 @@ typedef struct {
                                            run the SGPT_FP8W arithmetic.  Cannot meet the 1e-3 bar (3 mantissa bits): the
                                            tests report max |dcos| and top-10 overlap against the fp32 oracle instead */
     const uint8_t* layer_is_local;  /* host, [n_layers]: 1 = sliding-window layer (HF:gpt_neo:66) */
-    int32_t rotary_dim;      /* GPT-J: leading dims of every head that get rotary position embedding (64) */
+    int32_t rotary_dim;      /* GPT-J: leading dims of every head that get rotary position embedding (64).  SGPT_ARCH_LLAMA (ABI v16):
+                                the head dim, n_heads * rotary_dim need not be d_model; 0 = d_model / n_heads */
     int32_t qk_split;        /* SGPT_F16 / SGPT_BF16 only.  1 = split-precision Q / K projection: the LayerNorm output a and the
                                 Wq / Wk weights enter the projection as hi + lo pairs of 16-bit values (a_hi.W_hi + a_lo.W_hi +
                                 a_hi.W_lo: one GEMM over K' = 3 d on the same MFMA), i.e. to ~2^-22 instead of 2^-11 each; q / k
@@ -151,7 +163,9 @@ typedef struct {
  *           rows fused by the caller, [d + 2 d_kv, d] with d_kv = n_kv_heads * head_dim), "layers.0.self_attn.o_proj.weight",
  *           "layers.0.post_attention_layernorm.weight", "layers.0.mlp.gate_up_proj.weight" (gate_proj rows, then up_proj rows,
  *           [2 d_ffn, d]), "layers.0.mlp.down_proj.weight", "norm.weight", plus "rotary.sin" / "rotary.cos" fp32[max_pos, head_dim/2]
- *           (angle = pos * rope_theta^(-2i / head_dim), computed by the host); no biases;
+ *           (angle = pos * rope_theta^(-2i / head_dim), computed by the host); no biases but the optional
+ *           "layers.0.self_attn.qkv_proj.bias" [d_q + 2 d_kv]; optional "layers.0.self_attn.{q_norm,k_norm}.weight" [head_dim]
+ *           (ABI v16, see SGPT_ARCH_LLAMA; with an explicit head dim the fused weight is [d_q + 2 d_kv, d], o_proj [d, d_q]);
  *  BLOOM:   "word_embeddings.weight", "word_embeddings_layernorm.*", "h.0.self_attention.query_key_value.{weight,bias}"
  *           (fused, head-interleaved [n_head, 3, head_dim] rows, HF:bloom:214 -- de-interleaved by the library),
  *           "h.0.self_attention.dense.*", "h.0.mlp.dense_h_to_4h.*", ..., plus "alibi.slopes" fp32[n_head]
@@ -703,6 +717,12 @@ sgpt_status sgpt_attention_gqa(sgpt_ctx* ctx, int32_t dtype, const void* q, cons
  * sgpt_rope_half (ABI v15): HF rotate_half rotary embedding in place on buf [T, ld]: for the H query heads at column 0 and the H_kv key
  *   heads at column k_off, i < head_dim / 2: (x[i], x[i + head_dim/2]) <- (x[i] c - x[i + head_dim/2] s, x[i + head_dim/2] c + x[i] s)
  *   with s, c = sin_t / cos_t [max_pos, head_dim/2] at row pos[t] (clamped into the table, as sgpt_rope).  head_dim % 8.
+ * sgpt_qknorm_rope_half (ABI v16): the per-head q / k RMSNorm of HF Qwen3Attention.forward (HF:qwen3/modeling_qwen3.py: `q_norm(q_proj(x)
+ *   .view(.., head_dim))`, `k_norm(..)`, then apply_rotary_pos_emb) fused with sgpt_rope_half, in place on buf [T, ld]: every one of
+ *   the H query heads at column 0 and the H_kv key heads at column k_off becomes n = x * rsqrt(mean_over_head_dim(x^2) + eps) * g in
+ *   fp32 (g = q_gamma for query heads, k_gamma for key heads, fp32 [head_dim], 16-byte aligned), then sgpt_rope_half's rotation of n,
+ *   rounded once to dtype.  head_dim 64 | 128; otherwise sgpt_rope_half's rules.  An f16 value of magnitude >= 32768 raises bit 0 of
+ *   sgpt_range_check.
  * sgpt_lnf_pool_ex (ABI v15): sgpt_lnf_pool with a trailing norm_kind: 0 = LayerNorm (sgpt_lnf_pool exactly), 1 = RMSNorm(gamma)
  *   (beta is not read).
  * sgpt_lnf_pool: the final LayerNorm fused with the pooling of a packed batch (layout of sgpt_encode: sequence i holds rows
@@ -733,6 +753,9 @@ sgpt_status sgpt_rmsnorm(sgpt_ctx* ctx, const float* x, const float* gamma, int3
 sgpt_status sgpt_swiglu(sgpt_ctx* ctx, const void* gu, int32_t dtype, int32_t T, int32_t ffn, void* out, void* stream);
 sgpt_status sgpt_rope_half(sgpt_ctx* ctx, void* buf, int32_t dtype, int64_t ld, int64_t k_off, const int32_t* pos, const float* sin_t,
                            const float* cos_t, int32_t T, int32_t H, int32_t H_kv, int32_t head_dim, int32_t max_pos, void* stream);
+sgpt_status sgpt_qknorm_rope_half(sgpt_ctx* ctx, void* buf, int32_t dtype, int64_t ld, int64_t k_off, const int32_t* pos,
+                                  const float* sin_t, const float* cos_t, int32_t T, int32_t H, int32_t H_kv, int32_t head_dim,
+                                  int32_t max_pos, const float* q_gamma, const float* k_gamma, float eps, void* stream);
 sgpt_status sgpt_lnf_pool_ex(sgpt_ctx* ctx, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
                              const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
                              int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,

@@ -36,14 +36,14 @@ class CustomEmbedder:
 
     def __init__(self, model_name="EleutherAI/gpt-neo-1.3B", batch_size=250, device="cuda:0", save_emb=False,
                  reinit=False, layeridx=-1, method="mean", dataset="scifact", specb=False, maxseqlen=None,
-                 model: Optional[SGPTModel] = None, tokenizer=None, dtype="f16", **kwargs):
+                 model: Optional[SGPTModel] = None, tokenizer=None, dtype="f16", frame=None, **kwargs):
         if reinit:
             raise NotImplementedError("reinit (random re-initialisation ablation) is not part of the hot path")
         self.device = torch.device(device)
         self.model = model if model is not None else SGPTModel.from_pretrained(model_name, device=device, dtype=dtype)
         self.tokenizer = tokenizer if tokenizer is not None else load_tokenizer(model_name)
         self.max_token_len = maxseqlen if maxseqlen else self.model.cfg.max_position_embeddings   # :128
-        self.pipe = TextPipeline(self.tokenizer, self.max_token_len, specb=specb, family=family_of(self.model))
+        self.pipe = TextPipeline(self.tokenizer, self.max_token_len, specb=specb, family=family_of(self.model), frame=frame)   # frame: TextPipeline's
         self.max_token_len = self.pipe.max_token_len
         self.batch_size = batch_size
         self.save_emb = save_emb
@@ -416,7 +416,7 @@ class SentenceBERTBOSEOS:
 
     def __init__(self, model_path=None, sep: str = " ", speca=False, specb=False, model: Optional[SGPTModel] = None,
                  tokenizer=None, max_seq_length: int = 300, method: str = "weightedmean", dtype="f16",
-                 device="cuda:0", **kwargs):
+                 device="cuda:0", frame=None, **kwargs):
         self.sep = sep
         self.speca, self.specb = speca, specb
         if not (specb or speca):
@@ -424,7 +424,7 @@ class SentenceBERTBOSEOS:
         self.model = model if model is not None else SGPTModel.from_pretrained(model_path, device=device, dtype=dtype)
         tok = tokenizer if tokenizer is not None else load_tokenizer(model_path)
         self.pipe = TextPipeline(tok, max_seq_length, specb=specb and not speca, speca=speca, st_path=True,
-                                 family=family_of(self.model))
+                                 family=family_of(self.model), frame=frame)
         if speca and max(self.pipe.bos_q + self.pipe.eos_q + self.pipe.bos_d + self.pipe.eos_d) >= self.model.cfg.vocab_size:
             raise ValueError("speca: the checkpoint's embedding table has no rows for the added [SOS]/[EOS]/{SOS}/{EOS} ids")
         self.method = method
@@ -453,7 +453,7 @@ class SentenceBERTAsym:
 
     def __init__(self, model_path=None, sep: str = " ", query_model: Optional[SGPTModel] = None,
                  doc_model: Optional[SGPTModel] = None, tokenizer=None, max_seq_length: int = 300,
-                 method: str = "weightedmean", dtype="f16", device="cuda:0", **kwargs):
+                 method: str = "weightedmean", dtype="f16", device="cuda:0", frame=None, **kwargs):
         self.sep = sep
         if query_model is None or doc_model is None:
             from .formats import read_st_folder
@@ -465,7 +465,7 @@ class SentenceBERTAsym:
             method, max_seq_length = spec.pooling_mode, spec.max_seq_length or max_seq_length
             tokenizer = tokenizer if tokenizer is not None else load_tokenizer(spec.transformer_dirs["QRY"])
         self.query_model, self.doc_model = query_model, doc_model
-        self.pipe = TextPipeline(tokenizer, max_seq_length)
+        self.pipe = TextPipeline(tokenizer, max_seq_length, frame=frame)
         self.method = method
 
     def _encode(self, model, texts, convert_to_tensor=False, normalize_embeddings=False, **kwargs):

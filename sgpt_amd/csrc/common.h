@@ -433,6 +433,11 @@ void launch_rope(void* qk, int dtype, long ld, long k_off, const int* pos, const
 // half-split rotary embedding (HF rotate_half: the Llama family), in place on q (H heads, column 0) and k (H_kv heads, column k_off)
 void launch_rope_half(void* qk, int dtype, long ld, long k_off, const int* pos, const float* sin_t, const float* cos_t, int T,
                       int H, int H_kv, int dh, int max_pos, hipStream_t s);
+// per-head RMSNorm (gains q_g / k_g fp32 [dh], dh 64 | 128) fused with launch_rope_half's rotation, in place; range_flag (f16, or null):
+// raised when a rounded magnitude reaches RANGE_LIMIT
+void launch_qknorm_rope_half(void* qk, int dtype, long ld, long k_off, const int* pos, const float* sin_t, const float* cos_t,
+                             const float* q_g, const float* k_g, float eps, int T, int H, int H_kv, int dh, int max_pos, int* range_flag,
+                             hipStream_t s);
 // BLOOM fused QKV rows [n_head, 3, head_dim] -> [q rows | k rows | v rows] (row_len floats per row; 1 for the bias)
 void launch_qkv_deinterleave(const float* src, float* dst, int H, int dh, long row_len, hipStream_t s);
 void launch_fill_rand(void* p, long n, int dtype, unsigned seed, float scale, hipStream_t s);

@@ -512,6 +512,75 @@ __global__ __launch_bounds__(256) void rope_half_kernel(T* __restrict__ buf, lon
     }
 }
 
+// ---- per-head RMSNorm of q and k fused with the half-split rotary (HF:qwen3/modeling_qwen3.py Qwen3Attention: q_norm / k_norm over
+// head_dim, then apply_rotary_pos_emb) ----
+// For every token and head: n = x * rsqrt(mean_over_head_dim(x^2) + eps) * g (g = q_g for the H query heads, k_g for the H_kv key heads,
+// fp32 [DH] shared by the heads; HF's order: x * rstd first, then * g), then rope_half_kernel's rotation of n, rounded once.  The
+// thread-to-element map is rope_half_kernel's -- four consecutive i and their partners i + DH/2 per thread, 16- / 8-byte words -- so a
+// head is DH / 8 consecutive lanes (8 | 16: aligned inside a wave, 256 % (DH / 8) == 0) and its square sum a butterfly over those
+// lanes.  Threads past the last head carry zeros through the butterfly and store nothing.  f16: the rounded values pass the range
+// tracker (a gain is not bounded at load time).
+template <typename T, int DH>
+__global__ __launch_bounds__(256) void qknorm_rope_half_kernel(T* __restrict__ buf, long ld, long k_off, const int* __restrict__ pos,
+                                                               const float* __restrict__ sin_t, const float* __restrict__ cos_t,
+                                                               const float* __restrict__ q_g, const float* __restrict__ k_g, float eps,
+                                                               int Tn, int H, int H_kv, int max_pos, int* __restrict__ range_flag) {
+    constexpr int half = DH / 2, qpt = half / 4;        // quads (= lanes) per head
+    const long per_tok = (long)(H + H_kv) * qpt;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = idx < (long)Tn * per_tok;         // (whole heads: the count is a multiple of qpt)
+    float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
+    T *lo = nullptr, *hi = nullptr;
+    int tkn = 0, h = 0, i = 0;
+    if (live) {
+        tkn = (int)(idx / per_tok);
+        const int rem = (int)(idx - (long)tkn * per_tok);
+        h = rem / qpt; i = (rem - h * qpt) * 4;
+        // heads [0, H): q at column h * DH; heads [H, H + H_kv): k at column k_off + (h - H) * DH
+        lo = buf + (long)tkn * ld + (h < H ? (long)h * DH : k_off + (long)(h - H) * DH) + i;
+        hi = lo + half;
+        if constexpr (sizeof(T) == 4) {
+            const float4 va = *reinterpret_cast<const float4*>(lo), vb = *reinterpret_cast<const float4*>(hi);
+            a[0] = va.x; a[1] = va.y; a[2] = va.z; a[3] = va.w; b[0] = vb.x; b[1] = vb.y; b[2] = vb.z; b[3] = vb.w;
+        } else {
+            const uint2 ua = *reinterpret_cast<const uint2*>(lo), ub = *reinterpret_cast<const uint2*>(hi);
+            a[0] = Half<T>::lo(ua.x); a[1] = Half<T>::hi(ua.x); a[2] = Half<T>::lo(ua.y); a[3] = Half<T>::hi(ua.y);
+            b[0] = Half<T>::lo(ub.x); b[1] = Half<T>::hi(ub.x); b[2] = Half<T>::lo(ub.y); b[3] = Half<T>::hi(ub.y);
+        }
+    }
+    float ss = (a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3]) + ((b[0] * b[0] + b[1] * b[1]) + (b[2] * b[2] + b[3] * b[3]));
+#pragma unroll
+    for (int o = qpt / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    RangeTrack<T> range;
+    if (live) {
+        const float rstd = 1.0f / sqrtf(ss / (float)DH + eps);
+        const float* g = h < H ? q_g : k_g;
+        const float4 ga = *reinterpret_cast<const float4*>(g + i), gb = *reinterpret_cast<const float4*>(g + half + i);
+        // the position is clamped into the tables, as rope_kernel does
+        int ps = pos[tkn]; ps = ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps);
+        const float4 sn4 = *reinterpret_cast<const float4*>(sin_t + (long)ps * half + i);
+        const float4 cs4 = *reinterpret_cast<const float4*>(cos_t + (long)ps * half + i);
+        const float gav[4] = {ga.x, ga.y, ga.z, ga.w}, gbv[4] = {gb.x, gb.y, gb.z, gb.w};
+        const float sn[4] = {sn4.x, sn4.y, sn4.z, sn4.w}, cs[4] = {cs4.x, cs4.y, cs4.z, cs4.w};
+        float ra[4], rb[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float na = a[u] * rstd * gav[u], nb = b[u] * rstd * gbv[u];
+            ra[u] = na * cs[u] - nb * sn[u];
+            rb[u] = nb * cs[u] + na * sn[u];
+        }
+        if constexpr (sizeof(T) == 4) {
+            *reinterpret_cast<float4*>(lo) = make_float4(ra[0], ra[1], ra[2], ra[3]);
+            *reinterpret_cast<float4*>(hi) = make_float4(rb[0], rb[1], rb[2], rb[3]);
+        } else {
+            range.note(ra[0], ra[1]); range.note(ra[2], ra[3]); range.note(rb[0], rb[1]); range.note(rb[2], rb[3]);
+            *reinterpret_cast<uint2*>(lo) = make_uint2(Half<T>::pack2(ra[0], ra[1]), Half<T>::pack2(ra[2], ra[3]));
+            *reinterpret_cast<uint2*>(hi) = make_uint2(Half<T>::pack2(rb[0], rb[1]), Half<T>::pack2(rb[2], rb[3]));
+        }
+    }
+    if constexpr (sizeof(T) != 4) range.finish(range_flag);
+}
+
 // BLOOM stores the QKV projection fused and head-interleaved: row h*3*dh + which*dh + c (HF:bloom:214).
 // Re-order to row which*d + h*dh + c so the Q/K and V projections are the same contiguous blocks as for GPT-Neo.
 __global__ __launch_bounds__(256) void qkv_deinterleave_kernel(const float* __restrict__ src, float* __restrict__ dst,
@@ -986,6 +1055,21 @@ void launch_rope_half(void* qk, int dtype, long ld, long k_off, const int* pos, 
         hipLaunchKernelGGL(rope_half_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (f16_t*)qk, ld, k_off, pos, sin_t, cos_t, T, H, H_kv, dh, max_pos);
     else
         hipLaunchKernelGGL(rope_half_kernel<float>, dim3(grid), dim3(256), 0, s, (float*)qk, ld, k_off, pos, sin_t, cos_t, T, H, H_kv, dh, max_pos);
+}
+
+void launch_qknorm_rope_half(void* qk, int dtype, long ld, long k_off, const int* pos, const float* sin_t, const float* cos_t,
+                             const float* q_g, const float* k_g, float eps, int T, int H, int H_kv, int dh, int max_pos, int* range_flag,
+                             hipStream_t s) {
+    const long n = (long)T * (H + H_kv) * (dh / 8);
+    const int grid = (int)((n + 255) / 256);
+#define SGPT_QKNORM(TT, DH)                                                                                                          \
+    hipLaunchKernelGGL((qknorm_rope_half_kernel<TT, DH>), dim3(grid), dim3(256), 0, s, (TT*)qk, ld, k_off, pos, sin_t, cos_t, q_g, k_g, \
+                       eps, T, H, H_kv, max_pos, range_flag)
+    if (dh != 64 && dh != 128) return;                  // (the callers refuse it: sgpt_qknorm_rope_half, check_desc)
+    if (dtype == DT_BF16) { if (dh == 64) SGPT_QKNORM(bf16_t, 64); else SGPT_QKNORM(bf16_t, 128); }
+    else if (dtype == DT_F16) { if (dh == 64) SGPT_QKNORM(f16_t, 64); else SGPT_QKNORM(f16_t, 128); }
+    else { if (dh == 64) SGPT_QKNORM(float, 64); else SGPT_QKNORM(float, 128); }
+#undef SGPT_QKNORM
 }
 
 void launch_qkv_deinterleave(const float* src, float* dst, int H, int dh, long row_len, hipStream_t s) {

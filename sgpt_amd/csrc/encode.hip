@@ -10,7 +10,9 @@ struct Fwd {
     const Family* F;      // the model's family row (host.h)
     const int32_t *pos, *seq_off, *seq_len;
     int B, T, max_alloc;
-    int d_kv;             // key / value width n_kv_heads * head_dim: d_model unless the family groups K / V
+    // query width n_heads * head_dim and key / value width n_kv_heads * head_dim: both d_model unless the family carries its own head
+    // dim (d_q) or groups K / V (d_kv)
+    int d_q, d_kv;
     int dt;               // operand format of the projections: SGPT_F32 | SGPT_BF16 | SGPT_F16
     int* range_flag;      // the model's range words (SGPT_F16 stores, e4m3 codes of the fp8-MFMA block) or null
     // can_split: the format takes a precision plan (prec[]); any_*: a block of this call splits that class; split: any of them.
@@ -18,8 +20,8 @@ struct Fwd {
     // qpath: query-sized kernels (qgemm.hip), qln: with the LayerNorms of a block inside their prologues.
     bool can_split, any_ln, any_att, any_ctx, any_h, split, fp8, mlp8, qpath, qln;
     float* x;             // residual stream fp32
-    // LayerNorm output; attention context; 16-bit: [T][d + d_kv] q | k + V^T [d_kv][T] (x3 attention: the lo halves att_lo elements
-    // behind), fp32: [T][d + 2 d_kv]; MLP hidden
+    // LayerNorm output; attention context [T][d_q]; 16-bit: [T][d_q + d_kv] q | k + V^T [d_kv][T] (x3 attention: the lo halves att_lo
+    // elements behind), fp32: [T][d_q + 2 d_kv]; MLP hidden
     void *a, *ctx, *qkv, *vt, *h;
     void* gu;             // SGPT_ARCH_LLAMA: fc1 output [T][2 ffn] = gate | up columns, the input of the SwiGLU row kernel
     void* a8; float* sa;  // fp8-MFMA block: LayerNorm output as e4m3 codes + one scale per row
@@ -55,18 +57,19 @@ void proj_qk_vt(const Fwd& f, const GemmArgs& g, int n_qk, int n_v, const void* 
     gemm(f.c, f.dt, EPI_VT, f.dt, v, f.s);
 }
 
-// q | k | v of every family: q rows of d columns, k and v of d_kv (= d unless the family groups K / V: then kv_group query heads share one)
+// q | k | v of every family: q rows of d_q columns, k and v of d_kv (both d unless the family says otherwise: kv_group query heads share
+// one key / value head); the context has q's width
 AttnArgs attn_base(const Fwd& f, const LayerW& l, int k_qkv) {
     const sgpt_model_desc& d = f.m->d;
-    const int dm = d.d_model;
+    const int dq = f.d_q;
     AttnArgs at{};
     at.dtype = f.dt;
-    at.seq_off = f.seq_off; at.B = f.B; at.H = d.n_heads; at.dh = dm / d.n_heads; at.window = l.is_local ? d.window : 0;
+    at.seq_off = f.seq_off; at.B = f.B; at.H = d.n_heads; at.dh = dq / d.n_heads; at.window = l.is_local ? d.window : 0;
     at.scale = d.attn_scale * pow2f(2 * k_qkv);      // q and k are both stored down-shifted
-    at.max_alloc_len = f.max_alloc; at.ctx = f.ctx; at.ldo = dm; at.alibi = f.m->alibi;
+    at.max_alloc_len = f.max_alloc; at.ctx = f.ctx; at.ldo = dq; at.alibi = f.m->alibi;
     at.q = f.qkv; at.kv_group = d.n_heads / d.n_kv_heads;
-    if (f.vt) { at.k = (bf16_t*)f.qkv + dm; at.v = f.vt; at.ldq = dm + f.d_kv; at.ldvt = f.T; }
-    else { at.k = (float*)f.qkv + dm; at.v = (float*)f.qkv + dm + f.d_kv; at.ldq = dm + 2 * f.d_kv; }
+    if (f.vt) { at.k = (bf16_t*)f.qkv + dq; at.v = f.vt; at.ldq = dq + f.d_kv; at.ldvt = f.T; }
+    else { at.k = (float*)f.qkv + dq; at.v = (float*)f.qkv + dq + f.d_kv; at.ldq = dq + 2 * f.d_kv; }
     return at;
 }
 
@@ -114,19 +117,28 @@ sgpt_status block_bert16(const Fwd& f, const LayerW& l, int) {
 }
 
 // ---- the Llama / Mistral family (SGPT_ARCH_LLAMA; HF:llama/modeling_llama.py LlamaDecoderLayer): pre-RMSNorm, grouped K / V, half-split
-// rotary, SwiGLU, no bias ----
-//   a = RMS1(x) ; q | k | v = a W^T (d + 2 d_kv columns) ; rope_half(q, k) ; x += attention(kv_group) Wo^T ;
+// rotary, SwiGLU, no bias -- but the Q | K | V bias of a Qwen2 model (l.b_qkv) and the per-head q / k norm of a Qwen3 model (l.qn_g) ----
+//   a = RMS1(x) ; q | k | v = a W^T (+ b) (d_q + 2 d_kv columns) ; [q, k = RMS_head(q, k)] rope_half(q, k) ; x += attention(kv_group) Wo^T ;
 //   a = RMS2(x) ; gu = a [Wgate | Wup]^T ; h = silu(gate) * up ; x += h Wdown^T
 // No range shifts (every f16 store is tracked), no precision plan, bulk kernels at every layout.  l.b_o / l.b_proj are the model's
 // zero vector (the residual epilogue reads a bias).
+
+// the rotary on q (column 0) and k (column d_q) of the projection buffer, behind the head norm where the layer has its gains
+void rope_llama(const Fwd& f, const LayerW& l, int dt, long ld, int dh) {
+    const sgpt_model_desc& d = f.m->d;
+    if (l.qn_g)
+        launch_qknorm_rope_half(f.qkv, dt, ld, f.d_q, f.pos, f.m->rot_sin, f.m->rot_cos, l.qn_g, l.kn_g, d.ln_eps, f.T, d.n_heads, d.n_kv_heads,
+                                dh, d.max_pos, f.range_flag, f.s);
+    else launch_rope_half(f.qkv, dt, ld, f.d_q, f.pos, f.m->rot_sin, f.m->rot_cos, f.T, d.n_heads, d.n_kv_heads, dh, d.max_pos, f.s);
+}
 sgpt_status block_llama_f32(const Fwd& f, const LayerW& l, int) {
     const sgpt_model_desc& d = f.m->d;
-    const int dm = d.d_model, ffn = d.d_ffn, T = f.T, dh = dm / d.n_heads, dkv = f.d_kv;
+    const int dm = d.d_model, ffn = d.d_ffn, T = f.T, dq = f.d_q, dh = dq / d.n_heads, dkv = f.d_kv;
     launch_rmsnorm(f.x, l.ln1_g, f.a, SGPT_F32, T, dm, d.ln_eps, nullptr, f.s);
-    gemm(f.c, SGPT_F32, EPI_STORE, SGPT_F32, proj(f, f.a, dm, l.w_qkv, dm + 2 * dkv, dm, f.qkv, dm + 2 * dkv, nullptr), f.s);
-    launch_rope_half(f.qkv, SGPT_F32, dm + 2 * dkv, dm, f.pos, f.m->rot_sin, f.m->rot_cos, T, d.n_heads, d.n_kv_heads, dh, d.max_pos, f.s);
+    gemm(f.c, SGPT_F32, EPI_STORE, SGPT_F32, proj(f, f.a, dm, l.w_qkv, dq + 2 * dkv, dm, f.qkv, dq + 2 * dkv, l.b_qkv), f.s);
+    rope_llama(f, l, SGPT_F32, dq + 2 * dkv, dh);
     launch_attn_f32(attn_base(f, l, 0), f.s);
-    gemm(f.c, SGPT_F32, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dm, l.w_o, dm, dm, f.x, dm, l.b_o, f.x), f.s);
+    gemm(f.c, SGPT_F32, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dq, l.w_o, dm, dq, f.x, dm, l.b_o, f.x), f.s);
     launch_rmsnorm(f.x, l.ln2_g, f.a, SGPT_F32, T, dm, d.ln_eps, nullptr, f.s);
     gemm(f.c, SGPT_F32, EPI_STORE, SGPT_F32, proj(f, f.a, dm, l.w_fc, 2 * ffn, dm, f.gu, 2 * ffn, nullptr), f.s);
     launch_swiglu(f.gu, f.h, SGPT_F32, T, ffn, nullptr, f.s);
@@ -137,12 +149,12 @@ sgpt_status block_llama_f32(const Fwd& f, const LayerW& l, int) {
 // 16-bit: the context shares a's buffer (a is consumed by the Q | K and V projections before the attention writes)
 sgpt_status block_llama16(const Fwd& f, const LayerW& l, int) {
     const sgpt_model_desc& d = f.m->d;
-    const int dm = d.d_model, ffn = d.d_ffn, T = f.T, dt = f.dt, dh = dm / d.n_heads, dkv = f.d_kv;
+    const int dm = d.d_model, ffn = d.d_ffn, T = f.T, dt = f.dt, dq = f.d_q, dh = dq / d.n_heads, dkv = f.d_kv;
     launch_rmsnorm(f.x, l.ln1_g, f.a, dt, T, dm, d.ln_eps, f.range_flag, f.s);
-    proj_qk_vt(f, proj(f, f.a, dm, l.w_qkv, dm + dkv, dm, f.qkv, dm + dkv, nullptr), dm + dkv, dkv);
-    launch_rope_half(f.qkv, dt, dm + dkv, dm, f.pos, f.m->rot_sin, f.m->rot_cos, T, d.n_heads, d.n_kv_heads, dh, d.max_pos, f.s);
+    proj_qk_vt(f, proj(f, f.a, dm, l.w_qkv, dq + dkv, dm, f.qkv, dq + dkv, l.b_qkv), dq + dkv, dkv);
+    rope_llama(f, l, dt, dq + dkv, dh);
     launch_attn_bf16(attn_base(f, l, 0), f.s);
-    gemm(f.c, dt, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dm, l.w_o, dm, dm, f.x, dm, l.b_o, f.x), f.s);
+    gemm(f.c, dt, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dq, l.w_o, dm, dq, f.x, dm, l.b_o, f.x), f.s);
     launch_rmsnorm(f.x, l.ln2_g, f.a, dt, T, dm, d.ln_eps, f.range_flag, f.s);
     gemm(f.c, dt, EPI_STORE, dt, proj(f, f.a, dm, l.w_fc, 2 * ffn, dm, f.gu, 2 * ffn, nullptr), f.s);
     launch_swiglu(f.gu, f.h, dt, T, ffn, f.range_flag, f.s);
@@ -341,7 +353,8 @@ sgpt_status plan(Fwd& f, int n_layers_run, float** lp) {
     const size_t esz = bf ? 2 : 4;
     f.fp8 = m->d.compute_dtype == SGPT_FP8W || fp8m;
     f.dt = !bf ? SGPT_F32 : (m->d.compute_dtype == SGPT_F16 ? SGPT_F16 : SGPT_BF16);
-    f.d_kv = m->d.n_kv_heads * (dm / m->d.n_heads);
+    f.d_q = m->d.n_heads * head_dim(m->d); f.d_kv = m->d.n_kv_heads * head_dim(m->d);
+    const size_t dq = f.d_q, dkv = f.d_kv;
     // Precision plan (prec[]): a split class is stored as [hi | lo | hi] rows of 3 x its width (the consuming GEMM contracts over
     // all three blocks against [W_hi | W_hi | W_lo]; a consumer that is not split reads the first block alone).  Any split at
     // all: the attention context gets its own buffer (the LayerNorm buffer has 3 d rows then).
@@ -371,9 +384,14 @@ sgpt_status plan(Fwd& f, int n_layers_run, float** lp) {
     size_t off = 0;
     auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
     const size_t o_x = carve((size_t)T * dm * 4);                        // residual stream fp32
-    const size_t o_a = carve((size_t)T * dm * esz * (f.any_ln ? 3 : 1));    // LN output (GPT-Neo: also attention ctx)
+    // LN output [T][d]; where the attention context [T][d_q] shares the buffer it holds the wider of the two
+    const size_t o_a = carve((size_t)T * (dq > (size_t)dm ? dq : (size_t)dm) * esz * (f.any_ln ? 3 : 1));
     const size_t o_c = (gptj || f.split) ? carve((size_t)T * dm * esz * (f.any_ctx ? 3 : 1)) : o_a;   // GPT-J: ctx separate (ln_1 output feeds the MLP too)
-    const size_t qkv_bytes = ((size_t)T + SLACK) * 3 * dm * esz;
+    // q | k rows of d_q + d_kv columns with V^T (d_kv rows) behind them, or q | k | v rows: (T + SLACK) rows of d_q + 2 d_kv columns.
+    // 16-bit: the attention loads query fragments up to 255 rows past the last sequence -- never used, but inside this carve
+    size_t qkv_elems = ((size_t)T + SLACK) * (dq + 2 * dkv);
+    if (bf && ((size_t)T + 256) * (dq + dkv) > qkv_elems) qkv_elems = ((size_t)T + 256) * (dq + dkv);
+    const size_t qkv_bytes = qkv_elems * esz;
     const size_t o_qkv = carve(qkv_bytes * (f.any_att ? 2 : 1));         // 16-bit: q | k rows + V^T (x3 attention: the lo halves behind); fp32: q | k | v rows
     const size_t o_h = carve((size_t)T * ffn * esz * (f.any_h ? 3 : 1));                   // MLP hidden (FP8M: e4m3 codes in the same region)
     const size_t o_gu = f.F->swiglu ? carve((size_t)T * 2 * ffn * esz) : 0;                     // SGPT_ARCH_LLAMA: fc1 output, gate | up columns
@@ -386,7 +404,7 @@ sgpt_status plan(Fwd& f, int n_layers_run, float** lp) {
     f.range_flag = (f.mlp8 || f.dt == SGPT_F16) ? (int*)m->range_dev : nullptr;
     f.x = (float*)(base + o_x); f.a = base + o_a; f.ctx = base + o_c; f.qkv = base + o_qkv; f.h = base + o_h;
     if (f.F->swiglu) f.gu = base + o_gu;
-    f.vt = bf ? (void*)((bf16_t*)f.qkv + ((size_t)T + SLACK) * 2 * dm) : nullptr;
+    f.vt = bf ? (void*)((bf16_t*)f.qkv + ((size_t)T + SLACK) * (dq + dkv)) : nullptr;
     if (f.mlp8) { f.a8 = base + o_a8; f.sa = (float*)(base + o_sa); }
     if (lp) *lp = (float*)(base + o_lp);
     f.att_lo = (long)(qkv_bytes / 2);      // element distance of the lo halves of q | k and of V^T (x3 attention)
@@ -398,17 +416,20 @@ sgpt_status plan(Fwd& f, int n_layers_run, float** lp) {
 // the attention context has its own buffer (GPT-J) -- the filler rows past the last sequence.  The
 // workspace is reused across calls / dtypes, so stale bytes there can decode to NaN.
 sgpt_status zero_overread(const Fwd& f) {
-    sgpt_ctx* c = f.c; const size_t T = f.T, dm = f.m->d.d_model, dkv = f.d_kv, esz = f.vt ? 2 : 4;
-    if (f.vt)            // q | k rows of d + d_kv columns, V^T of d_kv rows; x3 attention: their lo halves too
+    sgpt_ctx* c = f.c; const size_t T = f.T, dm = f.m->d.d_model, dq = f.d_q, dkv = f.d_kv, esz = f.vt ? 2 : 4;
+    if (f.vt)            // q | k rows of d_q + d_kv columns, V^T of d_kv rows; x3 attention: their lo halves too
         for (long lo = 0; lo <= (f.any_att ? f.att_lo : 0); lo += f.att_lo) {
-            HIPC(c, hipMemsetAsync((bf16_t*)f.qkv + lo + T * (dm + dkv), 0, SLACK * (dm + dkv) * esz, f.s));
+            HIPC(c, hipMemsetAsync((bf16_t*)f.qkv + lo + T * (dq + dkv), 0, SLACK * (dq + dkv) * esz, f.s));
             HIPC(c, hipMemsetAsync((bf16_t*)f.vt + lo + T * dkv, 0, SLACK * dkv * esz, f.s));
         }
-    else if (f.F->slack_f32) HIPC(c, hipMemsetAsync((float*)f.qkv + T * (dm + 2 * dkv), 0, SLACK * (dm + 2 * dkv) * esz, f.s));
+    else if (f.F->slack_f32) HIPC(c, hipMemsetAsync((float*)f.qkv + T * (dq + 2 * dkv), 0, SLACK * (dq + 2 * dkv) * esz, f.s));
     // (query path with the LayerNorm inside the projections: no LayerNorm launch fills the buffer the context shares with it)
     // (post-LN family in fp32: no LayerNorm ever writes the buffer the context lives in)
     if (f.m->d.arch == SGPT_ARCH_GPTJ || f.mlp8 || f.split || f.qln || (f.F->post_ln && !f.vt))
         HIPC(c, hipMemsetAsync(f.ctx, 0, T * dm * esz * (f.any_ctx ? 3 : 1), f.s));   // (fp8: stale bytes would decode to NaN codes)
+    // (a context wider than the norm output it shares the buffer with: the norm fills T * d elements, and the filler rows of the rest
+    // feed the out-projection -- stale bytes there would raise the f16 range word from rows that belong to no sequence)
+    else if (dq > dm) HIPC(c, hipMemsetAsync(f.ctx, 0, T * dq * esz, f.s));
     return SGPT_OK;
 }
 

@@ -26,7 +26,8 @@ struct LayerW {
     void* w_fc = nullptr;    // [ffn, d]
     void* w_proj = nullptr;  // [d, ffn]
     float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *b_o, *b_fc, *b_proj;
-    float* b_qkv = nullptr;  // BLOOM: [3d] de-interleaved (q | k | v) projection bias
+    float* b_qkv = nullptr;  // BLOOM: [3d] de-interleaved (q | k | v) projection bias; SGPT_ARCH_LLAMA: [d_q + 2 d_kv] when the model has one (Qwen2)
+    float *qn_g = nullptr, *kn_g = nullptr;   // SGPT_ARCH_LLAMA: per-head RMSNorm gains of q and k [head_dim] when the model has them (Qwen3)
     // SGPT_FP8W: w_* hold e4m3fn codes, s_* the per-output-channel power-of-two scales
     float *s_qkv = nullptr, *s_o = nullptr, *s_fc = nullptr, *s_proj = nullptr;
     int is_local = 0;
@@ -133,6 +134,9 @@ constexpr Family FAMILIES[] = {
 constexpr int N_FAMILIES = sizeof(FAMILIES) / sizeof(FAMILIES[0]);
 static_assert(SGPT_ARCH_GPTNEO == 0 && SGPT_ARCH_GPTJ == 1 && SGPT_ARCH_BLOOM == 2 && SGPT_ARCH_BERT == 3 && SGPT_ARCH_LLAMA == 4 && N_FAMILIES == 5, "FAMILIES is indexed by SGPT_ARCH_*");
 inline const Family& family(int arch) { return FAMILIES[arch]; }
+// head dim of a descriptor: SGPT_ARCH_LLAMA carries an explicit one in rotary_dim (0 = d_model / n_heads), so n_heads * head_dim -- the
+// query width d_q -- need not be d_model there
+inline int head_dim(const sgpt_model_desc& d) { return d.arch == SGPT_ARCH_LLAMA && d.rotary_dim > 0 ? d.rotary_dim : d.d_model / d.n_heads; }
 // grow-only workspace (ctx.hip)
 sgpt_status ensure(sgpt_ctx* c, void** p, size_t* have, size_t need);
 

@@ -12,7 +12,7 @@ sgpt_status check_desc(sgpt_ctx* c, const sgpt_model_desc* d) {
     const Family& F = family(d->arch); const std::string fam = std::string(F.name) + ": ";
     const int dm = d->d_model, ffn = d->d_ffn, H = d->n_heads, cd = d->compute_dtype;
     if (dm % 128 || ffn % 128 || H <= 0 || dm % H) return fail(c, SGPT_ERR_INVALID, "d_model and d_ffn must be multiples of 128");
-    const int dh = dm / H;
+    const int dh = head_dim(*d);
     const bool fp8 = cd == SGPT_FP8W || cd == SGPT_FP8M, split = d->qk_split != 0 || d->split_weights != 0;
     if (cd != SGPT_F32 && dh != 64 && dh != 128 && dh != 256) return fail(c, SGPT_ERR_INVALID, "16-bit attention supports head_dim 64, 128 or 256");
     if (dh > 256 || dh % 4) return fail(c, SGPT_ERR_INVALID, "head_dim must be <= 256 and a multiple of 4");
@@ -28,6 +28,11 @@ sgpt_status check_desc(sgpt_ctx* c, const sgpt_model_desc* d) {
     if (F.window == WIN_ZERO && d->window != 0) return fail(c, SGPT_ERR_INVALID, fam + "window must be 0");
     if (F.window == WIN_NONNEG && d->window < 0) return fail(c, SGPT_ERR_INVALID, fam + "window >= 0");
     if (!F.gqa && d->n_kv_heads != 0 && d->n_kv_heads != H) return fail(c, SGPT_ERR_INVALID, "n_kv_heads (grouped K / V) belongs to SGPT_ARCH_LLAMA");
+    // an explicit head dim (SGPT_ARCH_LLAMA, rotary_dim > 0): the query width n_heads * head_dim is the K of the out-projection
+    if (d->arch == SGPT_ARCH_LLAMA && d->rotary_dim > 0 && (H * d->rotary_dim) % 128)
+        return fail(c, SGPT_ERR_INVALID, fam + "n_heads * rotary_dim (the query width) must be a multiple of 128");
+    if (d->arch == SGPT_ARCH_LLAMA && d->rotary_dim > 0 && H * d->rotary_dim > 4096)
+        return fail(c, SGPT_ERR_INVALID, fam + "n_heads * rotary_dim (the query width) > 4096 not supported");
     return SGPT_OK;
 }
 
@@ -86,9 +91,9 @@ struct Loader {
         const float* src = find(name, rows * cols);
         if (src) launch_pack_split_rows(src, rows, cols, dst3, f16 ? DT_F16 : DT_BF16, 0);
     }
-    // the four packed matrices of a block: w_qkv [qkv_rows, d], w_o [d, d], w_fc [fc_rows, d], w_proj [d, ffn]
-    void alloc_w(LayerW& l, size_t qkv_rows, size_t fc_rows) {
-        l.w_qkv = dalloc(qkv_rows * dm * esz); l.w_o = dalloc((size_t)dm * dm * esz);
+    // the four packed matrices of a block: w_qkv [qkv_rows, d], w_o [d, o_cols], w_fc [fc_rows, d], w_proj [d, ffn]
+    void alloc_w(LayerW& l, size_t qkv_rows, size_t fc_rows, size_t o_cols) {
+        l.w_qkv = dalloc(qkv_rows * dm * esz); l.w_o = dalloc((size_t)dm * o_cols * esz);
         l.w_fc = dalloc(fc_rows * dm * esz); l.w_proj = dalloc((size_t)dm * ffn * esz);
     }
     // What follows a family's own embedding tensors, in the order the tensors have always been read: the LM head, the final norm the
@@ -149,7 +154,7 @@ void load_decoder(Loader& L) {
         l.b_o = gptj ? m->zero_bias : L.copy_f32(wo + ".bias", dm);
         l.b_fc = L.copy_f32(p + fc1 + ".bias", ffn);
         l.b_proj = L.copy_f32(p + fc2 + ".bias", dm);
-        L.alloc_w(l, (size_t)3 * dm, ffn);
+        L.alloc_w(l, (size_t)3 * dm, ffn, dm);
         if (fp8) {
             l.s_qkv = (float*)L.dalloc((size_t)3 * dm * 4); l.s_o = (float*)L.dalloc((size_t)dm * 4);
             l.s_fc = (float*)L.dalloc((size_t)ffn * 4); l.s_proj = (float*)L.dalloc((size_t)dm * 4);
@@ -206,7 +211,7 @@ void load_bert(Loader& L) {
         l.b_fc = L.copy_f32(p + "intermediate.dense.bias", ffn);
         l.b_proj = L.copy_f32(p + "output.dense.bias", dm);
         l.b_qkv = (float*)L.dalloc((size_t)3 * dm * 4);
-        L.alloc_w(l, (size_t)3 * dm, ffn);
+        L.alloc_w(l, (size_t)3 * dm, ffn, dm);
         if (L.st != SGPT_OK) break;
         const char* qkv[3] = {"query", "key", "value"};
         for (int j = 0; j < 3 && L.st == SGPT_OK; ++j) {          // fused [q rows | k rows | v rows], biases alike
@@ -222,15 +227,20 @@ void load_bert(Loader& L) {
 }
 
 // LLAMA layers.N.input_layernorm / self_attn.{qkv_proj (q | k | v rows fused by the caller), o_proj} / post_attention_layernorm /
-//       mlp.{gate_up_proj (gate rows, then up rows), down_proj}; no biases      (HF:llama/modeling_llama.py LlamaDecoderLayer)
-// The RMSNorm gains carry no load-time bound (the f16 stores of rmsnorm_kernel are range-tracked at run time): shifts stay 0.
+//       mlp.{gate_up_proj (gate rows, then up rows), down_proj}             (HF:llama/modeling_llama.py LlamaDecoderLayer)
+// Optional, decided on layer 0 and then required of every layer: self_attn.qkv_proj.bias [d_q + 2 d_kv] (HF:qwen2/modeling_qwen2.py
+// Qwen2Attention) and self_attn.{q_norm,k_norm}.weight [head_dim], both or neither (HF:qwen3/modeling_qwen3.py Qwen3Attention).
+// The RMSNorm gains carry no load-time bound (the f16 stores of the norm kernels are range-tracked at run time): shifts stay 0.
 void load_llama(Loader& L) {
     sgpt_model* m = L.m; const sgpt_model_desc* d = L.d;
-    const int dm = L.dm, ffn = L.ffn; const int64_t dkv = (int64_t)m->d.n_kv_heads * L.dh;
+    const int dm = L.dm, ffn = L.ffn; const int64_t dq = (int64_t)L.H * L.dh, dkv = (int64_t)m->d.n_kv_heads * L.dh;
     // no position table: half-split rotary on q / k (tables from the host, include/sgpt_hip.h)
     m->rot_sin = L.copy_f32("rotary.sin", (int64_t)d->max_pos * (L.dh / 2));
     m->rot_cos = L.copy_f32("rotary.cos", (int64_t)d->max_pos * (L.dh / 2));
     L.head();
+    const std::string p0 = std::string(family(d->arch).prefix) + "0.self_attn.";
+    const bool has_bias = L.byname.count(p0 + "qkv_proj.bias") != 0;
+    const bool has_norm = L.byname.count(p0 + "q_norm.weight") != 0 || L.byname.count(p0 + "k_norm.weight") != 0;
     for (int i = 0; i < d->n_layers && L.st == SGPT_OK; ++i) {
         const std::string p = family(d->arch).prefix + std::to_string(i) + ".";
         LayerW& l = m->L[i];
@@ -239,10 +249,21 @@ void load_llama(Loader& L) {
         l.ln2_g = L.copy_f32(p + "post_attention_layernorm.weight", dm);
         l.ln1_b = l.ln2_b = l.b_fc = nullptr;
         l.b_o = l.b_proj = m->zero_bias;       // the residual epilogue reads a bias vector: zeros
-        L.alloc_w(l, dm + 2 * dkv, (size_t)2 * ffn);
+        // a later layer that has what layer 0 lacks: the tensor layer 0 misses is named
+        if (!has_bias && L.byname.count(p + "self_attn.qkv_proj.bias")) L.st = fail(L.c, SGPT_ERR_MISSING, "missing weight tensor: " + p0 + "qkv_proj.bias");
+        if (!has_norm && (L.byname.count(p + "self_attn.q_norm.weight") || L.byname.count(p + "self_attn.k_norm.weight")))
+            L.st = fail(L.c, SGPT_ERR_MISSING, "missing weight tensor: " + p0 + "q_norm.weight");
         if (L.st != SGPT_OK) break;
-        L.pack_w(p + "self_attn.qkv_proj.weight", dm + 2 * dkv, dm, l.w_qkv, 0, nullptr);
-        L.pack_w(p + "self_attn.o_proj.weight", dm, dm, l.w_o, 0, nullptr);
+        if (has_bias) l.b_qkv = L.copy_f32(p + "self_attn.qkv_proj.bias", dq + 2 * dkv);
+        if (has_norm) {
+            l.qn_g = L.copy_f32(p + "self_attn.q_norm.weight", L.dh);
+            l.kn_g = L.copy_f32(p + "self_attn.k_norm.weight", L.dh);
+            if (L.f16 && l.qn_g && l.kn_g) { launch_absmax(l.qn_g, L.dh, L.stats + 1, 0); launch_absmax(l.kn_g, L.dh, L.stats + 1, 0); }
+        }
+        L.alloc_w(l, dq + 2 * dkv, (size_t)2 * ffn, dq);
+        if (L.st != SGPT_OK) break;
+        L.pack_w(p + "self_attn.qkv_proj.weight", dq + 2 * dkv, dm, l.w_qkv, 0, nullptr);
+        L.pack_w(p + "self_attn.o_proj.weight", dm, dq, l.w_o, 0, nullptr);
         L.pack_w(p + "mlp.gate_up_proj.weight", (int64_t)2 * ffn, dm, l.w_fc, 0, nullptr);
         L.pack_w(p + "mlp.down_proj.weight", dm, ffn, l.w_proj, 0, nullptr);
     }
@@ -314,7 +335,7 @@ sgpt_status sgpt_model_load(sgpt_ctx* c, const sgpt_model_desc* d, const sgpt_te
     if (sgpt_status st = check_desc(c, d)) return st;
     const int cd = d->compute_dtype;
     Loader L{};                // (st = SGPT_OK)
-    L.c = c; L.d = d; L.dm = d->d_model; L.ffn = d->d_ffn; L.H = d->n_heads; L.dh = L.dm / L.H;
+    L.c = c; L.d = d; L.dm = d->d_model; L.ffn = d->d_ffn; L.H = d->n_heads; L.dh = head_dim(*d);
     L.fp8 = cd == SGPT_FP8W || cd == SGPT_FP8M; L.f16 = cd == SGPT_F16; L.bf = cd == SGPT_BF16 || L.f16;
     L.esz = L.fp8 ? 1 : (L.bf ? 2 : 4);
     if (L.f16 && hipMalloc((void**)&L.stats, 16) != hipSuccess) return fail(c, SGPT_ERR_OOM, "hipMalloc failed");

@@ -453,6 +453,29 @@ sgpt_status sgpt_rope_half(sgpt_ctx* c, void* buf, int32_t dtype, int64_t ld, in
     return SGPT_OK;
 }
 
+sgpt_status sgpt_qknorm_rope_half(sgpt_ctx* c, void* buf, int32_t dtype, int64_t ld, int64_t k_off, const int32_t* pos, const float* sin_t,
+                                  const float* cos_t, int32_t T, int32_t H, int32_t H_kv, int32_t head_dim, int32_t max_pos,
+                                  const float* q_gamma, const float* k_gamma, float eps, void* stream) {
+    if (!c || !buf || !pos || !sin_t || !cos_t || T <= 0 || H <= 0 || H_kv <= 0 || head_dim <= 0 || max_pos <= 0)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_qknorm_rope_half: bad arguments");
+    if (!q_gamma || !k_gamma || !(eps >= 0.f) || !std::isfinite(eps))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_qknorm_rope_half: needs q_gamma, k_gamma and eps >= 0");
+    if (dtype != SGPT_F32 && dtype != SGPT_BF16 && dtype != SGPT_F16)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_qknorm_rope_half: dtype SGPT_F32 | SGPT_BF16 | SGPT_F16");
+    if (head_dim != 64 && head_dim != 128) return fail(c, SGPT_ERR_INVALID, "sgpt_qknorm_rope_half: head_dim 64 | 128");
+    // sgpt_rope_half's words per thread; a head's square sum is a butterfly over its head_dim / 8 lanes
+    const int64_t dq = (int64_t)H * head_dim, dk = (int64_t)H_kv * head_dim;
+    if (ld % 4 || k_off % 4 || k_off < dq || ld < k_off + dk || mis(buf, dtype == SGPT_F32 ? 16 : 8) || mis(sin_t, 16) || mis(cos_t, 16) ||
+        mis(q_gamma, 16) || mis(k_gamma, 16))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_qknorm_rope_half: ld, k_off % 4; k_off >= H * head_dim; ld >= k_off + H_kv * head_dim; "
+                                         "buf aligned to four elements, tables and gains to 16 bytes");
+    HIPC(c, hipSetDevice(c->device));
+    launch_qknorm_rope_half(buf, dtype, ld, k_off, pos, sin_t, cos_t, q_gamma, k_gamma, eps, T, H, H_kv, head_dim, max_pos,
+                            dtype == SGPT_F16 ? c->range_flag : nullptr, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
 sgpt_status sgpt_logprob_rows(sgpt_ctx* c, const float* logits, int64_t ld, int32_t V, const int32_t* targets, int32_t n,
                               float* out_logprob, int32_t* out_greedy, void* stream) {
     if (!c || !logits || !targets || !out_logprob || n <= 0 || V <= 0 || ld < V)

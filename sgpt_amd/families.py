@@ -24,7 +24,9 @@ class SGPTConfig:
     attention_layers: Optional[List[str]] = None
     layer_norm_epsilon: float = 1e-5
     model_type: str = "gpt_neo"          # a Family.model_type: "gpt_neo" (SGPT-125M/1.3B/2.7B) | "gptj" (SGPT-5.8B) | "bloom" | "bert" | "llama"
-    rotary_dim: int = 0                   # GPT-J only (HF GPTJConfig.rotary_dim = 64)
+    # GPT-J: HF GPTJConfig.rotary_dim (64).  "llama": the head dim where the config gives one (Qwen3: num_heads * head_dim need not be
+    # hidden_size); 0 = hidden_size // num_heads.  Read it through head_dim(cfg)
+    rotary_dim: int = 0
     num_kv_heads: Optional[int] = None    # "llama" only: key / value heads (grouped K / V); None = num_heads
     rope_theta: float = 10000.0           # "llama" only: base of the rotary frequencies
 
@@ -43,6 +45,13 @@ class SGPTConfig:
             if mt in fam.hf_model_types:
                 return fam.parse_config(c)
         raise NotImplementedError(f"model_type {mt!r}: GPT-Neo, GPT-J, BLOOM, BERT and Llama / Mistral are the families built here")
+
+
+def head_dim(cfg: SGPTConfig) -> int:
+    """The width of one attention head: a Llama-family config may carry its own in `rotary_dim`, every other one is hidden_size // num_heads."""
+    if cfg.model_type == "llama" and cfg.rotary_dim:
+        return cfg.rotary_dim
+    return cfg.hidden_size // cfg.num_heads
 
 
 # ---- HF config.json -> SGPTConfig, per family ----
@@ -81,23 +90,32 @@ def _parse_bert(c: dict) -> SGPTConfig:   # HF BertConfig (HF:bert/configuration
                       model_type="bert", window_size=0, attention_layers=["global"] * c["num_hidden_layers"])
 
 
-def _parse_llama(c: dict) -> SGPTConfig:  # HF LlamaConfig / MistralConfig: one family here (model_type "llama"), Mistral adds the window
+def _parse_llama(c: dict) -> SGPTConfig:
+    """HF LlamaConfig / MistralConfig / Qwen2Config / Qwen3Config: one family here (model_type "llama").  Mistral adds the window; Qwen2 a
+    bias on q / k / v and Qwen3 a per-head q / k norm, both read off the tensors and not off the config; Qwen3 its own head_dim."""
     mt = c["model_type"]
+    qwen = mt in ("qwen2", "qwen3")
     L, H, d = c["num_hidden_layers"], c["num_attention_heads"], c["hidden_size"]
     if c.get("hidden_act", "silu") != "silu":
         raise NotImplementedError(f"{mt}: hidden_act {c.get('hidden_act')!r} (only 'silu', the SwiGLU MLP, is built)")
+    # (Qwen2Config has no such switches: its q / k / v bias is part of the model; Qwen3's attention_bias would bias o_proj too)
     for key in ("attention_bias", "mlp_bias"):
-        if c.get(key):
+        if c.get(key) and mt != "qwen2":
             raise NotImplementedError(f"{mt}: {key} = true (the biased variants are not built)")
+    if qwen and c.get("use_sliding_window"):
+        raise NotImplementedError(f"{mt}: use_sliding_window = true (the per-layer window of the Qwen models is not built)")
     rs = c.get("rope_scaling")
     if rs is None and isinstance(c.get("rope_parameters"), dict) and c["rope_parameters"].get("rope_type", "default") != "default":
         rs = c["rope_parameters"]
     if rs is not None and rs.get("rope_type", rs.get("type", "default")) != "default":
         raise NotImplementedError(f"{mt}: rope_scaling {rs!r} (only the default rotary frequencies are built)")
-    if c.get("head_dim") is not None and c["head_dim"] * H != d:
+    if not qwen and c.get("head_dim") is not None and c["head_dim"] * H != d:
         raise NotImplementedError(f"{mt}: head_dim {c['head_dim']} with head_dim * num_attention_heads != hidden_size {d}")
     if d > 4096:
         raise NotImplementedError(f"{mt}: hidden_size {d} > 4096 (the row kernels hold one row of at most 4096 columns per wave)")
+    dh = c.get("head_dim") if qwen else None           # Llama / Mistral: head_dim * H == d holds, the config keeps rotary_dim 0
+    if qwen and (dh or d // H) not in (64, 128):
+        raise NotImplementedError(f"{mt}: head_dim {dh or d // H} (the attention and the head norm of this family are built for 64 and 128)")
     theta = c.get("rope_theta")
     if theta is None and isinstance(c.get("rope_parameters"), dict):
         theta = c["rope_parameters"].get("rope_theta")
@@ -112,7 +130,8 @@ def _parse_llama(c: dict) -> SGPTConfig:  # HF LlamaConfig / MistralConfig: one 
     return SGPTConfig(vocab_size=c["vocab_size"], max_position_embeddings=c["max_position_embeddings"], hidden_size=d, num_layers=L,
                       num_heads=H, intermediate_size=c["intermediate_size"], layer_norm_epsilon=c.get("rms_norm_eps", 1e-6),
                       model_type="llama", window_size=window, attention_layers=["local" if window else "global"] * L,
-                      num_kv_heads=c.get("num_key_value_heads") or H, rope_theta=float(theta if theta is not None else 10000.0))
+                      num_kv_heads=c.get("num_key_value_heads") or H, rope_theta=float(theta if theta is not None else 10000.0),
+                      rotary_dim=int(dh or 0))
 
 
 # ---- state dict -> the tensors include/sgpt_hip.h lists for the family, host tables included ----
@@ -140,24 +159,35 @@ def bert_state_dict(weights) -> dict:
 
 
 def llama_state_dict(weights) -> dict:
-    """HF LlamaModel / LlamaForCausalLM / Mistral* state dict -> the tensors include/sgpt_hip.h asks for under SGPT_ARCH_LLAMA: the
-    `model.` prefix and `lm_head.*` are dropped (as are `rotary_emb.inv_freq` buffers of older checkpoints), q_proj | k_proj | v_proj
-    are stacked into `self_attn.qkv_proj.weight` [d + 2 d_kv, d] and gate_proj | up_proj into `mlp.gate_up_proj.weight` [2 ffn, d]
-    (gate rows first).  A bias tensor of a projection means a biased variant, which is not built."""
+    """HF LlamaModel / LlamaForCausalLM / Mistral* / Qwen2* / Qwen3* state dict -> the tensors include/sgpt_hip.h asks for under
+    SGPT_ARCH_LLAMA: the `model.` prefix and `lm_head.*` are dropped (as are `rotary_emb.inv_freq` buffers of older checkpoints), q_proj |
+    k_proj | v_proj are stacked into `self_attn.qkv_proj.weight` [d_q + 2 d_kv, d] -- their biases, where the model has all three
+    (Qwen2), into `self_attn.qkv_proj.bias` -- and gate_proj | up_proj into `mlp.gate_up_proj.weight` [2 ffn, d] (gate rows first).
+    `self_attn.q_norm.weight` / `k_norm.weight` (Qwen3) pass through.  Any other bias tensor of a projection means a biased variant,
+    which is not built."""
     flat = {}
     for k, v in weights.items():
         k2 = k[len("model."):] if k.startswith("model.") else k
         if k.startswith("lm_head.") or k2.endswith("rotary_emb.inv_freq"):
             continue
-        if k2.endswith("_proj.bias"):
+        if k2.endswith("_proj.bias") and not k2.endswith(tuple("self_attn." + n + "_proj.bias" for n in ("q", "k", "v", "qkv"))):
             raise NotImplementedError(f"llama: {k} (the biased variants are not built)")
         flat[k2] = v
-    out, fuse = {}, (("self_attn.", ("q_proj", "k_proj", "v_proj"), "qkv_proj"), ("mlp.", ("gate_proj", "up_proj"), "gate_up_proj"))
+    qkv = ("q_proj", "k_proj", "v_proj")
+    part_bias = tuple("self_attn." + n + ".bias" for n in qkv)
+    for k in flat:                                       # a q / k / v bias: all three or none
+        if k.endswith(part_bias) and any(k[: k.rindex("self_attn.")] + b not in flat for b in part_bias):
+            raise NotImplementedError(f"llama: {k} without the other two of q_proj / k_proj / v_proj .bias (a QKV bias is all three)")
+    out, fuse = {}, (("self_attn.", qkv, "qkv_proj"), ("mlp.", ("gate_proj", "up_proj"), "gate_up_proj"))
     for k, v in flat.items():
+        if k.endswith(part_bias):                        # fused behind its q_proj.weight
+            continue
         for mod, parts, fused in fuse:
             if k.endswith(mod + parts[0] + ".weight"):
                 base = k[: -len(parts[0] + ".weight")]
                 out[base + fused + ".weight"] = torch.cat([_as_f32(flat[base + n + ".weight"]) for n in parts], dim=0)
+                if parts is qkv and base + "q_proj.bias" in flat:
+                    out[base + fused + ".bias"] = torch.cat([_as_f32(flat[base + n + ".bias"]) for n in parts], dim=0)
                 break
         else:
             if not any(k.endswith(mod + n + ".weight") for mod, parts, _ in fuse for n in parts):
@@ -208,7 +238,8 @@ class Family:
     # scaled_logits: attn_scale = 1 / sqrt(head_dim) (HF:gptj:148, HF:bloom:186).  False: 1.0 (HF:gpt_neo:110) -- the logits grow with the
     # width, so default_precise_qk() may turn the structural precise_qk rule on
     scaled_logits: bool = True
-    # rotary_dim: "none" (0) | "config" (cfg.rotary_dim) | "head_dim".  Rotary runs in place on 16-bit q / k: split-precision attention
+    # rotary_dim: "none" (0) | "config" (cfg.rotary_dim) | "head_dim" (head_dim(cfg): the family's own head dim travels in the descriptor's
+    # rotary_dim, include/sgpt_hip.h).  Rotary runs in place on 16-bit q / k: split-precision attention
     # is built for "none" only
     rotary_dim: str = "none"
     grouped_kv: bool = False              # n_kv_heads travels in the descriptor
@@ -238,9 +269,9 @@ FAMILIES = (
            prepare_weights=lambda c, w: dict(w, **{"alibi.slopes": alibi_slopes(c.num_heads)})),
     Family("bert", ("bert",), _lib.SGPT_ARCH_BERT, "BERT", _parse_bert, prepare_weights=lambda c, w: bert_state_dict(w), sgpt_modes=False,
            framing="cls_sep", dtype_advice="'f16', 'bf16' or 'fp32'", no_lm_head="lm_logprobs: a BERT model carries no causal LM head"),
-    Family("llama", ("llama", "mistral"), _lib.SGPT_ARCH_LLAMA, "Llama / Mistral", _parse_llama, rotary_dim="head_dim", grouped_kv=True,
+    Family("llama", ("llama", "mistral", "qwen2", "qwen3"), _lib.SGPT_ARCH_LLAMA, "Llama / Mistral", _parse_llama, rotary_dim="head_dim", grouped_kv=True,
            prepare_weights=lambda c, w: dict(llama_state_dict(w), **dict(zip(_ROTARY, rotary_tables_half(
-               c.max_position_embeddings, c.hidden_size // c.num_heads, c.rope_theta)))),
+               c.max_position_embeddings, head_dim(c), c.rope_theta)))),
            sgpt_modes=False, framing="bos_eos", dtype_advice="'bf16', 'f16' or 'fp32'",
            no_lm_head="lm_logprobs is not built for Llama / Mistral models (their LM head is not loaded)"),
 )
@@ -279,6 +310,39 @@ def synthetic_llama_weights(cfg: SGPTConfig, seed: int = 0, std: float = 0.02) -
         w[p + "self_attn.k_proj.weight"] = nrm(dkv, d)
         w[p + "self_attn.v_proj.weight"] = nrm(dkv, d)
         w[p + "self_attn.o_proj.weight"] = nrm(d, d)
+        w[p + "post_attention_layernorm.weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
+        w[p + "mlp.gate_proj.weight"] = nrm(ffn, d)
+        w[p + "mlp.up_proj.weight"] = nrm(ffn, d)
+        w[p + "mlp.down_proj.weight"] = nrm(d, ffn)
+    w["norm.weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
+    return w
+
+
+def synthetic_qwen_weights(cfg: SGPTConfig, seed: int = 0, qkv_bias: bool = False, qk_norm: bool = False, std: float = 0.02,
+                            bias_std: float = 0.1, gain_std: float = 0.1) -> Dict[str, np.ndarray]:
+    """Seeded random-init weights under HF Qwen2Model (qkv_bias) / Qwen3Model (qk_norm) state-dict names, a generator stream of its own
+    (synthetic_llama_weights keeps the one its fixtures record).  The q / k / v biases have std 0.1 -- five times the weights', so that
+    a dropped bias cannot pass a parity test -- and the head-norm gains are 1 + 0.1 N(0, 1)."""
+    rng = np.random.default_rng(seed)
+    d, ffn, dh = cfg.hidden_size, cfg.intermediate_size, head_dim(cfg)
+    dq, dkv = cfg.num_heads * dh, cfg.num_kv_heads * dh
+    f32 = np.float32
+
+    def nrm(*shape, s=std):
+        return (rng.standard_normal(shape, dtype=np.float32) * f32(s)).astype(f32)
+
+    w = {"embed_tokens.weight": nrm(cfg.vocab_size, d)}
+    for i in range(cfg.num_layers):
+        p = f"layers.{i}."
+        w[p + "input_layernorm.weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
+        for n, rows in (("q", dq), ("k", dkv), ("v", dkv)):
+            w[p + f"self_attn.{n}_proj.weight"] = nrm(rows, d)
+            if qkv_bias:
+                w[p + f"self_attn.{n}_proj.bias"] = nrm(rows, s=bias_std)
+        if qk_norm:
+            w[p + "self_attn.q_norm.weight"] = (1.0 + nrm(dh, s=gain_std)).astype(f32)
+            w[p + "self_attn.k_norm.weight"] = (1.0 + nrm(dh, s=gain_std)).astype(f32)
+        w[p + "self_attn.o_proj.weight"] = nrm(d, dq)
         w[p + "post_attention_layernorm.weight"] = (1.0 + nrm(d, s=0.1)).astype(f32)
         w[p + "mlp.gate_proj.weight"] = nrm(ffn, d)
         w[p + "mlp.up_proj.weight"] = nrm(ffn, d)

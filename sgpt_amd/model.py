@@ -17,8 +17,8 @@ import torch
 from . import _lib
 from ._lib import (ModelDesc, TensorView, POOL_MODES, SGPT_BF16, SGPT_F16, SGPT_F32, SGPT_FP8M, SGPT_FP8W, SgptRangeError,
                    SGPT_PREC_CLASSES, PC_LN1, PC_ATT, PC_CTX, PC_LN2, PC_H)
-from .families import (MAX_SEQ_LEN, SGPTConfig, alibi_slopes, bert_state_dict, family, llama_state_dict, rotary_tables,  # noqa: F401
-                       rotary_tables_half, synthetic_bert_weights, synthetic_llama_weights, synthetic_weights)
+from .families import (MAX_SEQ_LEN, SGPTConfig, alibi_slopes, bert_state_dict, family, head_dim, llama_state_dict, rotary_tables,  # noqa: F401
+                       rotary_tables_half, synthetic_bert_weights, synthetic_llama_weights, synthetic_qwen_weights, synthetic_weights)
 from .runtime import Context, get_context, _p, _stream_ptr
 
 # Precision probe thresholds: crest factor max|v| / rms(v) of an operand row above which 11-bit operands are not trusted.
@@ -222,7 +222,7 @@ def default_precise_qk(cfg: "SGPTConfig", dtype: str):
     and SGPT-125M at 3.2e-4 without any of it."""
     if dtype != "f16" or family(cfg.model_type).scaled_logits or cfg.hidden_size < 2048:
         return False
-    if cfg.hidden_size // cfg.num_heads not in (64, 128):
+    if head_dim(cfg) not in (64, 128):
         return "full"      # the split-precision attention exists for head_dim 64 / 128: the split Q / K projection alone (round 3's default)
     return "act+logits" if cfg.hidden_size < 2560 else "qkv+logits"
 
@@ -264,7 +264,7 @@ def model_desc(cfg: SGPTConfig, dtype: str, precise_qk, precision: str):
     """The sgpt_model_desc of a model (arguments as check_args returns them) and the layer_is_local array it points to: keep both."""
     fam = family(cfg.model_type)
     local = (C.c_uint8 * cfg.num_layers)(*[1 if a == "local" else 0 for a in cfg.attention_layers])
-    dh = cfg.hidden_size // cfg.num_heads
+    dh = head_dim(cfg)
     ln1, _, ctx = PRECISE_QK_PLANS[precise_qk] if precise_qk else (0, 0, 0)
     return ModelDesc(arch=fam.arch, n_layers=cfg.num_layers, d_model=cfg.hidden_size, n_heads=cfg.num_heads, d_ffn=cfg.intermediate_size,
                      vocab=cfg.vocab_size, max_pos=cfg.max_position_embeddings, window=cfg.window_size, ln_eps=cfg.layer_norm_epsilon,
@@ -333,7 +333,7 @@ class SGPTModel:
         desc, _local = model_desc(cfg, dtype, precise_qk, precision)     # (_local: the array desc.layer_is_local points to)
         self.precise_qk, self.precision = precise_qk, precision
         self.precision_report = None      # filled by the probe: crest factors [num_layers, 4] and what was decided
-        self._att_ok = family(cfg.model_type).rotary_dim == "none" and cfg.hidden_size // cfg.num_heads in (64, 128)   # split-precision attention: head_dim 64 / 128, no rotary
+        self._att_ok = family(cfg.model_type).rotary_dim == "none" and head_dim(cfg) in (64, 128)   # split-precision attention: head_dim 64 / 128, no rotary
         self._plan_pending = precision in ("auto", "auto-class")
         keep = [(n.encode(), t.to(device=self.device, dtype=torch.float32).contiguous()) for n, t in load_tensors(cfg, weights)]   # H2D staging only
         views = (TensorView * len(keep))(*[TensorView(n, t.data_ptr(), t.numel()) for n, t in keep])

@@ -406,6 +406,23 @@ class Context:
                                           sin.shape[0] if max_pos is None else int(max_pos), _stream_ptr(self.device)), "sgpt_rope_half")
         return buf
 
+    def qknorm_rope_half(self, buf: torch.Tensor, pos: torch.Tensor, sin: torch.Tensor, cos: torch.Tensor, q_gamma: torch.Tensor,
+                         k_gamma: torch.Tensor, H: int, H_kv: int, head_dim: int, k_off: int, eps: float = 1e-6, T: Optional[int] = None,
+                         max_pos: Optional[int] = None) -> torch.Tensor:
+        """The per-head RMSNorm of q and k (gains q_gamma / k_gamma fp32 [head_dim], shared by the heads) fused with rope_half, in place
+        on the first T rows of buf [rows, ld]; head_dim 64 | 128 (include/sgpt_hip.h::sgpt_qknorm_rope_half)."""
+        if buf.dtype not in DT_CODE or buf.stride(1) != 1:
+            raise ValueError("qknorm_rope_half: buf is fp32, bf16 or f16 with a unit column stride")
+        if sin.stride() != (head_dim // 2, 1) or cos.stride() != (head_dim // 2, 1):
+            raise ValueError("qknorm_rope_half: sin / cos are row-contiguous [max_pos, head_dim / 2]")
+        if q_gamma.shape != (head_dim,) or k_gamma.shape != (head_dim,):
+            raise ValueError("qknorm_rope_half: q_gamma / k_gamma are [head_dim]")
+        self._chk(self.lib.sgpt_qknorm_rope_half(self.handle, _p(buf), DT_CODE[buf.dtype], buf.stride(0), int(k_off), _p(pos), _p(sin),
+                                                 _p(cos), buf.shape[0] if T is None else int(T), H, H_kv, head_dim,
+                                                 sin.shape[0] if max_pos is None else int(max_pos), _p(self._f32c(q_gamma)),
+                                                 _p(self._f32c(k_gamma)), float(eps), _stream_ptr(self.device)), "sgpt_qknorm_rope_half")
+        return buf
+
     def lnf_pool(self, x: torch.Tensor, seq_off: torch.Tensor, seq_len: torch.Tensor, pad_left: Optional[torch.Tensor] = None,
                  ln=None, mode: str = "weightedmean", normalize: bool = False, position_weights: Optional[torch.Tensor] = None,
                  n_weights: Optional[int] = None, nonfinite_flag: Optional[torch.Tensor] = None, rms=None) -> torch.Tensor:

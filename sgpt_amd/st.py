@@ -20,17 +20,17 @@ class SentenceTransformerSGPT:
     (the assembly of training_nli_v2.py:85-123 / modules.json)."""
 
     def __init__(self, model: SGPTModel, tokenizer, max_seq_length: int = 300, pooling_mode: str = "weightedmean",
-                 specb: bool = False, normalize: bool = False):
+                 specb: bool = False, normalize: bool = False, frame=None):
         self.model = model
         self.tokenizer = tokenizer
         self.max_seq_length = max_seq_length
         self.pooling_mode = pooling_mode
         self.specb = specb
         self.normalize = normalize          # a Normalize module in modules.json (models/Normalize.py)
-        self.pipe = TextPipeline(tokenizer, max_seq_length, specb=specb, family=family_of(model))
+        self.pipe = TextPipeline(tokenizer, max_seq_length, specb=specb, family=family_of(model), frame=frame)   # frame: TextPipeline's
 
     @classmethod
-    def from_pretrained(cls, path: str, tokenizer=None, device=None, dtype: str = "f16", specb: bool = False,
+    def from_pretrained(cls, path: str, tokenizer=None, device=None, dtype: str = "f16", specb: bool = False, frame=None,
                         **model_kw) -> "SentenceTransformerSGPT":
         """SentenceTransformer(model_path) for an SGPT folder (SentenceTransformer._load_sbert_model, :903-936):
         modules.json -> Transformer weights, Pooling / WeightedMeanPooling mode, optional Normalize."""
@@ -44,7 +44,7 @@ class SentenceTransformerSGPT:
             model.set_position_weights(torch.load(spec.position_weights_file, map_location="cpu", weights_only=True)["position_weights"])
         tok = tokenizer if tokenizer is not None else load_tokenizer(spec.transformer_dirs[""])
         return cls(model, tok, max_seq_length=spec.max_seq_length or model.cfg.max_position_embeddings,
-                   pooling_mode=spec.pooling_mode, specb=specb, normalize=spec.normalize)
+                   pooling_mode=spec.pooling_mode, specb=specb, normalize=spec.normalize, frame=frame)
 
     def get_sentence_embedding_dimension(self) -> int:
         return self.model.cfg.hidden_size

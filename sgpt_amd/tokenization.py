@@ -75,21 +75,31 @@ class TextPipeline:
     family: the model's row of sgpt_amd/families.py (or its model_type; None = a GPT model).  Its `framing` says what goes around the
            content, which is cut to max_token_len minus that; any but "brackets" refuses specb / speca (the reference brackets GPT inputs
            only).  "cls_sep": the tokenizer's cls_token_id .. sep_token_id (beir_dense_retriever.py:128-136).  "bos_eos": bos_token_id in
-           front if the tokenizer's `add_bos_token` is set (the HF default), eos_token_id behind if `add_eos_token` is (off by default)."""
+           front if the tokenizer's `add_bos_token` is set (the HF default), eos_token_id behind if `add_eos_token` is (off by default).
+    frame: an explicit (front_ids, back_ids) pair in place of what `framing` would resolve from the tokenizer, for a tokenizer whose
+           attributes do not say what its model was trained with: the Qwen tokenizers carry no BOS, and Qwen3-Embedding closes every
+           input with EOS -- frame=([], [tok.eos_token_id]).  The content is cut to max_token_len minus its length.  Not together with
+           specb / speca."""
 
-    def __init__(self, tokenizer, max_token_len: int, specb: bool = False, speca: bool = False, st_path: bool = False, family=None):
+    def __init__(self, tokenizer, max_token_len: int, specb: bool = False, speca: bool = False, st_path: bool = False, family=None,
+                 frame=None):
         if speca and specb:
             raise ValueError("speca and specb are mutually exclusive")
+        if frame is not None and (specb or speca):
+            raise ValueError("frame replaces the family's framing of the content: it does not go together with specb / speca brackets")
         fam = family if isinstance(family, Family) else (FAMILIES[0] if family is None else family_row(family))
         self.frame = None
         if fam.framing != "brackets" and (specb or speca):
             raise ValueError(f"specb / speca brackets belong to the GPT models; a {fam.name} model {FRAMED[fam.framing]}")
-        if fam.framing == "cls_sep":
+        if frame is not None:
+            front, back = frame
+            self.frame = ([int(t) for t in front], [int(t) for t in back])
+        elif fam.framing == "cls_sep":
             cls_id, sep_id = getattr(tokenizer, "cls_token_id", None), getattr(tokenizer, "sep_token_id", None)
             if cls_id is None or sep_id is None:
                 raise ValueError(f"a {fam.name} model needs a tokenizer with cls_token_id and sep_token_id")
             self.frame = ([int(cls_id)], [int(sep_id)])
-        if fam.framing == "bos_eos":
+        elif fam.framing == "bos_eos":
             front, back = [], []
             if getattr(tokenizer, "add_bos_token", True):
                 if getattr(tokenizer, "bos_token_id", None) is None:

@@ -17,14 +17,14 @@ class CustomEmbedder:
     <model>/1_WeightedMeanPooling by SGPTModel.from_pretrained or set with model.set_position_weights)."""
 
     def __init__(self, model: SGPTModel, tokenizer, layeridx: int = -1, method: str = "weightedmean",
-                 specb: bool = False, maxseqlen: Optional[int] = None):
+                 specb: bool = False, maxseqlen: Optional[int] = None, frame=None):
         if method not in SINGLE_LAYER_METHODS and method not in ALL_LAYER_METHODS and method != "learntmean":
             raise ValueError(f"unknown method {method}")
         self.model = model
         self.layeridx = layeridx
         self.method = method
         self.pipe = TextPipeline(tokenizer, maxseqlen or model.cfg.max_position_embeddings, specb=specb,
-                                 family=family_of(model))
+                                 family=family_of(model), frame=frame)
 
     def encode_device(self, sentences: List[str], is_query: bool = True) -> torch.Tensor:
         seqs = self.pipe.batch(sentences, is_query)
