@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 16
+#define SGPT_ABI_VERSION 17
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -807,9 +807,17 @@ sgpt_status sgpt_prof_read(sgpt_ctx* ctx, int64_t* launches, double* ms, double*
  *   a multiple of 8; 0 = one per CU, the default) -- for two contexts that run their calls half a block out of phase on two
  *   streams, so that one pipeline's LayerNorm / attention / embed kernels find free CUs while the other is in its k-loops
  *   (scripts/dual_stream_probe.py).  Results do not depend on it.  Returns the previous value. */
+ /* sgpt_ctx_set_query_tile (kernel tests): k > 0 = sgpt_linear_query launches the k-th candidate tile of csrc/qgemm.hip instead of
+ *   the one its cost rule picks from the CU count -- plain kernels k = 1 .. 7 = 32x16 (256-element stages), 32x32, 32x64, 64x32,
+ *   64x64, 128x64, 128x128; with the LayerNorm prologue k = 1 .. 3 = 32x32, 32x64, 64x64.  A tile that does not serve the shape
+ *   (N or n_split no multiple of its width, K / stage length no multiple of its ring depth, M <= 32 on a taller tile, k > 3 with
+ *   the prologue, LDS) is the entry's "not served" SGPT_ERR_INVALID with nothing launched.  0 (default) = the launcher chooses.
+ *   Read by sgpt_linear_query alone: sgpt_encode's launches do not see it.  Identical bits whichever tile runs.  Returns the
+ *   previous value; k outside 0 .. 7 changes nothing and returns -1. */
 int32_t sgpt_ctx_set_gemm_cu_cap(sgpt_ctx* ctx, int32_t n);
 int32_t sgpt_ctx_set_low_latency(sgpt_ctx* ctx, int32_t on);
 int32_t sgpt_ctx_set_tile_policy(sgpt_ctx* ctx, int32_t policy);
+int32_t sgpt_ctx_set_query_tile(sgpt_ctx* ctx, int32_t k);
 
 /* Micro-benchmark of one GEMM launch configuration (library-owned pseudo-random operands, never
  * zeros): average milliseconds per launch over `iters` launches.  epi: 0 store, 1 bias+gelu,

@@ -25,6 +25,7 @@ struct sgpt_ctx {
     int force256 = 0;                               // tile policy: 1 = 256x256 tiles even for small problems (sgpt_ctx_set_tile_policy)
     int no_qpath = 0;                               // tile policy 2: query- / mid-sized layouts keep the bulk path's small-tile kernels (A/B, tests)
     int cu_cap = 0;                                 // persistent 256x256 GEMM: workgroups per launch at most (0 = one per CU; sgpt_ctx_set_gemm_cu_cap)
+    int qtile = 0;                                  // sgpt_linear_query only: k > 0 = the k-th candidate tile of qgemm.hip (0 = the launcher's choice; sgpt_ctx_set_query_tile)
     // GEMM profiling (bench.py roofline)
     bool prof = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;

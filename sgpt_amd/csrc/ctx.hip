@@ -133,6 +133,12 @@ int32_t sgpt_ctx_set_tile_policy(sgpt_ctx* c, int32_t policy) {
     c->no_qpath = policy == 2 ? 1 : 0;
     return old;
 }
+int32_t sgpt_ctx_set_query_tile(sgpt_ctx* c, int32_t k) {
+    if (!c || k < 0 || k > 7) return -1;           // (7 plain candidates, 3 with the LayerNorm prologue: a k the kernel family lacks is "not served")
+    const int old = c->qtile;
+    c->qtile = k;
+    return old;
+}
 #ifdef SGPT_EXPERIMENTS
 int32_t sgpt_exp_set_gemm_skew(int32_t cycles) { return set_gemm_skew(cycles); }
 int32_t sgpt_exp_set_gemm_w(int32_t on) { return set_gemm_use_w(on); }

@@ -158,6 +158,7 @@ sgpt_status sgpt_linear_query(sgpt_ctx* c, int32_t dtype, int32_t epi, const voi
     const int out_dtype = epi == EPI_BIAS_RESID ? SGPT_F32 : dtype;
     q.g.range_flag = out_dtype == SGPT_F16 ? c->range_flag : nullptr;
     if (x) { q.x = x; q.ln_g = ln_gamma; q.ln_b = ln_beta; q.eps = ln_eps; q.g.A = nullptr; }
+    q.tile = c->qtile;              // the test knob of this entry alone (sgpt_ctx_set_query_tile): sgpt_encode's launches never read it
     if (!qgemm(c, dtype, epi, out_dtype, q, (hipStream_t)stream))
         return fail(c, SGPT_ERR_INVALID, "sgpt_linear_query: shape not served by the query-sized kernels (M % 32, M <= 4096; K / 128 a multiple of 4 or 6; "
                                          "N % 16; LayerNorm prologue: K = 512 | 768 | 1024, N % 32)");

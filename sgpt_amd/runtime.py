@@ -180,6 +180,13 @@ class Context:
         (A/Bs); identical bits whatever the policy.  Returns the previous policy (0 | 1 | 2)."""
         return int(self.lib.sgpt_ctx_set_tile_policy(self.handle, int(force_256)))
 
+    def set_query_tile(self, k: int) -> int:
+        """Per context, kernel tests: k > 0 = `linear_query` launches the k-th candidate tile of csrc/qgemm.hip (plain kernels 1 .. 7 =
+        32x16, 32x32, 32x64, 64x32, 64x64, 128x64, 128x128; LayerNorm prologue 1 .. 3 = 32x32, 32x64, 64x64) instead of the one the
+        cost rule picks; a tile that does not serve the shape raises "not served".  0 = the launcher chooses.  Encode calls never read
+        it (include/sgpt_hip.h::sgpt_ctx_set_query_tile).  Returns the previous value; -1 (nothing changed) for k outside 0 .. 7."""
+        return int(self.lib.sgpt_ctx_set_query_tile(self.handle, int(k)))
+
     def reserve(self, encode_bytes: int = 0, score_bytes: int = 0) -> None:
         self._chk(self.lib.sgpt_ctx_reserve(self.handle, encode_bytes, score_bytes), "sgpt_ctx_reserve")
 

@@ -1,7 +1,8 @@
 """Test infrastructure: the projection GEMM with its fused epilogues (include/sgpt_hip.h::sgpt_linear / sgpt_linear_split) in
 float64 numpy, a derived error bound for any fp32 accumulation of the same products, a Python mirror of the launch rule of
-csrc/gemm.hip and of the tile walk of its persistent 256x256 kernel, and the shape tables of tests/test_gpu_linear_edges.py and
-tests/test_gpu_linear_256.py.  Checked without a GPU by tests/test_gemm_ref.py.
+csrc/gemm.hip and of the tile walk of its persistent 256x256 kernel, a mirror of the launcher and workgroup list of the query-sized
+kernels (csrc/qgemm.hip), and the shape tables of tests/test_gpu_linear_edges.py, tests/test_gpu_linear_256.py and
+tests/test_gpu_linear_query.py.  Checked without a GPU by tests/test_gemm_ref.py.
 
 Operands are the exact values of the already rounded inputs (16-bit x 16-bit and fp32 x fp32 products are taken as the float64
 product of the stored values), so the only error a kernel may show is that of its fp32 accumulation, of the epilogue function
@@ -286,13 +287,259 @@ def launch_of(c, ncu=NCU256, cu_cap=None):
     return tiles256(c.M, c.N, ncu, c.cu_cap if cu_cap is None else cu_cap)
 
 
+# ---------------------------------------------------------------- the query-sized kernels: the launcher of csrc/qgemm.hip --------
+# A line-by-line mirror of q_chunks, q_depth_rule, q_class, q_pick_plain, q_plan_ln, qgemm_shape_ok, qgemm_ln_ok and of the
+# workgroup list at the top of qgemm_kernel.  A change of a rule in qgemm.hip must change the function here and the table CASESQ
+# with it: tests/test_gemm_ref.py fails until then.
+EPI_QKV = 7                                            # sgpt_linear_query: q | k row-major, V^T (common.h GemmEpi)
+QNT = 512                                              # threads per workgroup (8 waves)
+QGEMM_MAX_ROWS = 4096
+Q_LDS_LIMIT = 160 * 1024
+Q_TILES = ((32, 16, 256), (32, 32, 128), (32, 64, 128), (64, 32, 128), (64, 64, 128), (128, 64, 128), (128, 128, 128))   # bm, bn, kd
+Q_LN_TILES = ((32, 32), (32, 64), (64, 64))            # kd = 128
+Q_LN_AS_PLAIN = {1: 2, 2: 3, 3: 5}                     # forced prologue tile -> the forced plain tile of the same (bm, bn)
+
+
+def q_chunks(bm, bn, ln_a, kd):
+    """16-byte chunks per thread and ring stage of a tile."""
+    return ((0 if ln_a else bm) + bn) * kd * 2 // (QNT * 16)
+
+
+def q_depth_rule(ch, six):
+    """Ring stages in flight in registers."""
+    if ch >= 8:
+        return 2
+    if six:
+        return 6 if ch * 6 <= 24 else 3
+    return 4 if ch * 4 <= 16 else 2
+
+
+def q_class(tile, ln_a, K):
+    """Depth class of tile (bm, bn, kd) at this K: 6 -> the SIX kernels, 4 -> the others, 0 -> not served."""
+    bm, bn, kd = tile
+    if K % kd:
+        return 0
+    nk = K // kd
+    ch = q_chunks(bm, bn, ln_a, kd)
+    d6, d4 = q_depth_rule(ch, True), q_depth_rule(ch, False)
+    ok6, ok4 = nk % d6 == 0, nk % d4 == 0
+    if ok6 and (not ok4 or d6 >= d4):
+        return 6
+    return 4 if ok4 else 0
+
+
+def q_pick_plain(M, N, K, epi, n_split, ncu, force=0):
+    """Index into Q_TILES of the tile a plain launch takes (force: only candidate force - 1), or -1."""
+    best, best_cost = -1, 0
+    for i, tl in enumerate(Q_TILES):
+        bm, bn, _ = tl
+        if force > 0 and i != force - 1:
+            continue
+        if N % bn or not q_class(tl, False, K):
+            continue
+        if epi == EPI_QKV and (n_split % bn or bn < 16):
+            continue
+        if bm > 32 and M <= 32:
+            continue
+        tiles = ((M + bm - 1) // bm) * (N // bn)
+        rounds = (tiles + ncu - 1) // ncu
+        cost = rounds * (bm + bn)
+        if best < 0 or cost < best_cost or (cost == best_cost and bm * bn > Q_TILES[best][0] * Q_TILES[best][1]):
+            best, best_cost = i, cost
+    return best
+
+
+def q_plan_ln(M, N, d, epi, n_split, ncu, force=0):
+    """(bm, bn, group, LDS bytes) of a launch with the LayerNorm prologue, or None."""
+    if d % 128 or N % 32:
+        return None
+    nk = d // 128
+    if nk % 6 != 0 and nk % 4 != 0:
+        return None
+    best, best_cost = None, 0
+    for ci, (bm, bn) in enumerate(Q_LN_TILES):
+        if force > 0 and ci != force - 1:
+            continue
+        if N % bn or (epi == EPI_QKV and n_split % bn):
+            continue
+        if bm > 32 and M <= 32:
+            continue
+        mt, nt = (M + bm - 1) // bm, N // bn
+        gq = max(1, (mt * nt + ncu - 1) // ncu)
+        while mt * ((nt + gq - 1) // gq) > ncu:
+            gq += 1
+        lds = nk * bm * 256 + 2 * bn * 256 + gq * bn * 4
+        if lds > Q_LDS_LIMIT:
+            continue
+        cost = (6200 if bm == 32 else 9400) + gq * nk * (250 if bn == 32 else 350 if bm == 32 else 440)
+        if best is None or cost < best_cost:
+            best, best_cost = (bm, bn, gq, lds), cost
+    return best
+
+
+def qgemm_shape_ok(M, N, K, epi, n_split, ncu):
+    if M <= 0 or M > QGEMM_MAX_ROWS or M % 32 or K < 128 or N % 16:
+        return False
+    if epi == EPI_QKV and (n_split % 32 or n_split <= 0 or n_split >= N or N % 32):
+        return False
+    if epi not in (EPI_STORE, EPI_QKV, EPI_GELU, EPI_RESID):
+        return False
+    return q_pick_plain(M, N, K, epi, n_split, ncu) >= 0
+
+
+def qgemm_ln_ok(M, N, d, epi, n_split, ncu):
+    if M <= 0 or M > QGEMM_MAX_ROWS or M % 32 or epi not in (EPI_QKV, EPI_GELU):
+        return False
+    if epi == EPI_QKV and (n_split % 32 or n_split <= 0 or n_split >= N):
+        return False
+    if d not in (768, 1024, 512):
+        return False
+    return q_plan_ln(M, N, d, epi, n_split, ncu) is not None
+
+
+QLaunch = namedtuple("QLaunch", "bm bn kd D cls group lds MT NT NG R c0 rem grid blocks")
+
+
+def q_blocks(M, N, bm, bn, group):
+    """The workgroup list of qgemm_kernel: (MT, NT, NG, R, c0, rem, grid, blocks); blocks[b] = (mt, ng) of block index b -- row tile
+    mt, column group ng (column tiles ng * group .. below NT) -- or None where the block returns at once."""
+    MT, NT = (M + bm - 1) // bm, N // bn
+    NG = (NT + group - 1) // group
+    R = MT * NG
+    c0, rem = R >> 3, R & 7
+    grid = 8 * ((R + 7) // 8)
+    blocks = []
+    for b in range(grid):
+        xcd, local = b & 7, b >> 3
+        if local >= c0 + (1 if xcd < rem else 0):
+            blocks.append(None)
+            continue
+        gi = xcd * c0 + (xcd if xcd < rem else rem) + local
+        ng = gi // MT
+        blocks.append((gi - ng * MT, ng))
+    return MT, NT, NG, R, c0, rem, grid, blocks
+
+
+def q_launch(M, N, K, epi, n_split=0, ln=False, force=0, ncu=NCU256):
+    """What launch_qgemm does with the problem on a device of ncu CUs (force: sgpt_ctx_set_query_tile): a QLaunch, or None where the
+    entry answers "not served".  ln: the LayerNorm prologue (K = d)."""
+    if ln:
+        if not qgemm_ln_ok(M, N, K, epi, n_split, ncu):
+            return None
+        pl = q_plan_ln(M, N, K, epi, n_split, ncu, force)
+        if pl is None:
+            return None
+        bm, bn, group, lds = pl
+        kd = 128
+        D = q_depth_rule(q_chunks(bm, bn, True, kd), (K // 128) % 6 == 0)
+        cls = 6 if (K // 128) % 6 == 0 else 4
+        lds_launch = (K // kd) * bm * kd * 2 + group * bn * 4 + 2 * bn * kd * 2          # qlaunch
+        assert lds_launch == lds
+    else:
+        if not qgemm_shape_ok(M, N, K, epi, n_split, ncu):
+            return None
+        i = q_pick_plain(M, N, K, epi, n_split, ncu, force)
+        if i < 0:
+            return None
+        bm, bn, kd = Q_TILES[i]
+        cls = q_class(Q_TILES[i], False, K)
+        D = q_depth_rule(q_chunks(bm, bn, False, kd), cls == 6)
+        group, lds = 1, 2 * (bm + bn) * kd * 2
+    return QLaunch(bm, bn, kd, D, cls, group, lds, *q_blocks(M, N, bm, bn, group))
+
+
+# ---------------------------------------------------------------- shapes of tests/test_gpu_linear_query.py -----------------------
+# Written for a device of NCU256 CUs (only `group` of the prologue cases depends on it: a forced tile does not).  tile: the forced
+# candidate (sgpt_ctx_set_query_tile).  bm bn kd D: what the mirror must give.  group: column tiles per workgroup (prologue; 1 for
+# the plain kernels).  edges, each checked by tests/test_gemm_ref.py:
+#   ragged      M % bm != 0 (clamped loads, predicated stores)         one-tile    M < bm: the only row tile is ragged
+#   one-group   K / kd == D: the re-arm loop never runs                 long-ring   K / kd == 2 D or 3 D
+#   short-run   R = MT NG < 8: some XCDs have no workgroup              uneven-run  R = 8 c0 + rem, c0 >= 1, rem != 0
+#   short-last  the last column group has fewer than `group` tiles      split-inside  n_split falls inside a column group
+#   bias3       more than 1024 bias floats per workgroup (the third bias loop)
+# tag: 'plain' | 'ln' (every forced prologue tile at d = 512 / 768 / 1024) | 'ln-group' (group > 1).
+CaseQ = namedtuple("CaseQ", "name M N K n_split ln tile bm bn kd D group edges tag")
+
+# forced tile, bm, bn, kd, depth class, D, K with one ring group (K / kd == D), a longer K (2 D or 3 D)
+# (128x128: 8 chunks per stage, D = 2 whatever the class, and q_class answers 6 for every K it serves -- its class-4
+#  instantiation is never launched: no row for it)
+Q_PLAIN = (
+    (1, 32, 16, 256, 6, 6, 1536, 3072), (1, 32, 16, 256, 4, 4, 1024, 2048),
+    (2, 32, 32, 128, 6, 6, 768, 1536), (2, 32, 32, 128, 4, 4, 512, 1024),
+    (3, 32, 64, 128, 6, 6, 768, 1536), (3, 32, 64, 128, 4, 4, 512, 1024),
+    (4, 64, 32, 128, 6, 6, 768, 1536), (4, 64, 32, 128, 4, 4, 512, 1024),
+    (5, 64, 64, 128, 6, 6, 768, 1536), (5, 64, 64, 128, 4, 4, 512, 1024),
+    (6, 128, 64, 128, 6, 3, 384, 1152), (6, 128, 64, 128, 4, 2, 256, 512),
+    (7, 128, 128, 128, 6, 2, 256, 768),
+)
+Q_ROWS = {32: (32, 96), 64: (96, 64), 128: (160, 64)}                # bm -> M: whole tiles; a whole and a ragged, one whole; ragged, one ragged
+Q_COLS = {16: ((64, 32), (160, 96)), 32: ((64, 32), (288, 192)), 64: ((128, 64), (576, 384)), 128: ((256, 128), (1152, 768))}   # bn -> (N, n_split): 2 (bn 16: 4) and 9 (10) column tiles
+
+
+def _plain_cases():
+    out = []
+    for k, bm, bn, kd, cls, D, k_one, k_long in Q_PLAIN:
+        for K in (k_one, k_long):
+            for M in Q_ROWS[bm]:
+                for N, ns in Q_COLS[bn]:
+                    MT, NT = -(-M // bm), N // bn
+                    R = MT * NT
+                    e = {"one-group" if K // kd == D else "long-ring"}
+                    if M % bm:
+                        e.add("ragged")
+                    if M < bm:
+                        e.add("one-tile")
+                    if R < 8:
+                        e.add("short-run")
+                    elif R & 7:
+                        e.add("uneven-run")
+                    out.append(CaseQ(f"q{bm}x{bn}-c{cls}-{M}x{N}x{K}", M, N, K, ns, False, k, bm, bn, kd, D, 1, frozenset(e), "plain"))
+    return out
+
+
+def _ln(name, M, N, d, ns, tile, bm, bn, D, group, edges, tag="ln"):
+    return CaseQ(name, M, N, d, ns, True, tile, bm, bn, 128, D, group, frozenset(edges.split()), tag)
+
+
+def _ln_cases():
+    out = []
+    for d, six in ((512, False), (768, True), (1024, False)):
+        for tile, (bm, bn) in enumerate(Q_LN_TILES, 1):
+            if (bm, bn, d) == (64, 64, 1024):                        # 128 KiB of A panel + 32 KiB of ring + bias > 160 KiB: refused (Q_LN_REFUSED)
+                continue
+            D = 6 if six else 4                                       # 1 or 2 chunks per stage: the full depth of either class
+            for M in ((32, 96) if bm == 32 else (96, 160)):
+                R = -(-M // bm) * (192 // bn)
+                e = ("one-group" if d // 128 == D else "long-ring") + (" ragged" if M % bm else "") + (" short-run" if R < 8 else " uneven-run" if R & 7 else "")
+                out.append(_ln(f"ln{bm}x{bn}-d{d}-{M}", M, 192, d, 128, tile, bm, bn, D, 1, e))
+    return out
+
+
+CASESQ = _plain_cases() + _ln_cases() + [
+    # two column tiles per workgroup, 34 groups, the last of one tile; q | k ends at tile 45 = the second tile of group 22
+    _ln("lng-32x32-128x2144", 128, 2144, 768, 1440, 1, 32, 32, 6, 2, "one-group short-last split-inside", "ln-group"),
+    # the same on the 64-row tile with a ragged last row tile: 3 x 87 tiles, 44 groups, q | k ends at tile 57 = the second of group 28
+    _ln("lng-64x64-160x5568", 160, 5568, 768, 3648, 3, 64, 64, 6, 2, "one-group ragged short-last split-inside uneven-run", "ln-group"),
+    # 17 column tiles = 1088 bias floats per workgroup; the second group has 16; q | k ends at tile 22, inside it
+    _ln("lng-32x64-4096x2112", 4096, 2112, 512, 1408, 2, 32, 64, 4, 17, "one-group short-last split-inside bias3", "ln-group"),
+]
+Q_LN_REFUSED = (3, 96, 192, 1024, 128)                 # forced tile, M, N, d, n_split: 64x64 at d = 1024 needs more than 160 KiB of LDS
+
+
+def launch_q(c, epi=None, ncu=NCU256):
+    """q_launch of a CASESQ row (epi: EPI_QKV with the row's n_split by default for a prologue row, EPI_STORE for a plain one)."""
+    if epi is None:
+        epi = EPI_QKV if c.ln else EPI_STORE
+    return q_launch(c.M, c.N, c.K, epi, c.n_split if epi == EPI_QKV else 0, c.ln, c.tile, ncu)
+
+
 
 def case(name):
-    return next(c for c in CASES + CASES256 if c.name == name)
+    return next(c for c in CASES + CASES256 + CASESQ if c.name == name)
 
 
 def case_k(c, dtype):
-    if isinstance(c, Case256):
+    if isinstance(c, (Case256, CaseQ)):
         return c.K
     return c.K32 if dtype == "fp32" else c.K16
 

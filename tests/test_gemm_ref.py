@@ -306,3 +306,144 @@ def test_a_stale_slot_and_a_wrong_prefetch_are_detectable(name, dtype):
     worst = max(float((np.abs(G.fp32_chain(a[:bm], w[:bn], 32, reverse=rev).astype(np.float64) - ref) / bnd).max()) for rev in (False, True))
     print(f"{name} {dtype}: fp32 chain error / bound = {worst:.4f}")
     assert worst < 0.25
+
+
+# ---------------------------------------------------------------- the query-sized kernels: launcher mirror and case table --------
+
+QIDS = dict(ids=lambda c: c.name)
+
+
+def test_q_depth_rule_pins():
+    """The mirror against values worked out by hand from q_chunks / q_depth_rule / q_class of csrc/qgemm.hip."""
+    chunks = [G.q_chunks(bm, bn, False, kd) for bm, bn, kd in G.Q_TILES]
+    assert chunks == [3, 2, 3, 3, 4, 6, 8]
+    assert [G.q_depth_rule(ch, True) for ch in chunks] == [6, 6, 6, 6, 6, 3, 2]
+    assert [G.q_depth_rule(ch, False) for ch in chunks] == [4, 4, 4, 4, 4, 2, 2]
+    assert [G.q_chunks(bm, bn, True, 128) for bm, bn in G.Q_LN_TILES] == [1, 2, 2]
+    assert G.q_class((32, 32, 128), False, 768) == 6 and G.q_class((32, 32, 128), False, 512) == 4
+    assert G.q_class((32, 32, 128), False, 3072) == 6                                   # nk = 24: both divide, the deeper ring wins
+    assert G.q_class((32, 32, 128), False, 640) == 0 and G.q_class((32, 16, 256), False, 768) == 0 and G.q_class((32, 16, 256), False, 128) == 0
+    assert G.q_class((128, 64, 128), False, 384) == 6 and G.q_class((128, 64, 128), False, 256) == 4 and G.q_class((128, 64, 128), False, 768) == 6
+    # 128x128: D = 2 in both classes, so q_class answers 6 whenever it answers: the class-4 instantiation is never launched
+    assert {G.q_class((128, 128, 128), False, 128 * nk) for nk in range(1, 65)} == {0, 6}
+
+
+def test_q_pick_pins_on_the_shapes_of_test_gpu_linear():
+    """What the cost rule picks at 256 CUs for the shapes tests/test_gpu_linear.py runs (its docstring cites this): no ragged row tile,
+    no 64x32 tile, and only the depths listed."""
+    seen = set()
+    for M, N, K in [(32, 768, 768), (32, 768, 3072), (96, 2304, 768), (352, 768, 3072), (512, 3072, 768), (1024, 768, 768), (2304, 768, 3072),
+                    (2816, 2304, 768), (160, 1024, 1024), (64, 4096, 4096), (448, 2048, 8192)]:
+        for epi, ns in [(G.EPI_STORE, 0), (G.EPI_GELU, 0), (G.EPI_RESID, 0)] + ([(G.EPI_QKV, N // 3 * 2)] if N % 96 == 0 else []):
+            L = G.q_launch(M, N, K, epi, ns)
+            assert L is not None
+            if L.bm > 32:
+                assert M % L.bm == 0, (M, N, K, epi, L.bm)
+            seen.add((L.bm, L.bn, L.D))
+    assert seen == {(32, 16, 6), (32, 32, 6), (32, 32, 4), (32, 64, 6), (64, 64, 6), (64, 64, 4), (128, 64, 3), (128, 128, 2)}, sorted(seen)
+
+
+@pytest.mark.parametrize("c", G.CASESQ, **QIDS)
+def test_casesq_get_the_tile_depth_and_group_they_state(c):
+    epis = [(G.EPI_QKV, c.n_split), (G.EPI_GELU, 0)] + ([] if c.ln else [(G.EPI_STORE, 0), (G.EPI_RESID, 0)])
+    for epi, ns in epis:
+        L = G.q_launch(c.M, c.N, c.K, epi, ns, c.ln, c.tile)
+        assert L is not None, f"{c.name} epi {epi}: not served"
+        assert (L.bm, L.bn, L.kd, L.D, L.group) == (c.bm, c.bn, c.kd, c.D, c.group), f"{c.name} epi {epi}: {L[:6]}"
+        assert c.K // c.kd >= L.D and (c.K // c.kd) % L.D == 0 and L.lds <= G.Q_LDS_LIMIT
+        assert L.cls == (6 if L.D in (6, 3) or (c.bm, c.bn) == (128, 128) else 4)
+        assert G.Q_TILES[c.tile - 1][:2] == (c.bm, c.bn) if not c.ln else G.Q_LN_TILES[c.tile - 1] == (c.bm, c.bn)
+        if not c.ln:                                   # a forced tile does not read the CU count
+            assert G.q_launch(c.M, c.N, c.K, epi, ns, False, c.tile, ncu=304)[:6] == L[:6]
+    if c.ln:                                           # the partner of the bit comparison: the same tile without the prologue
+        P = G.q_launch(c.M, c.N, c.K, G.EPI_QKV, c.n_split, False, G.Q_LN_AS_PLAIN[c.tile])
+        assert P is not None and (P.bm, P.bn) == (c.bm, c.bn)
+
+
+@pytest.mark.parametrize("c", G.CASESQ, **QIDS)
+def test_casesq_show_the_edges_they_are_listed_for(c):
+    L = G.launch_q(c)
+    nk = c.K // c.kd
+    assert c.K % c.kd == 0 and c.M % 32 == 0 and c.N % c.bn == 0 and c.n_split % c.bn == 0 and 0 < c.n_split < c.N
+    assert ("ragged" in c.edges) == (c.M % c.bm != 0)
+    assert ("one-tile" in c.edges) == (c.M < c.bm)
+    assert ("one-group" in c.edges) == (nk == c.D) and ("long-ring" in c.edges) == (nk in (2 * c.D, 3 * c.D)) and nk in (c.D, 2 * c.D, 3 * c.D)
+    assert ("short-run" in c.edges) == (L.R < 8)
+    if "uneven-run" in c.edges:
+        assert L.c0 >= 1 and L.rem != 0
+    elif c.tag == "plain":
+        assert L.R < 8
+    last = L.NT - (L.NG - 1) * L.group
+    assert ("short-last" in c.edges) == (last < L.group)
+    split_tile = c.n_split // c.bn                      # the first V tile
+    assert ("split-inside" in c.edges) == (split_tile % L.group != 0)
+    assert ("bias3" in c.edges) == (L.group * c.bn > 2 * G.QNT)
+    if c.tag == "ln-group":
+        assert L.group > 1 and L.MT * L.NG <= G.NCU256 < L.MT * L.NT
+    # both q | k and V tiles exist, on either side of a tile boundary
+    assert 0 < split_tile < L.NT
+
+
+def test_casesq_cover_what_the_suite_is_for():
+    plain = [c for c in G.CASESQ if c.tag == "plain"]
+    assert {(c.tile, c.D) for c in plain} == {(1, 6), (1, 4), (2, 6), (2, 4), (3, 6), (3, 4), (4, 6), (4, 4), (5, 6), (5, 4), (6, 3), (6, 2), (7, 2)}
+    for k, bm, bn, kd, cls, D, k_one, k_long in G.Q_PLAIN:
+        rows = [c for c in plain if (c.tile, c.D) == (k, D)]
+        assert {c.K for c in rows} == {k_one, k_long} and k_one // kd == D and k_long // kd in (2 * D, 3 * D)
+        assert G.q_class((bm, bn, kd), False, k_one) == cls == G.q_class((bm, bn, kd), False, k_long)
+        for K in (k_one, k_long):
+            at_k = [c for c in rows if c.K == K]
+            assert {c.M for c in at_k} == set(G.Q_ROWS[bm])
+            assert any("short-run" in c.edges for c in at_k) and any("uneven-run" in c.edges for c in at_k)
+            if bm > 32:
+                assert any("ragged" in c.edges for c in at_k) and any("uneven-run" in c.edges and "ragged" in c.edges for c in at_k)
+            if bm == 64:
+                assert any("ragged" not in c.edges for c in at_k)
+            if bm == 128:
+                assert any("one-tile" in c.edges for c in at_k)
+    ln = [c for c in G.CASESQ if c.tag == "ln"]
+    assert {(c.tile, c.K) for c in ln} == {(t, d) for t in (1, 2, 3) for d in (512, 768, 1024)} - {(3, 1024)}
+    assert {c.M for c in ln if c.bm == 64} == {96, 160} and all("ragged" in c.edges for c in ln if c.bm == 64)
+    assert {c.M for c in ln if c.bm == 32} == {32, 96}
+    tile, M, N, d, ns = G.Q_LN_REFUSED
+    assert G.q_launch(M, N, d, G.EPI_QKV, ns, True, tile) is None and G.q_launch(M, N, d, G.EPI_QKV, ns, True, 0) is not None
+    assert G.q_launch(M, N, 768, G.EPI_QKV, ns, True, tile) is not None
+    grp = {c.name: c for c in G.CASESQ if c.tag == "ln-group"}
+    assert grp["lng-32x32-128x2144"].group == 2 and G.launch_q(grp["lng-32x32-128x2144"]).NG == 34
+    assert "ragged" in grp["lng-64x64-160x5568"].edges and grp["lng-32x64-4096x2112"].group * 64 == 1088
+    assert len({c.name for c in G.CASESQ}) == len(G.CASESQ)
+
+
+def test_q_refusals_of_a_forced_tile():
+    assert G.q_launch(32, 128, 768, G.EPI_STORE, force=5) is None                  # M <= 32 on a 64-row tile
+    assert G.q_launch(96, 96, 768, G.EPI_STORE, force=5) is None                   # N % 64
+    assert G.q_launch(96, 128, 768, G.EPI_STORE, force=1) is None                  # 256-element stages: K / 256 = 3
+    assert G.q_launch(96, 128, 768, G.EPI_QKV, 32, force=5) is None                # n_split off the tile boundary
+    assert G.q_launch(96, 192, 768, G.EPI_QKV, 128, True, force=4) is None         # the prologue has three candidates
+    assert G.q_launch(48, 128, 768, G.EPI_STORE) is None and G.q_launch(32, 128, 640, G.EPI_STORE) is None
+
+
+def _covers_once(M, N, bm, bn, group):
+    MT, NT, NG, R, c0, rem, grid, blocks = G.q_blocks(M, N, bm, bn, group)
+    live = [b for b in blocks if b is not None]
+    assert len(live) == R == len(set(live)) and set(live) == {(mt, ng) for mt in range(MT) for ng in range(NG)}
+    assert grid == len(blocks) and grid % 8 == 0 and grid - R < 8
+    # XCD x = blocks x, x + 8, ...: a contiguous run of the column-group-major list, of c0 or c0 + 1 workgroups
+    for x in range(8):
+        run = [ng * MT + mt for mt, ng in (b for b in blocks[x::8] if b is not None)]
+        assert run == list(range(run[0], run[0] + len(run))) if run else R < 8
+        assert len(run) == c0 + (1 if x < rem else 0)
+    tiles = sorted(t for mt, ng in live for t in range(ng * group, min(NT, ng * group + group)))
+    assert tiles == sorted(list(range(NT)) * MT)        # every column tile of every row tile in exactly one group
+
+
+def test_q_workgroup_list_covers_every_tile_group_once():
+    for c in G.CASESQ:
+        _covers_once(c.M, c.N, c.bm, c.bn, c.group)
+    for MT in (1, 2, 3, 5, 8, 128):                     # R around the multiples of 8
+        for R in list(range(1, 42)) + [255, 256, 257]:
+            if R % MT == 0:
+                for group in (1, 2, 3):
+                    NG = R // MT
+                    for NT in {NG * group, NG * group - (group - 1)}:
+                        _covers_once(MT * 32, NT * 32, 32, 32, group)

@@ -5,7 +5,16 @@ kernels (16x16x32 and 32x32x16 MFMA), bf16 and f16, the ring parities K = 128 / 
 multiple of 64: no shape here reaches its 128x128 tile, its row / column / K-tail guards or fp32 operands -- those are
 tests/test_gpu_linear_edges.py, against the float64 reference and derived bound of tests/gemm_ref.py; and every 256x256 shape here
 but one gives each workgroup a single tile -- runs of several tiles at every ring state, the supertile tile order, the workgroup
-cap and the bulk QKV launch of the 256x256 kernel are tests/test_gpu_linear_256.py, against the same reference).  Tolerance: fp32 accumulation-order noise only,
+cap and the bulk QKV launch of the 256x256 kernel are tests/test_gpu_linear_256.py, against the same reference).  The three tests
+of the query- / mid-sized kernels at the end (csrc/qgemm.hip) run whatever tile the launcher's cost rule picks for eleven large
+shapes: at 256 CUs that is never a ragged row tile (every M here is a multiple of the 64- or 128-row tile it gets), never the
+64x32 tile, the 32x16 / 32x64 tiles only at ring depth 6 and 128x64 only at depth 3, never q | k | V^T with a bias, and the
+LayerNorm prologue never with a ragged row tile, with n_split inside a column group once and at most 640 bias floats per
+workgroup -- each tile forced in each depth class, one-group
+rings, ragged and single row tiles, short per-XCD runs, the biased V^T tile, column groups with a short last group, n_split inside
+a group and more than 1024 bias floats, and the range word from a ragged tile are tests/test_gpu_linear_query.py, against the
+float64 reference and per-element bound of tests/gemm_ref.py (whose mirror of the launcher tests/test_gemm_ref.py pins on the
+shapes of this file).  Tolerance: fp32 accumulation-order noise only,
 1e-3 * sqrt(K / 64) relative to the output scale for fp32 outputs; one rounding to the 16-bit output format on top
 (2^-8 bf16 / 2^-11 f16 relative) for 16-bit outputs."""
 import math
