@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 17
+#define SGPT_ABI_VERSION 18
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -373,7 +373,9 @@ sgpt_status sgpt_ctx_reserve(sgpt_ctx* ctx, size_t encode_bytes, size_t score_by
 /* fp8 weight storage (SGPT_FP8W) building blocks, exported for parity tests and for callers that keep
  * their own quantised checkpoints.  w device fp32[rows, cols] (cols % 4 == 0) -> codes uint8[rows, cols]
  * (OCP e4m3fn, round-to-nearest-even) + scale fp32[rows], scale = the smallest power of two with
- * max|w_row| / scale <= 448.  De-quantisation code * scale is exact in bf16 and in fp32. */
+ * max|w_row| / scale <= 448.  De-quantisation code * scale is exact in bf16 and in fp32 (out_dtype SGPT_F32 | SGPT_BF16 | SGPT_F16; in
+ * f16 exact while code * scale is an f16 value -- the rows of a quantised corpus, sgpt_score_topk_q8); the NaN codes 0x7f / 0xff,
+ * which the quantiser emits for NaN input only, de-quantise to NaN. */
 sgpt_status sgpt_fp8_quantize_rows(sgpt_ctx* ctx, const float* w, int64_t rows, int64_t cols,
                                    uint8_t* codes, float* scale, void* stream);
 sgpt_status sgpt_fp8_dequantize_rows(sgpt_ctx* ctx, const uint8_t* codes, const float* scale, int64_t rows,
@@ -408,6 +410,27 @@ sgpt_status sgpt_score_topk(sgpt_ctx* ctx, const void* q, const void* corpus, in
                             int32_t nq, int64_t N, int32_t d, int32_t k, int64_t idx_base,
                             float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out,
                             void* stream);
+
+/* sgpt_score_topk_q8 (ABI v18): sgpt_score_topk over a corpus held as fp8 -- half the bytes of a 16-bit corpus in memory and
+ * per search pass.
+ *   format    codes device uint8 [N, d]: OCP e4m3fn; scale device fp32 [N]: one power of two per document, document n =
+ *             code[n][:] * scale[n].  The rule of sgpt_fp8_quantize_rows: scale = the smallest power of two with max|row| / scale <= 448,
+ *             codes round-to-nearest-even (NaN -> the NaN code).  Rows come from sgpt_l2_normalize (fp32 out) + sgpt_fp8_quantize_rows.
+ *   q         device f16 [nq, d], 16-byte aligned.
+ *   exactness every e4m3 value is an f16 value, so the kernel feeds the f16 MFMA with exactly the de-quantised corpus (the scale, a
+ *             power of two, multiplies the fp32 accumulator): the result equals sgpt_score_topk(SGPT_F16) on the de-quantised rows bit
+ *             for bit (as long as code * scale is an f16 value, which holds for unit rows).  The only approximation is the quantisation:
+ *             |s_fp8 - s| <= 2^-4 sum_i |q_i c_i| + 2^-10 scale sum_i |q_i| per score (e4m3 round-to-nearest, relative 2^-4 per element;
+ *             elements below half the smallest subnormal 2^-9 scale flush to zero), on top of the f16 scorer's own arithmetic.
+ *   shapes    nq <= 64 and d % 128 == 0 (codes 8-byte aligned): every whole 256-document tile streams through score64q8_kernel, which
+ *             reads the codes themselves; a ragged tail (< 256 documents) is de-quantised to f16 scratch.  Everything else (nq > 64:
+ *             MFMA-bound; other d): blocks of at most 131 072 documents are de-quantised to f16 workspace and scored by the f16 path,
+ *             the running list chained -- the memory saving holds, no speed is claimed.
+ *   result    as sgpt_score_topk: rows sorted descending, ties to the lowest index, NaN scores (a NaN code) -> -1, running list in/out.
+ * SGPT_ERR_INVALID (nothing launched, outputs untouched): null pointers, d % 8, k <= 0, n_run > k, q not 16-byte aligned. */
+sgpt_status sgpt_score_topk_q8(sgpt_ctx* ctx, const void* q, const uint8_t* codes, const float* scale, int32_t nq, int64_t N, int32_t d,
+                               int32_t k, int64_t idx_base, float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out,
+                               void* stream);
 
 /* sgpt_score_topk_refined (ABI v7): the reference's fp32 scoring + top-k (`torch.mm(a, b.T)`, util.py:41-43,63; `torch.topk`,
  * exact_search.py:96-108) -- fp32 scores of the returned documents, the fp32 top-k set -- at the speed of the 16-bit scorer.

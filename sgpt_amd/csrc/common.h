@@ -338,6 +338,16 @@ int set_gemm_use_w(int on);     // 1: the 32x32x16-MFMA re-tiling of the 256^2 k
 // EPI_STORE / EPI_VT (16-bit out) | EPI_NONE
 bool gemm_fp8_shape_ok(int M, int N, int K);
 void launch_gemm_fp8(int epi, int out_dtype, const GemmArgs& a, hipStream_t s);   // out_dtype: EPI_STORE / EPI_VT only
+// score8.hip: the short-batch scorer tile (64 padded f16 query rows x 256 documents) over e4m3fn document codes, g.W = codes
+// [N][g.ldw] bytes, document n scaled by scale[n * scale_stride] (a strided sample has g.ldw = d * stride, scale_stride = stride);
+// epi = EPI_SCORE | EPI_SCORE_FILTER with score64_kernel's contract.  The caller asks score64q8_shape_ok first.
+struct Score8Args {
+    GemmArgs g;
+    const float* scale;
+    long scale_stride;
+};
+bool score64q8_shape_ok(int M, long N, int K, const void* codes, long ldw);
+void launch_score64q8(int epi, const Score8Args& a, hipStream_t s);
 // gemm256w.hip: the 256x256 LDS-DMA kernel on v_mfma_f32_32x32x16 (16-bit operands and outputs as gemm256d_kernel)
 void launch_gemm256w(int dtype, int epi, const GemmArgs& a, hipStream_t s, bool deep_a);
 

@@ -611,6 +611,7 @@ __device__ __forceinline__ uint32_t e4m3fn_encode(float x) {
 __device__ __forceinline__ float e4m3fn_decode(uint32_t c) {
     const uint32_t e = (c >> 3) & 15u, m = c & 7u;
     const float a = e ? __uint_as_float(((e + 120u) << 23) | (m << 20)) : (float)m * 0.001953125f;
+    if ((c & 0x7fu) == 0x7fu) return __uint_as_float(0x7fc00000u);   // the NaN codes 0x7f / 0xff (the encoder emits them for NaN input only)
     return (c & 0x80u) ? -a : a;
 }
 
@@ -650,7 +651,7 @@ __global__ __launch_bounds__(256) void fp8_dequant_rows_kernel(const uint8_t* __
         const float v0 = e4m3fn_decode(u & 0xffu) * sc, v1 = e4m3fn_decode((u >> 8) & 0xffu) * sc;
         const float v2 = e4m3fn_decode((u >> 16) & 0xffu) * sc, v3 = e4m3fn_decode(u >> 24) * sc;
         if constexpr (sizeof(OutT) == 4) reinterpret_cast<float4*>(out)[i] = make_float4(v0, v1, v2, v3);
-        else reinterpret_cast<uint2*>(out)[i] = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+        else reinterpret_cast<uint2*>(out)[i] = make_uint2(Half<OutT>::pack2(v0, v1), Half<OutT>::pack2(v2, v3));
     }
 }
 
@@ -977,6 +978,9 @@ void launch_fp8_dequant_rows(const void* q, const float* scale, long rows, long 
     if (out_dtype == 1)
         hipLaunchKernelGGL(fp8_dequant_rows_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const uint8_t*)q, scale, rows,
                            cols, (bf16_t*)out);
+    else if (out_dtype == DT_F16)      // exact as long as code * scale stays an f16 value (a quantised corpus of unit rows does)
+        hipLaunchKernelGGL(fp8_dequant_rows_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (const uint8_t*)q, scale, rows,
+                           cols, (f16_t*)out);
     else
         hipLaunchKernelGGL(fp8_dequant_rows_kernel<float>, dim3(grid), dim3(256), 0, s, (const uint8_t*)q, scale, rows,
                            cols, (float*)out);

@@ -49,11 +49,18 @@ sgpt_status sgpt_scores(sgpt_ctx* c, const void* a, const void* b, int32_t dtype
 // it and the call takes the materialise-and-select path -- the sync-free fallback of sgpt_score_topk_refined.
 static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpus, int32_t dtype, int32_t nq, int64_t N,
                                    int32_t d, int32_t k, int64_t idx_base, const float* in_val, const int64_t* in_idx,
-                                   float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out, void* stream, const int* pred_all) {
+                                   float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out, void* stream, const int* pred_all,
+                                   const float* q8_scale = nullptr) {
+    // q8_scale (sgpt_score_topk_q8, short query batches): `corpus` holds e4m3fn codes [N][d] bytes, q8_scale one power-of-two scale per
+    // document, q is f16 (dtype SGPT_F16).  Same schedule; only the launches that read the corpus change: whole 256-document tiles go
+    // through score64q8_kernel (score8.hip), a ragged tail is de-quantised into f16 scratch for the register-staged kernel.
+    const bool q8 = q8_scale != nullptr;
     if (!c || !q || !corpus || !run_val || !run_idx || nq <= 0 || N <= 0 || k <= 0 || n_run < 0 || n_run > k)
         return fail(c, SGPT_ERR_INVALID, "sgpt_score_topk: bad arguments");
     sgpt_status st = check_score_dims(c, dtype, d);
     if (st != SGPT_OK) return st;
+    if (q8 && !(dtype == SGPT_F16 && nq <= 64 && score64q8_shape_ok(64, 256, d, corpus, d)))
+        return fail(c, SGPT_ERR_INVALID, "score (fp8 corpus): shape not served by the streaming tile");
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     // chunk the corpus so the fp32 score tile [nq, chunk] stays resident in the 256 MiB Infinity Cache, and so
@@ -177,6 +184,10 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
     st = ensure(c, &c->ws2, &c->ws2_bytes,
                 sc_bytes + 3 * (tv_bytes + ti_bytes) + qp_bytes + cv_bytes + ci_bytes + cc_bytes + th_bytes);
     if (st != SGPT_OK) return st;
+    if (q8) {       // f16 rows of a ragged tail (< 256 documents)
+        st = ensure(c, &c->ws6, &c->ws6_bytes, (size_t)256 * d * 2);
+        if (st != SGPT_OK) return st;
+    }
     char* base = (char*)c->ws2;
     size_t off = 0;
     auto take = [&](size_t bytes) { char* p_ = base + off; off += bytes; return p_; };
@@ -206,7 +217,19 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
         if (filt) HIPC(c, hipMemsetAsync(cand_cnt, 0, (size_t)(nq_pad + n_flags) * 4, s));
         if (fresh_list) HIPC(c, hipMemsetAsync(ti[0], 0xff, (size_t)nq * k * 8, s));
     }
-    const size_t esz = dtype == SGPT_F32 ? 4 : 2;
+    const size_t esz = q8 ? 1 : (dtype == SGPT_F32 ? 4 : 2);
+    // one launch that reads documents [doc0, doc0 + h.N) (at row_stride): h.W / h.ldw are set for them already
+    auto docs_gemm = [&](int epi, GemmArgs h, long doc0, long row_stride) {
+        if (!q8) { gemm(c, dtype, epi, SGPT_F32, h, s); return; }
+        if (h.N % 256 == 0) {
+            Score8Args a8{h, q8_scale + doc0, row_stride};
+            launch_score64q8(epi, a8, s);
+        } else {        // (the tail is never strided)
+            launch_fp8_dequant_rows(h.W, q8_scale + doc0, h.N, d, c->ws6, SGPT_F16, s);
+            h.W = c->ws6; h.ldw = d;
+            gemm(c, SGPT_F16, epi, SGPT_F32, h, s);
+        }
+    };
 
     // fp32 scores of documents [c0, c0 + nc) for every query -> sc[nq][ld]
     auto score_tile = [&](long c0, long nc, long ld, const int* pred, long row_stride = 1) {
@@ -226,11 +249,11 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
         if (na > 0) {
             GemmArgs h = g;
             h.A = qpad; h.M = nq_pad; h.N = (int)(fold ? na + 256 : na); h.n_valid = fold ? (int)nc : 0;
-            gemm(c, dtype, EPI_SCORE, SGPT_F32, h, s);
+            docs_gemm(EPI_SCORE, h, c0, row_stride);
         }
         if (na < nc && !fold) {                         // fp32, or the ragged tail (< 256 documents): register-staged kernel
             g.W = (const char*)corpus + (size_t)(c0 + na) * d * esz; g.N = (int)(nc - na); g.out = sc + na;
-            gemm(c, dtype, EPI_SCORE, SGPT_F32, g, s);
+            docs_gemm(EPI_SCORE, g, c0 + na, 1);
         }
     };
     // Materialise-and-select over documents [lo, hi): the reference's chunk loop (exact_search.py:96-132).
@@ -340,7 +363,7 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
             // columns, GemmArgs.n_valid) when documents are its streamed operand; the 64-row tile keeps its own tail launch
             const bool fold_tail = SGPT_FOLD_TAIL && seen + len == n256 && N > n256 && gemm_score_tail_foldable(nq_pad, len + 256, d);
             if (fold_tail) { g.N = (int)(len + 256); g.n_valid = (int)(len + (N - n256)); }
-            gemm(c, dtype, EPI_SCORE_FILTER, SGPT_F32, g, s);
+            docs_gemm(EPI_SCORE_FILTER, g, seen, 1);
             g.n_valid = 0;
             const long c_lo = seen;
             seen += len;
@@ -350,7 +373,7 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
                 // ragged tail (< 256 documents): filtered against the same thresholds by the small-tile kernel, its
                 // survivors join this chunk's candidate lists -- one merge, no materialise + select round for 72 documents
                 g.W = (const char*)corpus + (size_t)seen * d * esz; g.N = (int)(N - seen); g.idx_base = idx_base + seen;
-                gemm(c, dtype, EPI_SCORE_FILTER, SGPT_F32, g, s);
+                docs_gemm(EPI_SCORE_FILTER, g, seen, 1);
                 seen = N;
             }
             const bool fin = seen >= N;
@@ -384,6 +407,32 @@ sgpt_status sgpt_score_topk(sgpt_ctx* c, const void* q, const void* corpus, int3
                             int32_t d, int32_t k, int64_t idx_base, float* run_val, int64_t* run_idx, int32_t n_run,
                             int32_t* n_out, void* stream) {
     return score_topk_impl(c, q, corpus, dtype, nq, N, d, k, idx_base, run_val, run_idx, run_val, run_idx, n_run, n_out, stream, nullptr);
+}
+
+// The same over a corpus of e4m3fn codes + one power-of-two scale per document (include/sgpt_hip.h).
+sgpt_status sgpt_score_topk_q8(sgpt_ctx* c, const void* q, const uint8_t* codes, const float* scale, int32_t nq, int64_t N, int32_t d,
+                               int32_t k, int64_t idx_base, float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out, void* stream) {
+    if (!c || !q || !codes || !scale || !run_val || !run_idx || nq <= 0 || N <= 0 || d <= 0 || d % 8 || k <= 0 || n_run < 0 || n_run > k ||
+        ((size_t)q & 15) || ((size_t)codes & 3))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_score_topk_q8: bad arguments (d % 8 == 0, 0 <= n_run <= k, q 16-byte aligned)");
+    // short query batches on a served width: the streaming tile reads the codes themselves
+    if (nq <= 64 && score64q8_shape_ok(64, 256, d, codes, d))
+        return score_topk_impl(c, q, codes, SGPT_F16, nq, N, d, k, idx_base, run_val, run_idx, run_val, run_idx, n_run, n_out, stream, nullptr, scale);
+    // everything else (MFMA-bound, or a width the tile does not serve): blocks of at most 131 072 documents de-quantised to f16 rows
+    // and scored by the f16 path, the running list chained from block to block -- the corpus stays one byte per element in memory
+    const int64_t blk = 131072;
+    HIPC(c, hipSetDevice(c->device));
+    sgpt_status st = ensure(c, &c->ws6, &c->ws6_bytes, (size_t)(N < blk ? N : blk) * d * 2);
+    if (st != SGPT_OK) return st;
+    int32_t have = n_run;
+    for (int64_t b0 = 0; b0 < N; b0 += blk) {
+        const int64_t nb = N - b0 < blk ? N - b0 : blk;
+        launch_fp8_dequant_rows(codes + (size_t)b0 * d, scale + b0, nb, d, c->ws6, SGPT_F16, (hipStream_t)stream);
+        st = score_topk_impl(c, q, c->ws6, SGPT_F16, nq, nb, d, k, idx_base + b0, run_val, run_idx, run_val, run_idx, have, &have, stream, nullptr);
+        if (st != SGPT_OK) return st;
+    }
+    if (n_out) *n_out = have;
+    return SGPT_OK;
 }
 
 // The exact-fp32 top-k at the 16-bit scorer's speed (round 5): what `torch.mm(q, c.T)` + `torch.topk` of the reference compute in

@@ -2,6 +2,7 @@
 memory (torch.empty / .data_ptr()) and to name the current HIP stream -- every computation is
 a call into libsgpt_hip.so.  No torch compute op stands in for a kernel here."""
 import ctypes as C
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import numpy as np
@@ -20,6 +21,29 @@ def _stream_ptr(device) -> C.c_void_p:
 
 def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+@dataclass
+class QuantizedCorpus:
+    """A corpus held as fp8: `codes` uint8 [N, d] (OCP e4m3fn) and `scale` fp32 [N], one power of two per document (the format of
+    include/sgpt_hip.h::sgpt_score_topk_q8; document n = codes[n] * scale[n]).  `normalized`: the rows were L2-normalised before
+    quantisation (cosine scores) or not (dot scores).  Built by Context.quantize_corpus / util.quantize_embeddings."""
+    codes: torch.Tensor
+    scale: torch.Tensor
+    normalized: bool = True
+    dim: Optional[int] = None        # width of the embeddings; codes carry zero columns up to the next multiple of 8 (None: no padding)
+
+    def __len__(self) -> int:
+        return int(self.codes.shape[0])
+
+    @property
+    def nbytes(self) -> int:
+        return self.codes.numel() * self.codes.element_size() + self.scale.numel() * self.scale.element_size()
+
+    def dequantize(self, dtype=torch.float32) -> torch.Tensor:
+        """The rows the scorer sees, codes * scale, on the device: exact in fp32, and in f16 / bf16 while codes * scale is a value
+        of that format (unit rows are).  As wide as `codes` (zero columns behind `dim` included)."""
+        return get_context(self.codes.device).fp8_dequantize_rows(self.codes, self.scale, out_dtype=dtype)
 
 
 _contexts = {}
@@ -209,6 +233,29 @@ class Context:
                                                     DT_CODE[out_dtype],
                                                     _stream_ptr(self.device)), "sgpt_fp8_dequantize_rows")
         return out
+
+    def quantize_corpus(self, emb, normalize: bool = True, block_rows: int = 65536) -> QuantizedCorpus:
+        """Embeddings [N, d] -> QuantizedCorpus (d padded with zero columns to a multiple of 8): rows L2-normalised (normalize=True, cosine search) or taken as they are
+        (dot scores), then sgpt_fp8_quantize_rows.  Works in blocks of `block_rows` rows, so the fp32 (normalised) copy of a large
+        corpus never exists whole on the device; `emb` may live on the host."""
+        if not isinstance(emb, torch.Tensor):
+            emb = torch.as_tensor(np.asarray(emb))
+        if emb.dim() != 2 or emb.shape[0] == 0 or emb.shape[1] == 0:
+            raise ValueError(f"quantize_corpus needs a non-empty [N, d] matrix, got {tuple(emb.shape)}")
+        N, d0 = emb.shape
+        d = (d0 + 7) // 8 * 8          # the scorer takes d % 8 == 0: zero columns (zero codes) change no score
+        codes = torch.empty((N, d), dtype=torch.uint8, device=self.device)
+        scale = torch.empty((N,), dtype=torch.float32, device=self.device)
+        for r0 in range(0, N, block_rows):
+            n = min(block_rows, N - r0)
+            blk = self._dev_f32(emb[r0:r0 + n])
+            if normalize:
+                blk = self.l2_normalize(blk)
+            if d != d0:
+                blk = torch.nn.functional.pad(blk, (0, d - d0))
+            self._chk(self.lib.sgpt_fp8_quantize_rows(self.handle, _p(blk), n, d, _p(codes[r0:r0 + n]), _p(scale[r0:r0 + n]),
+                                                      _stream_ptr(self.device)), "sgpt_fp8_quantize_rows")
+        return QuantizedCorpus(codes, scale, bool(normalize), d0)
 
     def _operand(self, x: torch.Tensor, dtype) -> torch.Tensor:
         if x.dtype == dtype and x.device == self.device and x.is_contiguous():
@@ -532,7 +579,31 @@ class Context:
     def score_topk(self, q: torch.Tensor, corpus: torch.Tensor, k: int, idx_base: int = 0,
                    run: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None,
                    dtype=None) -> Tuple[torch.Tensor, torch.Tensor, int]:
-        """-> (values fp32[nq,k], indices int64[nq,k], n_valid); rows sorted by descending score."""
+        """-> (values fp32[nq,k], indices int64[nq,k], n_valid); rows sorted by descending score.  `corpus` may be a QuantizedCorpus
+        (fp8 codes + per-document scales): the queries are then f16 (dtype None / torch.float16 only) and the result equals the f16
+        scorer's on corpus.dequantize(torch.float16), sgpt_score_topk_q8."""
+        if isinstance(corpus, QuantizedCorpus):
+            if dtype not in (None, torch.float16):
+                raise ValueError(f"a QuantizedCorpus is scored with f16 queries: dtype must be None or torch.float16, got {dtype}")
+            if q.shape[1] != corpus.codes.shape[1] and q.shape[1] == corpus.dim:
+                q = torch.nn.functional.pad(q, (0, corpus.codes.shape[1] - q.shape[1]))
+            q = self._operand(q, torch.float16)
+            codes = corpus.codes.to(self.device).contiguous()
+            scale = corpus.scale.to(device=self.device, dtype=torch.float32).contiguous()
+            nq, d = q.shape
+            N, d2 = codes.shape
+            if d != d2:
+                raise ValueError(f"embedding dims differ: {d} vs {d2}")
+            if run is None:
+                val = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+                idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+                n_run = 0
+            else:
+                val, idx, n_run = run
+            n_out = C.c_int32(0)
+            self._chk(self.lib.sgpt_score_topk_q8(self.handle, _p(q), _p(codes), _p(scale), nq, N, d, k, idx_base, _p(val), _p(idx),
+                                                  n_run, C.byref(n_out), _stream_ptr(self.device)), "sgpt_score_topk_q8")
+            return val, idx, int(n_out.value)
         if dtype is None:
             dtype = corpus.dtype if corpus.dtype in DT_CODE else torch.float32
         q, corpus = self._operand(q, dtype), self._operand(corpus, dtype)

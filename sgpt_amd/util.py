@@ -6,7 +6,7 @@ from typing import Callable, List
 import numpy as np
 import torch
 
-from .runtime import get_context
+from .runtime import QuantizedCorpus, get_context
 
 
 def _ctx_for(*xs):
@@ -69,6 +69,35 @@ def pairwise_cos_sim(a, b) -> torch.Tensor:
     return out if home.type == "cuda" else out.cpu()
 
 
+def quantize_embeddings(embeddings, precision: str = "fp8", normalize: bool = True) -> QuantizedCorpus:
+    """Corpus embeddings -> QuantizedCorpus (e4m3fn codes + one power-of-two scale per row): one byte per element on the device, and
+    per search pass.  Named after sentence-transformers' later `quantize_embeddings`; "fp8" is the only precision.  normalize=True
+    L2-normalises the rows first (search with cos_sim), normalize=False keeps them (search with dot_score)."""
+    if precision != "fp8":
+        raise ValueError(f"quantize_embeddings: unknown precision {precision!r} (only 'fp8' is built)")
+    if isinstance(embeddings, list):
+        embeddings = torch.stack(embeddings)
+    e = _wrap(embeddings)
+    ctx, _ = _ctx_for(e)
+    return ctx.quantize_corpus(e, normalize=normalize)
+
+
+def _search_quantized(q, corpus: QuantizedCorpus, top_k: int, score_function) -> List[List[dict]]:
+    cosine = score_function in (cos_sim, pytorch_cos_sim)
+    if not cosine and score_function is not dot_score:
+        raise ValueError("semantic_search over a QuantizedCorpus scores with cos_sim or dot_score; an arbitrary score function needs "
+                         "the de-quantised rows (corpus.dequantize())")
+    if cosine != bool(corpus.normalized):
+        raise ValueError("semantic_search: cos_sim needs a corpus quantised with normalize=True, dot_score one with normalize=False "
+                         f"(this one has normalize={bool(corpus.normalized)})")
+    ctx, _ = _ctx_for(corpus.codes, q)
+    qd = ctx.l2_normalize(q) if cosine else ctx._dev_f32(q)
+    k = min(top_k, len(corpus))
+    val, idx, n = ctx.score_topk(qd, corpus, k)
+    val, idx = val.cpu().tolist(), idx.cpu().tolist()
+    return [[{"corpus_id": j, "score": s} for j, s in zip(ii[:n], vv[:n])] for vv, ii in zip(val, idx)]
+
+
 def semantic_search(query_embeddings, corpus_embeddings, query_chunk_size: int = 100,
                     corpus_chunk_size: int = 500000, top_k: int = 10,
                     score_function: Callable = cos_sim) -> List[List[dict]]:
@@ -77,6 +106,8 @@ def semantic_search(query_embeddings, corpus_embeddings, query_chunk_size: int =
     score + running-top-k pass on the GPU when score_function is cos_sim / dot_score."""
     if isinstance(query_embeddings, list):
         query_embeddings = torch.stack(query_embeddings)
+    if isinstance(corpus_embeddings, QuantizedCorpus):     # fp8 corpus (quantize_embeddings): one fused pass over the codes
+        return _search_quantized(_wrap(query_embeddings), corpus_embeddings, top_k, score_function)
     if isinstance(corpus_embeddings, list):
         corpus_embeddings = torch.stack(corpus_embeddings)
     q, c = _wrap(query_embeddings), _wrap(corpus_embeddings)
