@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 18
+#define SGPT_ABI_VERSION 19
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -431,6 +431,43 @@ sgpt_status sgpt_score_topk(sgpt_ctx* ctx, const void* q, const void* corpus, in
 sgpt_status sgpt_score_topk_q8(sgpt_ctx* ctx, const void* q, const uint8_t* codes, const float* scale, int32_t nq, int64_t N, int32_t d,
                                int32_t k, int64_t idx_base, float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out,
                                void* stream);
+
+/* Binary (1-bit) corpus (ABI v19): packed sign bits, Hamming search, re-scoring of an over-fetched candidate list -- the recipe known
+ * as quantize_embeddings(precision="ubinary") + Hamming search + rescoring.  96 bytes per document at d = 768: 1/16 of f16 rows.
+ *   format    bits device uint8 [N, ldb], ldb % 4 == 0, ldb >= 4 * ceil(d / 32).  Dimension i of a document is bit 7 - i % 8 of byte
+ *             i / 8 (the order of numpy.packbits); a bit is 1 exactly when the element is > 0 (NaN, +0, -0 give 0); bits d .. 8 ldb - 1
+ *             are zero.  bits[:, :ceil(d / 8)] equals numpy.packbits(x > 0, axis=-1).
+ * sgpt_pack_sign_bits: rows x - center (center device fp32 [d], or NULL: rows x) of x device fp32 [n, d] -> that format, pad bits
+ * included.  SGPT_ERR_INVALID: null pointers, n <= 0, d <= 0, a bad ldb. */
+sgpt_status sgpt_pack_sign_bits(sgpt_ctx* ctx, const float* x, int64_t n, int32_t d, const float* center /* fp32[d] or NULL */,
+                                uint8_t* bits, int64_t ldb, void* stream);
+
+/* sgpt_score_topk_bits (ABI v19): two-stage search over a binary corpus.
+ *   q         device fp32 [nq, d]: normalised by the caller, and centred if the corpus was; the call packs its sign bits itself.
+ *   stage 1   always fresh on this call's N documents: agreement a = d - 2 * hamming(sign q, bits[n]) = <sign q, sign d_n> (signs +-1), an
+ *             integer; the candidate list is the min(kp, N) best by (a descending, index ascending) -- exact, whatever ties there are.
+ *             The Hamming tile (csrc/scorebits.hip) streams the rows through registers under sgpt_score_topk's filtered schedule; a
+ *             candidate-list overflow (integer scores tie at the threshold) takes the same predicated, sync-free fallback.
+ *   mode 0    Hamming only, kp == k: value float(a) / float(d), one IEEE fp32 division; order a descending, ties to the lowest index.
+ *   mode 1    sign re-scoring, no extra memory: value <q, s_n> / sqrt(d), s_n the document's +-1 sign vector over its d true dimensions,
+ *             accumulated in fp32.
+ *   mode 2    fp8 re-scoring: codes / scale = the same documents in the format of sgpt_score_topk_q8, code rows ceil(d / 8) * 8 bytes
+ *             apart (the padded width the quantiser produced); value <q, code_n * scale_n> in fp32; a NaN code gives -1.
+ *             Modes 1 and 2 order by value descending, ties to the lowest index.  k <= kp <= 1024.
+ *   result    as sgpt_score_topk: this call's list is merged with the running list (run_val / run_idx, n_run) into the new top-k, unused
+ *             tail (-inf, -1), *n_out = min(k, n_run + N), a NaN value becomes -1.  The running list must hold values of the SAME mode
+ *             (and the same d for mode 0): values of different modes are not comparable.
+ *   shapes    any nq >= 1 (queries beyond 64 are served in groups of 64, each re-streaming the rows), any d >= 1, any N >= 1; speed is
+ *             claimed for d % 128 == 0 (16-byte loads need ldb % 16 == 0 and 16-byte aligned bits; a dword path serves the rest).
+ * SGPT_ERR_INVALID (nothing launched, outputs untouched): null pointers; ldb < 4 * ceil(d / 32) or ldb % 4; k <= 0, kp < k, kp > 1024,
+ * mode 0 with kp != k; mode outside 0..2; mode 2 without codes or scale; n_run < 0 or n_run > k. */
+sgpt_status sgpt_score_topk_bits(sgpt_ctx* ctx, const float* q, const uint8_t* bits, int64_t ldb, int32_t nq, int64_t N, int32_t d,
+                                 int32_t k, int32_t kp, int32_t mode, const uint8_t* codes, const float* scale, int64_t idx_base,
+                                 float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out, void* stream);
+
+/* Diagnostics (ABI v19): of the filtered chunks of the LAST score + top-k pass on this context (sgpt_score_topk, _q8; _bits: its last
+ * query group), how many overflowed their candidate lists and were recomputed by the predicated fallback.  Synchronises `stream`. */
+sgpt_status sgpt_score_overflow_count(sgpt_ctx* ctx, int32_t* n_chunks, int32_t* n_overflowed, void* stream);
 
 /* sgpt_score_topk_refined (ABI v7): the reference's fp32 scoring + top-k (`torch.mm(a, b.T)`, util.py:41-43,63; `torch.topk`,
  * exact_search.py:96-108) -- fp32 scores of the returned documents, the fp32 top-k set -- at the speed of the 16-bit scorer.

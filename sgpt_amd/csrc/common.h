@@ -348,6 +348,11 @@ struct Score8Args {
 };
 bool score64q8_shape_ok(int M, long N, int K, const void* codes, long ldw);
 void launch_score64q8(int epi, const Score8Args& a, hipStream_t s);
+// scorebits.hip: the Hamming tile over packed sign bits (sgpt_score_topk_bits).  g.A = packed query rows (g.m_valid of them, qw dwords
+// apart), g.W = document rows g.ldw BYTES apart (ldb bytes each, times the row stride of a sample), g.N documents (any number,
+// bounds-checked); score = d - 2 * hamming as an exact fp32; epi = EPI_SCORE | EPI_SCORE_FILTER with score64_kernel's contract.
+// spread: EPI_SCORE of a threshold SAMPLE -- a - (column & 4095) / 4096, so that the select over it does not meet masses of equal keys.
+void launch_scorebits(int epi, const GemmArgs& g, int d, int qw, long ldb, hipStream_t s, bool spread = false);
 // gemm256w.hip: the 256x256 LDS-DMA kernel on v_mfma_f32_32x32x16 (16-bit operands and outputs as gemm256d_kernel)
 void launch_gemm256w(int dtype, int epi, const GemmArgs& a, hipStream_t s, bool deep_a);
 
@@ -425,6 +430,8 @@ void launch_fp8_quant_rows(const float* w, long rows, long cols, void* q, float*
 void launch_fp8_dequant_rows(const void* q, const float* scale, long rows, long cols, void* out, int out_dtype,
                              hipStream_t s);
 void launch_l2norm(const float* in, long n, int d, void* out, int out_dtype, hipStream_t s);
+// bit 7 - i % 8 of bits[r][i / 8] = (x[r][i] - center[i] > 0) (center null: x[r][i] > 0); NaN, +-0 -> 0; bytes up to ldb zero-padded
+void launch_pack_sign_bits(const float* x, long n, int d, const float* center, uint8_t* bits, long ldb, hipStream_t s);
 void launch_pairwise(const float* a, const float* b, long n, int d, bool cosine, float* out, hipStream_t s);
 // cross-encoder scoring (sgptce.py): gather hidden rows; log_softmax + gather target + argmax per logits row
 void launch_gather_rows(const float* src, const int* row_idx, int n, int d, float* dst, hipStream_t s);
@@ -461,6 +468,12 @@ void launch_topk_select(const float* scores, long ld, long n, long idx_base, con
 // refined scorer (sgpt_score_topk_refined): exact fp32 scores of stage-1 candidates, the guarantee check, list concatenation
 void launch_rescore(const float* q, const float* corpus, const int64_t* idx, long ld_idx, int nq, int m, int d, long idx_base,
                     long n_docs, float* out_val, int64_t* out_idx, long ld_out, hipStream_t s);
+// sgpt_score_topk_bits, stage 2: the value of every stage-1 candidate (idx [nq, ld_idx], agreement a in val1) by `mode` -- 0: a / d;
+// 1: <q, sign row> / sqrt(d) from the bits; 2: <q, code row> * scale from an fp8 copy (codes ld8 bytes apart) -- into the first m
+// columns of a [nq, ld_out] list (launch_rescore's layout)
+void launch_rescore_bits(int mode, const float* q, const uint8_t* bits, long ldb, const uint8_t* codes, long ld8, const float* scale,
+                         const float* val1, const int64_t* idx, long ld_idx, int nq, int m, int d, long idx_base, long n_docs,
+                         float* out_val, int64_t* out_idx, long ld_out, hipStream_t s);
 void launch_refine_check(const float* v16, int k, int kp, float margin, int nq, int* flag, hipStream_t s);
 void launch_list_append(const float* in_val, const int64_t* in_idx, long ld_in, int n_run, int nq, float* out_val, int64_t* out_idx,
                         long ld_out, int col0, hipStream_t s);

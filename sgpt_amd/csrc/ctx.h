@@ -13,9 +13,10 @@ struct sgpt_ctx {
     void* ws = nullptr; size_t ws_bytes = 0;        // encoder activations
     void* ws2 = nullptr; size_t ws2_bytes = 0;      // scorer: score chunk + ping-pong top-k
     void* ws3 = nullptr; size_t ws3_bytes = 0;      // multi-GPU exchange staging (comm.hip)
-    void* ws4 = nullptr; size_t ws4_bytes = 0;      // refined scorer: 16-bit queries, stage-1 lists, candidate list, saved running list, flag
+    void* ws4 = nullptr; size_t ws4_bytes = 0;      // refined / binary-corpus scorer: 16-bit or packed queries, stage-1 lists, candidate list, saved running list, flag
     void* ws5 = nullptr; size_t ws5_bytes = 0;      // evaluation (useb_eval.hip): sort keys, flag scan, block partials of sgpt_eval_pairs
     void* ws6 = nullptr; size_t ws6_bytes = 0;      // fp8 corpus (sgpt_score_topk_q8): f16 rows of the de-quantised block / ragged tail
+    size_t filt_flag_off = 0; int filt_chunks = 0;   // scorer: overflow flags (offset into ws2, which only grows) of the last pass's filtered chunks (sgpt_score_overflow_count)
     void* comm = nullptr;                         // ncclComm_t of this ctx (sgpt_comm_init), one per process / GPU
     int comm_rank = 0, comm_world = 0;
     // bumped whenever a library-owned buffer that launched kernels point into is re-allocated (workspace growth,

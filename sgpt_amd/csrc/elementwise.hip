@@ -640,6 +640,30 @@ __global__ __launch_bounds__(256) void fp8_quant_rows_kernel(const float* __rest
     for (long c = lane; c < cols; c += 64) q[row * cols + c] = (uint8_t)e4m3fn_encode(wr[c] * inv);
 }
 
+// Sign bits of the rows x - center (center null: x), packed in the order of numpy.packbits: dimension i is bit 7 - i % 8 of byte i / 8,
+// set exactly when the element is > 0 (NaN, +0, -0: clear); bits d .. 8 ldb - 1 are zero.  One thread per output byte.  The test is
+// taken on the bit pattern (0 < bits <= +inf's), so a subnormal element counts as positive whatever the denormal mode of the compare.
+__global__ __launch_bounds__(256) void pack_sign_bits_kernel(const float* __restrict__ x, long n, int d, const float* __restrict__ center,
+                                                             uint8_t* __restrict__ bits, long ldb) {
+    const long total = n * ldb, stride = (long)gridDim.x * 256;
+    for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < total; o += stride) {
+        const long r = o / ldb;
+        const int i0 = (int)(o - r * ldb) * 8;
+        const float* xr = x + r * d;
+        uint32_t b = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int i = i0 + j;
+            if (i < d) {
+                const float v = center ? xr[i] - center[i] : xr[i];
+                const uint32_t u = __float_as_uint(v);
+                b |= (u - 1u < 0x7f800000u ? 1u : 0u) << (7 - j);
+            }
+        }
+        bits[o] = (uint8_t)b;
+    }
+}
+
 template <typename OutT>
 __global__ __launch_bounds__(256) void fp8_dequant_rows_kernel(const uint8_t* __restrict__ q, const float* __restrict__ scale,
                                                                long rows, long cols, OutT* __restrict__ out) {
@@ -965,6 +989,12 @@ void launch_pool(const void* hidden, int dtype, const int* mask, int B, int S, i
         hipLaunchKernelGGL(pool_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)hidden, mask, S, d, mode, pos_weights, out);
     else
         hipLaunchKernelGGL(pool_kernel<float>, grid, dim3(256), 0, s, (const float*)hidden, mask, S, d, mode, pos_weights, out);
+}
+
+void launch_pack_sign_bits(const float* x, long n, int d, const float* center, uint8_t* bits, long ldb, hipStream_t s) {
+    const long blocks = (n * ldb + 255) / 256;
+    hipLaunchKernelGGL(pack_sign_bits_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 65536 ? 65536 : blocks))), dim3(256), 0, s, x, n, d,
+                       center, bits, ldb);
 }
 
 void launch_fp8_quant_rows(const float* w, long rows, long cols, void* q, float* scale, hipStream_t s) {

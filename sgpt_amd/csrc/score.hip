@@ -47,18 +47,25 @@ sgpt_status sgpt_scores(sgpt_ctx* c, const void* a, const void* b, int32_t dtype
 // in_val / in_idx: the running list going in (n_run entries per row, row stride k); run_val / run_idx: the list coming out (they
 // may be the same buffers -- the public entry point).  pred_all (device flag or null): every launch of the call is predicated on
 // it and the call takes the materialise-and-select path -- the sync-free fallback of sgpt_score_topk_refined.
+// A corpus of packed sign bits (sgpt_score_topk_bits): rows of ldb bytes, queries packed alike in rows of qw dwords
+struct BitRows { long ldb; int qw; };
+
 static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpus, int32_t dtype, int32_t nq, int64_t N,
                                    int32_t d, int32_t k, int64_t idx_base, const float* in_val, const int64_t* in_idx,
                                    float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out, void* stream, const int* pred_all,
-                                   const float* q8_scale = nullptr) {
+                                   const float* q8_scale = nullptr, const BitRows* bits = nullptr) {
     // q8_scale (sgpt_score_topk_q8, short query batches): `corpus` holds e4m3fn codes [N][d] bytes, q8_scale one power-of-two scale per
     // document, q is f16 (dtype SGPT_F16).  Same schedule; only the launches that read the corpus change: whole 256-document tiles go
     // through score64q8_kernel (score8.hip), a ragged tail is de-quantised into f16 scratch for the register-staged kernel.
+    // bits (sgpt_score_topk_bits, at most 64 queries per call): `corpus` holds packed sign bits [N][bits->ldb] bytes, q the packed
+    // query rows; the score is the agreement d - 2 * hamming, an integer in fp32.  Same schedule again; every launch that reads the
+    // corpus is the Hamming tile (scorebits.hip), which takes any number of documents, so no launch is split for a ragged tail.
     const bool q8 = q8_scale != nullptr;
     if (!c || !q || !corpus || !run_val || !run_idx || nq <= 0 || N <= 0 || k <= 0 || n_run < 0 || n_run > k)
         return fail(c, SGPT_ERR_INVALID, "sgpt_score_topk: bad arguments");
-    sgpt_status st = check_score_dims(c, dtype, d);
+    sgpt_status st = bits ? SGPT_OK : check_score_dims(c, dtype, d);
     if (st != SGPT_OK) return st;
+    if (bits && (nq > 64 || d <= 0 || q8)) return fail(c, SGPT_ERR_INVALID, "score (binary corpus): at most 64 queries per pass");
     if (q8 && !(dtype == SGPT_F16 && nq <= 64 && score64q8_shape_ok(64, 256, d, corpus, d)))
         return fail(c, SGPT_ERR_INVALID, "score (fp8 corpus): shape not served by the streaming tile");
     HIPC(c, hipSetDevice(c->device));
@@ -77,7 +84,7 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
     // bf16 fast path: the 256x256 LDS-DMA GEMM needs the query rows padded to a multiple of 256 (zero rows,
     // never stored) and d % 64 == 0; chunks that are multiples of 256 documents take it, the ragged tail and
     // fp32 go through the 128^2 kernel.
-    const bool fast = dtype != SGPT_F32 && d % 64 == 0 && d >= 128;
+    const bool fast = bits || (dtype != SGPT_F32 && d % 64 == 0 && d >= 128);
     // nq <= 64: the 64-query-row scorer tile (score64_kernel) instead of 256 padded rows -- the pass is HBM-bound there
     static const bool no_small_q = exp_env("SGPT_SCORE_NO64") != nullptr;      // A/B switch (experiment build only)
     const int nq_pad = (fast && nq <= 64 && !no_small_q) ? 64 : (nq + 255) / 256 * 256;
@@ -132,7 +139,9 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
     const int growth = 1;
     const bool filt = fast && !classic_only && k <= 1024 && chunk % 256 == 0 && N >= 2 * chunk && pred_all == nullptr;
     const bool sampled = filt && sampled_k;
-    const double ratio = (double)cap / ((double)k * (1.0 + 6.0 / std::sqrt((double)k)));   // documents per threshold document
+    // (binary corpus: half the ratio.  Integer agreements tie at the threshold, and the inclusive threshold lets the whole tie class of
+    //  the k-th best through -- up to ~2x the survivors at d = 768.)
+    const double ratio = (double)cap / ((double)k * (1.0 + 6.0 / std::sqrt((double)k))) * (bits ? 0.5 : 1.0);   // documents per threshold document
     const long n256_all = N / 256 * 256;
     long S = 0, s_stride = 1;                           // sample size (documents) and row stride
     if (sampled) {
@@ -143,6 +152,11 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
         if (S < 2048) S = 2048;
         const long s_max = (long)(((size_t)512 << 20) / ((size_t)nq * 4)) / 256 * 256;
         if (S > s_max) S = s_max > 2048 ? s_max : 2048;
+        // binary corpus: a sample the select takes in ONE pass -- its LDS candidate list (2048 slots) expects k * S / 1024 entries, and
+        // past it the radix passes over a million columns on one workgroup per query cost more than the whole bit stream
+        // (profiles/score_bits_corpus.txt, variant B: 16 M x 768, nq = 1, 10.8 ms without this bound and the spread sample scores, 0.38 ms with both).  The filtered chunks then grow from S * ratio documents as the merges raise the
+        // thresholds: two launches for 16 M documents instead of one.
+        if (bits) { const long s_one = 1000L * 1024 / k / 256 * 256; if (S > s_one) S = s_one > 2048 ? s_one : 2048; }
         if (S > n256_all / 2) S = n256_all / 2 / 256 * 256;
         s_stride = n256_all / S;
         if (s_stride < 1) s_stride = 1;
@@ -177,7 +191,7 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
     const long n_flags = 64 + N / (1L << 19) + 1;      // one overflow flag per filtered chunk
     const size_t sc_bytes = align_up((size_t)nq * (fchunk > S ? fchunk : S) * 4, 256);
     const size_t tv_bytes = align_up((size_t)nq * k * 4, 256), ti_bytes = align_up((size_t)nq * k * 8, 256);
-    const size_t qp_bytes = fast ? align_up((size_t)nq_pad * d * 2, 256) : 0;
+    const size_t qp_bytes = fast && !bits ? align_up((size_t)nq_pad * d * 2, 256) : 0;     // (packed query rows are read where they are)
     const size_t cv_bytes = filt ? align_up((size_t)nq * cap * 4, 256) : 0, ci_bytes = filt ? align_up((size_t)nq * cap * 8, 256) : 0;
     const size_t cc_bytes = filt ? align_up((size_t)(nq_pad + n_flags) * 4, 256) : 0;  // counters + per-chunk overflow flags
     const size_t th_bytes = sampled ? tv_bytes + ti_bytes + align_up((size_t)nq * 4, 256) : 0;   // sample's list + dense thresholds
@@ -196,7 +210,7 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
     tv[0] = (float*)take(tv_bytes); tv[1] = (float*)take(tv_bytes);
     ti[0] = (int64_t*)take(ti_bytes); ti[1] = (int64_t*)take(ti_bytes);
     float* sav_v = (float*)take(tv_bytes); int64_t* sav_i = (int64_t*)take(ti_bytes);   // third list: ping-pong partner of a recomputation
-    void* qpad = fast ? take(qp_bytes) : nullptr;
+    void* qpad = bits ? const_cast<void*>(q) : (fast ? take(qp_bytes) : nullptr);
     float* cand_v = filt ? (float*)take(cv_bytes) : nullptr;
     long long* cand_i = filt ? (long long*)take(ci_bytes) : nullptr;
     int* cand_cnt = filt ? (int*)take(cc_bytes) : nullptr;
@@ -206,8 +220,8 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
     float* thr_dense = sampled ? (float*)take(align_up((size_t)nq * 4, 256)) : nullptr;
     // prologue: one launch (query rows into their zero-padded tile, counters and flags cleared, an empty running list marked)
     const bool fresh_list = sampled && n_run == 0;
-    if (fast && d % 8 == 0 && ((size_t)q & 15) == 0) {
-        launch_score_prep(q, qpad, (long)nq * d * 2, (long)nq_pad * d * 2, filt ? cand_cnt : nullptr, filt ? (long)(nq_pad + n_flags) : 0,
+    if (bits || (fast && d % 8 == 0 && ((size_t)q & 15) == 0)) {
+        launch_score_prep(q, qpad, bits ? 0 : (long)nq * d * 2, bits ? 0 : (long)nq_pad * d * 2, filt ? cand_cnt : nullptr, filt ? (long)(nq_pad + n_flags) : 0,
                           fresh_list ? (long long*)ti[0] : nullptr, fresh_list ? (long)nq * k : 0, s);
     } else {
         if (fast) {
@@ -218,8 +232,11 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
         if (fresh_list) HIPC(c, hipMemsetAsync(ti[0], 0xff, (size_t)nq * k * 8, s));
     }
     const size_t esz = q8 ? 1 : (dtype == SGPT_F32 ? 4 : 2);
+    const size_t rowb = bits ? (size_t)bits->ldb : (size_t)d * esz;     // bytes of a corpus row
+    const long ldw1 = bits ? bits->ldb : d;                             // GemmArgs.ldw of consecutive rows (the Hamming tile counts bytes)
     // one launch that reads documents [doc0, doc0 + h.N) (at row_stride): h.W / h.ldw are set for them already
-    auto docs_gemm = [&](int epi, GemmArgs h, long doc0, long row_stride) {
+    auto docs_gemm = [&](int epi, GemmArgs h, long doc0, long row_stride, bool sample = false) {
+        if (bits) { h.A = q; h.m_valid = nq; launch_scorebits(epi, h, d, bits->qw, bits->ldb, s, sample); return; }
         if (!q8) { gemm(c, dtype, epi, SGPT_F32, h, s); return; }
         if (h.N % 256 == 0) {
             Score8Args a8{h, q8_scale + doc0, row_stride};
@@ -232,11 +249,12 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
     };
 
     // fp32 scores of documents [c0, c0 + nc) for every query -> sc[nq][ld]
-    auto score_tile = [&](long c0, long nc, long ld, const int* pred, long row_stride = 1) {
+    auto score_tile = [&](long c0, long nc, long ld, const int* pred, long row_stride = 1, bool sample = false) {
         GemmArgs g{};
         g.A = q; g.lda = d; g.M = nq; g.m_valid = nq; g.K = d; g.pred = pred;
-        g.W = (const char*)corpus + (size_t)c0 * d * esz; g.ldw = (long)d * row_stride; g.N = (int)nc;   // row_stride > 1: a strided sample
+        g.W = (const char*)corpus + (size_t)c0 * rowb; g.ldw = ldw1 * row_stride; g.N = (int)nc;   // row_stride > 1: a strided sample
         g.out = sc; g.ldo = ld;
+        if (bits) { docs_gemm(EPI_SCORE, g, c0, row_stride, sample); return; }
         const long na = fast ? nc / 256 * 256 : 0;      // documents the 256-document tile kernels take
         // (round 5, measured and reverted: handing a predicated fallback piece to the register-staged kernel whole -- one no-op launch
         //  instead of two -- made the shard pass 12 % SLOWER: a no-op launch of the persistent 256x256 kernel is 256 workgroups that
@@ -252,7 +270,7 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
             docs_gemm(EPI_SCORE, h, c0, row_stride);
         }
         if (na < nc && !fold) {                         // fp32, or the ragged tail (< 256 documents): register-staged kernel
-            g.W = (const char*)corpus + (size_t)(c0 + na) * d * esz; g.N = (int)(nc - na); g.out = sc + na;
+            g.W = (const char*)corpus + (size_t)(c0 + na) * rowb; g.N = (int)(nc - na); g.out = sc + na;
             docs_gemm(EPI_SCORE, g, c0 + na, 1);
         }
     };
@@ -298,6 +316,7 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
 
     const float* pv0 = n_run > 0 ? in_val : nullptr;
     const int64_t* pi0 = n_run > 0 ? in_idx : nullptr;
+    c->filt_chunks = 0;
     if (!filt) {
         st = classic(0, N, pv0, pi0, n_run, run_val, run_idx, pred_all, chunk);
         if (st != SGPT_OK) return st;
@@ -325,7 +344,7 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
                 gemm(c, dtype, EPI_SCORE_TOP2, SGPT_F32, h, s);
                 launch_topk_select(sc, ld2, ld2, 0, tv[0], ti[0], k, k, nq, k, 0, nullptr, th_v, th_i, s, nullptr, thr_dense);
             } else {
-                score_tile(0, S, S, nullptr, s_stride);
+                score_tile(0, S, S, nullptr, s_stride, true);      // (binary corpus: the sample's ties spread, launch_scorebits)
                 launch_topk_select(sc, S, S, 0, tv[0], ti[0], k, k, nq, k, 0, nullptr, th_v, th_i, s, nullptr, thr_dense);   // (+ the inclusive threshold)
             }
             eff = S;
@@ -354,15 +373,15 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
             else if (len >= unit) len = len / unit * unit;      //  left a 17 k-document sixth launch behind 1 M documents at nq = 16)
             GemmArgs g{};
             g.A = qpad; g.lda = d; g.M = nq_pad; g.m_valid = nq; g.K = d;
-            g.W = (const char*)corpus + (size_t)seen * d * esz; g.ldw = d; g.N = (int)len;
+            g.W = (const char*)corpus + (size_t)seen * rowb; g.ldw = ldw1; g.N = (int)len;
             // sampled schedule: the dense thresholds -- the sample's k-th best, raised by every merge to the running k-th best
             if (sampled) { g.thr = thr_dense; g.thr_ld = 1; }
             else { g.thr = tv[cur] + (k - 1); g.thr_ld = k; }
             g.cand_val = cand_v; g.cand_idx = cand_i; g.cand_cnt = cand_cnt; g.cand_cap = cap; g.idx_base = idx_base + seen;
             // the < 256 trailing documents ride in the last chunk's launch (the 256x256 kernel clamps their rows and masks their
             // columns, GemmArgs.n_valid) when documents are its streamed operand; the 64-row tile keeps its own tail launch
-            const bool fold_tail = SGPT_FOLD_TAIL && seen + len == n256 && N > n256 && gemm_score_tail_foldable(nq_pad, len + 256, d);
-            if (fold_tail) { g.N = (int)(len + 256); g.n_valid = (int)(len + (N - n256)); }
+            const bool fold_tail = seen + len == n256 && N > n256 && (bits || (SGPT_FOLD_TAIL && gemm_score_tail_foldable(nq_pad, len + 256, d)));
+            if (fold_tail) { g.N = (int)(bits ? len + (N - n256) : len + 256); g.n_valid = (int)(len + (N - n256)); }
             docs_gemm(EPI_SCORE_FILTER, g, seen, 1);
             g.n_valid = 0;
             const long c_lo = seen;
@@ -372,7 +391,7 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
             if (seen == n256 && seen < N) {
                 // ragged tail (< 256 documents): filtered against the same thresholds by the small-tile kernel, its
                 // survivors join this chunk's candidate lists -- one merge, no materialise + select round for 72 documents
-                g.W = (const char*)corpus + (size_t)seen * d * esz; g.N = (int)(N - seen); g.idx_base = idx_base + seen;
+                g.W = (const char*)corpus + (size_t)seen * rowb; g.N = (int)(N - seen); g.idx_base = idx_base + seen;
                 docs_gemm(EPI_SCORE_FILTER, g, seen, 1);
                 seen = N;
             }
@@ -393,6 +412,7 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const void* corpu
             cur ^= 1;
             ++chunk_i;
         }
+        c->filt_flag_off = (size_t)((char*)flag - base); c->filt_chunks = (int)(chunk_i < n_flags ? (long)chunk_i : n_flags);
         if (seen < N) {   // (only when no filtered chunk ran: N - first < 256) ragged tail: materialise + select
             st = classic(seen, N, tv[cur], ti[cur], k, run_val, run_idx, nullptr, chunk);
             if (st != SGPT_OK) return st;
@@ -432,6 +452,80 @@ sgpt_status sgpt_score_topk_q8(sgpt_ctx* c, const void* q, const uint8_t* codes,
         if (st != SGPT_OK) return st;
     }
     if (n_out) *n_out = have;
+    return SGPT_OK;
+}
+
+// Hamming search over packed sign bits with optional re-scoring of the over-fetched candidates (include/sgpt_hip.h).
+sgpt_status sgpt_score_topk_bits(sgpt_ctx* c, const float* q, const uint8_t* bits, int64_t ldb, int32_t nq, int64_t N, int32_t d, int32_t k,
+                                 int32_t kp, int32_t mode, const uint8_t* codes, const float* scale, int64_t idx_base, float* run_val,
+                                 int64_t* run_idx, int32_t n_run, int32_t* n_out, void* stream) {
+    if (!c || !q || !bits || !run_val || !run_idx || nq <= 0 || N <= 0 || d <= 0 || ldb % 4 || ldb < 4 * (((int64_t)d + 31) / 32) ||
+        k <= 0 || kp < k || kp > 1024 || mode < 0 || mode > 2 || (mode == 0 && kp != k) || (mode == 2 && (!codes || !scale)) ||
+        n_run < 0 || n_run > k || ((size_t)bits & 3))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_score_topk_bits: bad arguments (ldb % 4 == 0, ldb >= 4 ceil(d / 32), 0 < k <= kp <= 1024, "
+                                         "mode 0 with kp == k, mode 2 with codes and scale, 0 <= n_run <= k)");
+    HIPC(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int qw = (d + 127) / 128 * 4;                 // dwords of a packed query row: whole 16-byte pieces
+    const int ldc = kp + k;
+    const size_t qb_b = align_up((size_t)nq * qw * 4, 256), lv_b = align_up((size_t)nq * kp * 4, 256), li_b = align_up((size_t)nq * kp * 8, 256);
+    const size_t cv_b = align_up((size_t)nq * ldc * 4, 256), ci_b = align_up((size_t)nq * ldc * 8, 256);
+    sgpt_status st = ensure(c, &c->ws4, &c->ws4_bytes, qb_b + lv_b + li_b + cv_b + ci_b);
+    if (st != SGPT_OK) return st;
+    char* b = (char*)c->ws4;
+    uint32_t* qbits = (uint32_t*)b; b += qb_b;
+    float* lv = (float*)b; b += lv_b;
+    int64_t* li = (int64_t*)b; b += li_b;
+    float* cv = (float*)b; b += cv_b;
+    int64_t* ci = (int64_t*)b; b += ci_b;
+    launch_pack_sign_bits(q, nq, d, nullptr, (uint8_t*)qbits, (long)qw * 4, s);
+    // stage 1: the kp best by agreement (a descending, index ascending), a fresh list per call.  Queries in groups of 64 (re-streaming
+    // 96-byte rows is cheap), documents in blocks the launches index with 32 bits, chained through the stage-1 list.
+    const BitRows br{(long)ldb, qw};
+    const int64_t blk = (int64_t)1 << 30;
+    for (int32_t g0 = 0; g0 < nq; g0 += 64) {
+        const int32_t gn = nq - g0 < 64 ? nq - g0 : 64;
+        float* gv = lv + (size_t)g0 * kp;
+        int64_t* gi = li + (size_t)g0 * kp;
+        int32_t have = 0;
+        for (int64_t b0 = 0; b0 < N; b0 += blk) {
+            const int64_t nb = N - b0 < blk ? N - b0 : blk;
+            st = score_topk_impl(c, qbits + (size_t)g0 * qw, bits + (size_t)b0 * ldb, SGPT_F16, gn, nb, d, kp, idx_base + b0, gv, gi, gv, gi,
+                                 have, &have, stream, nullptr, nullptr, &br);
+            if (st != SGPT_OK) return st;
+        }
+    }
+    // stage 2: the candidates' values by `mode` | the running list -> top-k (as sgpt_score_topk_refined)
+    launch_rescore_bits(mode, q, bits, (long)ldb, codes, ((long)d + 7) / 8 * 8, scale, lv, li, kp, nq, kp, d, idx_base, N, cv, ci, ldc, s);
+    launch_list_append(run_val, run_idx, k, n_run, nq, cv, ci, ldc, kp, s);
+    launch_topk_select(cv, ldc, 0, 0, cv, ci, kp + n_run, ldc, nq, k, 0, nullptr, run_val, run_idx, s);
+    if (n_out) { const int64_t tot = (int64_t)n_run + N; *n_out = (int32_t)(tot < k ? tot : k); }
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_pack_sign_bits(sgpt_ctx* c, const float* x, int64_t n, int32_t d, const float* center, uint8_t* bits, int64_t ldb,
+                                void* stream) {
+    if (!c || !x || !bits || n <= 0 || d <= 0 || ldb % 4 || ldb < 4 * (((int64_t)d + 31) / 32))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_pack_sign_bits: bad arguments (ldb % 4 == 0, ldb >= 4 ceil(d / 32))");
+    HIPC(c, hipSetDevice(c->device));
+    launch_pack_sign_bits(x, n, d, center, bits, ldb, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+// How many filtered chunks of the last score + top-k pass on this context overflowed their candidate lists and were recomputed by
+// the predicated fallback (diagnostics of the measurement scripts; synchronises `stream`).
+sgpt_status sgpt_score_overflow_count(sgpt_ctx* c, int32_t* n_chunks, int32_t* n_overflowed, void* stream) {
+    if (!c || !n_chunks || !n_overflowed) return fail(c, SGPT_ERR_INVALID, "sgpt_score_overflow_count: bad arguments");
+    HIPC(c, hipSetDevice(c->device));
+    *n_chunks = c->filt_chunks; *n_overflowed = 0;
+    if (c->ws2 && c->filt_chunks > 0) {
+        std::vector<int> f(c->filt_chunks);
+        HIPC(c, hipMemcpyAsync(f.data(), (const char*)c->ws2 + c->filt_flag_off, (size_t)c->filt_chunks * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIPC(c, hipStreamSynchronize((hipStream_t)stream));
+        for (int v : f) *n_overflowed += v != 0;
+    }
     return SGPT_OK;
 }
 

@@ -681,6 +681,58 @@ __global__ __launch_bounds__(256) void rescore_kernel(const float* __restrict__ 
     }
 }
 
+// Stage 2 of the binary-corpus scorer (sgpt_score_topk_bits): the value of every stage-1 candidate, one wave per (query, candidate)
+// as rescore_kernel.  MODE 1: lane l adds or subtracts q_i, i = l, l + 64, ..., as bit 7 - i % 8 of byte i / 8 of the document's row
+// says, over the d true dimensions; the wave's sum / sqrt(d) = <q, s_n> / sqrt(d).  MODE 2: the e4m3fn codes of the document's row in
+// an fp8 copy of the corpus, converted by the hardware conversion score8.hip uses (exact; the NaN codes give NaN -> -1), times q_i, the
+// sum times the document's power-of-two scale.  Both accumulate in fp32 in a fixed order (deterministic, independent of the launch shape).
+template <int MODE>
+__global__ __launch_bounds__(256) void rescore_bits_kernel(const float* __restrict__ q, const uint8_t* __restrict__ rows, long ld_rows,
+                                                           const float* __restrict__ scale, const int64_t* __restrict__ idx, long ld_idx,
+                                                           int m, int d, long idx_base, long n_docs, float* __restrict__ out_val,
+                                                           int64_t* __restrict__ out_idx, long ld_out) {
+    const int j = blockIdx.x * 4 + (threadIdx.x >> 6), qi = blockIdx.y, lane = threadIdx.x & 63;
+    if (j >= m) return;
+    const int64_t id = idx[(long)qi * ld_idx + j];
+    const long row = (long)(id - idx_base);
+    float v = -INFINITY;
+    if (id >= 0 && row >= 0 && row < n_docs) {
+        const float* a = q + (long)qi * d;
+        const uint8_t* b = rows + row * ld_rows;
+        float acc = 0.f;
+        for (int i = lane; i < d; i += 64) {
+            if constexpr (MODE == 1) {
+                const bool pos = (b[i >> 3] >> (7 - (i & 7))) & 1;
+                acc += pos ? a[i] : -a[i];
+            } else {
+                acc = __builtin_fmaf(a[i], __builtin_amdgcn_cvt_f32_fp8((int)b[i], 0), acc);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        if constexpr (MODE == 1) acc = acc / sqrtf((float)d);
+        else acc *= scale[row];
+        v = acc != acc ? -1.0f : acc;
+    }
+    if (lane == 0) {
+        out_val[(long)qi * ld_out + j] = v;
+        out_idx[(long)qi * ld_out + j] = v > -INFINITY ? id : (int64_t)-1;
+    }
+}
+
+// MODE 0 of the same: the agreement a (an integer held exactly in fp32) of a candidate -> a / d, one IEEE fp32 division; an unused
+// slot (idx < 0) -> (-inf, -1)
+__global__ __launch_bounds__(256) void agreement_div_kernel(const float* __restrict__ val1, const int64_t* __restrict__ idx, long ld_idx,
+                                                            int nq, int m, int d, float* __restrict__ out_val,
+                                                            int64_t* __restrict__ out_idx, long ld_out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)nq * m) return;
+    const long qi = i / m, j = i - qi * m;
+    const int64_t id = idx[qi * ld_idx + j];
+    out_val[qi * ld_out + j] = id >= 0 ? __fdiv_rn(val1[qi * ld_idx + j], (float)d) : -INFINITY;
+    out_idx[qi * ld_out + j] = id >= 0 ? id : (int64_t)-1;
+}
+
 // The guarantee of the refined scorer, checked per query on the stage-1 (16-bit) scores, sorted descending: every document
 // outside the kp candidates scores at most v16[kp-1]; if that is more than `margin` = 2 eps below the k-th best 16-bit score,
 // no outsider can reach the fp32 top-k (|s16 - s32| <= eps for every pair).  A query for which it does not hold -- a mass of
@@ -710,6 +762,20 @@ void launch_rescore(const float* q, const float* corpus, const int64_t* idx, lon
                     long n_docs, float* out_val, int64_t* out_idx, long ld_out, hipStream_t s) {
     hipLaunchKernelGGL(rescore_kernel, dim3((m + 3) / 4, nq), dim3(256), 0, s, q, corpus, idx, ld_idx, m, d, idx_base, n_docs,
                        out_val, out_idx, ld_out);
+}
+
+void launch_rescore_bits(int mode, const float* q, const uint8_t* bits, long ldb, const uint8_t* codes, long ld8, const float* scale,
+                         const float* val1, const int64_t* idx, long ld_idx, int nq, int m, int d, long idx_base, long n_docs,
+                         float* out_val, int64_t* out_idx, long ld_out, hipStream_t s) {
+    if (mode == 0)
+        hipLaunchKernelGGL(agreement_div_kernel, dim3((unsigned)(((long)nq * m + 255) / 256)), dim3(256), 0, s, val1, idx, ld_idx, nq, m, d,
+                           out_val, out_idx, ld_out);
+    else if (mode == 1)
+        hipLaunchKernelGGL(rescore_bits_kernel<1>, dim3((m + 3) / 4, nq), dim3(256), 0, s, q, bits, ldb, (const float*)nullptr, idx, ld_idx,
+                           m, d, idx_base, n_docs, out_val, out_idx, ld_out);
+    else
+        hipLaunchKernelGGL(rescore_bits_kernel<2>, dim3((m + 3) / 4, nq), dim3(256), 0, s, q, codes, ld8, scale, idx, ld_idx, m, d,
+                           idx_base, n_docs, out_val, out_idx, ld_out);
 }
 
 void launch_refine_check(const float* v16, int k, int kp, float margin, int nq, int* flag, hipStream_t s) {

@@ -46,6 +46,41 @@ class QuantizedCorpus:
         return get_context(self.codes.device).fp8_dequantize_rows(self.codes, self.scale, out_dtype=dtype)
 
 
+class BinaryCorpus:
+    """A corpus held as packed sign bits: `bits` uint8 [N, ldb], ldb = 4 * ceil(dim / 32) (include/sgpt_hip.h::sgpt_score_topk_bits;
+    dimension i of a document is bit 7 - i % 8 of byte i / 8, set when the element is > 0 -- numpy.packbits order, "ubinary" in
+    sentence-transformers).  `center` fp32 [dim] or None: what was subtracted from the normalised rows before the signs were taken, and
+    is subtracted from the queries; `fp8`: an optional QuantizedCorpus of the same (uncentred, normalised) rows for re-scoring.  Built
+    by Context.binarize_corpus / util.quantize_embeddings(precision="ubinary")."""
+
+    def __init__(self, bits: torch.Tensor, dim: int, center: Optional[torch.Tensor] = None, fp8: Optional[QuantizedCorpus] = None):
+        dim = int(dim)
+        if bits.dim() != 2 or bits.dtype != torch.uint8:
+            raise ValueError(f"BinaryCorpus: bits are uint8 [N, ldb], got {bits.dtype} {tuple(bits.shape)}")
+        if dim < 1 or bits.shape[1] % 4 or bits.shape[1] < 4 * ((dim + 31) // 32):
+            raise ValueError(f"BinaryCorpus: {bits.shape[1]} bytes per row do not hold dim = {dim} (ldb % 4 == 0, ldb >= 4 * ceil(dim / 32))")
+        if center is not None and tuple(center.shape) != (dim,):
+            raise ValueError(f"BinaryCorpus: center must be [{dim}], got {tuple(center.shape)}")
+        if fp8 is not None and (not isinstance(fp8, QuantizedCorpus) or len(fp8) != bits.shape[0] or
+                                fp8.codes.shape[1] != (dim + 7) // 8 * 8):
+            raise ValueError("BinaryCorpus: fp8 must be a QuantizedCorpus of the same rows (codes [N, ceil(dim / 8) * 8])")
+        self.bits, self.dim, self.center, self.fp8 = bits, dim, center, fp8
+
+    def __len__(self) -> int:
+        return int(self.bits.shape[0])
+
+    @property
+    def nbytes(self) -> int:
+        n = self.bits.numel()
+        if self.center is not None:
+            n += self.center.numel() * self.center.element_size()
+        if self.fp8 is not None:
+            n += self.fp8.nbytes
+        return n
+
+
+RESCORE_MODES = {"none": 0, "sign": 1, "fp8": 2}
+
 _contexts = {}
 
 
@@ -256,6 +291,107 @@ class Context:
             self._chk(self.lib.sgpt_fp8_quantize_rows(self.handle, _p(blk), n, d, _p(codes[r0:r0 + n]), _p(scale[r0:r0 + n]),
                                                       _stream_ptr(self.device)), "sgpt_fp8_quantize_rows")
         return QuantizedCorpus(codes, scale, bool(normalize), d0)
+
+    # ---- binary (1-bit) corpus: packed sign bits ----
+    def pack_sign_bits(self, x, center: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fp32 rows [n, d] -> uint8 [n, 4 * ceil(d / 32)]: the sign bits of x - center (center None: of x) in numpy.packbits order, pad
+        bits zero (include/sgpt_hip.h::sgpt_pack_sign_bits)."""
+        x = self._dev_f32(x)
+        n, d = x.shape
+        if n == 0 or d == 0:
+            raise ValueError(f"pack_sign_bits needs a non-empty [n, d] matrix, got {tuple(x.shape)}")
+        ldb = 4 * ((d + 31) // 32)
+        if center is not None:
+            center = center.to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(center.shape) != (d,):
+                raise ValueError(f"pack_sign_bits: center must be [{d}], got {tuple(center.shape)}")
+        if out is None:
+            out = torch.empty((n, ldb), dtype=torch.uint8, device=self.device)
+        elif (out.dtype != torch.uint8 or tuple(out.shape) != (n, ldb) or out.device != self.device or not out.is_contiguous()):
+            raise ValueError(f"pack_sign_bits: out must be a contiguous uint8 [{n}, {ldb}] tensor on {self.device}, got {out.dtype} "
+                             f"{tuple(out.shape)} on {out.device}")
+        self._chk(self.lib.sgpt_pack_sign_bits(self.handle, _p(x), n, d, _p(center), _p(out), ldb, _stream_ptr(self.device)),
+                  "sgpt_pack_sign_bits")
+        return out
+
+    def binarize_corpus(self, emb, normalize: bool = True, center=None, keep_fp8: bool = False,
+                        block_rows: int = 65536) -> BinaryCorpus:
+        """Embeddings [N, d] -> BinaryCorpus: rows L2-normalised, the centre subtracted, signs packed.  center: None | "mean" (the mean of
+        the normalised rows, kept on the corpus so that queries get the same shift) | a [d] tensor.  keep_fp8: the same normalised,
+        uncentred rows also go through quantize_corpus (re-scoring with rescore="fp8").  Works in blocks of `block_rows` rows, as
+        quantize_corpus does; `emb` may live on the host.  Sign bits carry no norms: normalize=False is refused."""
+        if keep_fp8 and center is not None:
+            raise ValueError("binarize_corpus: keep_fp8 with a centre is refused -- fp8 re-scoring needs the raw query, the centred bits "
+                             "q - center, and the search call takes one query matrix (score_topk)")
+        if not normalize:
+            raise ValueError("binarize_corpus: normalize=False is refused -- sign bits carry no norms, the search is a cosine search")
+        if not isinstance(emb, torch.Tensor):
+            emb = torch.as_tensor(np.asarray(emb))
+        if emb.dim() != 2 or emb.shape[0] == 0 or emb.shape[1] == 0:
+            raise ValueError(f"binarize_corpus needs a non-empty [N, d] matrix, got {tuple(emb.shape)}")
+        N, d = emb.shape
+        if isinstance(center, str):
+            if center != "mean":
+                raise ValueError(f"binarize_corpus: center must be None, 'mean' or a [d] tensor, got {center!r}")
+            acc = torch.zeros((d,), dtype=torch.float64, device=self.device)
+            for r0 in range(0, N, block_rows):
+                acc += self.l2_normalize(self._dev_f32(emb[r0:r0 + block_rows])).sum(dim=0, dtype=torch.float64)
+            center = (acc / N).to(torch.float32)
+        elif center is not None:
+            center = torch.as_tensor(center).to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(center.shape) != (d,):
+                raise ValueError(f"binarize_corpus: center must be [{d}], got {tuple(center.shape)}")
+        bits = torch.empty((N, 4 * ((d + 31) // 32)), dtype=torch.uint8, device=self.device)
+        for r0 in range(0, N, block_rows):
+            n = min(block_rows, N - r0)
+            self.pack_sign_bits(self.l2_normalize(self._dev_f32(emb[r0:r0 + n])), center, out=bits[r0:r0 + n])
+        fp8 = self.quantize_corpus(emb, normalize=True, block_rows=block_rows) if keep_fp8 else None
+        return BinaryCorpus(bits, d, center, fp8)
+
+    def _score_topk_bits(self, q, corpus: BinaryCorpus, k: int, idx_base: int, run, rescore: str, rescore_multiplier):
+        if rescore not in RESCORE_MODES:
+            raise ValueError(f"score_topk: rescore must be 'sign', 'none' or 'fp8', got {rescore!r}")
+        if rescore == "fp8" and corpus.fp8 is None:
+            raise ValueError("score_topk: rescore='fp8' needs a BinaryCorpus built with keep_fp8=True (corpus.fp8 is None)")
+        if k < 1 or k > 1024:
+            raise ValueError(f"score_topk over a BinaryCorpus takes 1 <= k <= 1024, got {k}")
+        mode = RESCORE_MODES[rescore]
+        kp = k if mode == 0 else min(1024, max(k, int(round(k * rescore_multiplier))))
+        q = self._dev_f32(q)
+        nq, d = q.shape
+        if d != corpus.dim:
+            raise ValueError(f"embedding dims differ: {d} vs {corpus.dim}")
+        # The C call takes ONE query matrix: it packs the stage-1 bits from it and re-scores with it.  A centred corpus needs the bits of
+        # q - center, its fp8 copy the raw q: no single matrix serves both, and the raw one would search sign(q) against sign(x - center).
+        if corpus.center is not None and mode == 2:
+            raise ValueError("score_topk: rescore='fp8' is refused on a centred BinaryCorpus -- the stage-1 bits need q - center, the fp8 "
+                             "rows the raw q, and sgpt_score_topk_bits takes one query matrix; use rescore='sign', or an uncentred corpus")
+        if corpus.center is not None:
+            q = q - corpus.center.to(self.device)
+        bits = corpus.bits.to(self.device).contiguous()
+        codes = scale = None
+        if mode == 2:
+            codes = corpus.fp8.codes.to(self.device).contiguous()
+            scale = corpus.fp8.scale.to(device=self.device, dtype=torch.float32).contiguous()
+        if run is None:
+            val = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+            idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+            n_run = 0
+        else:
+            val, idx, n_run = run
+        n_out = C.c_int32(0)
+        self._chk(self.lib.sgpt_score_topk_bits(self.handle, _p(q), _p(bits), bits.shape[1], nq, bits.shape[0], d, k, kp, mode, _p(codes),
+                                                _p(scale), idx_base, _p(val), _p(idx), n_run, C.byref(n_out),
+                                                _stream_ptr(self.device)), "sgpt_score_topk_bits")
+        return val, idx, int(n_out.value)
+
+    def score_overflow_count(self) -> Tuple[int, int]:
+        """(filtered chunks, chunks whose candidate lists overflowed and took the fallback) of the last score_topk pass on this
+        context; synchronises (include/sgpt_hip.h::sgpt_score_overflow_count)."""
+        a, b = C.c_int32(0), C.c_int32(0)
+        self._chk(self.lib.sgpt_score_overflow_count(self.handle, C.byref(a), C.byref(b), _stream_ptr(self.device)),
+                  "sgpt_score_overflow_count")
+        return int(a.value), int(b.value)
 
     def _operand(self, x: torch.Tensor, dtype) -> torch.Tensor:
         if x.dtype == dtype and x.device == self.device and x.is_contiguous():
@@ -578,10 +714,20 @@ class Context:
     # ---- a7+a8: fused chunked score + running top-k ----
     def score_topk(self, q: torch.Tensor, corpus: torch.Tensor, k: int, idx_base: int = 0,
                    run: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None,
-                   dtype=None) -> Tuple[torch.Tensor, torch.Tensor, int]:
+                   dtype=None, rescore: str = "sign", rescore_multiplier=4) -> Tuple[torch.Tensor, torch.Tensor, int]:
         """-> (values fp32[nq,k], indices int64[nq,k], n_valid); rows sorted by descending score.  `corpus` may be a QuantizedCorpus
         (fp8 codes + per-document scales): the queries are then f16 (dtype None / torch.float16 only) and the result equals the f16
-        scorer's on corpus.dequantize(torch.float16), sgpt_score_topk_q8."""
+        scorer's on corpus.dequantize(torch.float16), sgpt_score_topk_q8.  Over a BinaryCorpus (sgpt_score_topk_bits): q fp32, normalised
+        and UNcentred; stage 1 takes the kp = min(1024, max(k, k * rescore_multiplier)) best by Hamming distance, `rescore` orders
+        them -- "sign" (<q, signs> / sqrt(d), no extra memory), "fp8" (the corpus's fp8 copy), or "none" (Hamming only, kp = k, values
+        agreement / d); a running list must come from calls with the same `rescore`.  corpus.center is subtracted from q here, for the
+        bits and for "sign"; rescore="fp8" on a centred corpus is refused (ValueError: the C call takes one query matrix, and the fp8
+        rows need the raw q).  1 <= k <= 1024.  `rescore` / `rescore_multiplier` belong to a BinaryCorpus: any other corpus with
+        non-default values of them raises ValueError."""
+        if isinstance(corpus, BinaryCorpus):
+            return self._score_topk_bits(q, corpus, k, idx_base, run, rescore, rescore_multiplier)
+        if rescore != "sign" or rescore_multiplier != 4:
+            raise ValueError("score_topk: rescore / rescore_multiplier apply to a BinaryCorpus only")
         if isinstance(corpus, QuantizedCorpus):
             if dtype not in (None, torch.float16):
                 raise ValueError(f"a QuantizedCorpus is scored with f16 queries: dtype must be None or torch.float16, got {dtype}")

@@ -6,7 +6,7 @@ from typing import Callable, List
 import numpy as np
 import torch
 
-from .runtime import QuantizedCorpus, get_context
+from .runtime import BinaryCorpus, QuantizedCorpus, get_context
 
 
 def _ctx_for(*xs):
@@ -69,17 +69,50 @@ def pairwise_cos_sim(a, b) -> torch.Tensor:
     return out if home.type == "cuda" else out.cpu()
 
 
-def quantize_embeddings(embeddings, precision: str = "fp8", normalize: bool = True) -> QuantizedCorpus:
-    """Corpus embeddings -> QuantizedCorpus (e4m3fn codes + one power-of-two scale per row): one byte per element on the device, and
-    per search pass.  Named after sentence-transformers' later `quantize_embeddings`; "fp8" is the only precision.  normalize=True
-    L2-normalises the rows first (search with cos_sim), normalize=False keeps them (search with dot_score)."""
-    if precision != "fp8":
-        raise ValueError(f"quantize_embeddings: unknown precision {precision!r} (only 'fp8' is built)")
+def quantize_embeddings(embeddings, precision: str = "fp8", normalize: bool = True, center=None, keep_fp8: bool = False):
+    """Corpus embeddings -> a corpus object for semantic_search / Context.score_topk.  Named after sentence-transformers' later
+    `quantize_embeddings`.
+    precision="fp8": QuantizedCorpus (e4m3fn codes + one power-of-two scale per row), one byte per element on the device and per
+    search pass.  normalize=True L2-normalises the rows first (search with cos_sim), normalize=False keeps them (dot_score).
+    precision="ubinary" (sentence-transformers' name for packed unsigned bits): BinaryCorpus, one BIT per element -- Hamming search
+    plus re-scoring of an over-fetched candidate list.  center: None | "mean" | a [d] tensor, subtracted from the normalised rows (and
+    later from the queries) before the signs are taken; keep_fp8=True also keeps an fp8 copy to re-score with.  normalize=False is
+    refused: sign bits carry no norms."""
+    if precision not in ("fp8", "ubinary"):
+        raise ValueError(f"quantize_embeddings: unknown precision {precision!r} (only 'fp8' and 'ubinary' are built)")
+    if precision == "ubinary" and not normalize:
+        raise ValueError("quantize_embeddings: precision='ubinary' with normalize=False is refused -- sign bits carry no norms")
+    if precision == "ubinary" and keep_fp8 and center is not None:
+        raise ValueError("quantize_embeddings: keep_fp8 with a centre is refused -- fp8 re-scoring needs the raw query, the centred bits "
+                         "q - center, and the search call takes one query matrix")
+    if precision == "fp8" and (center is not None or keep_fp8):
+        raise ValueError("quantize_embeddings: center / keep_fp8 belong to precision='ubinary'")
     if isinstance(embeddings, list):
         embeddings = torch.stack(embeddings)
     e = _wrap(embeddings)
     ctx, _ = _ctx_for(e)
+    if precision == "ubinary":
+        return ctx.binarize_corpus(e, normalize=True, center=center, keep_fp8=keep_fp8)
     return ctx.quantize_corpus(e, normalize=normalize)
+
+
+def _binary_rescore(corpus: BinaryCorpus) -> str:
+    """What semantic_search re-scores a BinaryCorpus with: its fp8 copy where it has one and is not centred (a centred corpus needs
+    q - center for the bits and the raw q for the fp8 rows; the search call takes one matrix), the sign bits otherwise."""
+    return "fp8" if corpus.fp8 is not None and corpus.center is None else "sign"
+
+
+def _search_binary(q, corpus: BinaryCorpus, top_k: int, score_function) -> List[List[dict]]:
+    if score_function not in (cos_sim, pytorch_cos_sim):
+        raise ValueError("semantic_search over a BinaryCorpus scores with cos_sim only: sign bits carry no norms, so dot_score and "
+                         "arbitrary score functions cannot be computed from them")
+    if min(top_k, len(corpus)) > 1024:
+        raise ValueError(f"semantic_search over a BinaryCorpus takes top_k <= 1024 (the candidate lists of the Hamming stage), got {top_k}")
+    ctx, _ = _ctx_for(corpus.bits, q)
+    k = min(top_k, len(corpus))
+    val, idx, n = ctx.score_topk(ctx.l2_normalize(q), corpus, k, rescore=_binary_rescore(corpus))
+    val, idx = val.cpu().tolist(), idx.cpu().tolist()
+    return [[{"corpus_id": j, "score": s} for j, s in zip(ii[:n], vv[:n])] for vv, ii in zip(val, idx)]
 
 
 def _search_quantized(q, corpus: QuantizedCorpus, top_k: int, score_function) -> List[List[dict]]:
@@ -103,11 +136,15 @@ def semantic_search(query_embeddings, corpus_embeddings, query_chunk_size: int =
                     score_function: Callable = cos_sim) -> List[List[dict]]:
     """util.semantic_search (util.py:197-258).  Same result contract (per query a list of
     {'corpus_id','score'} sorted by decreasing score); the chunk loops collapse into one fused
-    score + running-top-k pass on the GPU when score_function is cos_sim / dot_score."""
+    score + running-top-k pass on the GPU when score_function is cos_sim / dot_score (query_chunk_size / corpus_chunk_size are then
+    not used).  Over a BinaryCorpus: cos_sim only, top_k <= 1024, re-scored with the corpus's fp8 copy when it has one and is not
+    centred, with its sign bits otherwise."""
     if isinstance(query_embeddings, list):
         query_embeddings = torch.stack(query_embeddings)
     if isinstance(corpus_embeddings, QuantizedCorpus):     # fp8 corpus (quantize_embeddings): one fused pass over the codes
         return _search_quantized(_wrap(query_embeddings), corpus_embeddings, top_k, score_function)
+    if isinstance(corpus_embeddings, BinaryCorpus):        # packed sign bits: Hamming search + re-scoring of the over-fetched list
+        return _search_binary(_wrap(query_embeddings), corpus_embeddings, top_k, score_function)
     if isinstance(corpus_embeddings, list):
         corpus_embeddings = torch.stack(corpus_embeddings)
     q, c = _wrap(query_embeddings), _wrap(corpus_embeddings)
