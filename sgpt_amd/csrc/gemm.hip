@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "score_plan.h"
 
 namespace {
 
@@ -1182,12 +1183,12 @@ bool gemm_qkv_bulk(int M, int N, int K, int n_split, bool force256) {
     return M % 256 == 0 && N % 256 == 0 && n_split % 256 == 0 && n_split < N && K % 64 == 0 && K >= 128 &&
            (long)(M / 256) * (n_split / 256) > SGPT_FEW_TILES;
 }
-// THE predicate of the folded ragged tail (score.hip asks it before folding; launch_gemm16 re-checks it): a scorer launch of M padded
+// THE predicate of the folded ragged tail (the scorer's planner asks its shape arithmetic before folding; launch_gemm16 re-checks it): a scorer launch of M padded
 // query rows against N = (whole 256-document tiles + 256) documents of width K takes the 256x256 kernel with the documents as its
 // streamed operand -- the only kernel that honours GemmArgs.n_valid.
 bool gemm_score_tail_foldable(int M, long N, int K) {
     if (exp_env("SGPT_GEMM128") != nullptr) return false;
-    return M >= 256 && M != 64 && M % 256 == 0 && N % 256 == 0 && N >= 512 && K % 64 == 0 && K >= 128 && (long)M < N;
+    return score_tail_foldable_shape(M, N, K);   // (score_plan.h: the shape arithmetic, shared with the scorer's planner)
 }
 #ifdef SGPT_EXPERIMENTS
 int set_gemm_skew(int cycles) { const int old = g_skew; g_skew = cycles; return old; }
