@@ -493,7 +493,13 @@ sgpt_status sgpt_score_topk_refined(sgpt_ctx* ctx, const float* q, const float* 
  * the candidate whose idx == exclude_idx[q] (the `corpus_id != query_id` rule of :118;
  * exclude_idx may be NULL).
  *   val device fp32[nq,m], idx device int64[nq,m] -> out_val fp32[nq,k], out_idx int64[nq,k]
- *   (sorted descending; tail (-inf,-1)). */
+ *   (sorted descending; tail (-inf,-1)).
+ * The order, here and in every list this library returns (sgpt_topk, sgpt_score_topk*, sgpt_exchange_topk, sgpt_fold_gathered_topk):
+ * higher score first, equal scores by ascending index, whatever the candidate's position in the row or the row's length.  It is
+ * total: -0.0 and +0.0 are equal scores, a positive NaN ranks above +inf and a negative NaN below -inf.  A candidate whose score is
+ * -inf counts as an unused slot: it comes back as (-inf, -1), like an ignored candidate, behind every score above -inf -- a list
+ * never holds an index behind its first -1.  A (score, idx) pair that the candidates repeat is returned as often as it occurs.
+ * k > 2048: the same k pairs, in NO particular order (unused slots anywhere among them). */
 sgpt_status sgpt_topk_merge(sgpt_ctx* ctx, const float* val, const int64_t* idx, int32_t nq,
                             int32_t m, int32_t k, const int64_t* exclude_idx,
                             float* out_val, int64_t* out_idx, void* stream);
@@ -539,7 +545,9 @@ sgpt_status sgpt_fold_gathered_topk(sgpt_ctx* ctx, const float* gathered_val, co
                                     int64_t* out_idx, void* stream);
 
 /* Plain top-k over a materialised score matrix: torch.topk(scores, k, dim=1)
- * (exact_search.py:102-108; util.semantic_search util.py:241).  NaN -> -1 first (:99). */
+ * (exact_search.py:102-108; util.semantic_search util.py:241).  NaN -> -1 first (:99).  Rows need no alignment (16-byte aligned rows
+ * are read with 16-byte loads).  Order, -inf scores and k > 2048 as documented at sgpt_topk_merge: sorted for k <= 2048, columns
+ * beyond n and scores of -inf are (-inf, -1). */
 sgpt_status sgpt_topk(sgpt_ctx* ctx, const float* scores, int32_t nq, int64_t n, int64_t ld,
                       int32_t k, int64_t idx_base, float* out_val, int64_t* out_idx, void* stream);
 

@@ -3,7 +3,8 @@
 //
 // One 256-thread workgroup per query scans a VIRTUAL row = [chunk scores (n) | previous best
 // (n_prev)].  Output: the k best, sorted by descending score, ties by ascending index
-// (deterministic), unused tail (-inf, -1).
+// (deterministic), unused tail (-inf, -1); a score of -inf is an unused slot (is_score).  k > 2048: the k best unsorted.
+// tests/topk_ref.py names the exits of the kernel and reads the constants between them out of this file.
 //
 //   fast path (k <= 128, row >= 4096): ONE pass.  A strided 1024-element sample is bitonic-sorted
 //     in LDS; its k-th largest value tau is a lower bound of the row's k-th largest, so every
@@ -26,6 +27,9 @@ __device__ __forceinline__ uint32_t f2key(float f) {  // ascending uint order ==
     const uint32_t u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+// the key the radix passes select on: -0.0 folded into +0.0 as in sorts_before (with a key of its own a -0.0 lost to every +0.0 at
+// the k-th place, whatever their indices)
+__device__ __forceinline__ uint32_t f2key_order(float f) { return f2key(f + 0.0f); }
 
 constexpr int TK_THREADS = 256;
 constexpr int TK_SORT_MAX = 2048;   // k <= 2048 sorted in LDS (the driver's k+1 = 1001 fits)
@@ -64,6 +68,12 @@ struct Row {
         return id == excl ? -1 : id;
     }
 };
+
+// A score of -inf is an unused slot on every path -- an empty or excluded entry of the previous leg, or a document that scored
+// -inf: it leaves as (-inf, -1), behind every score above -inf.  (With the document's index it would sit BEHIND the empty slots of
+// its row, index -1 sorting first, in a list that is read up to its first negative index.)  A NaN is a score.
+__device__ __forceinline__ bool is_score(float v) { return v > -INFINITY || v != v; }
+__device__ __forceinline__ int64_t out_id(float v, int64_t id) { return is_score(v) ? id : (int64_t)-1; }
 
 // The order of every path of this file (round 6: ONE order -- ADVICE r05).  Higher score first, ties -> lower index.  It is
 // taken on the order-preserving integer image of the score, so it is total over NaNs too: a positive NaN ranks above +inf and a
@@ -283,7 +293,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(const float* sc
             const bool ok = i < total;
             const float v = ok ? r.val(ok ? i : 0) : -INFINITY;
             const int64_t id = ok ? r.idx(ok ? i : 0) : -1;
-            if (in_lds) { s_val[i] = v; s_idx[i] = id; } else { ov[i] = v; oi[i] = id; }
+            if (in_lds) { s_val[i] = v; s_idx[i] = id; } else { ov[i] = v; oi[i] = out_id(v, id); }
         }
         done = true;
     } else if (k <= TK_FAST_KMAX && total <= TK_SORT_MAX && in_lds) {
@@ -345,13 +355,15 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(const float* sc
         const float tau = fmaxf(fmaxf(__uint_as_float(hist[0]), __uint_as_float(hist[1])),
                                 fmaxf(__uint_as_float(hist[2]), __uint_as_float(hist[3])));
         if (tau > -INFINITY) {
-            auto take = [&](float v, long i) {
+            auto take_id = [&](float v, auto id_of) {
                 if (nan_to_m1 && v != v) v = -1.0f;
-                if (v >= tau) {
+                if (!(v < tau)) {                  // (not `v >= tau`: a NaN is no score below tau -- a positive one ranks first)
                     const unsigned slot = atomicAdd(&sh_cnt, 1u);
-                    if (slot < TK_SORT_MAX) { s_val[slot] = v; s_idx[slot] = r.idx(i); }
+                    if (slot < TK_SORT_MAX) { s_val[slot] = v; s_idx[slot] = id_of(); }
                 }
             };
+            // (the 16-byte loads below read the fresh leg only: its index needs neither the leg test nor the gathered map of r.idx)
+            auto take = [&](float v, long i) { take_id(v, [&] { return (int64_t)(r.idx_base + i); }); };
             // fresh-score leg: 16-byte loads, two per thread in flight (row base and n are multiples of 4
             // for the scorer's chunks; anything else takes the scalar tail below)
             const bool vec_ok = ((reinterpret_cast<size_t>(r.sc) & 15) == 0);
@@ -380,7 +392,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(const float* sc
                 if (ia < nv) { take(a.x, 4 * ia); take(a.y, 4 * ia + 1); take(a.z, 4 * ia + 2); take(a.w, 4 * ia + 3); }
                 if (ib < nv) { take(b.x, 4 * ib); take(b.y, 4 * ib + 1); take(b.z, 4 * ib + 2); take(b.w, 4 * ib + 3); }
             }
-            for (long i = 4 * nv + t; i < total; i += TK_THREADS) take(r.val(i), i);   // tail + previous-best leg
+            for (long i = 4 * nv + t; i < total; i += TK_THREADS) take_id(r.val(i), [&] { return r.idx(i); });   // tail + previous-best leg
             __syncthreads();
             const unsigned cnt = sh_cnt;          // cnt >= k always: k sampled elements are >= tau
             if (cnt <= 1024 && in_lds) {
@@ -426,7 +438,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(const float* sc
             for (long i0 = 0; i0 < total; i0 += TK_THREADS) {
                 const long i = i0 + t;
                 const bool act = i < total;
-                const uint32_t key = f2key(r.val(act ? i : 0));
+                const uint32_t key = f2key_order(r.val(act ? i : 0));
                 hist_add(hist, act && (key & himask) == prefix, (key >> shift) & 0xff, lane);
             }
             __syncthreads();
@@ -454,9 +466,9 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(const float* sc
         __syncthreads();
         for (long i = t; i < total; i += TK_THREADS) {
             const float v = r.val(i);
-            if (f2key(v) > thr) {
+            if (f2key_order(v) > thr) {
                 const unsigned slot = atomicAdd(&sh_cnt, 1u);
-                if (in_lds) { s_val[slot] = v; s_idx[slot] = r.idx(i); } else { ov[slot] = v; oi[slot] = r.idx(i); }
+                if (in_lds) { s_val[slot] = v; s_idx[slot] = r.idx(i); } else { ov[slot] = v; oi[slot] = out_id(v, r.idx(i)); }
             }
         }
         // ---- ties at the threshold: the krem LOWEST INDICES among the equal scores ----
@@ -478,7 +490,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(const float* sc
                 for (long i0 = 0; i0 < total; i0 += TK_THREADS) {
                     const long i = i0 + t;
                     const bool act = i < total;
-                    const bool tie = act && f2key(r.val(act ? i : 0)) == thr;
+                    const bool tie = act && f2key_order(r.val(act ? i : 0)) == thr;
                     const unsigned long long key = (unsigned long long)r.idx(act ? i : 0);
                     hist_add(hist, tie && (key & himask) == pfx, (unsigned)(key >> shift) & 0xff, lane);
                 }
@@ -503,10 +515,10 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(const float* sc
         }
         for (long i = t; i < total; i += TK_THREADS) {
             const float v = r.val(i);
-            if (f2key(v) == thr && (unsigned long long)r.idx(i) <= cutoff) {
+            if (f2key_order(v) == thr && (unsigned long long)r.idx(i) <= cutoff) {
                 const unsigned slot = atomicAdd(&sh_cnt, 1u);       // continues behind the k - krem gathered elements
                 if (slot < (unsigned)k) {
-                    if (in_lds) { s_val[slot] = v; s_idx[slot] = r.idx(i); } else { ov[slot] = v; oi[slot] = r.idx(i); }
+                    if (in_lds) { s_val[slot] = v; s_idx[slot] = r.idx(i); } else { ov[slot] = v; oi[slot] = out_id(v, r.idx(i)); }
                 }
             }
         }
@@ -522,7 +534,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(const float* sc
     __syncthreads();
     bitonic_desc<true>(s_val, s_idx, np2, t);
     for (int i = t; i < k; i += TK_THREADS) {
-        const bool ok = i < kk;
+        const bool ok = i < kk && is_score(s_val[i]);
         ov[i] = ok ? s_val[i] : -INFINITY;
         oi[i] = ok ? s_idx[i] : -1;
         if (thr_out && i == k - 1) thr_out[qrow] = thr_below(ok ? s_val[i] : -INFINITY);
