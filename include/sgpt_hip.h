@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 19
+#define SGPT_ABI_VERSION 20
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -465,7 +465,55 @@ sgpt_status sgpt_score_topk_bits(sgpt_ctx* ctx, const float* q, const uint8_t* b
                                  int32_t k, int32_t kp, int32_t mode, const uint8_t* codes, const float* scale, int64_t idx_base,
                                  float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out, void* stream);
 
-/* Diagnostics (ABI v19): of the filtered chunks of the LAST score + top-k pass on this context (sgpt_score_topk, _q8; _bits: its last
+/* uint8 corpus (ABI v20): scalar quantisation with one range per DIMENSION -- quantize_embeddings(precision="uint8") of
+ * sentence-transformers.  One byte per element as the fp8 corpus; 256 uniform levels inside each column's own range instead of three
+ * mantissa bits under one scale per row, which suits anisotropic embeddings (a few channels carry the row) far better.
+ *   format    codes device uint8 [N, ld], ld = ceil(d / 128) * 128, columns d .. ld - 1 hold 128; start, step device fp32 [ld], pad columns
+ *             start = step = 0.  Document n is x^[n][j] = start[j] + codes[n][j] * step[j].  With mid = start + 128 * step and
+ *             c = code - 128 this is mid[j] + c * step[j]; codes - 128 as int8 are sentence-transformers' "int8" codes.
+ *   rule      codes = clamp(rint((x - start) / step), 0, 255) in fp32: IEEE subtraction and division, round-half-even; step == 0 or a NaN
+ *             element gives 128.  Elements outside [start, start + 255 step] clamp to the ends (ranges taken from a calibration sample).
+ *   ranges    start = the column minimum, step = (max - min) / 255 in fp32.
+ * sgpt_u8_col_minmax: column min / max of x device fp32 [n, d] into col_min / col_max [d]; NaN-propagating (a NaN in a column makes both
+ *   NaN); accumulate != 0: the two arrays go in holding the result of earlier blocks of rows, so blocks chain.
+ * sgpt_u8_quantize_rows: x device fp32 [n, d] -> codes [n, ld] by the rule, pad columns included (start / step are read for j < d).
+ * sgpt_u8_dequantize_rows: codes [n, ld] -> out [n, ld] (SGPT_F32 | SGPT_BF16 | SGPT_F16, 16-byte aligned): start + code * step with the
+ *   product and the sum each rounded once in fp32 (no fused multiply-add), then one rounding to the output format.
+ * SGPT_ERR_INVALID: null pointers, n <= 0, d <= 0, ld % 128, d > ld, codes not 4-byte aligned. */
+sgpt_status sgpt_u8_col_minmax(sgpt_ctx* ctx, const float* x, int64_t n, int32_t d, int32_t accumulate, float* col_min, float* col_max,
+                               void* stream);
+sgpt_status sgpt_u8_quantize_rows(sgpt_ctx* ctx, const float* x, int64_t n, int32_t d, int32_t ld, const float* start, const float* step,
+                                  uint8_t* codes, void* stream);
+sgpt_status sgpt_u8_dequantize_rows(sgpt_ctx* ctx, const uint8_t* codes, int64_t n, int32_t ld, const float* start, const float* step,
+                                    void* out, int32_t out_dtype, void* stream);
+
+/* sgpt_u8_prepare_queries (ABI v20; test entry): the query prologue sgpt_score_topk_u8 runs itself.  q device fp32 [nq, d], nq <= 64.
+ *   q'_j = q_j * step_j (fp32); e = the exponent with max_j |q'_j| * 2^-e in [1, 2) (0 for a zero or non-finite row);
+ *   qpad f16 [64, ld]: row r < nq holds RNE_f16(q'_j * 2^-e), rows nq .. 63 and columns d .. ld - 1 are zero;
+ *   qscale fp32 [64] = 2^e (1 for rows >= nq); qbias fp32 [64] = sum_j q_j * mid_j accumulated in fp32 (0 for rows >= nq).
+ * The power-of-two scale is needed: q_j * step_j is ~4e-5 for unit rows at d = 768, an f16 subnormal. */
+sgpt_status sgpt_u8_prepare_queries(sgpt_ctx* ctx, const float* q, const float* start, const float* step, int32_t nq, int32_t d, int32_t ld,
+                                    void* qpad, float* qscale, float* qbias, void* stream);
+
+/* sgpt_score_topk_u8 (ABI v20): sgpt_score_topk over a uint8 corpus.
+ *   q         device fp32 [nq, d], 1 <= nq <= 64 per call (larger batches: groups of 64, each re-streaming the corpus).
+ *   score     <q, x^_n> = qbias + qscale * <q'', c_n>: the kernel (csrc/scoreu8.hip) streams the code bytes, turns them into the exact f16
+ *             integers code - 128 and feeds the f16 MFMA with the pre-scaled query q''; products of an 11-bit by an 8-bit significand
+ *             are exact in fp32, sums accumulate in fp32 with k ascending, and ONE fma, score = fmaf(acc, qscale, qbias), returns to the
+ *             natural domain before the NaN rule (NaN -> -1) and the threshold compare.  The result equals sgpt_score_topk(SGPT_F16) of
+ *             q'' against the f16 rows codes - 128, followed by that fma, bit for bit.
+ *   error     arithmetic: |score - exact(q'', qscale, qbias, codes)| <= d 2^-23 qscale sum_j |q''_j c_j| + 2^-23 |score|;
+ *             quantisation, rows inside the ranges: |<q, x^> - <q, x>| <= sum_j |q_j| step_j / 2 (+ |q_j| times the clamp distance outside).
+ *   shapes    any N >= 1 (rows past the last document of a ragged 256-document tile are fetched from the last row and their columns
+ *             dropped: no scratch, no tail launch), any d >= 1 with ld = ceil(d / 128) * 128; codes 16-byte aligned.
+ *   result    as sgpt_score_topk: rows sorted descending, ties to the lowest index, running list in/out, *n_out = min(k, n_run + N).
+ * SGPT_ERR_INVALID (nothing launched, outputs untouched): null pointers; nq > 64; ld % 128; d > ld; codes not 16-byte aligned; k <= 0;
+ * n_run < 0 or n_run > k. */
+sgpt_status sgpt_score_topk_u8(sgpt_ctx* ctx, const float* q, const uint8_t* codes, const float* start, const float* step, int32_t nq,
+                               int64_t N, int32_t d, int32_t ld, int32_t k, int64_t idx_base, float* run_val, int64_t* run_idx,
+                               int32_t n_run, int32_t* n_out, void* stream);
+
+/* Diagnostics (ABI v19): of the filtered chunks of the LAST score + top-k pass on this context (sgpt_score_topk, _q8, _u8; _bits: its last
  * query group), how many overflowed their candidate lists and were recomputed by the predicated fallback.  Synchronises `stream`. */
 sgpt_status sgpt_score_overflow_count(sgpt_ctx* ctx, int32_t* n_chunks, int32_t* n_overflowed, void* stream);
 

@@ -348,6 +348,24 @@ struct Score8Args {
 };
 bool score64q8_shape_ok(int M, long N, int K, const void* codes, long ldw);
 void launch_score64q8(int epi, const Score8Args& a, hipStream_t s);
+// scoreu8.hip: the same tile over uint8 codes with one range per dimension (sgpt_score_topk_u8): g.A = the 64-row tile of pre-scaled
+// f16 queries launch_u8_prepare_queries writes, g.W = codes [N][g.ldw] bytes, g.K = ld (a multiple of 128), g.N documents (ANY number:
+// rows past the last are clamped, their columns dropped); score = fmaf(acc, qscale[m], qbias[m]), both fp32 [64].
+struct ScoreU8Args {
+    GemmArgs g;
+    const float* qscale;
+    const float* qbias;
+};
+bool score64u8_shape_ok(int M, long N, int K, const void* codes, long ldw);
+void launch_score64u8(int epi, const ScoreU8Args& a, hipStream_t s);
+// q fp32 [nq][d] (nq <= 64) -> qpad f16 [64][ld], qscale / qbias fp32 [64] (the arithmetic is in scoreu8.hip's header)
+void launch_u8_prepare_queries(const float* q, const float* start, const float* step, int nq, int d, int ld, void* qpad, float* qscale,
+                               float* qbias, hipStream_t s);
+// the row kernels of the uint8 format (include/sgpt_hip.h): column min / max (accumulate: mn / mx carry earlier blocks), quantise, de-quantise
+void launch_u8_col_minmax(const float* x, long n, int d, int accumulate, float* mn, float* mx, hipStream_t s);
+void launch_u8_quant_rows(const float* x, long n, int d, int ld, const float* start, const float* step, uint8_t* codes, hipStream_t s);
+void launch_u8_dequant_rows(const uint8_t* codes, long n, int ld, const float* start, const float* step, void* out, int out_dtype,
+                            hipStream_t s);
 // scorebits.hip: the Hamming tile over packed sign bits (sgpt_score_topk_bits).  g.A = packed query rows (g.m_valid of them, qw dwords
 // apart), g.W = document rows g.ldw BYTES apart (ldb bytes each, times the row stride of a sample), g.N documents (any number,
 // bounds-checked); score = d - 2 * hamming as an exact fp32; epi = EPI_SCORE | EPI_SCORE_FILTER with score64_kernel's contract.

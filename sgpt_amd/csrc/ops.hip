@@ -44,6 +44,16 @@ sgpt_status sgpt_fp8_dequantize_rows(sgpt_ctx* c, const uint8_t* codes, const fl
     return SGPT_OK;
 }
 
+sgpt_status sgpt_u8_prepare_queries(sgpt_ctx* c, const float* q, const float* start, const float* step, int32_t nq, int32_t d, int32_t ld,
+                                    void* qpad, float* qscale, float* qbias, void* stream) {
+    if (!c || !q || !start || !step || !qpad || !qscale || !qbias || nq <= 0 || nq > 64 || d <= 0 || ld < 128 || ld % 128 || d > ld)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_u8_prepare_queries: bad arguments (1 <= nq <= 64, ld % 128 == 0, 0 < d <= ld)");
+    HIPC(c, hipSetDevice(c->device));
+    launch_u8_prepare_queries(q, start, step, nq, d, ld, qpad, qscale, qbias, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
 sgpt_status sgpt_f32_to_16(sgpt_ctx* c, const float* in, int64_t numel, void* out, int32_t out_dtype, void* stream) {
     if (!c || !in || !out || numel <= 0 || (out_dtype != SGPT_BF16 && out_dtype != SGPT_F16))
         return fail(c, SGPT_ERR_INVALID, "sgpt_f32_to_16: bad arguments");

@@ -47,14 +47,18 @@ sgpt_status sgpt_scores(sgpt_ctx* c, const void* a, const void* b, int32_t dtype
     return SGPT_OK;
 }
 
-// What a score + top-k pass reads its documents from.  Three kinds share one schedule; only the launches that read the corpus differ:
+// What a score + top-k pass reads its documents from.  The kinds share one schedule; only the launches that read the corpus differ:
 //   rows (fp32 / bf16 / f16, `dtype`): the GEMM kernels;
 //   fp8 (sgpt_score_topk_q8, short query batches): `base` holds e4m3fn codes [N][d] bytes, `scale` one power-of-two scale per document,
 //     q is f16 (dtype SGPT_F16).  Whole 256-document tiles go through score64q8_kernel (score8.hip), a ragged tail is de-quantised
 //     into f16 scratch (ws6) for the register-staged kernel;
 //   bits (sgpt_score_topk_bits, at most 64 queries per call): `base` holds packed sign bits [N][ldb] bytes, q the packed query rows of
 //     qw dwords; the score is the agreement d - 2 * hamming, an integer in fp32.  Every launch that reads the corpus is the Hamming
-//     tile (scorebits.hip), which takes any number of documents, so no launch is split for a ragged tail.
+//     tile (scorebits.hip), which takes any number of documents, so no launch is split for a ragged tail;
+//   uint8 (sgpt_score_topk_u8, at most 64 queries per call): `base` holds uint8 codes [N][ld] bytes, `start` / `step` the range of every
+//     dimension, q the caller's fp32 rows of width d0; `d` is ld, the k extent of the tile.  The pass prologue turns q into the 64-row
+//     tile of pre-scaled f16 rows with qscale / qbias (ws2); every launch that reads the corpus is score64u8_kernel (scoreu8.hip),
+//     which takes any number of documents.
 struct Corpus {
     ScoreCorpusKind kind;
     const void* base;
@@ -64,6 +68,8 @@ struct Corpus {
     const float* scale;     // fp8: [N]
     long ldb; int qw;       // bits
     size_t ws6_bytes;       // scratch the launches need (fp8: the f16 rows of a ragged tail, < 256 documents)
+    const float *start = nullptr, *step = nullptr; int d0 = 0;        // uint8: ranges [ld], width of the caller's query rows
+    const float *qscale = nullptr, *qbias = nullptr;                  // uint8: [64] in ws2, set by the executor
 };
 static Corpus corpus_rows(const void* rows, int dtype, int d) {
     return {dtype == SGPT_F32 ? SCORE_CORPUS_F32 : SCORE_CORPUS_16, rows, dtype, d, (size_t)d * (dtype == SGPT_F32 ? 4 : 2), d, nullptr, 0, 0, 0};
@@ -75,11 +81,20 @@ static Corpus corpus_bits(const uint8_t* bits, long ldb, int qw, int d) {
     return {SCORE_CORPUS_BITS, bits, SGPT_F16, d, (size_t)ldb, ldb, nullptr, ldb, qw, 0};
 }
 
+static Corpus corpus_u8(const uint8_t* codes, const float* start, const float* step, int d0, int ld) {
+    Corpus cp{SCORE_CORPUS_U8, codes, SGPT_F16, ld, (size_t)ld, ld, nullptr, 0, 0, 0};
+    cp.start = start; cp.step = step; cp.d0 = d0;
+    return cp;
+}
+
 // one launch that reads documents [doc0, doc0 + h.N) (at row_stride): h.W / h.ldw are set for them already
 static void corpus_gemm(sgpt_ctx* c, const Corpus& cp, int epi, GemmArgs h, long doc0, long row_stride, bool sample, hipStream_t s) {
     switch (cp.kind) {
     case SCORE_CORPUS_BITS:
         launch_scorebits(epi, h, cp.d, cp.qw, cp.ldb, s, sample);
+        return;
+    case SCORE_CORPUS_U8:
+        launch_score64u8(epi, ScoreU8Args{h, cp.qscale, cp.qbias}, s);
         return;
     case SCORE_CORPUS_FP8:
         if (h.N % 256 == 0) {
@@ -113,6 +128,7 @@ static void score_tile(const ScoreRun& r, long c0, long nc, long ld, const int* 
     g.A = r.q; g.lda = r.d; g.M = r.nq; g.m_valid = r.nq; g.K = r.d; g.pred = pred;
     g.W = (const char*)r.cp.base + (size_t)c0 * r.cp.rowb; g.ldw = r.cp.ldw1 * row_stride; g.N = (int)nc;   // row_stride > 1: a strided sample
     g.out = r.sc; g.ldo = ld;
+    if (r.p.any_n && r.p.pad_queries) { g.A = r.qpad; g.M = r.p.nq_pad; }      // (uint8: the prologue's tile, not the caller's rows)
     if (r.p.any_n) { corpus_gemm(r.c, r.cp, EPI_SCORE, g, c0, row_stride, sample, r.s); return; }
     const long na = r.p.fast ? nc / 256 * 256 : 0;      // documents the 256-document tile kernels take
     // (round 5, measured and reverted: handing a predicated fallback piece to the register-staged kernel whole -- one no-op launch
@@ -200,15 +216,18 @@ static inline int32_t list_fill(int32_t n_run, int64_t N, int32_t k) { const int
 // in_val / in_idx: the running list going in (n_run entries per row, row stride k); run_val / run_idx: the list coming out (they
 // may be the same buffers -- the public entry point).  pred_all (device flag or null): every launch of the call is predicated on
 // it and the call takes the materialise-and-select path -- the sync-free fallback of sgpt_score_topk_refined.
-static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const Corpus& cp, int32_t nq, int64_t N, int32_t k, int64_t idx_base,
+static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const Corpus& cp_in, int32_t nq, int64_t N, int32_t k, int64_t idx_base,
                                    const float* in_val, const int64_t* in_idx, float* run_val, int64_t* run_idx, int32_t n_run,
                                    int32_t* n_out, void* stream, const int* pred_all) {
+    Corpus cp = cp_in;
     const int d = cp.d;
     if (!c || !q || !cp.base || !run_val || !run_idx || nq <= 0 || N <= 0 || k <= 0 || n_run < 0 || n_run > k)
         return fail(c, SGPT_ERR_INVALID, "sgpt_score_topk: bad arguments");
     sgpt_status st = cp.kind == SCORE_CORPUS_BITS ? SGPT_OK : check_score_dims(c, cp.dtype, d);
     if (st != SGPT_OK) return st;
     if (cp.kind == SCORE_CORPUS_BITS && (nq > 64 || d <= 0)) return fail(c, SGPT_ERR_INVALID, "score (binary corpus): at most 64 queries per pass");
+    if (cp.kind == SCORE_CORPUS_U8 && !(nq <= 64 && N <= ((int64_t)1 << 30) && cp.d0 > 0 && cp.d0 <= d && score64u8_shape_ok(64, N, d, cp.base, d)))
+        return fail(c, SGPT_ERR_INVALID, "score (uint8 corpus): shape not served by the streaming tile");
     if (cp.kind == SCORE_CORPUS_FP8 && !(nq <= 64 && score64q8_shape_ok(64, 256, d, cp.base, d)))
         return fail(c, SGPT_ERR_INVALID, "score (fp8 corpus): shape not served by the streaming tile");
     HIPC(c, hipSetDevice(c->device));
@@ -240,7 +259,12 @@ static sgpt_status score_topk_impl(sgpt_ctx* c, const void* q, const Corpus& cp,
     const int nq_pad = p.nq_pad;
     const long n_clear = p.filt ? (long)(nq_pad + p.n_flags) : 0;
     // prologue: one launch (query rows into their zero-padded tile, counters and flags cleared, an empty running list marked)
-    if (p.fast && (!p.pad_queries || (d % 8 == 0 && ((size_t)q & 15) == 0))) {
+    if (cp.kind == SCORE_CORPUS_U8) {      // the tile is computed, not copied: q'' = q * step / qscale, with qscale and qbias beside it
+        cp.qscale = (const float*)at(p.qscale); cp.qbias = (const float*)at(p.qbias);
+        launch_u8_prepare_queries((const float*)q, cp.start, cp.step, nq, cp.d0, d, qpad, (float*)at(p.qscale), (float*)at(p.qbias), s);
+        if (n_clear > 0 || p.fresh_list)
+            launch_score_prep(nullptr, nullptr, 0, 0, cand_cnt, n_clear, p.fresh_list ? (long long*)ti[0] : nullptr, p.fresh_list ? (long)nq * k : 0, s);
+    } else if (p.fast && (!p.pad_queries || (d % 8 == 0 && ((size_t)q & 15) == 0))) {
         launch_score_prep(q, qpad, p.pad_queries ? (long)nq * d * 2 : 0, p.pad_queries ? (long)nq_pad * d * 2 : 0, cand_cnt, n_clear,
                           p.fresh_list ? (long long*)ti[0] : nullptr, p.fresh_list ? (long)nq * k : 0, s);
     } else {
@@ -365,6 +389,58 @@ sgpt_status sgpt_score_topk_q8(sgpt_ctx* c, const void* q, const uint8_t* codes,
         if (st != SGPT_OK) return st;
     }
     if (n_out) *n_out = have;
+    return SGPT_OK;
+}
+
+// The same over a corpus of uint8 codes with one range per dimension (include/sgpt_hip.h): at most 64 fp32 query rows per call, every
+// launch that reads the corpus is the streaming tile of scoreu8.hip.  Documents in blocks the launches index with 32 bits, the running
+// list chained from block to block.
+sgpt_status sgpt_score_topk_u8(sgpt_ctx* c, const float* q, const uint8_t* codes, const float* start, const float* step, int32_t nq,
+                               int64_t N, int32_t d, int32_t ld, int32_t k, int64_t idx_base, float* run_val, int64_t* run_idx, int32_t n_run,
+                               int32_t* n_out, void* stream) {
+    if (!c || !q || !codes || !start || !step || !run_val || !run_idx || nq <= 0 || nq > 64 || N <= 0 || d <= 0 || ld < 128 || ld % 128 || d > ld ||
+        k <= 0 || n_run < 0 || n_run > k || ((size_t)codes & 15))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_score_topk_u8: bad arguments (1 <= nq <= 64, ld % 128 == 0, 0 < d <= ld, 0 <= n_run <= k, codes "
+                                         "16-byte aligned)");
+    const int64_t blk = (int64_t)1 << 30;
+    int32_t have = n_run;
+    for (int64_t b0 = 0; b0 < N; b0 += blk) {
+        const int64_t nb = N - b0 < blk ? N - b0 : blk;
+        sgpt_status st = score_topk_impl(c, q, corpus_u8(codes + (size_t)b0 * ld, start, step, d, ld), nq, nb, k, idx_base + b0, run_val, run_idx,
+                                         run_val, run_idx, have, &have, stream, nullptr);
+        if (st != SGPT_OK) return st;
+    }
+    if (n_out) *n_out = have;
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_u8_col_minmax(sgpt_ctx* c, const float* x, int64_t n, int32_t d, int32_t accumulate, float* col_min, float* col_max,
+                               void* stream) {
+    if (!c || !x || !col_min || !col_max || n <= 0 || d <= 0) return fail(c, SGPT_ERR_INVALID, "sgpt_u8_col_minmax: bad arguments");
+    HIPC(c, hipSetDevice(c->device));
+    launch_u8_col_minmax(x, n, d, accumulate != 0, col_min, col_max, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_u8_quantize_rows(sgpt_ctx* c, const float* x, int64_t n, int32_t d, int32_t ld, const float* start, const float* step,
+                                  uint8_t* codes, void* stream) {
+    if (!c || !x || !start || !step || !codes || n <= 0 || d <= 0 || ld < 128 || ld % 128 || d > ld || ((size_t)codes & 3))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_u8_quantize_rows: bad arguments (ld % 128 == 0, 0 < d <= ld)");
+    HIPC(c, hipSetDevice(c->device));
+    launch_u8_quant_rows(x, n, d, ld, start, step, codes, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_u8_dequantize_rows(sgpt_ctx* c, const uint8_t* codes, int64_t n, int32_t ld, const float* start, const float* step, void* out,
+                                    int32_t out_dtype, void* stream) {
+    if (!c || !codes || !start || !step || !out || n <= 0 || ld < 128 || ld % 128 || ((size_t)codes & 3) || ((size_t)out & 15) ||
+        (out_dtype != SGPT_F32 && out_dtype != SGPT_BF16 && out_dtype != SGPT_F16))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_u8_dequantize_rows: bad arguments (ld % 128 == 0, out 16-byte aligned)");
+    HIPC(c, hipSetDevice(c->device));
+    launch_u8_dequant_rows(codes, n, ld, start, step, out, out_dtype, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
     return SGPT_OK;
 }
 

@@ -7,8 +7,9 @@
 #include <vector>
 
 // what the corpus rows are: fp32 | bf16 / f16 | e4m3fn codes + one scale per document (sgpt_score_topk_q8, queries f16) | packed sign
-// bits (sgpt_score_topk_bits, at most 64 packed query rows)
-enum ScoreCorpusKind { SCORE_CORPUS_F32, SCORE_CORPUS_16, SCORE_CORPUS_FP8, SCORE_CORPUS_BITS };
+// bits (sgpt_score_topk_bits, at most 64 packed query rows) | uint8 codes with one range per dimension (sgpt_score_topk_u8, at most 64
+// fp32 query rows, d = the padded row width ld): planned like fp8, with the any-N launches and tail folding of the binary corpus
+enum ScoreCorpusKind { SCORE_CORPUS_F32, SCORE_CORPUS_16, SCORE_CORPUS_FP8, SCORE_CORPUS_BITS, SCORE_CORPUS_U8 };
 
 // A/B switches of the schedule, filled once by score.hip: the exp_env() results (experiment build only) and the build-time macros
 struct ScoreSwitches {
@@ -46,6 +47,7 @@ struct ScorePlan {
     // ws2: byte offsets of the regions (a region of 0 bytes is not there), in this order
     struct Region { size_t off, bytes; };
     Region sc, tv[2], ti[2], sav_v, sav_i, qpad, cand_v, cand_i, cand_cnt, th_v, th_i, thr;
+    Region qscale, qbias;   // uint8 corpus: the two fp32 values per padded query row of the scorer's fma (0 bytes for every other kind)
     size_t total;
 
     // May the < 256 trailing documents of a materialised tile ride in its 256x256 launch (na whole-tile documents of nc, score rows of ld)?
@@ -68,7 +70,8 @@ inline bool ScorePlan::tile_folds(long na, long nc, long ld, long row_stride, in
 static inline void plan_score_topk(const ScorePlanIn& in, ScorePlan& p) {
     const int nq = in.nq, d = in.d, k = in.k;
     const long N = in.N;
-    const bool bits = in.kind == SCORE_CORPUS_BITS;
+    const bool bits = in.kind == SCORE_CORPUS_BITS, u8 = in.kind == SCORE_CORPUS_U8;
+    const bool any_n = bits || u8;                    // the corpus launches take any number of documents
     // chunk the corpus so the fp32 score tile [nq, chunk] stays resident in the 256 MiB Infinity Cache, and so
     // that the score GEMM has a whole number of 256-CU waves of 256x256 tiles (query tiles x document tiles)
     const size_t budget = (size_t)160 << 20;
@@ -177,7 +180,8 @@ static inline void plan_score_topk(const ScorePlanIn& in, ScorePlan& p) {
     const size_t cc_bytes = filt ? score_align_up((size_t)(nq_pad + n_flags) * 4, 256) : 0;  // counters + per-chunk overflow flags
     const size_t td_bytes = score_align_up((size_t)nq * 4, 256);
     const size_t th_bytes = sampled ? tv_bytes + ti_bytes + td_bytes : 0;   // sample's list + dense thresholds
-    p.total = sc_bytes + 3 * (tv_bytes + ti_bytes) + qp_bytes + cv_bytes + ci_bytes + cc_bytes + th_bytes;
+    const size_t qs_bytes = u8 ? score_align_up((size_t)nq_pad * 4, 256) : 0;
+    p.total = sc_bytes + 3 * (tv_bytes + ti_bytes) + qp_bytes + cv_bytes + ci_bytes + cc_bytes + th_bytes + 2 * qs_bytes;
     size_t off = 0;
     auto take = [&](size_t bytes) { ScorePlan::Region r{off, bytes}; off += bytes; return r; };
     p.sc = take(sc_bytes);
@@ -187,12 +191,13 @@ static inline void plan_score_topk(const ScorePlanIn& in, ScorePlan& p) {
     p.qpad = take(qp_bytes);
     p.cand_v = take(cv_bytes); p.cand_i = take(ci_bytes); p.cand_cnt = take(cc_bytes);
     p.th_v = take(sampled ? tv_bytes : 0); p.th_i = take(sampled ? ti_bytes : 0); p.thr = take(sampled ? td_bytes : 0);
+    p.qscale = take(qs_bytes); p.qbias = take(qs_bytes);
 
     p.chunk = chunk; p.unit = unit; p.fchunk = fchunk; p.S = S; p.s_stride = s_stride; p.n_flags = n_flags;
     p.nq_pad = nq_pad; p.cap = cap; p.ratio = ratio;
     p.fast = fast; p.filt = filt; p.sampled = sampled;
     p.pad_queries = fast && !bits;
-    p.any_n = bits;
+    p.any_n = any_n;
     p.fold_score = in.sw.fold_tail && in.sw.fold_tail_score && !in.sw.gemm128;
     p.fresh_list = sampled && in.n_run == 0;
     p.sample_top2 = sampled && in.sw.sample_top2 && nq_pad >= 256 && S % 256 == 0;
@@ -226,7 +231,7 @@ static inline void plan_score_topk(const ScorePlanIn& in, ScorePlan& p) {
             // the < 256 trailing documents ride in the last chunk's launch (the 256x256 kernel clamps their rows and masks their
             // columns, GemmArgs.n_valid) when documents are its streamed operand; the 64-row tile keeps its own tail launch
             const bool fold_tail = seen + len == n256 && N > n256 &&
-                                   (bits || (in.sw.fold_tail && !in.sw.gemm128 && score_tail_foldable_shape(nq_pad, len + 256, d)));
+                                   (any_n || (in.sw.fold_tail && !in.sw.gemm128 && score_tail_foldable_shape(nq_pad, len + 256, d)));
             ScoreChunk c{seen, len, fold_tail, fold_tail ? len + (N - n256) : 0, false};
             seen += len;
             if (fold_tail) seen = N;

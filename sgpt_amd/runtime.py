@@ -79,6 +79,40 @@ class BinaryCorpus:
         return n
 
 
+class Uint8Corpus:
+    """A corpus held as uint8 codes with one range per dimension (include/sgpt_hip.h::sgpt_score_topk_u8; sentence-transformers'
+    precision="uint8"): `codes` uint8 [N, ld], ld = ceil(dim / 128) * 128, pad columns 128; `start`, `step` fp32 [ld], pad columns 0;
+    document n = start + codes[n] * step.  `normalized`: the rows were L2-normalised before quantisation (cosine scores) or not (dot
+    scores).  Built by Context.scalar_quantize_corpus / util.quantize_embeddings(precision="uint8")."""
+
+    def __init__(self, codes: torch.Tensor, start: torch.Tensor, step: torch.Tensor, normalized: bool = True, dim: Optional[int] = None):
+        if codes.dim() != 2 or codes.dtype != torch.uint8 or codes.shape[1] == 0 or codes.shape[1] % 128:
+            raise ValueError(f"Uint8Corpus: codes are uint8 [N, ld] with ld % 128 == 0, got {codes.dtype} {tuple(codes.shape)}")
+        ld = int(codes.shape[1])
+        dim = ld if dim is None else int(dim)
+        if dim < 1 or dim > ld or (dim + 127) // 128 * 128 != ld:
+            raise ValueError(f"Uint8Corpus: {ld} bytes per row do not hold dim = {dim} (ld = ceil(dim / 128) * 128)")
+        if tuple(start.shape) != (ld,) or tuple(step.shape) != (ld,):
+            raise ValueError(f"Uint8Corpus: start and step must be [{ld}], got {tuple(start.shape)} and {tuple(step.shape)}")
+        self.codes, self.start, self.step, self.normalized, self.dim = codes, start, step, bool(normalized), dim
+
+    def __len__(self) -> int:
+        return int(self.codes.shape[0])
+
+    @property
+    def nbytes(self) -> int:
+        return self.codes.numel() + self.start.numel() * self.start.element_size() + self.step.numel() * self.step.element_size()
+
+    def dequantize(self, dtype=torch.float32) -> torch.Tensor:
+        """The rows the scorer stands for, start + codes * step (product and sum each rounded once in fp32, then to `dtype`), on the
+        device.  As wide as `codes` (zero columns behind `dim` included)."""
+        return get_context(self.codes.device).u8_dequantize_rows(self.codes, self.start, self.step, out_dtype=dtype)
+
+    def codes_int8(self) -> torch.Tensor:
+        """sentence-transformers' "int8" view of the same levels: codes - 128 as int8 [N, dim]."""
+        return (self.codes[:, :self.dim].to(torch.int16) - 128).to(torch.int8)
+
+
 RESCORE_MODES = {"none": 0, "sign": 1, "fp8": 2}
 
 _contexts = {}
@@ -291,6 +325,129 @@ class Context:
             self._chk(self.lib.sgpt_fp8_quantize_rows(self.handle, _p(blk), n, d, _p(codes[r0:r0 + n]), _p(scale[r0:r0 + n]),
                                                       _stream_ptr(self.device)), "sgpt_fp8_quantize_rows")
         return QuantizedCorpus(codes, scale, bool(normalize), d0)
+
+    # ---- uint8 corpus: scalar quantisation with one range per dimension ----
+    def u8_col_minmax(self, x, run: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Column min / max of fp32 rows [n, d] (NaN-propagating); run = (min, max) of earlier blocks of rows, updated in place."""
+        x = self._dev_f32(x)
+        n, d = x.shape
+        if n == 0 or d == 0:
+            raise ValueError(f"u8_col_minmax needs a non-empty [n, d] matrix, got {tuple(x.shape)}")
+        if run is None:
+            mn = torch.empty((d,), dtype=torch.float32, device=self.device)
+            mx = torch.empty((d,), dtype=torch.float32, device=self.device)
+        else:
+            mn, mx = run
+        self._chk(self.lib.sgpt_u8_col_minmax(self.handle, _p(x), n, d, 0 if run is None else 1, _p(mn), _p(mx),
+                                              _stream_ptr(self.device)), "sgpt_u8_col_minmax")
+        return mn, mx
+
+    def u8_quantize_rows(self, x, start: torch.Tensor, step: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fp32 rows [n, d] -> uint8 [n, ld] by the rule of include/sgpt_hip.h; start / step fp32 [ld], ld = ceil(d / 128) * 128."""
+        x = self._dev_f32(x)
+        n, d = x.shape
+        ld = int(start.shape[0])
+        if out is None:
+            out = torch.empty((n, ld), dtype=torch.uint8, device=self.device)
+        self._chk(self.lib.sgpt_u8_quantize_rows(self.handle, _p(x), n, d, ld, _p(start), _p(step), _p(out),
+                                                 _stream_ptr(self.device)), "sgpt_u8_quantize_rows")
+        return out
+
+    def u8_dequantize_rows(self, codes: torch.Tensor, start: torch.Tensor, step: torch.Tensor, out_dtype=torch.float32) -> torch.Tensor:
+        codes = codes.to(device=self.device, dtype=torch.uint8).contiguous()
+        start = start.to(device=self.device, dtype=torch.float32).contiguous()
+        step = step.to(device=self.device, dtype=torch.float32).contiguous()
+        n, ld = codes.shape
+        out = torch.empty((n, ld), dtype=out_dtype, device=self.device)
+        self._chk(self.lib.sgpt_u8_dequantize_rows(self.handle, _p(codes), n, ld, _p(start), _p(step), _p(out), DT_CODE[out_dtype],
+                                                   _stream_ptr(self.device)), "sgpt_u8_dequantize_rows")
+        return out
+
+    def u8_prepare_queries(self, q, start: torch.Tensor, step: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The scorer's query prologue on its own (tests): q fp32 [nq <= 64, d] -> (q'' f16 [64, ld], qscale fp32 [64], qbias fp32 [64])."""
+        q = self._dev_f32(q)
+        nq, d = q.shape
+        ld = int(start.shape[0])
+        qpad = torch.empty((64, ld), dtype=torch.float16, device=self.device)
+        qscale = torch.empty((64,), dtype=torch.float32, device=self.device)
+        qbias = torch.empty((64,), dtype=torch.float32, device=self.device)
+        self._chk(self.lib.sgpt_u8_prepare_queries(self.handle, _p(q), _p(start), _p(step), nq, d, ld, _p(qpad), _p(qscale), _p(qbias),
+                                                   _stream_ptr(self.device)), "sgpt_u8_prepare_queries")
+        return qpad, qscale, qbias
+
+    def scalar_quantize_corpus(self, emb, normalize: bool = True, ranges=None, calibration_embeddings=None,
+                               block_rows: int = 65536) -> Uint8Corpus:
+        """Embeddings [N, d] -> Uint8Corpus: rows L2-normalised (normalize=True, cosine search) or taken as they are (dot scores), then
+        quantised to 256 levels between each column's min and max.  The ranges are `ranges` ([2, d]: min row, max row -- the layout of
+        sentence-transformers), or those of `calibration_embeddings` (normalised like the corpus), or the corpus's own; elements outside
+        them clamp.  Non-finite ranges (a NaN or inf in the rows they come from) raise ValueError.  Works in blocks of `block_rows` rows,
+        as quantize_corpus does; `emb` may live on the host."""
+        if ranges is not None and calibration_embeddings is not None:
+            raise ValueError("scalar_quantize_corpus: give ranges or calibration_embeddings, not both")
+        if not isinstance(emb, torch.Tensor):
+            emb = torch.as_tensor(np.asarray(emb))
+        if emb.dim() != 2 or emb.shape[0] == 0 or emb.shape[1] == 0:
+            raise ValueError(f"scalar_quantize_corpus needs a non-empty [N, d] matrix, got {tuple(emb.shape)}")
+        N, d = emb.shape
+        ld = (d + 127) // 128 * 128
+
+        def rows(src, r0):
+            blk = self._dev_f32(src[r0:r0 + block_rows])
+            return self.l2_normalize(blk) if normalize else blk
+        if ranges is not None:
+            ranges = torch.as_tensor(np.asarray(ranges.cpu() if isinstance(ranges, torch.Tensor) else ranges)).to(torch.float32)
+            if tuple(ranges.shape) != (2, d):
+                raise ValueError(f"scalar_quantize_corpus: ranges must be [2, {d}] (min row, max row), got {tuple(ranges.shape)}")
+            mn, mx = ranges[0].to(self.device).contiguous(), ranges[1].to(self.device).contiguous()
+        else:
+            src = emb if calibration_embeddings is None else calibration_embeddings
+            if not isinstance(src, torch.Tensor):
+                src = torch.as_tensor(np.asarray(src))
+            if src.dim() != 2 or src.shape[0] == 0 or src.shape[1] != d:
+                raise ValueError(f"scalar_quantize_corpus: calibration_embeddings must be a non-empty [n, {d}] matrix, got {tuple(src.shape)}")
+            run = None
+            for r0 in range(0, src.shape[0], block_rows):
+                run = self.u8_col_minmax(rows(src, r0), run)
+            mn, mx = run
+        if not bool(torch.isfinite(mn).all()) or not bool(torch.isfinite(mx).all()) or bool((mx < mn).any()):
+            raise ValueError("scalar_quantize_corpus: the ranges are not finite, or a max lies below its min (a NaN or inf in the rows they "
+                             "come from)")
+        start = torch.zeros((ld,), dtype=torch.float32, device=self.device)
+        step = torch.zeros((ld,), dtype=torch.float32, device=self.device)
+        start[:d] = mn
+        step[:d] = (mx - mn) / torch.full_like(mx, 255.0)      # (a tensor divisor: one IEEE division per column, not a multiplication by 1 / 255)
+        if not bool(torch.isfinite(step).all()):
+            raise ValueError("scalar_quantize_corpus: max - min overflows fp32")
+        codes = torch.empty((N, ld), dtype=torch.uint8, device=self.device)
+        for r0 in range(0, N, block_rows):
+            self.u8_quantize_rows(rows(emb, r0), start, step, out=codes[r0:r0 + block_rows])
+        return Uint8Corpus(codes, start, step, bool(normalize), d)
+
+    def _score_topk_u8(self, q, corpus: Uint8Corpus, k: int, idx_base: int, run, dtype):
+        if dtype is not None:
+            raise ValueError(f"a Uint8Corpus is scored from fp32 queries (the kernel pre-scales them itself): dtype must be None, got {dtype}")
+        if q.dim() != 2 or q.shape[1] != corpus.dim:
+            raise ValueError(f"embedding dims differ: {tuple(q.shape)[-1]} vs {corpus.dim}")
+        q = self._dev_f32(q)
+        codes = corpus.codes.to(self.device).contiguous()
+        start = corpus.start.to(device=self.device, dtype=torch.float32).contiguous()
+        step = corpus.step.to(device=self.device, dtype=torch.float32).contiguous()
+        nq, d = q.shape
+        N, ld = codes.shape
+        if run is None:
+            val = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+            idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+            n_run = 0
+        else:
+            val, idx, n_run = run
+        n_out = C.c_int32(0)
+        # groups of 64 queries, each re-streaming the codes (the pass is HBM-bound there); the running list is chained per group
+        for g0 in range(0, nq, 64):
+            gn = min(64, nq - g0)
+            self._chk(self.lib.sgpt_score_topk_u8(self.handle, _p(q[g0:g0 + gn]), _p(codes), _p(start), _p(step), gn, N, d, ld, k, idx_base,
+                                                  _p(val[g0:g0 + gn]), _p(idx[g0:g0 + gn]), n_run, C.byref(n_out),
+                                                  _stream_ptr(self.device)), "sgpt_score_topk_u8")
+        return val, idx, int(n_out.value)
 
     # ---- binary (1-bit) corpus: packed sign bits ----
     def pack_sign_bits(self, x, center: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -717,7 +874,8 @@ class Context:
                    dtype=None, rescore: str = "sign", rescore_multiplier=4) -> Tuple[torch.Tensor, torch.Tensor, int]:
         """-> (values fp32[nq,k], indices int64[nq,k], n_valid); rows sorted by descending score.  `corpus` may be a QuantizedCorpus
         (fp8 codes + per-document scales): the queries are then f16 (dtype None / torch.float16 only) and the result equals the f16
-        scorer's on corpus.dequantize(torch.float16), sgpt_score_topk_q8.  Over a BinaryCorpus (sgpt_score_topk_bits): q fp32, normalised
+        scorer's on corpus.dequantize(torch.float16), sgpt_score_topk_q8.  Over a Uint8Corpus (sgpt_score_topk_u8): q of any float
+        dtype, upcast to fp32, `dtype` None; queries run in groups of 64, each re-streaming the codes.  Over a BinaryCorpus (sgpt_score_topk_bits): q fp32, normalised
         and UNcentred; stage 1 takes the kp = min(1024, max(k, k * rescore_multiplier)) best by Hamming distance, `rescore` orders
         them -- "sign" (<q, signs> / sqrt(d), no extra memory), "fp8" (the corpus's fp8 copy), or "none" (Hamming only, kp = k, values
         agreement / d); a running list must come from calls with the same `rescore`.  corpus.center is subtracted from q here, for the
@@ -728,6 +886,8 @@ class Context:
             return self._score_topk_bits(q, corpus, k, idx_base, run, rescore, rescore_multiplier)
         if rescore != "sign" or rescore_multiplier != 4:
             raise ValueError("score_topk: rescore / rescore_multiplier apply to a BinaryCorpus only")
+        if isinstance(corpus, Uint8Corpus):
+            return self._score_topk_u8(q, corpus, k, idx_base, run, dtype)
         if isinstance(corpus, QuantizedCorpus):
             if dtype not in (None, torch.float16):
                 raise ValueError(f"a QuantizedCorpus is scored with f16 queries: dtype must be None or torch.float16, got {dtype}")

@@ -6,7 +6,7 @@ from typing import Callable, List
 import numpy as np
 import torch
 
-from .runtime import BinaryCorpus, QuantizedCorpus, get_context
+from .runtime import BinaryCorpus, QuantizedCorpus, Uint8Corpus, get_context
 
 
 def _ctx_for(*xs):
@@ -69,7 +69,8 @@ def pairwise_cos_sim(a, b) -> torch.Tensor:
     return out if home.type == "cuda" else out.cpu()
 
 
-def quantize_embeddings(embeddings, precision: str = "fp8", normalize: bool = True, center=None, keep_fp8: bool = False):
+def quantize_embeddings(embeddings, precision: str = "fp8", normalize: bool = True, center=None, keep_fp8: bool = False,
+                        ranges=None, calibration_embeddings=None):
     """Corpus embeddings -> a corpus object for semantic_search / Context.score_topk.  Named after sentence-transformers' later
     `quantize_embeddings`.
     precision="fp8": QuantizedCorpus (e4m3fn codes + one power-of-two scale per row), one byte per element on the device and per
@@ -77,9 +78,23 @@ def quantize_embeddings(embeddings, precision: str = "fp8", normalize: bool = Tr
     precision="ubinary" (sentence-transformers' name for packed unsigned bits): BinaryCorpus, one BIT per element -- Hamming search
     plus re-scoring of an over-fetched candidate list.  center: None | "mean" | a [d] tensor, subtracted from the normalised rows (and
     later from the queries) before the signs are taken; keep_fp8=True also keeps an fp8 copy to re-score with.  normalize=False is
-    refused: sign bits carry no norms."""
-    if precision not in ("fp8", "ubinary"):
-        raise ValueError(f"quantize_embeddings: unknown precision {precision!r} (only 'fp8' and 'ubinary' are built)")
+    refused: sign bits carry no norms.
+    precision="uint8" (sentence-transformers' scalar quantisation): Uint8Corpus, one byte per element with one range per DIMENSION --
+    256 uniform levels between each column's min and max.  ranges: None | a [2, d] matrix of (min, max) per column, as
+    sentence-transformers takes it; calibration_embeddings: rows to take the ranges from instead of the corpus itself (elements outside
+    them clamp).  The ranges are those of the rows as they are quantised: the normalised rows with normalize=True.  Its signed
+    spelling 'int8' (the same levels, code - 128) stays refused: Uint8Corpus.codes_int8() gives that view."""
+    if precision == "int8":
+        raise ValueError("quantize_embeddings: precision 'int8' is not built -- the same scalar quantisation is precision=\"uint8\" "
+                         "(its codes are the int8 codes + 128; Uint8Corpus.codes_int8() gives the signed view)")
+    if precision not in ("fp8", "ubinary", "uint8"):
+        raise ValueError(f"quantize_embeddings: unknown precision {precision!r} (only 'fp8', 'ubinary' and 'uint8' are built)")
+    if precision != "uint8" and (ranges is not None or calibration_embeddings is not None):
+        raise ValueError("quantize_embeddings: ranges / calibration_embeddings belong to precision='uint8'")
+    if precision == "uint8" and (center is not None or keep_fp8):
+        raise ValueError("quantize_embeddings: center / keep_fp8 belong to precision='ubinary'")
+    if precision == "uint8" and ranges is not None and calibration_embeddings is not None:
+        raise ValueError("quantize_embeddings: give ranges or calibration_embeddings, not both")
     if precision == "ubinary" and not normalize:
         raise ValueError("quantize_embeddings: precision='ubinary' with normalize=False is refused -- sign bits carry no norms")
     if precision == "ubinary" and keep_fp8 and center is not None:
@@ -93,6 +108,11 @@ def quantize_embeddings(embeddings, precision: str = "fp8", normalize: bool = Tr
     ctx, _ = _ctx_for(e)
     if precision == "ubinary":
         return ctx.binarize_corpus(e, normalize=True, center=center, keep_fp8=keep_fp8)
+    if precision == "uint8":
+        if isinstance(calibration_embeddings, list):
+            calibration_embeddings = torch.stack(calibration_embeddings)
+        cal = None if calibration_embeddings is None else _wrap(calibration_embeddings)
+        return ctx.scalar_quantize_corpus(e, normalize=normalize, ranges=ranges, calibration_embeddings=cal)
     return ctx.quantize_corpus(e, normalize=normalize)
 
 
@@ -131,6 +151,22 @@ def _search_quantized(q, corpus: QuantizedCorpus, top_k: int, score_function) ->
     return [[{"corpus_id": j, "score": s} for j, s in zip(ii[:n], vv[:n])] for vv, ii in zip(val, idx)]
 
 
+def _search_uint8(q, corpus: Uint8Corpus, top_k: int, score_function) -> List[List[dict]]:
+    cosine = score_function in (cos_sim, pytorch_cos_sim)
+    if not cosine and score_function is not dot_score:
+        raise ValueError("semantic_search over a Uint8Corpus scores with cos_sim or dot_score; an arbitrary score function needs "
+                         "the de-quantised rows (corpus.dequantize())")
+    if cosine != bool(corpus.normalized):
+        raise ValueError("semantic_search: cos_sim needs a corpus quantised with normalize=True, dot_score one with normalize=False "
+                         f"(this one has normalize={bool(corpus.normalized)})")
+    ctx, _ = _ctx_for(corpus.codes, q)
+    qd = ctx.l2_normalize(q) if cosine else ctx._dev_f32(q)
+    k = min(top_k, len(corpus))
+    val, idx, n = ctx.score_topk(qd, corpus, k)
+    val, idx = val.cpu().tolist(), idx.cpu().tolist()
+    return [[{"corpus_id": j, "score": s} for j, s in zip(ii[:n], vv[:n])] for vv, ii in zip(val, idx)]
+
+
 def semantic_search(query_embeddings, corpus_embeddings, query_chunk_size: int = 100,
                     corpus_chunk_size: int = 500000, top_k: int = 10,
                     score_function: Callable = cos_sim) -> List[List[dict]]:
@@ -143,6 +179,8 @@ def semantic_search(query_embeddings, corpus_embeddings, query_chunk_size: int =
         query_embeddings = torch.stack(query_embeddings)
     if isinstance(corpus_embeddings, QuantizedCorpus):     # fp8 corpus (quantize_embeddings): one fused pass over the codes
         return _search_quantized(_wrap(query_embeddings), corpus_embeddings, top_k, score_function)
+    if isinstance(corpus_embeddings, Uint8Corpus):         # uint8 codes, one range per dimension: one fused pass per 64 queries
+        return _search_uint8(_wrap(query_embeddings), corpus_embeddings, top_k, score_function)
     if isinstance(corpus_embeddings, BinaryCorpus):        # packed sign bits: Hamming search + re-scoring of the over-fetched list
         return _search_binary(_wrap(query_embeddings), corpus_embeddings, top_k, score_function)
     if isinstance(corpus_embeddings, list):
