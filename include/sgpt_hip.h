@@ -422,7 +422,7 @@ sgpt_status sgpt_score_topk(sgpt_ctx* ctx, const void* q, const void* corpus, in
  *             for bit (as long as code * scale is an f16 value, which holds for unit rows).  The only approximation is the quantisation:
  *             |s_fp8 - s| <= 2^-4 sum_i |q_i c_i| + 2^-10 scale sum_i |q_i| per score (e4m3 round-to-nearest, relative 2^-4 per element;
  *             elements below half the smallest subnormal 2^-9 scale flush to zero), on top of the f16 scorer's own arithmetic.
- *   shapes    nq <= 64 and d % 128 == 0 (codes 8-byte aligned): every whole 256-document tile streams through score64q8_kernel, which
+ *   shapes    nq <= 64 and d % 128 == 0 (codes 8-byte aligned): every whole 256-document tile streams through the one-byte tile (score64c.h), which
  *             reads the codes themselves; a ragged tail (< 256 documents) is de-quantised to f16 scratch.  Everything else (nq > 64:
  *             MFMA-bound; other d): blocks of at most 131 072 documents are de-quantised to f16 workspace and scored by the f16 path,
  *             the running list chained -- the memory saving holds, no speed is claimed.

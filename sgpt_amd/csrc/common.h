@@ -236,6 +236,18 @@ __device__ __forceinline__ bool cand_room(const int* cnt, int cap) {
     return __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap;
 }
 
+// Compute units of the current device, asked once per process on the first call (256 when the runtime does not say): the persistent
+// launchers size their grids by it.
+inline int device_cu_count() {
+    static const int ncu = [] {
+        int dev = 0, n = 256;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        return n;
+    }();
+    return ncu;
+}
+
 // ---- launch descriptors shared between the kernel translation units and the host ones (host.h) ----
 enum GemmEpi {
     EPI_STORE = 0,        // out[m][n] = acc                          (row-major, OutT)

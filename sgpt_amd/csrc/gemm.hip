@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "score64_epilogue.h"
 #include "score_plan.h"
 
 namespace {
@@ -791,12 +792,7 @@ template <typename T, int EPI, typename OutT, bool SWAP, bool LO = false>
 void launch256d(const GemmArgs& a, hipStream_t s, bool deep_a) {
     const int MT = a.M / 256, NT = a.N / 256;
     const int AT = MT >= NT ? MT : NT, BT = MT >= NT ? NT : MT;
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n / 8 * 8;
-    }();
+    const int ncu = device_cu_count() / 8 * 8;
     GemmArgs b = a;
 #ifdef SGPT_EXPERIMENTS
     static const int env_gm = getenv("SGPT_GM") ? atoi(getenv("SGPT_GM")) : 0, env_gn = getenv("SGPT_GN") ? atoi(getenv("SGPT_GN")) : 0;
@@ -912,103 +908,16 @@ __global__ __launch_bounds__(512, 2) void score64_kernel(const GemmArgs p) {
             ss ^= 1;
             sd = sd + 1 >= 3 ? 0 : sd + 1;
         }
-        // ---- epilogue, straight from the registers: lane = query row i*16 + fr, documents n0 + 32 w + 16 j + 4 g .. + 3 ----
-        const long n0 = (long)tile * 256 + wave * 32;
+        // ---- epilogue, straight from the registers (score64_epilogue.h) ----
+        // the thresholds are read HERE, not under the k-loop: its vmcnt(4) counts assume no other vector load in flight there
+        float thv[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
         if constexpr (EPI == EPI_SCORE_FILTER) {
-            // survivors staged in LDS by ballot positions, one flush per tile (see gemm256_epilogue.inc)
-            uint2_a* stage = reinterpret_cast<uint2_a*>(&stage_all[wave * 256]);
-            int staged = 0;                                                // wave-uniform
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int m = i * 16 + fr;
-                const float th = m < p.m_valid ? p.thr[(long)m * p.thr_ld] : INFINITY;
-                float mx = -INFINITY;                                // fast reject on the raw accumulators
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) mx = fmaxf(mx, acc[i][j][r]);
-                if (__ballot(th < -1.0f) != 0) {                      // thresholds below -1 (dot scores): the per-lane path, NaN -> -1 may survive
-                    if ((mx > th || th < -1.0f) && cand_room(p.cand_cnt + m, p.cand_cap)) {
-                        int c = 0;
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                const float v = acc[i][j][r];
-                                acc[i][j][r] = v != v ? -1.0f : v;       // cos_scores[isnan] = -1 (exact_search.py:99)
-                                c += acc[i][j][r] > th ? 1 : 0;
-                            }
-                        int slot = atomicAdd(p.cand_cnt + m, c);
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                const float v = acc[i][j][r];
-                                if (v > th) {
-                                    if (slot < p.cand_cap) {
-                                        p.cand_val[(long)m * p.cand_cap + slot] = v;
-                                        p.cand_idx[(long)m * p.cand_cap + slot] = p.idx_base + n0 + j * 16 + 4 * g + r;
-                                    }
-                                    ++slot;
-                                }
-                            }
-                    }
-                } else if (__ballot(mx > th) != 0) {
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float v = acc[i][j][r];
-                            const bool sv = v > th;
-                            const unsigned long long mask = __ballot(sv);
-                            if (mask != 0) {
-                                if (sv) {
-                                    const int pos = staged + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-                                    if (pos < 256) stage[pos] = make_uint2((unsigned)(m << 16) | (unsigned)(j * 16 + 4 * g + r), __float_as_uint(v));
-                                }
-                                staged += __builtin_popcountll(mask);
-                            }
-                        }
-                }
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-            if (staged > 0) {
-                __builtin_amdgcn_wave_barrier();
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                if (staged <= 256) {                                       // one global round trip per flush (see gemm256_epilogue.inc)
-                    for (int e = lane; e < staged; e += 64) {
-                        const uint2 ent = stage[e];
-                        const int m = (int)(ent.x >> 16);
-                        const int slot = atomicAdd(p.cand_cnt + m, 1);
-                        if (slot < p.cand_cap) {
-                            p.cand_val[(long)m * p.cand_cap + slot] = __uint_as_float(ent.y);
-                            p.cand_idx[(long)m * p.cand_cap + slot] = p.idx_base + n0 + (int)(ent.x & 0xffffu);
-                        }
-                    }
-                } else if (lane == 0) {
-                    atomicAdd(p.cand_cnt + (int)(stage[0].x >> 16), p.cand_cap + 1);   // more than the scratch holds: force the fallback
-                }
-                __builtin_amdgcn_wave_barrier();
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int m = i * 16 + fr;
-                if (m < p.m_valid) {
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        float4 v = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-                        v.x = v.x != v.x ? -1.0f : v.x; v.y = v.y != v.y ? -1.0f : v.y;
-                        v.z = v.z != v.z ? -1.0f : v.z; v.w = v.w != v.w ? -1.0f : v.w;
-                        *reinterpret_cast<float4*>(static_cast<float*>(p.out) + (long)m * p.ldo + n0 + j * 16 + 4 * g) = v;
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
+            for (int i = 0; i < 4; ++i)
+                if (i * 16 + fr < p.m_valid) thv[i] = p.thr[(long)(i * 16 + fr) * p.thr_ld];
         }
+        score64_epilogue<EPI, false>(p, acc, thv, (long)tile * 256 + wave * 32, g, fr, lane,
+                                     reinterpret_cast<uint2_a*>(stage_all) + (EPI == EPI_SCORE_FILTER ? wave * 256 : 0));
         if (!has_next) break;
         tile = ntile; dsrc = ndsrc;
     }
@@ -1017,12 +926,7 @@ __global__ __launch_bounds__(512, 2) void score64_kernel(const GemmArgs p) {
 
 template <typename T, int EPI>
 void launch_score64(const GemmArgs& a, hipStream_t s) {
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n;
-    }();
+    const int ncu = device_cu_count();
     const int NT = a.N / 256;
     hipLaunchKernelGGL((score64_kernel<T, EPI>), dim3(NT < ncu ? NT : ncu), dim3(512), 0, s, a);
 }

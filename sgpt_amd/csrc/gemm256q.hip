@@ -339,12 +339,7 @@ template <int EPI, typename OutT, bool SWAP>
 void launch256q(const GemmArgs& a, hipStream_t s) {
     const int MT = a.M / 256, NT = a.N / 256;
     const int AT = MT >= NT ? MT : NT, BT = MT >= NT ? NT : MT;
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n / 8 * 8;
-    }();
+    const int ncu = device_cu_count() / 8 * 8;
     GemmArgs b = a;
     const int gm = b.gm > 0 ? b.gm : 4;
     const int tiles_pad = ((AT + 7) / 8 + gm - 1) / gm * gm * 8 * BT;

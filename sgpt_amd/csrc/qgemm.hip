@@ -354,16 +354,6 @@ void qlaunch(const QGemmArgs& a, int group, hipStream_t s) {
     hipLaunchKernelGGL(kern, dim3(8 * ((R + 7) / 8)), dim3(QNT), lds, s, b);
 }
 
-inline int q_ncu() {
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n;
-    }();
-    return ncu;
-}
-
 // ---- tile choice (plain kernels): one launch = rounds x (BM + BN) K 2 bytes per workgroup; the fewest wins, ties to the larger tile ----
 struct QTile { int bm, bn, kd; };
 constexpr QTile Q_TILES[] = {{32, 16, 256}, {32, 32, 128}, {32, 64, 128}, {64, 32, 128}, {64, 64, 128}, {128, 64, 128}, {128, 128, 128}};
@@ -387,7 +377,7 @@ inline int q_class(const QTile& tl, bool ln_a, int K) {
 }
 
 inline int q_pick_plain(int M, int N, int K, int epi, int n_split, int force = 0) {
-    const int ncu = q_ncu();
+    const int ncu = device_cu_count();
     int best = -1; long best_cost = 0;
     for (int i = 0; i < Q_NTILES; ++i) {
         const QTile& tl = Q_TILES[i];
@@ -433,7 +423,7 @@ inline bool q_plan_ln(int M, int N, int d, int epi, int n_split, QLnPlan* out, i
     if (d % 128 || N % 32) return false;
     const int nk = d / 128;
     if (nk % 6 != 0 && nk % 4 != 0) return false;
-    const int ncu = q_ncu();
+    const int ncu = device_cu_count();
     QLnPlan best{0, 0, 0}; long best_cost = 0;
     const int cands[3][2] = {{32, 32}, {32, 64}, {64, 64}};
     for (int ci = 0; ci < 3; ++ci) {

@@ -50,14 +50,14 @@ sgpt_status sgpt_scores(sgpt_ctx* c, const void* a, const void* b, int32_t dtype
 // What a score + top-k pass reads its documents from.  The kinds share one schedule; only the launches that read the corpus differ:
 //   rows (fp32 / bf16 / f16, `dtype`): the GEMM kernels;
 //   fp8 (sgpt_score_topk_q8, short query batches): `base` holds e4m3fn codes [N][d] bytes, `scale` one power-of-two scale per document,
-//     q is f16 (dtype SGPT_F16).  Whole 256-document tiles go through score64q8_kernel (score8.hip), a ragged tail is de-quantised
+//     q is f16 (dtype SGPT_F16).  Whole 256-document tiles go through launch_score64q8 (score8.hip), a ragged tail is de-quantised
 //     into f16 scratch (ws6) for the register-staged kernel;
 //   bits (sgpt_score_topk_bits, at most 64 queries per call): `base` holds packed sign bits [N][ldb] bytes, q the packed query rows of
 //     qw dwords; the score is the agreement d - 2 * hamming, an integer in fp32.  Every launch that reads the corpus is the Hamming
 //     tile (scorebits.hip), which takes any number of documents, so no launch is split for a ragged tail;
 //   uint8 (sgpt_score_topk_u8, at most 64 queries per call): `base` holds uint8 codes [N][ld] bytes, `start` / `step` the range of every
 //     dimension, q the caller's fp32 rows of width d0; `d` is ld, the k extent of the tile.  The pass prologue turns q into the 64-row
-//     tile of pre-scaled f16 rows with qscale / qbias (ws2); every launch that reads the corpus is score64u8_kernel (scoreu8.hip),
+//     tile of pre-scaled f16 rows with qscale / qbias (ws2); every launch that reads the corpus is launch_score64u8 (scoreu8.hip),
 //     which takes any number of documents.
 struct Corpus {
     ScoreCorpusKind kind;

@@ -181,12 +181,7 @@ void launch_scorebits(int epi, const GemmArgs& a, int d, int qw, long ldb, hipSt
     if ((epi != EPI_SCORE && epi != EPI_SCORE_FILTER) || (epi == EPI_SCORE_FILTER && a.m_valid > 64) || a.N <= 0 || a.m_valid <= 0 || d <= 0 || ldb % 4 || ldb < 4L * words ||
         a.ldw < ldb || a.ldw % ldb || qw < (words + 3) / 4 * 4 || ((size_t)a.W & 3))
         abort();
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n;
-    }();
+    const int ncu = device_cu_count();
     // 16-byte loads need 16-byte aligned rows that own whole pieces (a row of ldb % 16 == 0 bytes ends behind its last piece)
     const bool vec = ldb % 16 == 0 && ((size_t)a.W & 15) == 0;
     const long ntiles = ((long)a.N + 255) / 256;

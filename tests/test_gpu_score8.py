@@ -1,4 +1,4 @@
-"""-m gpu: score and rank against an fp8 (e4m3fn) corpus -- sgpt_score_topk_q8, score64q8_kernel (csrc/score8.hip), the composed
+"""-m gpu: score and rank against an fp8 (e4m3fn) corpus -- sgpt_score_topk_q8, score64c_kernel with the fp8 codec (csrc/score8.hip), the composed
 route, Context.quantize_corpus / score_topk(QuantizedCorpus), util.quantize_embeddings / semantic_search.
 
 Exact where the arithmetic is exact (integer probes, subnormal / NaN codes, equality with the f16 scorer on the de-quantised rows);

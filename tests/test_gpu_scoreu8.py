@@ -1,4 +1,4 @@
-"""-m gpu: score and rank against a uint8 corpus with one range per dimension -- sgpt_score_topk_u8, score64u8_kernel and the prologue /
+"""-m gpu: score and rank against a uint8 corpus with one range per dimension -- sgpt_score_topk_u8, score64c_kernel with the uint8 codec and the prologue /
 row kernels (csrc/scoreu8.hip), Context.scalar_quantize_corpus / score_topk(Uint8Corpus), util.quantize_embeddings(precision="uint8")
 / semantic_search.
 

@@ -79,7 +79,7 @@ def test_plan_properties_over_the_grid(dump):
         for i, (doc0, ln, fold, n_valid, tail_launch) in enumerate(chunks):
             last = i == len(chunks) - 1
             assert doc0 == pos, ctx
-            # whole 256-document tiles: score64_kernel / score64q8_kernel / the 256x256 kernel take N % 256 == 0 (common.h: Score8Args,
+            # whole 256-document tiles: score64_kernel / the fp8 byte tile (launch_score64q8) / the 256x256 kernel take N % 256 == 0 (common.h: Score8Args,
             # "64 padded f16 query rows x 256 documents"; gemm.hip: shape256).  A binary corpus folds an exact tail on top (common.h:
             # launch_scorebits, "g.N documents (any number, bounds-checked)"): then n_valid, not len, is the launch's count
             assert ln > 0 and ln % 256 == 0, ctx
