@@ -444,9 +444,8 @@ void launch_pack_split_rows(const float* src, long rows, long cols, void* dst, i
 void launch_crest16(const void* in, int T, int cols, long ld, int dtype, unsigned* out_bits, hipStream_t s);
 // fp32 [n][d] -> 16-bit [n][3 d]: layout 0 = [hi | lo | hi] (documents / activations), 1 = [hi | hi | lo] (queries / weights)
 void launch_split16_rows(const float* in, long n, int d, int layout, void* out, int out_dtype, hipStream_t s);
-// LayerNorm -> e4m3fn codes q[T,d] + one power-of-two scale per row (+ optionally the same rows in a 16-bit format)
-void launch_layernorm_q8(const float* x, const float* g, const float* b, void* q, float* scale, void* out16, int out16_dtype,
-                         int T, int d, float eps, hipStream_t s);
+// LayerNorm -> e4m3fn codes q[T,d] + one power-of-two scale per row
+void launch_layernorm_q8(const float* x, const float* g, const float* b, void* q, float* scale, int T, int d, float eps, hipStream_t s);
 void launch_absmax16(const void* in, long numel, int dtype, unsigned* out_bits, hipStream_t s);   // max|x| of a bf16 / f16 array
 void launch_lnf_pool(const float* x, const float* g, const float* b, const int* seq_off, const int* seq_len,
                      const int* pad_left, int B, int d, float eps, int apply_ln, int mode, int normalize,
@@ -469,7 +468,6 @@ void launch_logprob_rows(const float* logits, long ld, int V, const int* targets
                          hipStream_t s);
 // out[i] = mean_j in[j][i], in fp32 [n0][n] (layer average of the meanmean / lasttokenmean methods)
 void launch_mean_over_axis0(const float* in, int n0, long n, float* out, hipStream_t s);
-void launch_f32_to_bf16(const float* in, long numel, void* out, hipStream_t s);
 void launch_f32_to_16(const float* in, long numel, void* out, int out_dtype, hipStream_t s);   // DT_BF16 | DT_F16, RNE
 // max |in[i]| folded into *out_bits (the fp32 bit pattern of a non-negative float, atomicMax; zero it first)
 void launch_absmax(const float* in, long numel, unsigned* out_bits, hipStream_t s);

@@ -1,12 +1,21 @@
-// HBM-bound streaming kernels of the encoder: embedding gather-add, LayerNorm, the fused
-// final-LayerNorm + position-weighted mean pool, stand-alone pooling, L2 normalise.
-// All are one-wave-per-row (64 lanes x float4 = 1 KiB per instruction, coalesced) with
-// wavefront-shuffle reductions; no LDS except the cross-wave combine of the pool.
+// The HBM-bound kernels around the GEMMs and the attention, and their launchers:
+//   row normalisation (one wave per row, rowln.h): LayerNorm to fp32 / 16 bit, with write-back, as [hi | lo | hi], as fp8 codes; RMSNorm;
+//     the fused final norm + pooling + L2 normalise (one workgroup per sequence, LDS for its cross-wave combine only);
+//   other row kernels: embedding gather-add, stand-alone pooling, L2 normalise, pairwise scores, row gather, log-prob of a logits row,
+//     crest factor;
+//   element maps: SwiGLU, the three rotary embeddings (GPT-J pairs, half-split, half-split behind a per-head RMSNorm);
+//   formats: fp8 row quantise / de-quantise, split-precision rows and weights, sign bits, fp32 -> 16 bit, BLOOM's QKV re-ordering;
+//   small tools: abs-max (fp32, 16 bit), mean over axis 0, fill, pseudo-random fill.
+#include <type_traits>
+
 #include "common.h"
 #include "rowln.h"
 
-
 namespace {
+
+// an index from outside clamped into a table of n rows: a C-ABI caller's bad id / position / target reads a wrong row, never out of
+// bounds (the Python host validates and raises before the call, model.py::SGPTModel.pack)
+__device__ __forceinline__ int clamp_index(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 
 // ---- wte[ids] + wpe[pos]  (HF:gpt_neo/modeling_gpt_neo.py:444,462-463) ----
 __global__ __launch_bounds__(256) void embed_kernel(const int* __restrict__ ids, const int* __restrict__ pos,
@@ -15,17 +24,13 @@ __global__ __launch_bounds__(256) void embed_kernel(const int* __restrict__ ids,
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= T) return;
     const int lane = threadIdx.x & 63;
-    // ids / positions are clamped into the tables: a C-ABI caller's bad id reads a wrong row, never out of bounds
-    // (the Python host validates and raises before the call, model.py::SGPTModel.pack)
-    int id = ids[row]; id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    const float4* a = reinterpret_cast<const float4*>(wte + (long)id * d);
+    const float4* a = reinterpret_cast<const float4*>(wte + (long)clamp_index(ids[row], vocab) * d);
     float4* o = reinterpret_cast<float4*>(x + (long)row * d);
     if (wpe == nullptr) {  // GPT-J: no learned position embedding (HF:gptj:484)
         for (int c = lane; c < d / 4; c += 64) o[c] = a[c];
         return;
     }
-    int ps = pos[row]; ps = ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps);
-    const float4* b = reinterpret_cast<const float4*>(wpe + (long)ps * d);
+    const float4* b = reinterpret_cast<const float4*>(wpe + (long)clamp_index(pos[row], max_pos) * d);
     for (int c = lane; c < d / 4; c += 64) {
         const float4 u = a[c], v = b[c];
         o[c] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
@@ -38,101 +43,25 @@ template <typename OutT, int NV>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                         const float* __restrict__ b, OutT* __restrict__ out, int T,
                                                         int d, float eps, float out_mul) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= T) return;
-    const int lane = threadIdx.x & 63;
-    RowLN<NV> r;
-    r.load(x + (long)row * d, d, lane);
-    r.normalize(g, b, d, eps, lane);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < d) {
-            if constexpr (sizeof(OutT) == 4) {
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + (long)row * d + c) = r.v[i];
-            } else {
-                *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(out) + (long)row * d + c) =
-                    make_uint2(Half<OutT>::pack2(r.v[i].x * out_mul, r.v[i].y * out_mul),
-                               Half<OutT>::pack2(r.v[i].z * out_mul, r.v[i].w * out_mul));
-            }
-        }
-    }
+    rownorm_row<NV>(x, T, d, RowLayerNorm<>(g, b, eps), RowStore<OutT, true, false>{out, out_mul, nullptr});
 }
 
 // Post-LayerNorm blocks (SGPT_ARCH_BERT, HF:bert/modeling_bert.py BertSelfOutput / BertOutput: `LayerNorm(dense(h) + input)`): the
-// normalised row IS the next residual stream, so it goes back to x in fp32, in place, and -- the same registers, rounded once -- to
-// the 16-bit operand buffer the next projection reads.  A wave owns its row (all loads precede all stores): in place is safe.
-// f16: every rounded value passes the range tracker (no load-time bound on gamma / beta is relied upon for this family).
+// normalised row IS the next residual stream, so it goes back to x in fp32, in place, and to the 16-bit operand buffer the next
+// projection reads.  f16: every rounded value passes the range tracker (no load-time bound on gamma / beta is relied upon for this family).
 template <typename OutT, int NV>
 __global__ __launch_bounds__(256) void layernorm_writeback_kernel(float* __restrict__ x, const float* __restrict__ g,
                                                                   const float* __restrict__ b, OutT* __restrict__ out16, int T,
                                                                   int d, float eps, int* __restrict__ range_flag) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= T) return;
-    const int lane = threadIdx.x & 63;
-    RowLN<NV> r;
-    r.load(x + (long)row * d, d, lane);
-    r.normalize(g, b, d, eps, lane);
-    RangeTrack<OutT> range;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < d) {
-            *reinterpret_cast<float4*>(x + (long)row * d + c) = r.v[i];
-            range.note(r.v[i].x, r.v[i].y); range.note(r.v[i].z, r.v[i].w);
-            *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(out16) + (long)row * d + c) =
-                make_uint2(Half<OutT>::pack2(r.v[i].x, r.v[i].y), Half<OutT>::pack2(r.v[i].z, r.v[i].w));
-        }
-    }
-    range.finish(range_flag);
+    rownorm_row<NV>(x, T, d, RowLayerNorm<>(g, b, eps), RowStoreWriteback<OutT>{x, out16, range_flag});
 }
 
-// RMSNorm of the Llama family (HF:llama/modeling_llama.py LlamaRMSNorm): out = x * rsqrt(mean(x^2) + eps) * g -- no mean subtraction,
-// no bias.  The row in registers with layernorm_kernel's load pattern (RowLN::load), the square sum through the same butterfly;
-// HF's order of operations: (x * rstd) first, then * g.  Columns past d hold zeros and add nothing to the sum.
-template <int NV, bool FAST = false>
-__device__ __forceinline__ void rms_normalize(RowLN<NV>& r, const float* __restrict__ g, int d, float eps, int lane) {
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) q += (r.v[i].x * r.v[i].x + r.v[i].y * r.v[i].y) + (r.v[i].z * r.v[i].z + r.v[i].w * r.v[i].w);
-    const float rstd = 1.0f / sqrtf((FAST ? wave_sum_valu(q) : wave_sum(q)) / (float)d + eps);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < d) {
-            const float4 gg = *reinterpret_cast<const float4*>(g + c);
-            r.v[i].x = r.v[i].x * rstd * gg.x; r.v[i].y = r.v[i].y * rstd * gg.y;
-            r.v[i].z = r.v[i].z * rstd * gg.z; r.v[i].w = r.v[i].w * rstd * gg.w;
-        }
-    }
-}
-
-// One wave per row; the output is rounded once to OutT (fp32: stored as it is, out may alias x -- a wave owns its row and all of
-// its loads precede its stores).  f16: every rounded value passes the range tracker (no load-time bound on the gain is relied upon).
+// RMSNorm of the Llama family (rowln.h: rms_normalize), rounded once to OutT (fp32: stored as it is, out may alias x).  f16: every
+// rounded value passes the range tracker (no load-time bound on the gain is relied upon).
 template <typename OutT, int NV>
 __global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ x, const float* __restrict__ g, OutT* __restrict__ out,
                                                       int T, int d, float eps, int* __restrict__ range_flag) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= T) return;
-    const int lane = threadIdx.x & 63;
-    RowLN<NV> r;
-    r.load(x + (long)row * d, d, lane);
-    rms_normalize<NV>(r, g, d, eps, lane);
-    RangeTrack<OutT> range;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < d) {
-            if constexpr (sizeof(OutT) == 4) {
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + (long)row * d + c) = r.v[i];
-            } else {
-                range.note(r.v[i].x, r.v[i].y); range.note(r.v[i].z, r.v[i].w);
-                *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(out) + (long)row * d + c) =
-                    make_uint2(Half<OutT>::pack2(r.v[i].x, r.v[i].y), Half<OutT>::pack2(r.v[i].z, r.v[i].w));
-            }
-        }
-    }
-    if constexpr (sizeof(OutT) != 4) range.finish(range_flag);
+    rownorm_row<NV>(x, T, d, RowRMSNorm<>(g, nullptr, eps), RowStore<OutT, false, true>{out, 1.0f, range_flag});
 }
 
 // SwiGLU of the Llama family (HF:llama/modeling_llama.py LlamaMLP: down(silu(gate(x)) * up(x))): gu [T][2 ffn] holds the gate
@@ -183,26 +112,7 @@ template <typename OutT, int NV>
 __global__ __launch_bounds__(256) void layernorm_split_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                               const float* __restrict__ b, uint16_t* __restrict__ out, int T,
                                                               int d, float eps, float out_mul) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= T) return;
-    const int lane = threadIdx.x & 63;
-    RowLN<NV> r;
-    r.load(x + (long)row * d, d, lane);
-    r.normalize(g, b, d, eps, lane);
-    uint16_t* o = out + (long)row * 3 * d;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < d) {
-            const float v0 = r.v[i].x * out_mul, v1 = r.v[i].y * out_mul, v2 = r.v[i].z * out_mul, v3 = r.v[i].w * out_mul;
-            const uint32_t h01 = Half<OutT>::pack2(v0, v1), h23 = Half<OutT>::pack2(v2, v3);
-            const uint32_t l01 = Half<OutT>::pack2(v0 - Half<OutT>::lo(h01), v1 - Half<OutT>::hi(h01));
-            const uint32_t l23 = Half<OutT>::pack2(v2 - Half<OutT>::lo(h23), v3 - Half<OutT>::hi(h23));
-            *reinterpret_cast<uint2*>(o + c) = make_uint2(h01, h23);
-            *reinterpret_cast<uint2*>(o + d + c) = make_uint2(l01, l23);
-            *reinterpret_cast<uint2*>(o + 2 * d + c) = make_uint2(h01, h23);
-        }
-    }
+    rownorm_row<NV>(x, T, d, RowLayerNorm<>(g, b, eps), RowStoreSplit<OutT>{out, out_mul});
 }
 
 // weights of the split-precision projection: src fp32 [rows, cols] -> dst 16-bit [rows, 3 * cols] = [W_hi | W_hi | W_lo]
@@ -221,49 +131,12 @@ __global__ __launch_bounds__(256) void pack_split_rows_kernel(const float* __res
 }
 
 // LayerNorm whose output feeds an fp8-MFMA GEMM (gemm256q.hip): the normalised row is quantised to OCP e4m3fn codes under
-// ONE power-of-two scale per row -- the smallest 2^k with max|row| / 2^k <= 448 (the rule of fp8_quant_rows_kernel) --
-// which factors out of the GEMM's k-sum and is applied to its accumulators.  Optionally the same row is also written in
-// a 16-bit format (GPT-J: ln_1 feeds the attention projections and the MLP).
-template <int NV, typename H16>
+// ONE power-of-two scale per row (fp8_pow2_scale), which factors out of the GEMM's k-sum and is applied to its accumulators.
+template <int NV>
 __global__ __launch_bounds__(256) void layernorm_q8_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                            const float* __restrict__ b, uint8_t* __restrict__ q,
-                                                           float* __restrict__ scale, uint16_t* __restrict__ out16, int T,
-                                                           int d, float eps) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= T) return;
-    const int lane = threadIdx.x & 63;
-    RowLN<NV> r;
-    r.load(x + (long)row * d, d, lane);
-    r.normalize(g, b, d, eps, lane);
-    float amax = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < d) amax = fmaxf(amax, fmaxf(fmaxf(fabsf(r.v[i].x), fabsf(r.v[i].y)), fmaxf(fabsf(r.v[i].z), fabsf(r.v[i].w))));
-    }
-    amax = wave_max(amax);
-    float sc = 1.0f;
-    if (amax > 0.f && amax < 3.0e38f) {
-        const uint32_t u = __float_as_uint(amax);
-        const int e = (int)((u >> 23) & 0xffu) - 127;
-        int k = e - ((u & 0x7fffffu) > 0x600000u ? 7 : 8);               // amax / 2^k in (224, 448]
-        k = k < -126 ? -126 : (k > 127 ? 127 : k);
-        sc = __uint_as_float((uint32_t)(k + 127) << 23);
-    }
-    if (lane == 0) scale[row] = sc;
-    const float inv = 1.0f / sc;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < d) {
-            int w = __builtin_amdgcn_cvt_pk_fp8_f32(r.v[i].x * inv, r.v[i].y * inv, 0, false);
-            w = __builtin_amdgcn_cvt_pk_fp8_f32(r.v[i].z * inv, r.v[i].w * inv, w, true);
-            *reinterpret_cast<uint32_t*>(q + (long)row * d + c) = (uint32_t)w;
-            if (out16 != nullptr)
-                *reinterpret_cast<uint2*>(out16 + (long)row * d + c) =
-                    make_uint2(Half<H16>::pack2(r.v[i].x, r.v[i].y), Half<H16>::pack2(r.v[i].z, r.v[i].w));
-        }
-    }
+                                                           float* __restrict__ scale, int T, int d, float eps) {
+    rownorm_row<NV>(x, T, d, RowLayerNorm<>(g, b, eps), RowStoreFp8{q, scale});
 }
 
 // ---- ln_f + pooling + optional L2 normalise, one workgroup (4 waves) per sequence ----
@@ -271,9 +144,8 @@ __global__ __launch_bounds__(256) void layernorm_q8_kernel(const float* __restri
 //   (Pooling.py:99-125; beir_dense_retriever.py:258-270; weights follow the PADDED index)
 // mean: Pooling.py:117-125 / beir_dense_retriever.py:238-242;  lasttoken: :271-282 (index len-1)
 // learntmean (mode 3): w_t = position_weights[P+t], clamp 1e-9 (WeightedMeanPooling.py:21-39)
-// RMS = true (the Llama family): the final norm is the RMSNorm of rms_normalize (g alone; b is not read).  The LayerNorm
-// instantiations do not see it (if constexpr).
-template <int NV, bool RMS = false>
+// Norm: RowLayerNorm<true>, or RowRMSNorm<true> for the final norm of the Llama family (g alone; b is not read).
+template <int NV, typename Norm>
 __global__ __launch_bounds__(256) void lnf_pool_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                        const float* __restrict__ b, const int* __restrict__ seq_off,
                                                        const int* __restrict__ seq_len,
@@ -285,6 +157,7 @@ __global__ __launch_bounds__(256) void lnf_pool_kernel(const float* __restrict__
     const int sq = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s0 = seq_off[sq], len = seq_len[sq], P = pad_left ? pad_left[sq] : 0;
+    const Norm norm(g, b, eps);
 
     float4 acc[NV];
 #pragma unroll
@@ -305,8 +178,7 @@ __global__ __launch_bounds__(256) void lnf_pool_kernel(const float* __restrict__
         for (int u = 0; u < LPB; ++u) {
             const int tt = t + 4 * u;
             if (tt >= t_hi) break;
-            if constexpr (RMS) { if (apply_ln) rms_normalize<NV, true>(r[u], g, d, eps, lane); }
-            else if (apply_ln) r[u].template normalize<true>(g, b, d, eps, lane);
+            if (apply_ln) norm(r[u], d, lane);
             // mode 3 (learntmean): trained per-position weights, indexed like the padded position
             // (WeightedMeanPooling.py:21-39; useb_dense_retriever.py:253-270)
             const float w = mode == 0 ? (float)(P + tt + 1) : (mode == 3 ? pw[P + tt < pw_n ? P + tt : pw_n - 1] : 1.0f);   // index clamped: no OOB read
@@ -318,11 +190,7 @@ __global__ __launch_bounds__(256) void lnf_pool_kernel(const float* __restrict__
             }
         }
     }
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < d) *reinterpret_cast<float4*>(sm + wave * d + c) = acc[i];
-    }
+    RowLN<NV>::for_cols(d, lane, [&](int i, int c) { *reinterpret_cast<float4*>(sm + wave * d + c) = acc[i]; });
     float* red = sm + 4 * d;
     if (lane == 0) red[wave] = den;
     __syncthreads();
@@ -417,7 +285,7 @@ __global__ __launch_bounds__(256) void l2norm_kernel(const float* __restrict__ i
 // out[i] = sum_j a[i][j] b[i][j]            (COS = false: `(a * b).sum(dim=-1)`)
 //        = sum_j (a[i][j] / max(|a[i]|, 1e-12)) (b[i][j] / max(|b[i]|, 1e-12))   (COS = true: both sides through
 //          normalize_embeddings first, then the same product sum -- the reference's order of operations, not dot / (|a| |b|)).
-// One wave per row pair, float4 loads where the row allows, wavefront butterflies for the three sums.
+// One wave per row pair, scalar loads strided by the wave (any d), wavefront butterflies for the three sums.
 template <bool COS>
 __global__ __launch_bounds__(256) void pairwise_kernel(const float* __restrict__ a, const float* __restrict__ b, long n, int d,
                                                        float* __restrict__ out) {
@@ -456,8 +324,7 @@ __global__ __launch_bounds__(256) void rope_kernel(T* __restrict__ buf, long ld,
     const int tkn = (int)(idx / per_tok);
     const int rem = (int)(idx - (long)tkn * per_tok);
     const int h = rem / half, i = rem - h * half;
-    // the position is clamped into the tables, as embed_kernel does: a C-ABI caller's bad position reads a wrong row, never out of bounds
-    int ps = pos[tkn]; ps = ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps);
+    const int ps = clamp_index(pos[tkn], max_pos);
     const float sn = sin_t[(long)ps * half + i], cs = cos_t[(long)ps * half + i];
     T* q = buf + (long)tkn * ld + (long)h * dh + 2 * i;
 #pragma unroll
@@ -479,6 +346,41 @@ __global__ __launch_bounds__(256) void rope_kernel(T* __restrict__ buf, long ld,
 // pos * inv_freq[i] -- the two halves of a head pair up, not GPT-J's neighbours.  In place on the H query heads at column 0 and the
 // H_kv key heads at column k_off of [T][ld].  One thread per four consecutive i of one head: two 16- / 8-byte words of the row and
 // one float4 of each table; fp32 arithmetic, one rounding.  f16: |rotated| <= sqrt(2) * RANGE_LIMIT < 65504, as rope_kernel.
+// the thread's two groups of four consecutive T at lo / hi (one 16- / 8-byte word each) -> fp32, and back rounded once
+template <typename T>
+__device__ __forceinline__ void load_2x4(const T* lo, const T* hi, float (&a)[4], float (&b)[4]) {
+    if constexpr (sizeof(T) == 4) {
+        const float4 va = *reinterpret_cast<const float4*>(lo), vb = *reinterpret_cast<const float4*>(hi);
+        a[0] = va.x; a[1] = va.y; a[2] = va.z; a[3] = va.w; b[0] = vb.x; b[1] = vb.y; b[2] = vb.z; b[3] = vb.w;
+    } else {
+        const uint2 ua = *reinterpret_cast<const uint2*>(lo), ub = *reinterpret_cast<const uint2*>(hi);
+        a[0] = Half<T>::lo(ua.x); a[1] = Half<T>::hi(ua.x); a[2] = Half<T>::lo(ua.y); a[3] = Half<T>::hi(ua.y);
+        b[0] = Half<T>::lo(ub.x); b[1] = Half<T>::hi(ub.x); b[2] = Half<T>::lo(ub.y); b[3] = Half<T>::hi(ub.y);
+    }
+}
+template <typename T>
+__device__ __forceinline__ void store_2x4(T* lo, T* hi, const float (&a)[4], const float (&b)[4]) {
+    if constexpr (sizeof(T) == 4) {
+        *reinterpret_cast<float4*>(lo) = make_float4(a[0], a[1], a[2], a[3]);
+        *reinterpret_cast<float4*>(hi) = make_float4(b[0], b[1], b[2], b[3]);
+    } else {
+        *reinterpret_cast<uint2*>(lo) = make_uint2(Half<T>::pack2(a[0], a[1]), Half<T>::pack2(a[2], a[3]));
+        *reinterpret_cast<uint2*>(hi) = make_uint2(Half<T>::pack2(b[0], b[1]), Half<T>::pack2(b[2], b[3]));
+    }
+}
+// (a, b) <- (a cos - b sin, b cos + a sin) by the table row of position ps (clamped into the tables), columns i .. i + 3 of `half`
+__device__ __forceinline__ void rotate_half_2x4(float (&a)[4], float (&b)[4], const float* __restrict__ sin_t, const float* __restrict__ cos_t,
+                                                int ps, int max_pos, int half, int i) {
+    const long at = (long)clamp_index(ps, max_pos) * half + i;
+    const float4 sn4 = *reinterpret_cast<const float4*>(sin_t + at), cs4 = *reinterpret_cast<const float4*>(cos_t + at);
+    const float sn[4] = {sn4.x, sn4.y, sn4.z, sn4.w}, cs[4] = {cs4.x, cs4.y, cs4.z, cs4.w};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const float ra = a[u] * cs[u] - b[u] * sn[u], rb = b[u] * cs[u] + a[u] * sn[u];
+        a[u] = ra; b[u] = rb;
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void rope_half_kernel(T* __restrict__ buf, long ld, long k_off, const int* __restrict__ pos,
                                                         const float* __restrict__ sin_t, const float* __restrict__ cos_t,
@@ -490,26 +392,13 @@ __global__ __launch_bounds__(256) void rope_half_kernel(T* __restrict__ buf, lon
     const int tkn = (int)(idx / per_tok);
     const int rem = (int)(idx - (long)tkn * per_tok);
     const int h = rem / qpt, i = (rem - h * qpt) * 4;
-    // the position is clamped into the tables, as rope_kernel does
-    int ps = pos[tkn]; ps = ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps);
-    const float4 sn = *reinterpret_cast<const float4*>(sin_t + (long)ps * half + i);
-    const float4 cs = *reinterpret_cast<const float4*>(cos_t + (long)ps * half + i);
     // heads [0, H): q at column h * dh; heads [H, H + H_kv): k at column k_off + (h - H) * dh
     T* lo = buf + (long)tkn * ld + (h < H ? (long)h * dh : k_off + (long)(h - H) * dh) + i;
     T* hi = lo + half;
-    if constexpr (sizeof(T) == 4) {
-        const float4 a = *reinterpret_cast<const float4*>(lo), b = *reinterpret_cast<const float4*>(hi);
-        *reinterpret_cast<float4*>(lo) = make_float4(a.x * cs.x - b.x * sn.x, a.y * cs.y - b.y * sn.y, a.z * cs.z - b.z * sn.z, a.w * cs.w - b.w * sn.w);
-        *reinterpret_cast<float4*>(hi) = make_float4(b.x * cs.x + a.x * sn.x, b.y * cs.y + a.y * sn.y, b.z * cs.z + a.z * sn.z, b.w * cs.w + a.w * sn.w);
-    } else {
-        const uint2 ua = *reinterpret_cast<const uint2*>(lo), ub = *reinterpret_cast<const uint2*>(hi);
-        const float a0 = Half<T>::lo(ua.x), a1 = Half<T>::hi(ua.x), a2 = Half<T>::lo(ua.y), a3 = Half<T>::hi(ua.y);
-        const float b0 = Half<T>::lo(ub.x), b1 = Half<T>::hi(ub.x), b2 = Half<T>::lo(ub.y), b3 = Half<T>::hi(ub.y);
-        *reinterpret_cast<uint2*>(lo) = make_uint2(Half<T>::pack2(a0 * cs.x - b0 * sn.x, a1 * cs.y - b1 * sn.y),
-                                                   Half<T>::pack2(a2 * cs.z - b2 * sn.z, a3 * cs.w - b3 * sn.w));
-        *reinterpret_cast<uint2*>(hi) = make_uint2(Half<T>::pack2(b0 * cs.x + a0 * sn.x, b1 * cs.y + a1 * sn.y),
-                                                   Half<T>::pack2(b2 * cs.z + a2 * sn.z, b3 * cs.w + a3 * sn.w));
-    }
+    float a[4], b[4];
+    load_2x4(lo, hi, a, b);
+    rotate_half_2x4(a, b, sin_t, cos_t, pos[tkn], max_pos, half, i);
+    store_2x4(lo, hi, a, b);
 }
 
 // ---- per-head RMSNorm of q and k fused with the half-split rotary (HF:qwen3/modeling_qwen3.py Qwen3Attention: q_norm / k_norm over
@@ -539,14 +428,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_half_kernel(T* __restrict__ b
         // heads [0, H): q at column h * DH; heads [H, H + H_kv): k at column k_off + (h - H) * DH
         lo = buf + (long)tkn * ld + (h < H ? (long)h * DH : k_off + (long)(h - H) * DH) + i;
         hi = lo + half;
-        if constexpr (sizeof(T) == 4) {
-            const float4 va = *reinterpret_cast<const float4*>(lo), vb = *reinterpret_cast<const float4*>(hi);
-            a[0] = va.x; a[1] = va.y; a[2] = va.z; a[3] = va.w; b[0] = vb.x; b[1] = vb.y; b[2] = vb.z; b[3] = vb.w;
-        } else {
-            const uint2 ua = *reinterpret_cast<const uint2*>(lo), ub = *reinterpret_cast<const uint2*>(hi);
-            a[0] = Half<T>::lo(ua.x); a[1] = Half<T>::hi(ua.x); a[2] = Half<T>::lo(ua.y); a[3] = Half<T>::hi(ua.y);
-            b[0] = Half<T>::lo(ub.x); b[1] = Half<T>::hi(ub.x); b[2] = Half<T>::lo(ub.y); b[3] = Half<T>::hi(ub.y);
-        }
+        load_2x4(lo, hi, a, b);
     }
     float ss = (a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3]) + ((b[0] * b[0] + b[1] * b[1]) + (b[2] * b[2] + b[3] * b[3]));
 #pragma unroll
@@ -556,27 +438,12 @@ __global__ __launch_bounds__(256) void qknorm_rope_half_kernel(T* __restrict__ b
         const float rstd = 1.0f / sqrtf(ss / (float)DH + eps);
         const float* g = h < H ? q_g : k_g;
         const float4 ga = *reinterpret_cast<const float4*>(g + i), gb = *reinterpret_cast<const float4*>(g + half + i);
-        // the position is clamped into the tables, as rope_kernel does
-        int ps = pos[tkn]; ps = ps < 0 ? 0 : (ps >= max_pos ? max_pos - 1 : ps);
-        const float4 sn4 = *reinterpret_cast<const float4*>(sin_t + (long)ps * half + i);
-        const float4 cs4 = *reinterpret_cast<const float4*>(cos_t + (long)ps * half + i);
         const float gav[4] = {ga.x, ga.y, ga.z, ga.w}, gbv[4] = {gb.x, gb.y, gb.z, gb.w};
-        const float sn[4] = {sn4.x, sn4.y, sn4.z, sn4.w}, cs[4] = {cs4.x, cs4.y, cs4.z, cs4.w};
-        float ra[4], rb[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float na = a[u] * rstd * gav[u], nb = b[u] * rstd * gbv[u];
-            ra[u] = na * cs[u] - nb * sn[u];
-            rb[u] = nb * cs[u] + na * sn[u];
-        }
-        if constexpr (sizeof(T) == 4) {
-            *reinterpret_cast<float4*>(lo) = make_float4(ra[0], ra[1], ra[2], ra[3]);
-            *reinterpret_cast<float4*>(hi) = make_float4(rb[0], rb[1], rb[2], rb[3]);
-        } else {
-            range.note(ra[0], ra[1]); range.note(ra[2], ra[3]); range.note(rb[0], rb[1]); range.note(rb[2], rb[3]);
-            *reinterpret_cast<uint2*>(lo) = make_uint2(Half<T>::pack2(ra[0], ra[1]), Half<T>::pack2(ra[2], ra[3]));
-            *reinterpret_cast<uint2*>(hi) = make_uint2(Half<T>::pack2(rb[0], rb[1]), Half<T>::pack2(rb[2], rb[3]));
-        }
+        for (int u = 0; u < 4; ++u) { a[u] = a[u] * rstd * gav[u]; b[u] = b[u] * rstd * gbv[u]; }
+        rotate_half_2x4(a, b, sin_t, cos_t, pos[tkn], max_pos, half, i);
+        if constexpr (sizeof(T) != 4) { range.note(a[0], a[1]); range.note(a[2], a[3]); range.note(b[0], b[1]); range.note(b[2], b[3]); }
+        store_2x4(lo, hi, a, b);
     }
     if constexpr (sizeof(T) != 4) range.finish(range_flag);
 }
@@ -624,17 +491,7 @@ __global__ __launch_bounds__(256) void fp8_quant_rows_kernel(const float* __rest
     const float* wr = w + row * cols;
     float amax = 0.f;
     for (long c = lane; c < cols; c += 64) amax = fmaxf(amax, fabsf(wr[c]));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-    float sc = 1.0f;
-    if (amax > 0.f && amax < 3.0e38f) {
-        const uint32_t u = __float_as_uint(amax);
-        const int e = (int)((u >> 23) & 0xffu) - 127;                 // amax = m * 2^e, 1 <= m < 2 (subnormal amax: e = -127)
-        const uint32_t frac = u & 0x7fffffu;
-        int k = e - (frac > 0x600000u ? 7 : 8);                       // m <= 1.75 -> 2^(e-8), else 2^(e-7)
-        k = k < -126 ? -126 : (k > 127 ? 127 : k);
-        sc = __uint_as_float((uint32_t)(k + 127) << 23);
-    }
+    const float sc = fp8_pow2_scale(wave_max(amax));
     if (lane == 0) scale[row] = sc;
     const float inv = 1.0f / sc;                                      // exact: power of two
     for (long c = lane; c < cols; c += 64) q[row * cols + c] = (uint8_t)e4m3fn_encode(wr[c] * inv);
@@ -754,9 +611,7 @@ __global__ __launch_bounds__(256) void logprob_rows_kernel(const float* __restri
     __syncthreads();
     if (t == 0) {
         const float tot = (s_f[0] + s_f[1]) + (s_f[2] + s_f[3]);
-        // the target is clamped into the row, as embed_kernel does its ids: a bad target scores a wrong token, never out of bounds
-        int tg = targets[r]; tg = tg < 0 ? 0 : (tg >= V ? V - 1 : tg);
-        out_lp[r] = (x[tg] - mx) - logf(tot);
+        out_lp[r] = (x[clamp_index(targets[r], V)] - mx) - logf(tot);   // a bad target scores a wrong token
         if (out_arg) out_arg[r] = am;
     }
 }
@@ -841,154 +696,144 @@ __global__ __launch_bounds__(256) void split16_rows_kernel(const float* __restri
 }
 
 inline int cap_grid(long blocks) { return (int)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks)); }
+inline dim3 row_grid(long rows) { return dim3((unsigned)((rows + 3) / 4)); }   // one wave per row, four rows per workgroup
+
+// f(std::integral_constant<int, NV>) with the rung NV >= ceil(d / 256) the one-wave-per-row kernels are instantiated for: NV float4
+// column blocks per lane (d <= 4096)
+template <typename F>
+inline void for_row_width(int d, F&& f) {
+    const int nv = (d + 255) / 256;
+    if (nv <= 1) f(std::integral_constant<int, 1>{});
+    else if (nv <= 2) f(std::integral_constant<int, 2>{});
+    else if (nv <= 3) f(std::integral_constant<int, 3>{});
+    else if (nv <= 4) f(std::integral_constant<int, 4>{});
+    else if (nv <= 8) f(std::integral_constant<int, 8>{});
+    else if (nv <= 10) f(std::integral_constant<int, 10>{});
+    else f(std::integral_constant<int, 16>{});
+}
+// f(E{}) with E the element type of a dtype code: bf16, f16, anything else float -- or, 16-bit alone, f16, anything else bf16
+template <typename F>
+inline void for_dtype(int dtype, F&& f) {
+    if (dtype == DT_BF16) f(bf16_t{});
+    else if (dtype == DT_F16) f(f16_t{});
+    else f(float{});
+}
+template <typename F>
+inline void for_dtype16(int dtype, F&& f) {
+    if (dtype == DT_F16) f(f16_t{});
+    else f(bf16_t{});
+}
 
 }  // namespace
 
 void launch_embed(const int* ids, const int* pos, const float* wte, const float* wpe, float* x, int T, int d, int vocab,
                   int max_pos, hipStream_t s) {
-    hipLaunchKernelGGL(embed_kernel, dim3((T + 3) / 4), dim3(256), 0, s, ids, pos, wte, wpe, x, T, d, vocab, max_pos);
+    hipLaunchKernelGGL(embed_kernel, row_grid(T), dim3(256), 0, s, ids, pos, wte, wpe, x, T, d, vocab, max_pos);
 }
 
 void launch_layernorm(const float* x, const float* g, const float* b, void* out, int out_dtype, int T, int d,
                       float eps, hipStream_t s, float out_mul) {
-#define LN_CASE(NV)                                                                                              \
-    if (out_dtype == DT_BF16)                                                                                    \
-        hipLaunchKernelGGL((layernorm_kernel<bf16_t, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, b,          \
-                           (bf16_t*)out, T, d, eps, 1.0f);                                                       \
-    else if (out_dtype == DT_F16)                                                                                \
-        hipLaunchKernelGGL((layernorm_kernel<f16_t, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, b,           \
-                           (f16_t*)out, T, d, eps, out_mul);                                                     \
-    else                                                                                                         \
-        hipLaunchKernelGGL((layernorm_kernel<float, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, b,           \
-                           (float*)out, T, d, eps, 1.0f);
-    const int nv = (d + 255) / 256;
-    if (nv <= 1) { LN_CASE(1) } else if (nv <= 2) { LN_CASE(2) } else if (nv <= 3) { LN_CASE(3) }
-    else if (nv <= 4) { LN_CASE(4) } else if (nv <= 8) { LN_CASE(8) } else if (nv <= 10) { LN_CASE(10) }
-    else { LN_CASE(16) }
-#undef LN_CASE
+    const float mul = out_dtype == DT_F16 ? out_mul : 1.0f;
+    for_row_width(d, [&](auto nv) {
+        for_dtype(out_dtype, [&](auto e) {
+            using E = decltype(e);
+            hipLaunchKernelGGL((layernorm_kernel<E, decltype(nv)::value>), row_grid(T), dim3(256), 0, s, x, g, b, (E*)out, T, d, eps, mul);
+        });
+    });
 }
 
 void launch_layernorm_writeback(float* x, const float* g, const float* b, void* out16, int out_dtype, int T, int d, float eps,
                                 int* range_flag, hipStream_t s) {
-#define LW_CASE(NV)                                                                                                  \
-    if (out_dtype == DT_F16)                                                                                         \
-        hipLaunchKernelGGL((layernorm_writeback_kernel<f16_t, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, b,     \
-                           (f16_t*)out16, T, d, eps, range_flag);                                                    \
-    else                                                                                                             \
-        hipLaunchKernelGGL((layernorm_writeback_kernel<bf16_t, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, b,    \
-                           (bf16_t*)out16, T, d, eps, range_flag);
-    const int nv = (d + 255) / 256;
-    if (nv <= 1) { LW_CASE(1) } else if (nv <= 2) { LW_CASE(2) } else if (nv <= 3) { LW_CASE(3) }
-    else if (nv <= 4) { LW_CASE(4) } else if (nv <= 8) { LW_CASE(8) } else if (nv <= 10) { LW_CASE(10) }
-    else { LW_CASE(16) }
-#undef LW_CASE
+    for_row_width(d, [&](auto nv) {
+        for_dtype16(out_dtype, [&](auto e) {
+            using E = decltype(e);
+            hipLaunchKernelGGL((layernorm_writeback_kernel<E, decltype(nv)::value>), row_grid(T), dim3(256), 0, s, x, g, b, (E*)out16, T, d,
+                               eps, range_flag);
+        });
+    });
 }
 
 void launch_rmsnorm(const float* x, const float* g, void* out, int out_dtype, int T, int d, float eps, int* range_flag, hipStream_t s) {
-#define RN_CASE(NV)                                                                                                              \
-    if (out_dtype == DT_BF16)                                                                                                    \
-        hipLaunchKernelGGL((rmsnorm_kernel<bf16_t, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, (bf16_t*)out, T, d, eps, range_flag); \
-    else if (out_dtype == DT_F16)                                                                                                \
-        hipLaunchKernelGGL((rmsnorm_kernel<f16_t, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, (f16_t*)out, T, d, eps, range_flag);   \
-    else                                                                                                                         \
-        hipLaunchKernelGGL((rmsnorm_kernel<float, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, (float*)out, T, d, eps, range_flag);
-    const int nv = (d + 255) / 256;
-    if (nv <= 1) { RN_CASE(1) } else if (nv <= 2) { RN_CASE(2) } else if (nv <= 3) { RN_CASE(3) }
-    else if (nv <= 4) { RN_CASE(4) } else if (nv <= 8) { RN_CASE(8) } else if (nv <= 10) { RN_CASE(10) }
-    else { RN_CASE(16) }
-#undef RN_CASE
+    for_row_width(d, [&](auto nv) {
+        for_dtype(out_dtype, [&](auto e) {
+            using E = decltype(e);
+            hipLaunchKernelGGL((rmsnorm_kernel<E, decltype(nv)::value>), row_grid(T), dim3(256), 0, s, x, g, (E*)out, T, d, eps, range_flag);
+        });
+    });
 }
 
 void launch_swiglu(const void* gu, void* h, int dtype, int T, int ffn, int* range_flag, hipStream_t s) {
     const long n_vec = (long)T * ffn / (dtype == DT_F32 ? 4 : 8);
     const unsigned grid = (unsigned)((n_vec + 255) / 256);
-    if (dtype == DT_BF16) hipLaunchKernelGGL(swiglu_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)gu, (bf16_t*)h, n_vec, ffn, range_flag);
-    else if (dtype == DT_F16) hipLaunchKernelGGL(swiglu_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (const f16_t*)gu, (f16_t*)h, n_vec, ffn, range_flag);
-    else hipLaunchKernelGGL(swiglu_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)gu, (float*)h, n_vec, ffn, range_flag);
+    for_dtype(dtype, [&](auto e) {
+        using E = decltype(e);
+        hipLaunchKernelGGL(swiglu_kernel<E>, dim3(grid), dim3(256), 0, s, (const E*)gu, (E*)h, n_vec, ffn, range_flag);
+    });
 }
 
 void launch_layernorm_split(const float* x, const float* g, const float* b, void* out, int out_dtype, int T, int d,
                             float eps, hipStream_t s, float out_mul) {
-#define LS_CASE(NV)                                                                                              \
-    if (out_dtype == DT_F16)                                                                                     \
-        hipLaunchKernelGGL((layernorm_split_kernel<f16_t, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, b,     \
-                           (uint16_t*)out, T, d, eps, out_mul);                                                  \
-    else                                                                                                         \
-        hipLaunchKernelGGL((layernorm_split_kernel<bf16_t, NV>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, b,    \
-                           (uint16_t*)out, T, d, eps, 1.0f);
-    const int nv = (d + 255) / 256;
-    if (nv <= 1) { LS_CASE(1) } else if (nv <= 2) { LS_CASE(2) } else if (nv <= 3) { LS_CASE(3) }
-    else if (nv <= 4) { LS_CASE(4) } else if (nv <= 8) { LS_CASE(8) } else if (nv <= 10) { LS_CASE(10) }
-    else { LS_CASE(16) }
-#undef LS_CASE
+    const float mul = out_dtype == DT_F16 ? out_mul : 1.0f;
+    for_row_width(d, [&](auto nv) {
+        for_dtype16(out_dtype, [&](auto e) {
+            hipLaunchKernelGGL((layernorm_split_kernel<decltype(e), decltype(nv)::value>), row_grid(T), dim3(256), 0, s, x, g, b,
+                               (uint16_t*)out, T, d, eps, mul);
+        });
+    });
 }
 
 void launch_crest16(const void* in, int T, int cols, long ld, int dtype, unsigned* out_bits, hipStream_t s) {
-    if (dtype == DT_F16) hipLaunchKernelGGL(crest16_kernel<f16_t>, dim3((T + 3) / 4), dim3(256), 0, s, (const uint16_t*)in, T, cols, ld, out_bits);
-    else hipLaunchKernelGGL(crest16_kernel<bf16_t>, dim3((T + 3) / 4), dim3(256), 0, s, (const uint16_t*)in, T, cols, ld, out_bits);
+    for_dtype16(dtype, [&](auto e) {
+        hipLaunchKernelGGL(crest16_kernel<decltype(e)>, row_grid(T), dim3(256), 0, s, (const uint16_t*)in, T, cols, ld, out_bits);
+    });
 }
 
 void launch_split16_rows(const float* in, long n, int d, int layout, void* out, int out_dtype, hipStream_t s) {
     const int grid = cap_grid((n * (d / 4) + 255) / 256);
-    if (out_dtype == DT_F16) hipLaunchKernelGGL(split16_rows_kernel<f16_t>, dim3(grid), dim3(256), 0, s, in, n, d, layout, (uint16_t*)out);
-    else hipLaunchKernelGGL(split16_rows_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, in, n, d, layout, (uint16_t*)out);
+    for_dtype16(out_dtype, [&](auto e) {
+        hipLaunchKernelGGL(split16_rows_kernel<decltype(e)>, dim3(grid), dim3(256), 0, s, in, n, d, layout, (uint16_t*)out);
+    });
 }
 
 void launch_pack_split_rows(const float* src, long rows, long cols, void* dst, int out_dtype, hipStream_t s) {
     const int grid = cap_grid((rows * cols + 255) / 256);
-    if (out_dtype == DT_F16) hipLaunchKernelGGL(pack_split_rows_kernel<f16_t>, dim3(grid), dim3(256), 0, s, src, rows, cols, (uint16_t*)dst);
-    else hipLaunchKernelGGL(pack_split_rows_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, src, rows, cols, (uint16_t*)dst);
+    for_dtype16(out_dtype, [&](auto e) {
+        hipLaunchKernelGGL(pack_split_rows_kernel<decltype(e)>, dim3(grid), dim3(256), 0, s, src, rows, cols, (uint16_t*)dst);
+    });
 }
 
-void launch_layernorm_q8(const float* x, const float* g, const float* b, void* q, float* scale, void* out16, int out16_dtype,
-                         int T, int d, float eps, hipStream_t s) {
-#define LQ_CASE(NV)                                                                                                  \
-    if (out16_dtype == DT_F16)                                                                                       \
-        hipLaunchKernelGGL((layernorm_q8_kernel<NV, f16_t>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, b, (uint8_t*)q, scale, \
-                           (uint16_t*)out16, T, d, eps);                                                             \
-    else                                                                                                             \
-        hipLaunchKernelGGL((layernorm_q8_kernel<NV, bf16_t>), dim3((T + 3) / 4), dim3(256), 0, s, x, g, b, (uint8_t*)q, scale, \
-                           (uint16_t*)out16, T, d, eps);
-    const int nv = (d + 255) / 256;
-    if (nv <= 1) { LQ_CASE(1) } else if (nv <= 2) { LQ_CASE(2) } else if (nv <= 3) { LQ_CASE(3) }
-    else if (nv <= 4) { LQ_CASE(4) } else if (nv <= 8) { LQ_CASE(8) } else if (nv <= 10) { LQ_CASE(10) }
-    else { LQ_CASE(16) }
-#undef LQ_CASE
+void launch_layernorm_q8(const float* x, const float* g, const float* b, void* q, float* scale, int T, int d, float eps, hipStream_t s) {
+    for_row_width(d, [&](auto nv) {
+        hipLaunchKernelGGL(layernorm_q8_kernel<decltype(nv)::value>, row_grid(T), dim3(256), 0, s, x, g, b, (uint8_t*)q, scale, T, d, eps);
+    });
 }
 
 void launch_absmax16(const void* in, long numel, int dtype, unsigned* out_bits, hipStream_t s) {
     const int grid = cap_grid((numel / 2 + 255) / 256);
-    if (dtype == DT_F16) hipLaunchKernelGGL(absmax16_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (const uint32_t*)in, numel / 2, out_bits);
-    else hipLaunchKernelGGL(absmax16_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const uint32_t*)in, numel / 2, out_bits);
+    for_dtype16(dtype, [&](auto e) {
+        hipLaunchKernelGGL(absmax16_kernel<decltype(e)>, dim3(grid), dim3(256), 0, s, (const uint32_t*)in, numel / 2, out_bits);
+    });
 }
 
 void launch_lnf_pool(const float* x, const float* g, const float* b, const int* seq_off, const int* seq_len,
                      const int* pad_left, int B, int d, float eps, int apply_ln, int mode, int normalize,
                      const float* pos_weights, int pos_weights_n, float* out, hipStream_t s, int* nonfinite_flag, int norm_kind) {
     const size_t sm = (size_t)(4 * d + 8) * sizeof(float);
-#define LP_CASE(NV)                                                                                              \
-    if (norm_kind == 1)                                                                                          \
-        hipLaunchKernelGGL((lnf_pool_kernel<NV, true>), dim3(B), dim3(256), sm, s, x, g, b, seq_off, seq_len, pad_left, d, \
-                           eps, apply_ln, mode, normalize, pos_weights, pos_weights_n, out, nonfinite_flag);     \
-    else                                                                                                         \
-    hipLaunchKernelGGL((lnf_pool_kernel<NV>), dim3(B), dim3(256), sm, s, x, g, b, seq_off, seq_len, pad_left, d, \
-                       eps, apply_ln, mode, normalize, pos_weights, pos_weights_n, out, nonfinite_flag);
-    const int nv = (d + 255) / 256;
-    if (nv <= 1) { LP_CASE(1) } else if (nv <= 2) { LP_CASE(2) } else if (nv <= 3) { LP_CASE(3) }
-    else if (nv <= 4) { LP_CASE(4) } else if (nv <= 8) { LP_CASE(8) } else if (nv <= 10) { LP_CASE(10) }
-    else { LP_CASE(16) }
-#undef LP_CASE
+    for_row_width(d, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        const auto kernel = norm_kind == 1 ? lnf_pool_kernel<NV, RowRMSNorm<true>> : lnf_pool_kernel<NV, RowLayerNorm<true>>;
+        hipLaunchKernelGGL(kernel, dim3(B), dim3(256), sm, s, x, g, b, seq_off, seq_len, pad_left, d, eps, apply_ln, mode, normalize,
+                           pos_weights, pos_weights_n, out, nonfinite_flag);
+    });
 }
 
 void launch_pool(const void* hidden, int dtype, const int* mask, int B, int S, int d, int mode,
                  const float* pos_weights, float* out, hipStream_t s) {
     dim3 grid(B, (d / 4 + 255) / 256);
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL(pool_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)hidden, mask, S, d, mode, pos_weights, out);
-    else if (dtype == DT_F16)
-        hipLaunchKernelGGL(pool_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)hidden, mask, S, d, mode, pos_weights, out);
-    else
-        hipLaunchKernelGGL(pool_kernel<float>, grid, dim3(256), 0, s, (const float*)hidden, mask, S, d, mode, pos_weights, out);
+    for_dtype(dtype, [&](auto e) {
+        using E = decltype(e);
+        hipLaunchKernelGGL(pool_kernel<E>, grid, dim3(256), 0, s, (const E*)hidden, mask, S, d, mode, pos_weights, out);
+    });
 }
 
 void launch_pack_sign_bits(const float* x, long n, int d, const float* center, uint8_t* bits, long ldb, hipStream_t s) {
@@ -998,26 +843,21 @@ void launch_pack_sign_bits(const float* x, long n, int d, const float* center, u
 }
 
 void launch_fp8_quant_rows(const float* w, long rows, long cols, void* q, float* scale, hipStream_t s) {
-    hipLaunchKernelGGL(fp8_quant_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, w, rows, cols,
-                       (uint8_t*)q, scale);
+    hipLaunchKernelGGL(fp8_quant_rows_kernel, row_grid(rows), dim3(256), 0, s, w, rows, cols, (uint8_t*)q, scale);
 }
 
+// f16: exact as long as code * scale stays an f16 value (a quantised corpus of unit rows does)
 void launch_fp8_dequant_rows(const void* q, const float* scale, long rows, long cols, void* out, int out_dtype,
                              hipStream_t s) {
     const int grid = cap_grid((rows * cols / 4 + 255) / 256);
-    if (out_dtype == 1)
-        hipLaunchKernelGGL(fp8_dequant_rows_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const uint8_t*)q, scale, rows,
-                           cols, (bf16_t*)out);
-    else if (out_dtype == DT_F16)      // exact as long as code * scale stays an f16 value (a quantised corpus of unit rows does)
-        hipLaunchKernelGGL(fp8_dequant_rows_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (const uint8_t*)q, scale, rows,
-                           cols, (f16_t*)out);
-    else
-        hipLaunchKernelGGL(fp8_dequant_rows_kernel<float>, dim3(grid), dim3(256), 0, s, (const uint8_t*)q, scale, rows,
-                           cols, (float*)out);
+    for_dtype(out_dtype, [&](auto e) {
+        using E = decltype(e);
+        hipLaunchKernelGGL(fp8_dequant_rows_kernel<E>, dim3(grid), dim3(256), 0, s, (const uint8_t*)q, scale, rows, cols, (E*)out);
+    });
 }
 
 void launch_gather_rows(const float* src, const int* row_idx, int n, int d, float* dst, hipStream_t s) {
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, s, src, row_idx, n, d, dst);
+    hipLaunchKernelGGL(gather_rows_kernel, row_grid(n), dim3(256), 0, s, src, row_idx, n, d, dst);
 }
 
 void launch_logprob_rows(const float* logits, long ld, int V, const int* targets, int n, float* out_lp, int* out_arg,
@@ -1030,24 +870,22 @@ void launch_mean_over_axis0(const float* in, int n0, long n, float* out, hipStre
 }
 
 void launch_pairwise(const float* a, const float* b, long n, int d, bool cosine, float* out, hipStream_t s) {
-    const unsigned grid = (unsigned)((n + 3) / 4);
-    if (cosine) hipLaunchKernelGGL(pairwise_kernel<true>, dim3(grid), dim3(256), 0, s, a, b, n, d, out);
-    else hipLaunchKernelGGL(pairwise_kernel<false>, dim3(grid), dim3(256), 0, s, a, b, n, d, out);
+    hipLaunchKernelGGL(cosine ? pairwise_kernel<true> : pairwise_kernel<false>, row_grid(n), dim3(256), 0, s, a, b, n, d, out);
 }
 
 void launch_l2norm(const float* in, long n, int d, void* out, int out_dtype, hipStream_t s) {
-    const int grid = (int)((n + 3) / 4);
-    if (out_dtype == DT_BF16) hipLaunchKernelGGL(l2norm_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, in, n, d, (bf16_t*)out);
-    else if (out_dtype == DT_F16) hipLaunchKernelGGL(l2norm_kernel<f16_t>, dim3(grid), dim3(256), 0, s, in, n, d, (f16_t*)out);
-    else hipLaunchKernelGGL(l2norm_kernel<float>, dim3(grid), dim3(256), 0, s, in, n, d, (float*)out);
+    for_dtype(out_dtype, [&](auto e) {
+        using E = decltype(e);
+        hipLaunchKernelGGL(l2norm_kernel<E>, row_grid(n), dim3(256), 0, s, in, n, d, (E*)out);
+    });
 }
 
 void launch_f32_to_16(const float* in, long numel, void* out, int out_dtype, hipStream_t s) {
     const int grid = cap_grid((numel + 255) / 256);
-    if (out_dtype == DT_F16) hipLaunchKernelGGL(cvt16_kernel<f16_t>, dim3(grid), dim3(256), 0, s, in, numel, (uint16_t*)out);
-    else hipLaunchKernelGGL(cvt16_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, in, numel, (uint16_t*)out);
+    for_dtype16(out_dtype, [&](auto e) {
+        hipLaunchKernelGGL(cvt16_kernel<decltype(e)>, dim3(grid), dim3(256), 0, s, in, numel, (uint16_t*)out);
+    });
 }
-void launch_f32_to_bf16(const float* in, long numel, void* out, hipStream_t s) { launch_f32_to_16(in, numel, out, DT_BF16, s); }
 
 void launch_absmax(const float* in, long numel, unsigned* out_bits, hipStream_t s) {
     hipLaunchKernelGGL(absmax_kernel, dim3(cap_grid((numel + 255) / 256)), dim3(256), 0, s, in, numel, out_bits);
@@ -1058,12 +896,10 @@ void launch_fill_f32(float* p, long n, float v, hipStream_t s) {
 }
 
 void launch_fill_rand(void* p, long n, int dtype, unsigned seed, float scale, hipStream_t s) {
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL(fill_rand_kernel<bf16_t>, dim3(cap_grid((n + 255) / 256)), dim3(256), 0, s, (bf16_t*)p, n, seed, scale);
-    else if (dtype == DT_F16)
-        hipLaunchKernelGGL(fill_rand_kernel<f16_t>, dim3(cap_grid((n + 255) / 256)), dim3(256), 0, s, (f16_t*)p, n, seed, scale);
-    else
-        hipLaunchKernelGGL(fill_rand_kernel<float>, dim3(cap_grid((n + 255) / 256)), dim3(256), 0, s, (float*)p, n, seed, scale);
+    for_dtype(dtype, [&](auto e) {
+        using E = decltype(e);
+        hipLaunchKernelGGL(fill_rand_kernel<E>, dim3(cap_grid((n + 255) / 256)), dim3(256), 0, s, (E*)p, n, seed, scale);
+    });
 }
 
 void launch_rope(void* qk, int dtype, long ld, long k_off, const int* pos, const float* sin_t, const float* cos_t, int T,
@@ -1071,24 +907,20 @@ void launch_rope(void* qk, int dtype, long ld, long k_off, const int* pos, const
     const int half = rotary_dim / 2;
     const long n = (long)T * H * half;
     const int grid = (int)((n + 255) / 256);
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL(rope_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (bf16_t*)qk, ld, k_off, pos, sin_t, cos_t, T, H, dh, half, max_pos);
-    else if (dtype == DT_F16)
-        hipLaunchKernelGGL(rope_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (f16_t*)qk, ld, k_off, pos, sin_t, cos_t, T, H, dh, half, max_pos);
-    else
-        hipLaunchKernelGGL(rope_kernel<float>, dim3(grid), dim3(256), 0, s, (float*)qk, ld, k_off, pos, sin_t, cos_t, T, H, dh, half, max_pos);
+    for_dtype(dtype, [&](auto e) {
+        using E = decltype(e);
+        hipLaunchKernelGGL(rope_kernel<E>, dim3(grid), dim3(256), 0, s, (E*)qk, ld, k_off, pos, sin_t, cos_t, T, H, dh, half, max_pos);
+    });
 }
 
 void launch_rope_half(void* qk, int dtype, long ld, long k_off, const int* pos, const float* sin_t, const float* cos_t, int T,
                       int H, int H_kv, int dh, int max_pos, hipStream_t s) {
     const long n = (long)T * (H + H_kv) * (dh / 8);
     const int grid = (int)((n + 255) / 256);
-    if (dtype == DT_BF16)
-        hipLaunchKernelGGL(rope_half_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (bf16_t*)qk, ld, k_off, pos, sin_t, cos_t, T, H, H_kv, dh, max_pos);
-    else if (dtype == DT_F16)
-        hipLaunchKernelGGL(rope_half_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (f16_t*)qk, ld, k_off, pos, sin_t, cos_t, T, H, H_kv, dh, max_pos);
-    else
-        hipLaunchKernelGGL(rope_half_kernel<float>, dim3(grid), dim3(256), 0, s, (float*)qk, ld, k_off, pos, sin_t, cos_t, T, H, H_kv, dh, max_pos);
+    for_dtype(dtype, [&](auto e) {
+        using E = decltype(e);
+        hipLaunchKernelGGL(rope_half_kernel<E>, dim3(grid), dim3(256), 0, s, (E*)qk, ld, k_off, pos, sin_t, cos_t, T, H, H_kv, dh, max_pos);
+    });
 }
 
 void launch_qknorm_rope_half(void* qk, int dtype, long ld, long k_off, const int* pos, const float* sin_t, const float* cos_t,
@@ -1096,14 +928,12 @@ void launch_qknorm_rope_half(void* qk, int dtype, long ld, long k_off, const int
                              hipStream_t s) {
     const long n = (long)T * (H + H_kv) * (dh / 8);
     const int grid = (int)((n + 255) / 256);
-#define SGPT_QKNORM(TT, DH)                                                                                                          \
-    hipLaunchKernelGGL((qknorm_rope_half_kernel<TT, DH>), dim3(grid), dim3(256), 0, s, (TT*)qk, ld, k_off, pos, sin_t, cos_t, q_g, k_g, \
-                       eps, T, H, H_kv, max_pos, range_flag)
     if (dh != 64 && dh != 128) return;                  // (the callers refuse it: sgpt_qknorm_rope_half, check_desc)
-    if (dtype == DT_BF16) { if (dh == 64) SGPT_QKNORM(bf16_t, 64); else SGPT_QKNORM(bf16_t, 128); }
-    else if (dtype == DT_F16) { if (dh == 64) SGPT_QKNORM(f16_t, 64); else SGPT_QKNORM(f16_t, 128); }
-    else { if (dh == 64) SGPT_QKNORM(float, 64); else SGPT_QKNORM(float, 128); }
-#undef SGPT_QKNORM
+    for_dtype(dtype, [&](auto e) {
+        using E = decltype(e);
+        hipLaunchKernelGGL((dh == 64 ? qknorm_rope_half_kernel<E, 64> : qknorm_rope_half_kernel<E, 128>), dim3(grid), dim3(256), 0, s,
+                           (E*)qk, ld, k_off, pos, sin_t, cos_t, q_g, k_g, eps, T, H, H_kv, max_pos, range_flag);
+    });
 }
 
 void launch_qkv_deinterleave(const float* src, float* dst, int H, int dh, long row_len, hipStream_t s) {

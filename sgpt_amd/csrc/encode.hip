@@ -187,7 +187,7 @@ sgpt_status block_fp8(const Fwd& f, const LayerW& l, int li) {
     const float s_h = f.m->act_scale[li], s_c = f.m->act_scale[d.n_layers + li];     // scales of the GELU output's / the context's codes
     auto launch = [&](int epi, int out_dtype, const GemmArgs& q) { Prof pr(f.c, f.s, 2.0 * T * (double)q.N * q.K); launch_gemm_fp8(epi, out_dtype, q, f.s); };
     // attention projections: a8 = e4m3(LN1(x) / sa[row]) feeds Q, K (row-major 16-bit) and V^T
-    launch_layernorm_q8(f.x, l.ln1_g, l.ln1_b, f.a8, f.sa, nullptr, f.dt, T, dm, d.ln_eps, f.s);
+    launch_layernorm_q8(f.x, l.ln1_g, l.ln1_b, f.a8, f.sa, T, dm, d.ln_eps, f.s);
     GemmArgs qk = proj(f, f.a8, dm, l.w_qkv, 2 * dm, dm, f.qkv, 2 * dm, l.b_qkv);
     qk.a_scale = f.sa; qk.a_scalar = 1.0f; qk.w_scale = l.s_qkv;
     launch(EPI_STORE, f.dt, qk);
@@ -203,7 +203,7 @@ sgpt_status block_fp8(const Fwd& f, const LayerW& l, int li) {
     launch(EPI_BIAS_RESID, 0, o);
     // a8 = e4m3(LN(x) / sa[row]);  h8 = e4m3(gelu(a8 . W1_8^T * sa * s1 + b1) / s_h);  x += h8 . W2_8^T * s_h * s2 + b2
     // (GPT-J, parallel block: a8 still holds LN1(x_old))
-    if (!gptj) launch_layernorm_q8(f.x, l.ln2_g, l.ln2_b, f.a8, f.sa, nullptr, f.dt, T, dm, d.ln_eps, f.s);
+    if (!gptj) launch_layernorm_q8(f.x, l.ln2_g, l.ln2_b, f.a8, f.sa, T, dm, d.ln_eps, f.s);
     GemmArgs fc = proj(f, f.a8, dm, l.w_fc, ffn, dm, f.h, ffn, l.b_fc);
     fc.a_scale = f.sa; fc.a_scalar = 1.0f; fc.w_scale = l.s_fc; fc.out_scale = s_h;
     launch(EPI_BIAS_GELU, 0, fc);

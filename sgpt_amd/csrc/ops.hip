@@ -72,7 +72,7 @@ sgpt_status sgpt_layernorm_fp8(sgpt_ctx* c, const float* x, const float* gamma, 
     if (!c || !x || !gamma || !beta || !codes || !row_scale || T <= 0 || d <= 0 || d % 4 || d > 4096)
         return fail(c, SGPT_ERR_INVALID, "sgpt_layernorm_fp8: bad arguments (d % 4 == 0, d <= 4096)");
     HIPC(c, hipSetDevice(c->device));
-    launch_layernorm_q8(x, gamma, beta, codes, row_scale, nullptr, SGPT_BF16, T, d, eps, (hipStream_t)stream);
+    launch_layernorm_q8(x, gamma, beta, codes, row_scale, T, d, eps, (hipStream_t)stream);
     HIPC(c, hipGetLastError());
     return SGPT_OK;
 }

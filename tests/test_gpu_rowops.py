@@ -124,6 +124,71 @@ def test_layernorm_prologue_of_the_query_projection_gives_the_standalone_bits(ct
     assert float(h.float().abs().max()) > 0.1 and torch.equal(h.view(torch.int16), h2.view(torch.int16))
 
 
+DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 3}          # element-type codes of include/sgpt_hip.h
+
+
+def bits16(t):
+    return t.contiguous().view(torch.int16)
+
+
+@pytest.mark.parametrize("d", R.LN_WIDTHS)
+def test_writeback_rmsnorm_and_fp8_stores_every_width(ctx, d):
+    """The three store loops the tests above do not reach, at every NV rung with its masked tail, T = 5: one full workgroup of
+    four rows and one row of the next, whose other three waves leave at the row guard.  Every output has T + 3 rows of sentinel.
+    Write-back: x becomes the bits of the fp32 LayerNorm and the 16-bit copy is x rounded once.  RMSNorm: the bars of
+    tests/test_gpu_llama.py::test_rmsnorm_vs_float64 -- fp32 within 4 B of float64 (rms_setup's unit), in place = out of place,
+    16 bit = the fp32 output rounded once, range word 0.  Quantising LayerNorm against y = the fp32 LayerNorm of the same inputs
+    (csrc/rowln.h: the same loads, reductions and arithmetic, so the bits the fp8 kernel holds): the scale is the power of two with
+    224 < max|y| / scale <= 448 (csrc/rowln.h::fp8_pow2_scale: m 2^e -> 256 m for m <= 1.75, else 128 m), and every code is one
+    round-to-nearest of the exactly scaled y / scale to e4m3 -- |decode(code) scale - y| <= scale / 2 * max(2^(floor(log2 |y / scale|) - 3),
+    2^-9), half a spacing of the format at that value (2^-9 below its normal range); nothing saturates since |y / scale| <= 448."""
+    from test_gpu_llama import rms_setup
+    T = 5
+    x, g, b, _, _ = ln_setup(T, d, "plain")
+    y = ctx.layernorm(x, g, b, EPS)
+    p = lambda t: t.data_ptr()                                                                  # noqa: E731
+    for fmt in ("f16", "bf16"):
+        xin = torch.full((T + 3, d), SENTINEL, dtype=torch.float32, device="cuda:0")
+        xin[:T] = x
+        o16 = torch.full((T + 3, d), SENTINEL, dtype=HALF[fmt], device="cuda:0")
+        ctx._chk(ctx.lib.sgpt_layernorm_writeback(ctx.handle, p(xin), p(g), p(b), T, d, EPS, p(o16), DT[HALF[fmt]], None), "writeback")
+        assert (xin[T:] == SENTINEL).all() and (o16[T:] == SENTINEL).all(), "rows past T were written"
+        assert torch.equal(xin[:T].view(torch.int32), y.view(torch.int32)), f"write-back {fmt}: x is not the fp32 LayerNorm"
+        assert torch.equal(bits16(o16[:T]), bits16(xin[:T].to(HALF[fmt]))), f"write-back {fmt}: the 16-bit copy is not x rounded once"
+
+    xr, gr, ref, unit = rms_setup(T, d)
+    xr, gr = dev(xr), dev(gr)
+    ctx.range_check()
+    out = torch.full((T + 3, d), SENTINEL, dtype=torch.float32, device="cuda:0")
+    ctx.rmsnorm(xr, gr, 1e-5, out=out)
+    assert (out[T:] == SENTINEL).all(), "rows past T were written"
+    assert report(f"rmsnorm fp32 d={d} T={T}", float((np.abs(host64(out[:T]) - ref) / unit).max())) <= 4.0
+    xin = xr.clone()
+    ctx.rmsnorm(xin, gr, 1e-5, out=xin)
+    assert torch.equal(xin, out[:T]), "in place differs from out of place"
+    for fmt in ("f16", "bf16"):
+        o16 = torch.full((T + 3, d), SENTINEL, dtype=HALF[fmt], device="cuda:0")
+        ctx.rmsnorm(xr, gr, 1e-5, out_dtype=HALF[fmt], out=o16)
+        assert (o16[T:] == SENTINEL).all(), "rows past T were written"
+        assert torch.equal(bits16(o16[:T]), bits16(out[:T].to(HALF[fmt]))), f"rmsnorm {fmt} is not the fp32 output rounded once"
+    assert ctx.range_check() == 0
+
+    codes = torch.full((T + 3, d), 0x55, dtype=torch.uint8, device="cuda:0")
+    scale = torch.full((T + 3,), SENTINEL, dtype=torch.float32, device="cuda:0")
+    ctx._chk(ctx.lib.sgpt_layernorm_fp8(ctx.handle, p(x), p(g), p(b), T, d, EPS, p(codes), p(scale), None), "layernorm_fp8")
+    assert (codes[T:] == 0x55).all() and (scale[T:] == SENTINEL).all(), "rows past T were written"
+    y64, sc = host64(y), host64(scale[:T])[:, None]
+    assert (np.frexp(sc)[0] == 0.5).all(), "a row scale is not a power of two"
+    top = np.abs(y64).max(axis=1, keepdims=True) / sc
+    print(f"rowops: layernorm_fp8 d={d}: max|y| / scale in [{top.min():.2f}, {top.max():.2f}]")
+    assert ((top > 224) & (top <= 448)).all(), "not the smallest power-of-two scale that keeps the row inside e4m3"
+    v = np.abs(y64) / sc
+    spacing = np.maximum(np.ldexp(1.0, np.frexp(v)[1] - 1 - 3), 2.0 ** -9)      # frexp: v = m 2^e, 1/2 <= m < 1 -> floor(log2 v) = e - 1
+    err = np.abs(host64(codes[:T].view(torch.float8_e4m3fn).float()) * sc - y64) / (0.5 * sc * spacing)
+    over = int((err > 1.0).sum())
+    assert report(f"layernorm_fp8 d={d} T={T} ({over} elements over)", float(err.max())) <= 1.0
+
+
 # ============================================================================================================ ln_f + pool
 POOL_LENS = [1, 2, 3, 4, 5, 15, 16, 17, 31, 33, 127, 128, 300, 2048]
 POOL_PAD = [0, 3, 0, 1, 0, 7, 0, 0, 12, 0, 5, 0, 40, 0]
