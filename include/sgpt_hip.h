@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 20
+#define SGPT_ABI_VERSION 21
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -434,6 +434,9 @@ sgpt_status sgpt_score_topk_q8(sgpt_ctx* ctx, const void* q, const uint8_t* code
 
 /* Binary (1-bit) corpus (ABI v19): packed sign bits, Hamming search, re-scoring of an over-fetched candidate list -- the recipe known
  * as quantize_embeddings(precision="ubinary") + Hamming search + rescoring.  96 bytes per document at d = 768: 1/16 of f16 rows.
+ * The candidates are re-scored from the sign bits or an fp8 copy (sgpt_score_topk_bits: one query matrix, so an fp8 copy serves uncentred
+ * bits only) or from a uint8 copy (sgpt_score_topk_bits_u8, ABI v21, below the uint8 corpus: raw queries plus the centre, so it serves
+ * centred bits too).
  *   format    bits device uint8 [N, ldb], ldb % 4 == 0, ldb >= 4 * ceil(d / 32).  Dimension i of a document is bit 7 - i % 8 of byte
  *             i / 8 (the order of numpy.packbits); a bit is 1 exactly when the element is > 0 (NaN, +0, -0 give 0); bits d .. 8 ldb - 1
  *             are zero.  bits[:, :ceil(d / 8)] equals numpy.packbits(x > 0, axis=-1).
@@ -512,6 +515,53 @@ sgpt_status sgpt_u8_prepare_queries(sgpt_ctx* ctx, const float* q, const float* 
 sgpt_status sgpt_score_topk_u8(sgpt_ctx* ctx, const float* q, const uint8_t* codes, const float* start, const float* step, int32_t nq,
                                int64_t N, int32_t d, int32_t ld, int32_t k, int64_t idx_base, float* run_val, int64_t* run_idx,
                                int32_t n_run, int32_t* n_out, void* stream);
+
+/* Binary corpus with a uint8 second stage (ABI v21): binary retrieval + int8 re-scoring -- the Hamming search of sgpt_score_topk_bits,
+ * its candidates re-scored from a uint8 copy of the same documents, on a centred corpus or not.
+ *
+ * sgpt_u8_rescore: the second stage alone -- the values of caller-given candidate lists against a uint8 corpus (the candidates may come
+ * from any first stage).
+ *   q         device fp32 [nq, d]; codes / start / step / ld: the uint8 corpus above (N documents, codes 16-byte aligned).
+ *   idx       device int64 [nq, m], rows ld_idx >= m apart: candidate document indices idx_base + n, 0 <= n < N.
+ *   value     out_val[i][j] = <q_i, x^_n> = qbias_i + sum_j q'_ij (code[n][j] - 128), q'_ij = q_ij * step_j (fp32, one rounding),
+ *             qbias_i = sum_j q_ij * mid_j, mid_j = start_j + 128 * step_j (fp32; thread t of 256 adds columns t, t + 256, ... in
+ *             ascending order, the 256 partial sums are added in a fixed tree).  One launch computes q' and qbias per call; the gather kernel
+ *             (csrc/scoreu8.hip) reads the code rows in 16-byte pieces, lane l of a wave owning pieces l, l + 64, ...: four fp32
+ *             accumulators per lane (one per dword of a piece) take their products by fma with columns ascending, are added as
+ *             (a0 + a1) + (a2 + a3), the 64 lanes in a fixed butterfly, then qbias.  The order depends on ld alone -- not on nq, m, the
+ *             slot a candidate sits in or the launch shape: equal inputs give equal bits.  code - 128 and its conversion to fp32 are exact.  NaN -> -1.
+ *   error     |value - <q, x^_n> in exact arithmetic| <= (d + 2) 2^-23 (sum_j |q_j step_j c_nj| + sum_j |q_j mid_j|) + 2^-23 |value|,
+ *             c = code - 128: every partial sum passes at most d inexact additions (a pad column adds an exact zero), q' and
+ *             q_j * mid_j round once and mid_j once more, each rounding relative 2^-24, with the customary factor 2 for the
+ *             second-order terms; the last addition rounds the value itself.
+ *   result    out_val / out_idx [nq, m], slot for slot, NOT sorted: out_idx = idx.  A slot with idx < 0 or idx - idx_base outside [0, N)
+ *             gives (-inf, -1) and reads no row.
+ *   shapes    any nq, m, N >= 1, any d >= 1 with ld = ceil(d / 128) * 128; q' stays in registers for d <= 2048 and is re-read beyond.
+ * SGPT_ERR_INVALID (nothing launched, outputs untouched): null pointers; nq, N, d or m <= 0; ld % 128; d > ld; ld_idx < m; codes not
+ * 16-byte aligned. */
+sgpt_status sgpt_u8_rescore(sgpt_ctx* ctx, const float* q, const uint8_t* codes, const float* start, const float* step, int32_t nq, int64_t N,
+                            int32_t d, int32_t ld, const int64_t* idx, int64_t ld_idx, int32_t m, int64_t idx_base, float* out_val,
+                            int64_t* out_idx, void* stream);
+
+/* sgpt_score_topk_bits_u8 (ABI v21): sgpt_score_topk_bits with that second stage.
+ *   q         device fp32 [nq, d]: normalised by the caller and RAW -- not centred, unlike sgpt_score_topk_bits.
+ *   center    device fp32 [d] or NULL: what the corpus bits were centred on.
+ *   bits/ldb  as sgpt_score_topk_bits; codes / start / step / ld: the same N documents as a uint8 corpus (rows from sgpt_u8_quantize_rows of
+ *             the UNcentred rows), codes 16-byte aligned.
+ *   stage 1   that of sgpt_score_topk_bits on the matrix q - center (one IEEE fp32 subtraction per element, taken by sgpt_pack_sign_bits'
+ *             kernel as it packs the query bits): the same Hamming tile, schedule and predicated fallback, the same candidate list index
+ *             for index.
+ *   stage 2   sgpt_u8_rescore's value of every candidate from the raw q (its arithmetic, order and error bound); NaN -> -1; order by value
+ *             descending, ties to the lowest index.
+ *   result    as sgpt_score_topk_bits: merged with the running list (which must hold values of this entry), unused tail (-inf, -1),
+ *             *n_out = min(k, n_run + N).
+ *   shapes    any nq >= 1, any d >= 1, any N >= 1, k <= kp <= 1024.
+ * SGPT_ERR_INVALID (nothing launched, outputs untouched): null pointers (center may be NULL); ldb < 4 * ceil(d / 32) or ldb % 4; ld % 128;
+ * d > ld; codes not 16-byte aligned; k <= 0, kp < k, kp > 1024; n_run < 0 or n_run > k. */
+sgpt_status sgpt_score_topk_bits_u8(sgpt_ctx* ctx, const float* q, const float* center /* fp32[d] or NULL */, const uint8_t* bits, int64_t ldb,
+                                    const uint8_t* codes, const float* start, const float* step, int32_t ld, int32_t nq, int64_t N, int32_t d,
+                                    int32_t k, int32_t kp, int64_t idx_base, float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out,
+                                    void* stream);
 
 /* Diagnostics (ABI v19): of the filtered chunks of the LAST score + top-k pass on this context (sgpt_score_topk, _q8, _u8; _bits: its last
  * query group), how many overflowed their candidate lists and were recomputed by the predicated fallback.  Synchronises `stream`. */

@@ -378,6 +378,13 @@ void launch_u8_col_minmax(const float* x, long n, int d, int accumulate, float* 
 void launch_u8_quant_rows(const float* x, long n, int d, int ld, const float* start, const float* step, uint8_t* codes, hipStream_t s);
 void launch_u8_dequant_rows(const uint8_t* codes, long n, int ld, const float* start, const float* step, void* out, int out_dtype,
                             hipStream_t s);
+// re-scoring of candidate lists from the codes (sgpt_u8_rescore, stage 2 of sgpt_score_topk_bits_u8).  prepare: q fp32 [nq][d] (any nq)
+// -> qs fp32 [nq][ld] = q_j step_j (pad columns zero), qbias fp32 [nq] = sum_j q_j mid_j.  rescore: the value qbias + <qs, code - 128> of
+// every slot of idx [nq, ld_idx] (m per row) into the first m columns of a [nq, ld_out] list (launch_rescore's layout and slot rules)
+void launch_u8_rescore_prepare(const float* q, const float* start, const float* step, int nq, int d, int ld, float* qs, float* qbias,
+                               hipStream_t s);
+void launch_u8_rescore(const float* qs, const float* qbias, const uint8_t* codes, int ld, const int64_t* idx, long ld_idx, int nq, int m,
+                       long idx_base, long n_docs, float* out_val, int64_t* out_idx, long ld_out, hipStream_t s);
 // scorebits.hip: the Hamming tile over packed sign bits (sgpt_score_topk_bits).  g.A = packed query rows (g.m_valid of them, qw dwords
 // apart), g.W = document rows g.ldw BYTES apart (ldb bytes each, times the row stride of a sample), g.N documents (any number,
 // bounds-checked); score = d - 2 * hamming as an exact fp32; epi = EPI_SCORE | EPI_SCORE_FILTER with score64_kernel's contract.

@@ -474,6 +474,29 @@ static void two_stage_finish(const TwoStage& t, float* run_val, int64_t* run_idx
     launch_topk_select(t.cv, t.ldc, 0, 0, t.cv, t.ci, kp + n_run, t.ldc, nq, k, 0, nullptr, run_val, run_idx, s);
 }
 
+static inline int bits_query_words(int d) { return (d + 127) / 128 * 4; }     // dwords of a packed query row: whole 16-byte pieces
+
+// Stage 1 of the binary-corpus searches: the kp best by agreement (a descending, index ascending) of every packed query row, a fresh list
+// per call, into (t.lv, t.li).  Queries in groups of 64 (re-streaming 96-byte rows is cheap), documents in blocks the launches index
+// with 32 bits, chained through the stage-1 list.
+static sgpt_status bits_stage1(sgpt_ctx* c, const uint32_t* qbits, int qw, const uint8_t* bits, int64_t ldb, int32_t nq, int64_t N, int32_t d,
+                               int32_t kp, int64_t idx_base, const TwoStage& t, void* stream) {
+    const int64_t blk = (int64_t)1 << 30;
+    for (int32_t g0 = 0; g0 < nq; g0 += 64) {
+        const int32_t gn = nq - g0 < 64 ? nq - g0 : 64;
+        float* gv = t.lv + (size_t)g0 * kp;
+        int64_t* gi = t.li + (size_t)g0 * kp;
+        int32_t have = 0;
+        for (int64_t b0 = 0; b0 < N; b0 += blk) {
+            const int64_t nb = N - b0 < blk ? N - b0 : blk;
+            sgpt_status st = score_topk_impl(c, qbits + (size_t)g0 * qw, corpus_bits(bits + (size_t)b0 * ldb, (long)ldb, qw, d), gn, nb, kp,
+                                             idx_base + b0, gv, gi, gv, gi, have, &have, stream, nullptr);
+            if (st != SGPT_OK) return st;
+        }
+    }
+    return SGPT_OK;
+}
+
 // Hamming search over packed sign bits with optional re-scoring of the over-fetched candidates (include/sgpt_hip.h).
 sgpt_status sgpt_score_topk_bits(sgpt_ctx* c, const float* q, const uint8_t* bits, int64_t ldb, int32_t nq, int64_t N, int32_t d, int32_t k,
                                  int32_t kp, int32_t mode, const uint8_t* codes, const float* scale, int64_t idx_base, float* run_val,
@@ -485,31 +508,71 @@ sgpt_status sgpt_score_topk_bits(sgpt_ctx* c, const float* q, const uint8_t* bit
                                          "mode 0 with kp == k, mode 2 with codes and scale, 0 <= n_run <= k)");
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    const int qw = (d + 127) / 128 * 4;                 // dwords of a packed query row: whole 16-byte pieces
+    const int qw = bits_query_words(d);
     TwoStage t;
     sgpt_status st = two_stage_carve(c, align_up((size_t)nq * qw * 4, 256), 0, nq, kp, k, t);
     if (st != SGPT_OK) return st;
     uint32_t* qbits = (uint32_t*)t.head;
     launch_pack_sign_bits(q, nq, d, nullptr, (uint8_t*)qbits, (long)qw * 4, s);
-    // stage 1: the kp best by agreement (a descending, index ascending), a fresh list per call.  Queries in groups of 64 (re-streaming
-    // 96-byte rows is cheap), documents in blocks the launches index with 32 bits, chained through the stage-1 list.
-    const int64_t blk = (int64_t)1 << 30;
-    for (int32_t g0 = 0; g0 < nq; g0 += 64) {
-        const int32_t gn = nq - g0 < 64 ? nq - g0 : 64;
-        float* gv = t.lv + (size_t)g0 * kp;
-        int64_t* gi = t.li + (size_t)g0 * kp;
-        int32_t have = 0;
-        for (int64_t b0 = 0; b0 < N; b0 += blk) {
-            const int64_t nb = N - b0 < blk ? N - b0 : blk;
-            st = score_topk_impl(c, qbits + (size_t)g0 * qw, corpus_bits(bits + (size_t)b0 * ldb, (long)ldb, qw, d), gn, nb, kp, idx_base + b0,
-                                 gv, gi, gv, gi, have, &have, stream, nullptr);
-            if (st != SGPT_OK) return st;
-        }
-    }
+    st = bits_stage1(c, qbits, qw, bits, ldb, nq, N, d, kp, idx_base, t, stream);
+    if (st != SGPT_OK) return st;
     // stage 2: the candidates' values by `mode` | the running list -> top-k (as sgpt_score_topk_refined)
     launch_rescore_bits(mode, q, bits, (long)ldb, codes, ((long)d + 7) / 8 * 8, scale, t.lv, t.li, kp, nq, kp, d, idx_base, N, t.cv, t.ci, t.ldc, s);
     two_stage_finish(t, run_val, run_idx, k, n_run, nq, kp, s);
     if (n_out) *n_out = list_fill(n_run, N, k);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+// The same first stage with a uint8 second stage (include/sgpt_hip.h): the bits are searched with q - center, the candidates re-scored
+// from the codes with the raw q.  ws4 head = [packed query bits | qs fp32 [nq][ld] | qbias fp32 [nq]].
+sgpt_status sgpt_score_topk_bits_u8(sgpt_ctx* c, const float* q, const float* center, const uint8_t* bits, int64_t ldb, const uint8_t* codes,
+                                    const float* start, const float* step, int32_t ld, int32_t nq, int64_t N, int32_t d, int32_t k,
+                                    int32_t kp, int64_t idx_base, float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out,
+                                    void* stream) {
+    if (!c || !q || !bits || !codes || !start || !step || !run_val || !run_idx || nq <= 0 || N <= 0 || d <= 0 || ldb % 4 ||
+        ldb < 4 * (((int64_t)d + 31) / 32) || ld < 128 || ld % 128 || d > ld || k <= 0 || kp < k || kp > 1024 || n_run < 0 || n_run > k ||
+        ((size_t)bits & 3) || ((size_t)codes & 15))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_score_topk_bits_u8: bad arguments (ldb % 4 == 0, ldb >= 4 ceil(d / 32), ld % 128 == 0, 0 < d <= ld, "
+                                         "codes 16-byte aligned, 0 < k <= kp <= 1024, 0 <= n_run <= k)");
+    HIPC(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int qw = bits_query_words(d);
+    const size_t qbits_b = align_up((size_t)nq * qw * 4, 256), qs_b = align_up((size_t)nq * ld * 4, 256), qb_b = align_up((size_t)nq * 4, 256);
+    TwoStage t;
+    sgpt_status st = two_stage_carve(c, qbits_b + qs_b + qb_b, 0, nq, kp, k, t);
+    if (st != SGPT_OK) return st;
+    uint32_t* qbits = (uint32_t*)t.head;
+    float* qs = (float*)(t.head + qbits_b);
+    float* qbias = (float*)(t.head + qbits_b + qs_b);
+    launch_pack_sign_bits(q, nq, d, center, (uint8_t*)qbits, (long)qw * 4, s);
+    launch_u8_rescore_prepare(q, start, step, nq, d, ld, qs, qbias, s);
+    st = bits_stage1(c, qbits, qw, bits, ldb, nq, N, d, kp, idx_base, t, stream);
+    if (st != SGPT_OK) return st;
+    // stage 2: <q, x^_n> of the candidates from the codes | the running list -> top-k
+    launch_u8_rescore(qs, qbias, codes, ld, t.li, kp, nq, kp, idx_base, N, t.cv, t.ci, t.ldc, s);
+    two_stage_finish(t, run_val, run_idx, k, n_run, nq, kp, s);
+    if (n_out) *n_out = list_fill(n_run, N, k);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+// The second stage of the above alone: the values of the caller's candidate lists (include/sgpt_hip.h).  ws4 = [qs | qbias].
+sgpt_status sgpt_u8_rescore(sgpt_ctx* c, const float* q, const uint8_t* codes, const float* start, const float* step, int32_t nq, int64_t N,
+                            int32_t d, int32_t ld, const int64_t* idx, int64_t ld_idx, int32_t m, int64_t idx_base, float* out_val,
+                            int64_t* out_idx, void* stream) {
+    if (!c || !q || !codes || !start || !step || !idx || !out_val || !out_idx || nq <= 0 || N <= 0 || d <= 0 || ld < 128 || ld % 128 || d > ld ||
+        m <= 0 || ld_idx < m || ((size_t)codes & 15))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_u8_rescore: bad arguments (ld % 128 == 0, 0 < d <= ld, codes 16-byte aligned, 0 < m <= ld_idx)");
+    HIPC(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t qs_b = align_up((size_t)nq * ld * 4, 256);
+    sgpt_status st = ensure(c, &c->ws4, &c->ws4_bytes, qs_b + align_up((size_t)nq * 4, 256));
+    if (st != SGPT_OK) return st;
+    float* qs = (float*)c->ws4;
+    float* qbias = (float*)((char*)c->ws4 + qs_b);
+    launch_u8_rescore_prepare(q, start, step, nq, d, ld, qs, qbias, s);
+    launch_u8_rescore(qs, qbias, codes, ld, idx, (long)ld_idx, nq, m, idx_base, N, out_val, out_idx, m, s);
     HIPC(c, hipGetLastError());
     return SGPT_OK;
 }

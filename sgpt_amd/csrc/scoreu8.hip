@@ -194,6 +194,126 @@ unsigned row_grid(long n, int ld) {
     return (unsigned)(blocks < 1 ? 1 : (blocks > 65536 ? 65536 : blocks));
 }
 
+// ---- re-scoring of a candidate list from the codes (sgpt_u8_rescore; stage 2 of sgpt_score_topk_bits_u8) ----
+// A candidate's value is <q, x^_n> = qbias + sum_j q'_j (code[n][j] - 128) with q'_j = q_j step_j and qbias = sum_j q_j mid_j: the form of
+// the scorer above without the f16 rounding of q' and without its power-of-two scale, since no MFMA reads it -- everything is fp32.
+
+// Query prologue, one workgroup per query: qs[r][j] = q_j * step_j (fp32, one rounding; zero in the pad columns d .. ld - 1) and
+// qbias[r] as u8_prepare_queries_kernel sums it (thread t adds columns t, t + 256, ... in ascending order, the 256 partial sums are
+// added in a fixed butterfly).  Once per call, not once per candidate.
+__global__ __launch_bounds__(256) void u8_rescore_prepare_kernel(const float* __restrict__ q, const float* __restrict__ start,
+                                                                 const float* __restrict__ step, int d, int ld, float* __restrict__ qs,
+                                                                 float* __restrict__ qbias) {
+    __shared__ float red[4];
+    const int t = threadIdx.x;
+    const float* row = q + (long)blockIdx.x * d;
+    float* out = qs + (long)blockIdx.x * ld;
+    float bias = 0.f;
+    for (int j = t; j < ld; j += 256) {
+        float v = 0.f;
+        if (j < d) {
+            const float st = step[j];
+            v = __fmul_rn(row[j], st);
+            bias = __fadd_rn(bias, __fmul_rn(row[j], __fadd_rn(start[j], __fmul_rn(128.0f, st))));
+        }
+        out[j] = v;
+    }
+    bias = wave_sum(bias);
+    if ((t & 63) == 0) red[t >> 6] = bias;
+    __syncthreads();
+    if (t == 0) qbias[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// 16 codes of one 16-byte piece against the 16 q' values of the same columns: dword e of the piece feeds accumulator e, its bytes in
+// ascending order.  code - 128 is exact however it is formed: the compiler takes the byte by an SDWA select, subtracts in integers and
+// converts with v_cvt_f32_i32 (two instructions per code, as v_cvt_f32_ubyteN and a subtraction would be); the fmas pair up as v_pk_fma_f32.
+__device__ __forceinline__ void u8_piece_fma(const uint4 w, const float (&qf)[16], float (&acc)[4]) {
+    const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+            acc[e] = __builtin_fmaf(qf[4 * e + b], (float)((ws[e] >> (8 * b)) & 0xffu) - 128.0f, acc[e]);
+}
+
+// The gather.  blockIdx.y = query, blockIdx.x = a group of 4 * CPW candidate slots; wave w of the workgroup serves slots
+// 4 CPW blockIdx.x + w + 4 i, i < CPW.  A wave covers a row in rounds of 1024 columns: lane l owns the 16-byte piece l + 64 r of round r.
+// Rows are ld-padded (pad codes 128, q' = 0 there), so the loop runs over ld / 16 whole pieces with no tail mask; at ld = 768 lanes
+// 48 .. 63 idle in the only round.  q' of the first NR rounds sits in registers for all CPW candidates of the wave (NR * 16 floats per
+// lane); rows wider than NR * 1024 columns re-read the rest of q' per candidate (any d is served; the register set covers d <= 2048).
+// The CPW index loads, then the CPW * NR row loads, are issued back to back before the arithmetic: two memory latencies per wave.
+// Order of the arithmetic, fixed by the slot alone (independent of nq, m and the launch shape): per lane four accumulators (one per
+// dword of a piece) take their products by fma, columns ascending, rounds ascending; s = (a0 + a1) + (a2 + a3); the wave's 64 sums
+// are added in the xor butterfly 32, 16, .., 1; value = s + qbias.  NaN -> -1.  A slot with idx < 0 or idx - idx_base outside [0, n_docs)
+// -> (-inf, -1): no row is read for it.
+template <int NR, int CPW>
+__global__ __launch_bounds__(256) void u8_rescore_kernel(const float* __restrict__ qs, const float* __restrict__ qbias,
+                                                         const uint8_t* __restrict__ codes, int ld, const int64_t* __restrict__ idx,
+                                                         long ld_idx, int m, long idx_base, long n_docs, float* __restrict__ out_val,
+                                                         int64_t* __restrict__ out_idx, long ld_out) {
+    const int qi = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int np = ld >> 4;                                        // 16-byte pieces of a row
+    const float* __restrict__ qrow = qs + (long)qi * ld;
+    float qf[NR][16];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const int p = lane + 64 * r;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float4 v = p < np ? reinterpret_cast<const float4*>(qrow)[4 * p + e] : make_float4(0.f, 0.f, 0.f, 0.f);
+            qf[r][4 * e + 0] = v.x; qf[r][4 * e + 1] = v.y; qf[r][4 * e + 2] = v.z; qf[r][4 * e + 3] = v.w;
+        }
+    }
+    const float qb = qbias[qi];
+    const int j0 = blockIdx.x * (4 * CPW) + wave;
+    int64_t id[CPW];
+    const uint4* row[CPW];
+    uint4 w[CPW][NR];
+#pragma unroll
+    for (int i = 0; i < CPW; ++i) {
+        const int j = j0 + 4 * i;
+        id[i] = j < m ? idx[(long)qi * ld_idx + j] : (int64_t)-1;
+    }
+#pragma unroll
+    for (int i = 0; i < CPW; ++i) {
+        const long r = (long)(id[i] - idx_base);
+        row[i] = id[i] >= 0 && r >= 0 && r < n_docs ? reinterpret_cast<const uint4*>(codes + r * ld) : nullptr;
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) {
+            const int p = lane + 64 * rr;
+            w[i][rr] = row[i] != nullptr && p < np ? row[i][p] : make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < CPW; ++i) {
+        const int j = j0 + 4 * i;
+        if (j >= m) break;                                         // (wave-uniform)
+        float v = -INFINITY;
+        if (row[i] != nullptr) {
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int rr = 0; rr < NR; ++rr) u8_piece_fma(w[i][rr], qf[rr], acc);
+            for (int p = lane + 64 * NR; p < np; p += 64) {        // (rows wider than the register set)
+                float qx[16];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float4 t = reinterpret_cast<const float4*>(qrow)[4 * p + e];
+                    qx[4 * e + 0] = t.x; qx[4 * e + 1] = t.y; qx[4 * e + 2] = t.z; qx[4 * e + 3] = t.w;
+                }
+                u8_piece_fma(row[i][p], qx, acc);
+            }
+            float s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+            s = wave_sum(s);
+            s = s + qb;
+            v = s != s ? -1.0f : s;
+        }
+        if (lane == 0) {
+            out_val[(long)qi * ld_out + j] = v;
+            out_idx[(long)qi * ld_out + j] = v > -INFINITY ? id[i] : (int64_t)-1;
+        }
+    }
+}
+
 }  // namespace
 
 // 64 padded f16 query rows, any number of documents, rows of whole 128-code k-steps, 16-byte aligned code rows (the 16-byte loads)
@@ -228,4 +348,23 @@ void launch_u8_dequant_rows(const uint8_t* codes, long n, int ld, const float* s
         hipLaunchKernelGGL(u8_dequant_rows_kernel<f16_t>, dim3(grid), dim3(256), 0, s, codes, n, ld, start, step, static_cast<f16_t*>(out));
     else
         hipLaunchKernelGGL(u8_dequant_rows_kernel<float>, dim3(grid), dim3(256), 0, s, codes, n, ld, start, step, static_cast<float*>(out));
+}
+
+void launch_u8_rescore_prepare(const float* q, const float* start, const float* step, int nq, int d, int ld, float* qs, float* qbias,
+                               hipStream_t s) {
+    hipLaunchKernelGGL(u8_rescore_prepare_kernel, dim3(nq), dim3(256), 0, s, q, start, step, d, ld, qs, qbias);
+}
+
+// qs / qbias: launch_u8_rescore_prepare's output for the same nq queries; ld % 128 == 0, codes 16-byte aligned (the 16-byte loads)
+void launch_u8_rescore(const float* qs, const float* qbias, const uint8_t* codes, int ld, const int64_t* idx, long ld_idx, int nq, int m,
+                       long idx_base, long n_docs, float* out_val, int64_t* out_idx, long ld_out, hipStream_t s) {
+    if (ld < 128 || ld % 128 || ((size_t)codes & 15) || ((size_t)qs & 15) || nq <= 0 || m <= 0) abort();
+    constexpr int CPW = 4;
+    const unsigned gx = (unsigned)((m + 4 * CPW - 1) / (4 * CPW));
+    for (int q0 = 0; q0 < nq; q0 += 32768) {         // (grid.y is a 16-bit count)
+        const int gn = nq - q0 < 32768 ? nq - q0 : 32768;
+        const auto kernel = ld <= 1024 ? u8_rescore_kernel<1, CPW> : u8_rescore_kernel<2, CPW>;
+        hipLaunchKernelGGL(kernel, dim3(gx, gn), dim3(256), 0, s, qs + (long)q0 * ld, qbias + q0, codes, ld, idx + (long)q0 * ld_idx, ld_idx,
+                           m, idx_base, n_docs, out_val + (long)q0 * ld_out, out_idx + (long)q0 * ld_out, ld_out);
+    }
 }

@@ -50,10 +50,12 @@ class BinaryCorpus:
     """A corpus held as packed sign bits: `bits` uint8 [N, ldb], ldb = 4 * ceil(dim / 32) (include/sgpt_hip.h::sgpt_score_topk_bits;
     dimension i of a document is bit 7 - i % 8 of byte i / 8, set when the element is > 0 -- numpy.packbits order, "ubinary" in
     sentence-transformers).  `center` fp32 [dim] or None: what was subtracted from the normalised rows before the signs were taken, and
-    is subtracted from the queries; `fp8`: an optional QuantizedCorpus of the same (uncentred, normalised) rows for re-scoring.  Built
-    by Context.binarize_corpus / util.quantize_embeddings(precision="ubinary")."""
+    is subtracted from the queries; `fp8`: an optional QuantizedCorpus of the same (uncentred, normalised) rows for re-scoring; `u8`: an
+    optional Uint8Corpus of the same rows for re-scoring (rescore="uint8": binary retrieval + int8 re-scoring, with or without a
+    centre).  Built by Context.binarize_corpus / util.quantize_embeddings(precision="ubinary")."""
 
-    def __init__(self, bits: torch.Tensor, dim: int, center: Optional[torch.Tensor] = None, fp8: Optional[QuantizedCorpus] = None):
+    def __init__(self, bits: torch.Tensor, dim: int, center: Optional[torch.Tensor] = None, fp8: Optional[QuantizedCorpus] = None,
+                 u8: Optional["Uint8Corpus"] = None):
         dim = int(dim)
         if bits.dim() != 2 or bits.dtype != torch.uint8:
             raise ValueError(f"BinaryCorpus: bits are uint8 [N, ldb], got {bits.dtype} {tuple(bits.shape)}")
@@ -64,7 +66,9 @@ class BinaryCorpus:
         if fp8 is not None and (not isinstance(fp8, QuantizedCorpus) or len(fp8) != bits.shape[0] or
                                 fp8.codes.shape[1] != (dim + 7) // 8 * 8):
             raise ValueError("BinaryCorpus: fp8 must be a QuantizedCorpus of the same rows (codes [N, ceil(dim / 8) * 8])")
-        self.bits, self.dim, self.center, self.fp8 = bits, dim, center, fp8
+        if u8 is not None and (not isinstance(u8, Uint8Corpus) or len(u8) != bits.shape[0] or u8.dim != dim):
+            raise ValueError(f"BinaryCorpus: u8 must be a Uint8Corpus of the same rows (N = {bits.shape[0]}, dim = {dim})")
+        self.bits, self.dim, self.center, self.fp8, self.u8 = bits, dim, center, fp8, u8
 
     def __len__(self) -> int:
         return int(self.bits.shape[0])
@@ -76,6 +80,8 @@ class BinaryCorpus:
             n += self.center.numel() * self.center.element_size()
         if self.fp8 is not None:
             n += self.fp8.nbytes
+        if self.u8 is not None:
+            n += self.u8.nbytes
         return n
 
 
@@ -113,7 +119,7 @@ class Uint8Corpus:
         return (self.codes[:, :self.dim].to(torch.int16) - 128).to(torch.int8)
 
 
-RESCORE_MODES = {"none": 0, "sign": 1, "fp8": 2}
+RESCORE_MODES = {"none": 0, "sign": 1, "fp8": 2}      # the modes of sgpt_score_topk_bits; "uint8" is an entry of its own (_bits_u8)
 
 _contexts = {}
 
@@ -382,12 +388,23 @@ class Context:
         sentence-transformers), or those of `calibration_embeddings` (normalised like the corpus), or the corpus's own; elements outside
         them clamp.  Non-finite ranges (a NaN or inf in the rows they come from) raise ValueError.  Works in blocks of `block_rows` rows,
         as quantize_corpus does; `emb` may live on the host."""
-        if ranges is not None and calibration_embeddings is not None:
-            raise ValueError("scalar_quantize_corpus: give ranges or calibration_embeddings, not both")
         if not isinstance(emb, torch.Tensor):
             emb = torch.as_tensor(np.asarray(emb))
         if emb.dim() != 2 or emb.shape[0] == 0 or emb.shape[1] == 0:
             raise ValueError(f"scalar_quantize_corpus needs a non-empty [N, d] matrix, got {tuple(emb.shape)}")
+        N, d = emb.shape
+        start, step = self._u8_ranges(emb, normalize, ranges, calibration_embeddings, block_rows)
+        codes = torch.empty((N, start.shape[0]), dtype=torch.uint8, device=self.device)
+        for r0 in range(0, N, block_rows):
+            blk = self._dev_f32(emb[r0:r0 + block_rows])
+            self.u8_quantize_rows(self.l2_normalize(blk) if normalize else blk, start, step, out=codes[r0:r0 + block_rows])
+        return Uint8Corpus(codes, start, step, bool(normalize), d)
+
+    def _u8_ranges(self, emb: torch.Tensor, normalize: bool, ranges, calibration_embeddings, block_rows: int):
+        """(start, step) fp32 [ld] of scalar_quantize_corpus's rule for the rows of emb [N, d]: from `ranges`, from
+        `calibration_embeddings`, or from emb itself."""
+        if ranges is not None and calibration_embeddings is not None:
+            raise ValueError("scalar_quantize_corpus: give ranges or calibration_embeddings, not both")
         N, d = emb.shape
         ld = (d + 127) // 128 * 128
 
@@ -418,10 +435,7 @@ class Context:
         step[:d] = (mx - mn) / torch.full_like(mx, 255.0)      # (a tensor divisor: one IEEE division per column, not a multiplication by 1 / 255)
         if not bool(torch.isfinite(step).all()):
             raise ValueError("scalar_quantize_corpus: max - min overflows fp32")
-        codes = torch.empty((N, ld), dtype=torch.uint8, device=self.device)
-        for r0 in range(0, N, block_rows):
-            self.u8_quantize_rows(rows(emb, r0), start, step, out=codes[r0:r0 + block_rows])
-        return Uint8Corpus(codes, start, step, bool(normalize), d)
+        return start, step
 
     def _score_topk_u8(self, q, corpus: Uint8Corpus, k: int, idx_base: int, run, dtype):
         if dtype is not None:
@@ -472,11 +486,15 @@ class Context:
         return out
 
     def binarize_corpus(self, emb, normalize: bool = True, center=None, keep_fp8: bool = False,
-                        block_rows: int = 65536) -> BinaryCorpus:
+                        block_rows: int = 65536, keep_uint8: bool = False, ranges=None, calibration_embeddings=None) -> BinaryCorpus:
         """Embeddings [N, d] -> BinaryCorpus: rows L2-normalised, the centre subtracted, signs packed.  center: None | "mean" (the mean of
         the normalised rows, kept on the corpus so that queries get the same shift) | a [d] tensor.  keep_fp8: the same normalised,
-        uncentred rows also go through quantize_corpus (re-scoring with rescore="fp8").  Works in blocks of `block_rows` rows, as
+        uncentred rows also go through quantize_corpus (re-scoring with rescore="fp8").  keep_uint8: the same normalised, uncentred
+        rows are also quantised by scalar_quantize_corpus's rule (its `ranges` / `calibration_embeddings`), block by block beside the
+        bits (re-scoring with rescore="uint8", with or without a centre).  Works in blocks of `block_rows` rows, as
         quantize_corpus does; `emb` may live on the host.  Sign bits carry no norms: normalize=False is refused."""
+        if not keep_uint8 and (ranges is not None or calibration_embeddings is not None):
+            raise ValueError("binarize_corpus: ranges / calibration_embeddings belong to keep_uint8=True")
         if keep_fp8 and center is not None:
             raise ValueError("binarize_corpus: keep_fp8 with a centre is refused -- fp8 re-scoring needs the raw query, the centred bits "
                              "q - center, and the search call takes one query matrix (score_topk)")
@@ -499,25 +517,54 @@ class Context:
             if tuple(center.shape) != (d,):
                 raise ValueError(f"binarize_corpus: center must be [{d}], got {tuple(center.shape)}")
         bits = torch.empty((N, 4 * ((d + 31) // 32)), dtype=torch.uint8, device=self.device)
+        start = step = codes = None
+        if keep_uint8:
+            start, step = self._u8_ranges(emb, True, ranges, calibration_embeddings, block_rows)
+            codes = torch.empty((N, start.shape[0]), dtype=torch.uint8, device=self.device)
         for r0 in range(0, N, block_rows):
             n = min(block_rows, N - r0)
-            self.pack_sign_bits(self.l2_normalize(self._dev_f32(emb[r0:r0 + n])), center, out=bits[r0:r0 + n])
+            rows = self.l2_normalize(self._dev_f32(emb[r0:r0 + n]))
+            self.pack_sign_bits(rows, center, out=bits[r0:r0 + n])
+            if keep_uint8:
+                self.u8_quantize_rows(rows, start, step, out=codes[r0:r0 + n])
         fp8 = self.quantize_corpus(emb, normalize=True, block_rows=block_rows) if keep_fp8 else None
-        return BinaryCorpus(bits, d, center, fp8)
+        u8 = Uint8Corpus(codes, start, step, True, d) if keep_uint8 else None
+        return BinaryCorpus(bits, d, center, fp8, u8)
 
     def _score_topk_bits(self, q, corpus: BinaryCorpus, k: int, idx_base: int, run, rescore: str, rescore_multiplier):
-        if rescore not in RESCORE_MODES:
-            raise ValueError(f"score_topk: rescore must be 'sign', 'none' or 'fp8', got {rescore!r}")
+        if rescore not in RESCORE_MODES and rescore != "uint8":
+            raise ValueError(f"score_topk: rescore must be 'sign', 'none', 'fp8' or 'uint8', got {rescore!r}")
         if rescore == "fp8" and corpus.fp8 is None:
             raise ValueError("score_topk: rescore='fp8' needs a BinaryCorpus built with keep_fp8=True (corpus.fp8 is None)")
+        if rescore == "uint8" and corpus.u8 is None:
+            raise ValueError("score_topk: rescore='uint8' needs a BinaryCorpus built with keep_uint8=True (corpus.u8 is None)")
         if k < 1 or k > 1024:
             raise ValueError(f"score_topk over a BinaryCorpus takes 1 <= k <= 1024, got {k}")
-        mode = RESCORE_MODES[rescore]
+        mode = RESCORE_MODES.get(rescore)
         kp = k if mode == 0 else min(1024, max(k, int(round(k * rescore_multiplier))))
         q = self._dev_f32(q)
         nq, d = q.shape
         if d != corpus.dim:
             raise ValueError(f"embedding dims differ: {d} vs {corpus.dim}")
+        if rescore == "uint8":
+            # an entry of its own: it takes the RAW q and the centre, packs the stage-1 bits of q - center and re-scores with q
+            u8 = corpus.u8
+            bits = corpus.bits.to(self.device).contiguous()
+            codes = u8.codes.to(self.device).contiguous()
+            start = u8.start.to(device=self.device, dtype=torch.float32).contiguous()
+            step = u8.step.to(device=self.device, dtype=torch.float32).contiguous()
+            center = None if corpus.center is None else corpus.center.to(device=self.device, dtype=torch.float32).contiguous()
+            if run is None:
+                val = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+                idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+                n_run = 0
+            else:
+                val, idx, n_run = run
+            n_out = C.c_int32(0)
+            self._chk(self.lib.sgpt_score_topk_bits_u8(self.handle, _p(q), _p(center), _p(bits), bits.shape[1], _p(codes), _p(start), _p(step),
+                                                       codes.shape[1], nq, bits.shape[0], d, k, kp, idx_base, _p(val), _p(idx), n_run,
+                                                       C.byref(n_out), _stream_ptr(self.device)), "sgpt_score_topk_bits_u8")
+            return val, idx, int(n_out.value)
         # The C call takes ONE query matrix: it packs the stage-1 bits from it and re-scores with it.  A centred corpus needs the bits of
         # q - center, its fp8 copy the raw q: no single matrix serves both, and the raw one would search sign(q) against sign(x - center).
         if corpus.center is not None and mode == 2:
@@ -541,6 +588,28 @@ class Context:
                                                 _p(scale), idx_base, _p(val), _p(idx), n_run, C.byref(n_out),
                                                 _stream_ptr(self.device)), "sgpt_score_topk_bits")
         return val, idx, int(n_out.value)
+
+    def rescore_u8(self, q, corpus_u8: Uint8Corpus, idx: torch.Tensor, idx_base: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The values <q_i, document idx[i][j]> of candidate lists against a Uint8Corpus (include/sgpt_hip.h::sgpt_u8_rescore): q [nq, dim]
+        (upcast to fp32), idx int64 [nq, m] of document indices idx_base + n -> (values fp32 [nq, m], indices int64 [nq, m]), slot for
+        slot and unsorted; a slot with idx < 0 or idx - idx_base outside [0, N) gives (-inf, -1).  The candidates may come from any
+        first stage."""
+        q = self._dev_f32(q)
+        if q.dim() != 2 or q.shape[1] != corpus_u8.dim:
+            raise ValueError(f"embedding dims differ: {tuple(q.shape)[-1]} vs {corpus_u8.dim}")
+        if idx.dim() != 2 or idx.shape[0] != q.shape[0] or idx.shape[1] == 0 or idx.dtype != torch.int64:
+            raise ValueError(f"rescore_u8: idx must be int64 [{q.shape[0]}, m], got {idx.dtype} {tuple(idx.shape)}")
+        idx = idx.to(self.device).contiguous()
+        codes = corpus_u8.codes.to(self.device).contiguous()
+        start = corpus_u8.start.to(device=self.device, dtype=torch.float32).contiguous()
+        step = corpus_u8.step.to(device=self.device, dtype=torch.float32).contiguous()
+        nq, d = q.shape
+        m = int(idx.shape[1])
+        val = torch.empty((nq, m), dtype=torch.float32, device=self.device)
+        out = torch.empty((nq, m), dtype=torch.int64, device=self.device)
+        self._chk(self.lib.sgpt_u8_rescore(self.handle, _p(q), _p(codes), _p(start), _p(step), nq, codes.shape[0], d, codes.shape[1], _p(idx), m,
+                                           m, idx_base, _p(val), _p(out), _stream_ptr(self.device)), "sgpt_u8_rescore")
+        return val, out
 
     def score_overflow_count(self) -> Tuple[int, int]:
         """(filtered chunks, chunks whose candidate lists overflowed and took the fallback) of the last score_topk pass on this
@@ -877,10 +946,12 @@ class Context:
         scorer's on corpus.dequantize(torch.float16), sgpt_score_topk_q8.  Over a Uint8Corpus (sgpt_score_topk_u8): q of any float
         dtype, upcast to fp32, `dtype` None; queries run in groups of 64, each re-streaming the codes.  Over a BinaryCorpus (sgpt_score_topk_bits): q fp32, normalised
         and UNcentred; stage 1 takes the kp = min(1024, max(k, k * rescore_multiplier)) best by Hamming distance, `rescore` orders
-        them -- "sign" (<q, signs> / sqrt(d), no extra memory), "fp8" (the corpus's fp8 copy), or "none" (Hamming only, kp = k, values
+        them -- "sign" (<q, signs> / sqrt(d), no extra memory), "fp8" (the corpus's fp8 copy), "uint8" (the corpus's uint8 copy,
+        sgpt_score_topk_bits_u8), or "none" (Hamming only, kp = k, values
         agreement / d); a running list must come from calls with the same `rescore`.  corpus.center is subtracted from q here, for the
         bits and for "sign"; rescore="fp8" on a centred corpus is refused (ValueError: the C call takes one query matrix, and the fp8
-        rows need the raw q).  1 <= k <= 1024.  `rescore` / `rescore_multiplier` belong to a BinaryCorpus: any other corpus with
+        rows need the raw q); rescore="uint8" serves a centred corpus too (its entry takes the raw q and the centre: the bits come from
+        q - center, the values from q).  1 <= k <= 1024.  `rescore` / `rescore_multiplier` belong to a BinaryCorpus: any other corpus with
         non-default values of them raises ValueError."""
         if isinstance(corpus, BinaryCorpus):
             return self._score_topk_bits(q, corpus, k, idx_base, run, rescore, rescore_multiplier)

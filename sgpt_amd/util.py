@@ -70,15 +70,16 @@ def pairwise_cos_sim(a, b) -> torch.Tensor:
 
 
 def quantize_embeddings(embeddings, precision: str = "fp8", normalize: bool = True, center=None, keep_fp8: bool = False,
-                        ranges=None, calibration_embeddings=None):
+                        ranges=None, calibration_embeddings=None, keep_uint8: bool = False):
     """Corpus embeddings -> a corpus object for semantic_search / Context.score_topk.  Named after sentence-transformers' later
     `quantize_embeddings`.
     precision="fp8": QuantizedCorpus (e4m3fn codes + one power-of-two scale per row), one byte per element on the device and per
     search pass.  normalize=True L2-normalises the rows first (search with cos_sim), normalize=False keeps them (dot_score).
     precision="ubinary" (sentence-transformers' name for packed unsigned bits): BinaryCorpus, one BIT per element -- Hamming search
     plus re-scoring of an over-fetched candidate list.  center: None | "mean" | a [d] tensor, subtracted from the normalised rows (and
-    later from the queries) before the signs are taken; keep_fp8=True also keeps an fp8 copy to re-score with.  normalize=False is
-    refused: sign bits carry no norms.
+    later from the queries) before the signs are taken; keep_fp8=True also keeps an fp8 copy to re-score with (uncentred corpora
+    only); keep_uint8=True also keeps a uint8 copy of the same rows (its ranges from `ranges` / `calibration_embeddings` as below) to
+    re-score with, centred or not -- binary retrieval plus int8 re-scoring.  normalize=False is refused: sign bits carry no norms.
     precision="uint8" (sentence-transformers' scalar quantisation): Uint8Corpus, one byte per element with one range per DIMENSION --
     256 uniform levels between each column's min and max.  ranges: None | a [2, d] matrix of (min, max) per column, as
     sentence-transformers takes it; calibration_embeddings: rows to take the ranges from instead of the corpus itself (elements outside
@@ -89,11 +90,15 @@ def quantize_embeddings(embeddings, precision: str = "fp8", normalize: bool = Tr
                          "(its codes are the int8 codes + 128; Uint8Corpus.codes_int8() gives the signed view)")
     if precision not in ("fp8", "ubinary", "uint8"):
         raise ValueError(f"quantize_embeddings: unknown precision {precision!r} (only 'fp8', 'ubinary' and 'uint8' are built)")
-    if precision != "uint8" and (ranges is not None or calibration_embeddings is not None):
-        raise ValueError("quantize_embeddings: ranges / calibration_embeddings belong to precision='uint8'")
+    if keep_uint8 and precision != "ubinary":
+        raise ValueError("quantize_embeddings: keep_uint8 belongs to precision='ubinary'")
+    takes_ranges = precision == "uint8" or (precision == "ubinary" and keep_uint8)
+    if not takes_ranges and (ranges is not None or calibration_embeddings is not None):
+        raise ValueError("quantize_embeddings: ranges / calibration_embeddings belong to precision='uint8' (and to precision='ubinary' "
+                         "with keep_uint8=True)")
     if precision == "uint8" and (center is not None or keep_fp8):
         raise ValueError("quantize_embeddings: center / keep_fp8 belong to precision='ubinary'")
-    if precision == "uint8" and ranges is not None and calibration_embeddings is not None:
+    if takes_ranges and ranges is not None and calibration_embeddings is not None:
         raise ValueError("quantize_embeddings: give ranges or calibration_embeddings, not both")
     if precision == "ubinary" and not normalize:
         raise ValueError("quantize_embeddings: precision='ubinary' with normalize=False is refused -- sign bits carry no norms")
@@ -106,19 +111,23 @@ def quantize_embeddings(embeddings, precision: str = "fp8", normalize: bool = Tr
         embeddings = torch.stack(embeddings)
     e = _wrap(embeddings)
     ctx, _ = _ctx_for(e)
+    if isinstance(calibration_embeddings, list):
+        calibration_embeddings = torch.stack(calibration_embeddings)
+    cal = None if calibration_embeddings is None else _wrap(calibration_embeddings)
     if precision == "ubinary":
-        return ctx.binarize_corpus(e, normalize=True, center=center, keep_fp8=keep_fp8)
+        return ctx.binarize_corpus(e, normalize=True, center=center, keep_fp8=keep_fp8, keep_uint8=keep_uint8, ranges=ranges,
+                                   calibration_embeddings=cal)
     if precision == "uint8":
-        if isinstance(calibration_embeddings, list):
-            calibration_embeddings = torch.stack(calibration_embeddings)
-        cal = None if calibration_embeddings is None else _wrap(calibration_embeddings)
         return ctx.scalar_quantize_corpus(e, normalize=normalize, ranges=ranges, calibration_embeddings=cal)
     return ctx.quantize_corpus(e, normalize=normalize)
 
 
 def _binary_rescore(corpus: BinaryCorpus) -> str:
-    """What semantic_search re-scores a BinaryCorpus with: its fp8 copy where it has one and is not centred (a centred corpus needs
-    q - center for the bits and the raw q for the fp8 rows; the search call takes one matrix), the sign bits otherwise."""
+    """What semantic_search re-scores a BinaryCorpus with: its uint8 copy where it has one (centred or not); else its fp8 copy where it
+    has one and is not centred (a centred corpus needs q - center for the bits and the raw q for the fp8 rows; that search call takes
+    one matrix); the sign bits otherwise."""
+    if corpus.u8 is not None:
+        return "uint8"
     return "fp8" if corpus.fp8 is not None and corpus.center is None else "sign"
 
 
@@ -173,8 +182,8 @@ def semantic_search(query_embeddings, corpus_embeddings, query_chunk_size: int =
     """util.semantic_search (util.py:197-258).  Same result contract (per query a list of
     {'corpus_id','score'} sorted by decreasing score); the chunk loops collapse into one fused
     score + running-top-k pass on the GPU when score_function is cos_sim / dot_score (query_chunk_size / corpus_chunk_size are then
-    not used).  Over a BinaryCorpus: cos_sim only, top_k <= 1024, re-scored with the corpus's fp8 copy when it has one and is not
-    centred, with its sign bits otherwise."""
+    not used).  Over a BinaryCorpus: cos_sim only, top_k <= 1024, re-scored with the corpus's uint8 copy when it has one, else with its
+    fp8 copy when it has one and is not centred, with its sign bits otherwise."""
     if isinstance(query_embeddings, list):
         query_embeddings = torch.stack(query_embeddings)
     if isinstance(corpus_embeddings, QuantizedCorpus):     # fp8 corpus (quantize_embeddings): one fused pass over the codes
