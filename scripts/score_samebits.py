@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """score_samebits.py save FILE | check FILE: seeded score_topk results (values, indices, n, filtered-chunk and overflow counts) over
 f16 / fp8 / uint8 corpora at nq = 1, 16, 64, fresh and with a running list, at a materialised size (N = 1000) and the smallest filtered
-one (N = 262 144 + 77), d = 128, k = 11: 36 results.  `save` writes them (run with SGPT_HIP_LIB = the build to compare against), `check`
+one (N = 262 144 + 77), d = 128, k = 11: 36 results; and over the binary corpus at the same two sizes, nq = 16 and 70 (two stage-1 query
+groups), fresh and running, with rescore none / sign / fp8 on an uncentred corpus and rescore uint8 on one centred on its mean: 32
+more.  `save` writes them (run with SGPT_HIP_LIB = the build to compare against), `check`
 requires torch.equal on every one from the library now selected.  For refactors of the scorer that must not change a bit."""
 import os
 import sys
@@ -9,7 +11,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from sgpt_amd import QuantizedCorpus, Uint8Corpus, _lib, get_context  # noqa: E402
+from sgpt_amd import BinaryCorpus, QuantizedCorpus, Uint8Corpus, _lib, get_context  # noqa: E402
 
 
 def results():
@@ -39,6 +41,22 @@ def results():
                 val, idx, n = ctx.score_topk(q, part(700, 700 + N), k, idx_base=700, run=(v0, i0, n0))
                 over = ctx.score_overflow_count()
                 out[f"{fmt} N={N} nq={nq} running"] = (val.cpu().clone(), idx.cpu().clone(), n, over)
+        q70 = torch.nn.functional.normalize(torch.randn(70, d, device="cuda", generator=g), dim=1)
+        cb = ctx.binarize_corpus(c32, keep_fp8=True)
+        cc = ctx.binarize_corpus(c32, center="mean", keep_uint8=True)
+        plain = lambda a, b: BinaryCorpus(cb.bits[a:b], d, fp8=QuantizedCorpus(cb.fp8.codes[a:b], cb.fp8.scale[a:b], True, d))  # noqa: E731
+        centred = lambda a, b: BinaryCorpus(cc.bits[a:b], d, center=cc.center,  # noqa: E731
+                                            u8=Uint8Corpus(cc.u8.codes[a:b].contiguous(), cc.u8.start, cc.u8.step, True, d))
+        for rescore, part in (("none", plain), ("sign", plain), ("fp8", plain), ("uint8", centred)):
+            for nq in (16, 70):
+                q = q70[:nq].contiguous()
+                val, idx, n = ctx.score_topk(q, part(700, 700 + N), k, idx_base=700, rescore=rescore)
+                over = ctx.score_overflow_count()
+                out[f"bits {rescore} N={N} nq={nq} fresh"] = (val.cpu().clone(), idx.cpu().clone(), n, over)
+                run = ctx.score_topk(q, part(0, 700), k, idx_base=0, rescore=rescore)
+                val, idx, n = ctx.score_topk(q, part(700, 700 + N), k, idx_base=700, run=run, rescore=rescore)
+                over = ctx.score_overflow_count()
+                out[f"bits {rescore} N={N} nq={nq} running"] = (val.cpu().clone(), idx.cpu().clone(), n, over)
     return out
 
 

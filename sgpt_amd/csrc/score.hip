@@ -60,32 +60,49 @@ sgpt_status sgpt_scores(sgpt_ctx* c, const void* a, const void* b, int32_t dtype
 //     tile of pre-scaled f16 rows with qscale / qbias (ws2); every launch that reads the corpus is launch_score64u8 (scoreu8.hip),
 //     which takes any number of documents.
 struct Corpus {
-    ScoreCorpusKind kind;
-    const void* base;
-    int dtype, d;
-    size_t rowb;            // bytes of a corpus row
-    long ldw1;              // GemmArgs.ldw of consecutive rows (the Hamming tile counts bytes)
-    const float* scale;     // fp8: [N]
-    long ldb; int qw;       // bits
-    size_t ws6_bytes;       // scratch the launches need (fp8: the f16 rows of a ragged tail, < 256 documents)
+    ScoreCorpusKind kind = SCORE_CORPUS_F32;
+    const void* base = nullptr;
+    int dtype = SGPT_F16, d = 0;    // (dtype: of the query rows the GEMM kernels take; rows: of the corpus too)
+    size_t rowb = 0;                // bytes of a corpus row
+    long ldw1 = 0;                  // GemmArgs.ldw of consecutive rows (the Hamming tile counts bytes)
+    const float* scale = nullptr;   // fp8: [N]
+    long ldb = 0; int qw = 0;       // bits
+    size_t ws6_bytes = 0;           // scratch the launches need (fp8: the f16 rows of a ragged tail, < 256 documents)
     const float *start = nullptr, *step = nullptr; int d0 = 0;        // uint8: ranges [ld], width of the caller's query rows
     const float *qscale = nullptr, *qbias = nullptr;                  // uint8: [64] in ws2, set by the executor
 };
+// every kind: its tag, its rows and their extent; then the fields of its kind by name
+static Corpus corpus_of(ScoreCorpusKind kind, const void* base, int d, size_t rowb, long ldw1) {
+    Corpus cp;
+    cp.kind = kind; cp.base = base; cp.d = d; cp.rowb = rowb; cp.ldw1 = ldw1;
+    return cp;
+}
 static Corpus corpus_rows(const void* rows, int dtype, int d) {
-    return {dtype == SGPT_F32 ? SCORE_CORPUS_F32 : SCORE_CORPUS_16, rows, dtype, d, (size_t)d * (dtype == SGPT_F32 ? 4 : 2), d, nullptr, 0, 0, 0};
+    Corpus cp = corpus_of(dtype == SGPT_F32 ? SCORE_CORPUS_F32 : SCORE_CORPUS_16, rows, d, (size_t)d * (dtype == SGPT_F32 ? 4 : 2), d);
+    cp.dtype = dtype;
+    return cp;
 }
 static Corpus corpus_fp8(const uint8_t* codes, const float* scale, int d) {
-    return {SCORE_CORPUS_FP8, codes, SGPT_F16, d, (size_t)d, d, scale, 0, 0, (size_t)256 * d * 2};
+    Corpus cp = corpus_of(SCORE_CORPUS_FP8, codes, d, (size_t)d, d);
+    cp.scale = scale; cp.ws6_bytes = (size_t)256 * d * 2;
+    return cp;
 }
 static Corpus corpus_bits(const uint8_t* bits, long ldb, int qw, int d) {
-    return {SCORE_CORPUS_BITS, bits, SGPT_F16, d, (size_t)ldb, ldb, nullptr, ldb, qw, 0};
+    Corpus cp = corpus_of(SCORE_CORPUS_BITS, bits, d, (size_t)ldb, ldb);
+    cp.ldb = ldb; cp.qw = qw;
+    return cp;
 }
-
 static Corpus corpus_u8(const uint8_t* codes, const float* start, const float* step, int d0, int ld) {
-    Corpus cp{SCORE_CORPUS_U8, codes, SGPT_F16, ld, (size_t)ld, ld, nullptr, 0, 0, 0};
+    Corpus cp = corpus_of(SCORE_CORPUS_U8, codes, ld, (size_t)ld, ld);
     cp.start = start; cp.step = step; cp.d0 = d0;
     return cp;
 }
+
+// The row layouts the entries check, once each.  `align`: what the entry's kernels load or store the rows with, in bytes.
+//   uint8: codes [N][ld] bytes, ld whole 128-byte pieces that hold the d columns
+static inline bool u8_layout_ok(const void* codes, int64_t d, int64_t ld, size_t align) { return codes && d > 0 && d <= ld && ld >= 128 && ld % 128 == 0 && !((size_t)codes & (align - 1)); }
+//   bits: [N][ldb] bytes, ldb whole dwords that hold the d bits
+static inline bool bits_layout_ok(const void* bits, int64_t d, int64_t ldb, size_t align) { return bits && d > 0 && ldb % 4 == 0 && ldb >= 4 * ((d + 31) / 32) && !((size_t)bits & (align - 1)); }
 
 // one launch that reads documents [doc0, doc0 + h.N) (at row_stride): h.W / h.ldw are set for them already
 static void corpus_gemm(sgpt_ctx* c, const Corpus& cp, int epi, GemmArgs h, long doc0, long row_stride, bool sample, hipStream_t s) {
@@ -366,6 +383,23 @@ sgpt_status sgpt_score_topk(sgpt_ctx* c, const void* q, const void* corpus, int3
     return score_topk_impl(c, q, corpus_rows(corpus, dtype, d), nq, N, k, idx_base, run_val, run_idx, run_val, run_idx, n_run, n_out, stream, nullptr);
 }
 
+// Documents [0, N) in blocks of at most `blk`, the running list chained from block to block: corpus_at(b0, nb) is the corpus of documents
+// [b0, b0 + nb) (and may launch what makes it).
+extern "C++" {     // (a template cannot have the C linkage this file is wrapped in)
+template <class CorpusAt>
+static sgpt_status score_topk_blocks(sgpt_ctx* c, const void* q, CorpusAt corpus_at, int64_t blk, int32_t nq, int64_t N, int32_t k,
+                                     int64_t idx_base, float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out, void* stream) {
+    int32_t have = n_run;
+    for (int64_t b0 = 0; b0 < N; b0 += blk) {
+        const int64_t nb = N - b0 < blk ? N - b0 : blk;
+        sgpt_status st = score_topk_impl(c, q, corpus_at(b0, nb), nq, nb, k, idx_base + b0, run_val, run_idx, run_val, run_idx, have, &have, stream, nullptr);
+        if (st != SGPT_OK) return st;
+    }
+    if (n_out) *n_out = have;
+    return SGPT_OK;
+}
+}  // extern "C++"
+
 // The same over a corpus of e4m3fn codes + one power-of-two scale per document (include/sgpt_hip.h).
 sgpt_status sgpt_score_topk_q8(sgpt_ctx* c, const void* q, const uint8_t* codes, const float* scale, int32_t nq, int64_t N, int32_t d,
                                int32_t k, int64_t idx_base, float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out, void* stream) {
@@ -381,15 +415,11 @@ sgpt_status sgpt_score_topk_q8(sgpt_ctx* c, const void* q, const uint8_t* codes,
     HIPC(c, hipSetDevice(c->device));
     sgpt_status st = ensure(c, &c->ws6, &c->ws6_bytes, (size_t)(N < blk ? N : blk) * d * 2);
     if (st != SGPT_OK) return st;
-    int32_t have = n_run;
-    for (int64_t b0 = 0; b0 < N; b0 += blk) {
-        const int64_t nb = N - b0 < blk ? N - b0 : blk;
+    auto f16_block = [&](int64_t b0, int64_t nb) {
         launch_fp8_dequant_rows(codes + (size_t)b0 * d, scale + b0, nb, d, c->ws6, SGPT_F16, (hipStream_t)stream);
-        st = score_topk_impl(c, q, corpus_rows(c->ws6, SGPT_F16, d), nq, nb, k, idx_base + b0, run_val, run_idx, run_val, run_idx, have, &have, stream, nullptr);
-        if (st != SGPT_OK) return st;
-    }
-    if (n_out) *n_out = have;
-    return SGPT_OK;
+        return corpus_rows(c->ws6, SGPT_F16, d);
+    };
+    return score_topk_blocks(c, q, f16_block, blk, nq, N, k, idx_base, run_val, run_idx, n_run, n_out, stream);
 }
 
 // The same over a corpus of uint8 codes with one range per dimension (include/sgpt_hip.h): at most 64 fp32 query rows per call, every
@@ -398,20 +428,12 @@ sgpt_status sgpt_score_topk_q8(sgpt_ctx* c, const void* q, const uint8_t* codes,
 sgpt_status sgpt_score_topk_u8(sgpt_ctx* c, const float* q, const uint8_t* codes, const float* start, const float* step, int32_t nq,
                                int64_t N, int32_t d, int32_t ld, int32_t k, int64_t idx_base, float* run_val, int64_t* run_idx, int32_t n_run,
                                int32_t* n_out, void* stream) {
-    if (!c || !q || !codes || !start || !step || !run_val || !run_idx || nq <= 0 || nq > 64 || N <= 0 || d <= 0 || ld < 128 || ld % 128 || d > ld ||
-        k <= 0 || n_run < 0 || n_run > k || ((size_t)codes & 15))
+    if (!c || !q || !start || !step || !run_val || !run_idx || nq <= 0 || nq > 64 || N <= 0 || !u8_layout_ok(codes, d, ld, 16) ||
+        k <= 0 || n_run < 0 || n_run > k)
         return fail(c, SGPT_ERR_INVALID, "sgpt_score_topk_u8: bad arguments (1 <= nq <= 64, ld % 128 == 0, 0 < d <= ld, 0 <= n_run <= k, codes "
                                          "16-byte aligned)");
-    const int64_t blk = (int64_t)1 << 30;
-    int32_t have = n_run;
-    for (int64_t b0 = 0; b0 < N; b0 += blk) {
-        const int64_t nb = N - b0 < blk ? N - b0 : blk;
-        sgpt_status st = score_topk_impl(c, q, corpus_u8(codes + (size_t)b0 * ld, start, step, d, ld), nq, nb, k, idx_base + b0, run_val, run_idx,
-                                         run_val, run_idx, have, &have, stream, nullptr);
-        if (st != SGPT_OK) return st;
-    }
-    if (n_out) *n_out = have;
-    return SGPT_OK;
+    auto block = [&](int64_t b0, int64_t) { return corpus_u8(codes + (size_t)b0 * ld, start, step, d, ld); };
+    return score_topk_blocks(c, q, block, (int64_t)1 << 30, nq, N, k, idx_base, run_val, run_idx, n_run, n_out, stream);
 }
 
 sgpt_status sgpt_u8_col_minmax(sgpt_ctx* c, const float* x, int64_t n, int32_t d, int32_t accumulate, float* col_min, float* col_max,
@@ -425,7 +447,7 @@ sgpt_status sgpt_u8_col_minmax(sgpt_ctx* c, const float* x, int64_t n, int32_t d
 
 sgpt_status sgpt_u8_quantize_rows(sgpt_ctx* c, const float* x, int64_t n, int32_t d, int32_t ld, const float* start, const float* step,
                                   uint8_t* codes, void* stream) {
-    if (!c || !x || !start || !step || !codes || n <= 0 || d <= 0 || ld < 128 || ld % 128 || d > ld || ((size_t)codes & 3))
+    if (!c || !x || !start || !step || n <= 0 || !u8_layout_ok(codes, d, ld, 4))
         return fail(c, SGPT_ERR_INVALID, "sgpt_u8_quantize_rows: bad arguments (ld % 128 == 0, 0 < d <= ld)");
     HIPC(c, hipSetDevice(c->device));
     launch_u8_quant_rows(x, n, d, ld, start, step, codes, (hipStream_t)stream);
@@ -435,7 +457,7 @@ sgpt_status sgpt_u8_quantize_rows(sgpt_ctx* c, const float* x, int64_t n, int32_
 
 sgpt_status sgpt_u8_dequantize_rows(sgpt_ctx* c, const uint8_t* codes, int64_t n, int32_t ld, const float* start, const float* step, void* out,
                                     int32_t out_dtype, void* stream) {
-    if (!c || !codes || !start || !step || !out || n <= 0 || ld < 128 || ld % 128 || ((size_t)codes & 3) || ((size_t)out & 15) ||
+    if (!c || !start || !step || !out || n <= 0 || !u8_layout_ok(codes, ld, ld, 4) || ((size_t)out & 15) ||
         (out_dtype != SGPT_F32 && out_dtype != SGPT_BF16 && out_dtype != SGPT_F16))
         return fail(c, SGPT_ERR_INVALID, "sgpt_u8_dequantize_rows: bad arguments (ld % 128 == 0, out 16-byte aligned)");
     HIPC(c, hipSetDevice(c->device));
@@ -476,110 +498,105 @@ static void two_stage_finish(const TwoStage& t, float* run_val, int64_t* run_idx
 
 static inline int bits_query_words(int d) { return (d + 127) / 128 * 4; }     // dwords of a packed query row: whole 16-byte pieces
 
-// Stage 1 of the binary-corpus searches: the kp best by agreement (a descending, index ascending) of every packed query row, a fresh list
-// per call, into (t.lv, t.li).  Queries in groups of 64 (re-streaming 96-byte rows is cheap), documents in blocks the launches index
-// with 32 bits, chained through the stage-1 list.
-static sgpt_status bits_stage1(sgpt_ctx* c, const uint32_t* qbits, int qw, const uint8_t* bits, int64_t ldb, int32_t nq, int64_t N, int32_t d,
-                               int32_t kp, int64_t idx_base, const TwoStage& t, void* stream) {
-    const int64_t blk = (int64_t)1 << 30;
+// The two-stage search over packed sign bits that sgpt_score_topk_bits and sgpt_score_topk_bits_u8 are: the bits of q - center (center
+// null: of q) packed, stage 1, the caller's second stage, the running list appended and selected.  ws4 head = [packed query bits | head_b
+// bytes of the caller].  rescore(t, head, s) launches what values the candidates (t.lv, t.li) into (t.cv, t.ci); `head` is the caller's
+// part of the head.  entry_ok: the caller's own argument checks; `bad`: its message for them and for the shared ones.
+// Stage 1: the kp best by agreement (a descending, index ascending) of every packed query row, a fresh list per call, into (t.lv, t.li).
+// Queries in groups of 64 (re-streaming 96-byte rows is cheap), documents in blocks the launches index with 32 bits, chained through the
+// stage-1 list.
+extern "C++" {
+template <class Rescore>
+static sgpt_status bits_two_stage(sgpt_ctx* c, const char* bad, bool entry_ok, const float* q, const float* center, const uint8_t* bits,
+                                  int64_t ldb, int32_t nq, int64_t N, int32_t d, int32_t k, int32_t kp, int64_t idx_base, float* run_val,
+                                  int64_t* run_idx, int32_t n_run, int32_t* n_out, void* stream, size_t head_b, Rescore rescore) {
+    if (!entry_ok || !c || !q || !run_val || !run_idx || nq <= 0 || N <= 0 || !bits_layout_ok(bits, d, ldb, 4) || k <= 0 || kp < k || kp > 1024 ||
+        n_run < 0 || n_run > k)
+        return fail(c, SGPT_ERR_INVALID, bad);
+    HIPC(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int qw = bits_query_words(d);
+    const size_t qbits_b = align_up((size_t)nq * qw * 4, 256);
+    TwoStage t;
+    sgpt_status st = two_stage_carve(c, qbits_b + head_b, 0, nq, kp, k, t);
+    if (st != SGPT_OK) return st;
+    uint32_t* qbits = (uint32_t*)t.head;
+    launch_pack_sign_bits(q, nq, d, center, (uint8_t*)qbits, (long)qw * 4, s);
+    auto block = [&](int64_t b0, int64_t) { return corpus_bits(bits + (size_t)b0 * ldb, (long)ldb, qw, d); };
     for (int32_t g0 = 0; g0 < nq; g0 += 64) {
-        const int32_t gn = nq - g0 < 64 ? nq - g0 : 64;
-        float* gv = t.lv + (size_t)g0 * kp;
-        int64_t* gi = t.li + (size_t)g0 * kp;
-        int32_t have = 0;
-        for (int64_t b0 = 0; b0 < N; b0 += blk) {
-            const int64_t nb = N - b0 < blk ? N - b0 : blk;
-            sgpt_status st = score_topk_impl(c, qbits + (size_t)g0 * qw, corpus_bits(bits + (size_t)b0 * ldb, (long)ldb, qw, d), gn, nb, kp,
-                                             idx_base + b0, gv, gi, gv, gi, have, &have, stream, nullptr);
-            if (st != SGPT_OK) return st;
-        }
+        st = score_topk_blocks(c, qbits + (size_t)g0 * qw, block, (int64_t)1 << 30, nq - g0 < 64 ? nq - g0 : 64, N, kp, idx_base,
+                               t.lv + (size_t)g0 * kp, t.li + (size_t)g0 * kp, 0, nullptr, stream);
+        if (st != SGPT_OK) return st;
     }
+    rescore(t, t.head + qbits_b, s);
+    two_stage_finish(t, run_val, run_idx, k, n_run, nq, kp, s);
+    if (n_out) *n_out = list_fill(n_run, N, k);
+    HIPC(c, hipGetLastError());
     return SGPT_OK;
 }
+}  // extern "C++"
 
 // Hamming search over packed sign bits with optional re-scoring of the over-fetched candidates (include/sgpt_hip.h).
 sgpt_status sgpt_score_topk_bits(sgpt_ctx* c, const float* q, const uint8_t* bits, int64_t ldb, int32_t nq, int64_t N, int32_t d, int32_t k,
                                  int32_t kp, int32_t mode, const uint8_t* codes, const float* scale, int64_t idx_base, float* run_val,
                                  int64_t* run_idx, int32_t n_run, int32_t* n_out, void* stream) {
-    if (!c || !q || !bits || !run_val || !run_idx || nq <= 0 || N <= 0 || d <= 0 || ldb % 4 || ldb < 4 * (((int64_t)d + 31) / 32) ||
-        k <= 0 || kp < k || kp > 1024 || mode < 0 || mode > 2 || (mode == 0 && kp != k) || (mode == 2 && (!codes || !scale)) ||
-        n_run < 0 || n_run > k || ((size_t)bits & 3))
-        return fail(c, SGPT_ERR_INVALID, "sgpt_score_topk_bits: bad arguments (ldb % 4 == 0, ldb >= 4 ceil(d / 32), 0 < k <= kp <= 1024, "
-                                         "mode 0 with kp == k, mode 2 with codes and scale, 0 <= n_run <= k)");
-    HIPC(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int qw = bits_query_words(d);
-    TwoStage t;
-    sgpt_status st = two_stage_carve(c, align_up((size_t)nq * qw * 4, 256), 0, nq, kp, k, t);
-    if (st != SGPT_OK) return st;
-    uint32_t* qbits = (uint32_t*)t.head;
-    launch_pack_sign_bits(q, nq, d, nullptr, (uint8_t*)qbits, (long)qw * 4, s);
-    st = bits_stage1(c, qbits, qw, bits, ldb, nq, N, d, kp, idx_base, t, stream);
-    if (st != SGPT_OK) return st;
-    // stage 2: the candidates' values by `mode` | the running list -> top-k (as sgpt_score_topk_refined)
-    launch_rescore_bits(mode, q, bits, (long)ldb, codes, ((long)d + 7) / 8 * 8, scale, t.lv, t.li, kp, nq, kp, d, idx_base, N, t.cv, t.ci, t.ldc, s);
-    two_stage_finish(t, run_val, run_idx, k, n_run, nq, kp, s);
-    if (n_out) *n_out = list_fill(n_run, N, k);
-    HIPC(c, hipGetLastError());
-    return SGPT_OK;
+    const bool ok = mode >= 0 && mode <= 2 && !(mode == 0 && kp != k) && !(mode == 2 && (!codes || !scale));
+    // stage 2: the candidates' values by `mode` (as sgpt_score_topk_refined)
+    auto rescore = [&](const TwoStage& t, char*, hipStream_t s) {
+        launch_rescore_bits(mode, q, bits, (long)ldb, codes, ((long)d + 7) / 8 * 8, scale, t.lv, t.li, kp, nq, kp, d, idx_base, N, t.cv, t.ci, t.ldc, s);
+    };
+    return bits_two_stage(c, "sgpt_score_topk_bits: bad arguments (ldb % 4 == 0, ldb >= 4 ceil(d / 32), 0 < k <= kp <= 1024, "
+                             "mode 0 with kp == k, mode 2 with codes and scale, 0 <= n_run <= k)",
+                          ok, q, nullptr, bits, ldb, nq, N, d, k, kp, idx_base, run_val, run_idx, n_run, n_out, stream, 0, rescore);
+}
+
+// What launch_u8_rescore reads of the queries, carved from `b` and made there: [qs fp32 [nq][ld] | qbias fp32 [nq]].
+struct U8RescoreQueries { const float *qs, *qbias; };
+static inline size_t u8_rescore_queries_bytes(int nq, int ld) { return align_up((size_t)nq * ld * 4, 256) + align_up((size_t)nq * 4, 256); }
+static U8RescoreQueries u8_rescore_queries(char* b, const float* q, const float* start, const float* step, int nq, int d, int ld, hipStream_t s) {
+    float* qs = (float*)b;
+    float* qbias = (float*)(b + align_up((size_t)nq * ld * 4, 256));
+    launch_u8_rescore_prepare(q, start, step, nq, d, ld, qs, qbias, s);
+    return {qs, qbias};
 }
 
 // The same first stage with a uint8 second stage (include/sgpt_hip.h): the bits are searched with q - center, the candidates re-scored
-// from the codes with the raw q.  ws4 head = [packed query bits | qs fp32 [nq][ld] | qbias fp32 [nq]].
+// from the codes with the raw q.
 sgpt_status sgpt_score_topk_bits_u8(sgpt_ctx* c, const float* q, const float* center, const uint8_t* bits, int64_t ldb, const uint8_t* codes,
                                     const float* start, const float* step, int32_t ld, int32_t nq, int64_t N, int32_t d, int32_t k,
                                     int32_t kp, int64_t idx_base, float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out,
                                     void* stream) {
-    if (!c || !q || !bits || !codes || !start || !step || !run_val || !run_idx || nq <= 0 || N <= 0 || d <= 0 || ldb % 4 ||
-        ldb < 4 * (((int64_t)d + 31) / 32) || ld < 128 || ld % 128 || d > ld || k <= 0 || kp < k || kp > 1024 || n_run < 0 || n_run > k ||
-        ((size_t)bits & 3) || ((size_t)codes & 15))
-        return fail(c, SGPT_ERR_INVALID, "sgpt_score_topk_bits_u8: bad arguments (ldb % 4 == 0, ldb >= 4 ceil(d / 32), ld % 128 == 0, 0 < d <= ld, "
-                                         "codes 16-byte aligned, 0 < k <= kp <= 1024, 0 <= n_run <= k)");
-    HIPC(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int qw = bits_query_words(d);
-    const size_t qbits_b = align_up((size_t)nq * qw * 4, 256), qs_b = align_up((size_t)nq * ld * 4, 256), qb_b = align_up((size_t)nq * 4, 256);
-    TwoStage t;
-    sgpt_status st = two_stage_carve(c, qbits_b + qs_b + qb_b, 0, nq, kp, k, t);
-    if (st != SGPT_OK) return st;
-    uint32_t* qbits = (uint32_t*)t.head;
-    float* qs = (float*)(t.head + qbits_b);
-    float* qbias = (float*)(t.head + qbits_b + qs_b);
-    launch_pack_sign_bits(q, nq, d, center, (uint8_t*)qbits, (long)qw * 4, s);
-    launch_u8_rescore_prepare(q, start, step, nq, d, ld, qs, qbias, s);
-    st = bits_stage1(c, qbits, qw, bits, ldb, nq, N, d, kp, idx_base, t, stream);
-    if (st != SGPT_OK) return st;
-    // stage 2: <q, x^_n> of the candidates from the codes | the running list -> top-k
-    launch_u8_rescore(qs, qbias, codes, ld, t.li, kp, nq, kp, idx_base, N, t.cv, t.ci, t.ldc, s);
-    two_stage_finish(t, run_val, run_idx, k, n_run, nq, kp, s);
-    if (n_out) *n_out = list_fill(n_run, N, k);
-    HIPC(c, hipGetLastError());
-    return SGPT_OK;
+    const bool ok = start && step && u8_layout_ok(codes, d, ld, 16);
+    // stage 2: <q, x^_n> of the candidates from the codes
+    auto rescore = [&](const TwoStage& t, char* head, hipStream_t s) {
+        const U8RescoreQueries u = u8_rescore_queries(head, q, start, step, nq, d, ld, s);
+        launch_u8_rescore(u.qs, u.qbias, codes, ld, t.li, kp, nq, kp, idx_base, N, t.cv, t.ci, t.ldc, s);
+    };
+    return bits_two_stage(c, "sgpt_score_topk_bits_u8: bad arguments (ldb % 4 == 0, ldb >= 4 ceil(d / 32), ld % 128 == 0, 0 < d <= ld, "
+                             "codes 16-byte aligned, 0 < k <= kp <= 1024, 0 <= n_run <= k)",
+                          ok, q, center, bits, ldb, nq, N, d, k, kp, idx_base, run_val, run_idx, n_run, n_out, stream,
+                          u8_rescore_queries_bytes(nq, ld), rescore);
 }
 
 // The second stage of the above alone: the values of the caller's candidate lists (include/sgpt_hip.h).  ws4 = [qs | qbias].
 sgpt_status sgpt_u8_rescore(sgpt_ctx* c, const float* q, const uint8_t* codes, const float* start, const float* step, int32_t nq, int64_t N,
                             int32_t d, int32_t ld, const int64_t* idx, int64_t ld_idx, int32_t m, int64_t idx_base, float* out_val,
                             int64_t* out_idx, void* stream) {
-    if (!c || !q || !codes || !start || !step || !idx || !out_val || !out_idx || nq <= 0 || N <= 0 || d <= 0 || ld < 128 || ld % 128 || d > ld ||
-        m <= 0 || ld_idx < m || ((size_t)codes & 15))
+    if (!c || !q || !start || !step || !idx || !out_val || !out_idx || nq <= 0 || N <= 0 || !u8_layout_ok(codes, d, ld, 16) || m <= 0 || ld_idx < m)
         return fail(c, SGPT_ERR_INVALID, "sgpt_u8_rescore: bad arguments (ld % 128 == 0, 0 < d <= ld, codes 16-byte aligned, 0 < m <= ld_idx)");
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    const size_t qs_b = align_up((size_t)nq * ld * 4, 256);
-    sgpt_status st = ensure(c, &c->ws4, &c->ws4_bytes, qs_b + align_up((size_t)nq * 4, 256));
+    sgpt_status st = ensure(c, &c->ws4, &c->ws4_bytes, u8_rescore_queries_bytes(nq, ld));
     if (st != SGPT_OK) return st;
-    float* qs = (float*)c->ws4;
-    float* qbias = (float*)((char*)c->ws4 + qs_b);
-    launch_u8_rescore_prepare(q, start, step, nq, d, ld, qs, qbias, s);
-    launch_u8_rescore(qs, qbias, codes, ld, idx, (long)ld_idx, nq, m, idx_base, N, out_val, out_idx, m, s);
+    const U8RescoreQueries u = u8_rescore_queries((char*)c->ws4, q, start, step, nq, d, ld, s);
+    launch_u8_rescore(u.qs, u.qbias, codes, ld, idx, (long)ld_idx, nq, m, idx_base, N, out_val, out_idx, m, s);
     HIPC(c, hipGetLastError());
     return SGPT_OK;
 }
 
 sgpt_status sgpt_pack_sign_bits(sgpt_ctx* c, const float* x, int64_t n, int32_t d, const float* center, uint8_t* bits, int64_t ldb,
                                 void* stream) {
-    if (!c || !x || !bits || n <= 0 || d <= 0 || ldb % 4 || ldb < 4 * (((int64_t)d + 31) / 32))
+    if (!c || !x || n <= 0 || !bits_layout_ok(bits, d, ldb, 1))
         return fail(c, SGPT_ERR_INVALID, "sgpt_pack_sign_bits: bad arguments (ldb % 4 == 0, ldb >= 4 ceil(d / 32))");
     HIPC(c, hipSetDevice(c->device));
     launch_pack_sign_bits(x, n, d, center, bits, ldb, (hipStream_t)stream);

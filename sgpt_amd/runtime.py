@@ -2,7 +2,6 @@
 memory (torch.empty / .data_ptr()) and to name the current HIP stream -- every computation is
 a call into libsgpt_hip.so.  No torch compute op stands in for a kernel here."""
 import ctypes as C
-from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import numpy as np
@@ -10,6 +9,7 @@ import torch
 
 from . import _lib
 from ._lib import SGPT_BF16, SGPT_F16, SGPT_F32, POOL_MODES
+from .corpus import CORPUS_KINDS, RESCORE_MODES, BinaryCorpus, CorpusBuilders, QuantizedCorpus, Uint8Corpus, _no_rescore  # noqa: F401  (re-exported)
 
 # torch dtype <-> element-type code of include/sgpt_hip.h
 DT_CODE = {torch.float32: SGPT_F32, torch.bfloat16: SGPT_BF16, torch.float16: SGPT_F16}
@@ -22,104 +22,6 @@ def _stream_ptr(device) -> C.c_void_p:
 def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
 
-
-@dataclass
-class QuantizedCorpus:
-    """A corpus held as fp8: `codes` uint8 [N, d] (OCP e4m3fn) and `scale` fp32 [N], one power of two per document (the format of
-    include/sgpt_hip.h::sgpt_score_topk_q8; document n = codes[n] * scale[n]).  `normalized`: the rows were L2-normalised before
-    quantisation (cosine scores) or not (dot scores).  Built by Context.quantize_corpus / util.quantize_embeddings."""
-    codes: torch.Tensor
-    scale: torch.Tensor
-    normalized: bool = True
-    dim: Optional[int] = None        # width of the embeddings; codes carry zero columns up to the next multiple of 8 (None: no padding)
-
-    def __len__(self) -> int:
-        return int(self.codes.shape[0])
-
-    @property
-    def nbytes(self) -> int:
-        return self.codes.numel() * self.codes.element_size() + self.scale.numel() * self.scale.element_size()
-
-    def dequantize(self, dtype=torch.float32) -> torch.Tensor:
-        """The rows the scorer sees, codes * scale, on the device: exact in fp32, and in f16 / bf16 while codes * scale is a value
-        of that format (unit rows are).  As wide as `codes` (zero columns behind `dim` included)."""
-        return get_context(self.codes.device).fp8_dequantize_rows(self.codes, self.scale, out_dtype=dtype)
-
-
-class BinaryCorpus:
-    """A corpus held as packed sign bits: `bits` uint8 [N, ldb], ldb = 4 * ceil(dim / 32) (include/sgpt_hip.h::sgpt_score_topk_bits;
-    dimension i of a document is bit 7 - i % 8 of byte i / 8, set when the element is > 0 -- numpy.packbits order, "ubinary" in
-    sentence-transformers).  `center` fp32 [dim] or None: what was subtracted from the normalised rows before the signs were taken, and
-    is subtracted from the queries; `fp8`: an optional QuantizedCorpus of the same (uncentred, normalised) rows for re-scoring; `u8`: an
-    optional Uint8Corpus of the same rows for re-scoring (rescore="uint8": binary retrieval + int8 re-scoring, with or without a
-    centre).  Built by Context.binarize_corpus / util.quantize_embeddings(precision="ubinary")."""
-
-    def __init__(self, bits: torch.Tensor, dim: int, center: Optional[torch.Tensor] = None, fp8: Optional[QuantizedCorpus] = None,
-                 u8: Optional["Uint8Corpus"] = None):
-        dim = int(dim)
-        if bits.dim() != 2 or bits.dtype != torch.uint8:
-            raise ValueError(f"BinaryCorpus: bits are uint8 [N, ldb], got {bits.dtype} {tuple(bits.shape)}")
-        if dim < 1 or bits.shape[1] % 4 or bits.shape[1] < 4 * ((dim + 31) // 32):
-            raise ValueError(f"BinaryCorpus: {bits.shape[1]} bytes per row do not hold dim = {dim} (ldb % 4 == 0, ldb >= 4 * ceil(dim / 32))")
-        if center is not None and tuple(center.shape) != (dim,):
-            raise ValueError(f"BinaryCorpus: center must be [{dim}], got {tuple(center.shape)}")
-        if fp8 is not None and (not isinstance(fp8, QuantizedCorpus) or len(fp8) != bits.shape[0] or
-                                fp8.codes.shape[1] != (dim + 7) // 8 * 8):
-            raise ValueError("BinaryCorpus: fp8 must be a QuantizedCorpus of the same rows (codes [N, ceil(dim / 8) * 8])")
-        if u8 is not None and (not isinstance(u8, Uint8Corpus) or len(u8) != bits.shape[0] or u8.dim != dim):
-            raise ValueError(f"BinaryCorpus: u8 must be a Uint8Corpus of the same rows (N = {bits.shape[0]}, dim = {dim})")
-        self.bits, self.dim, self.center, self.fp8, self.u8 = bits, dim, center, fp8, u8
-
-    def __len__(self) -> int:
-        return int(self.bits.shape[0])
-
-    @property
-    def nbytes(self) -> int:
-        n = self.bits.numel()
-        if self.center is not None:
-            n += self.center.numel() * self.center.element_size()
-        if self.fp8 is not None:
-            n += self.fp8.nbytes
-        if self.u8 is not None:
-            n += self.u8.nbytes
-        return n
-
-
-class Uint8Corpus:
-    """A corpus held as uint8 codes with one range per dimension (include/sgpt_hip.h::sgpt_score_topk_u8; sentence-transformers'
-    precision="uint8"): `codes` uint8 [N, ld], ld = ceil(dim / 128) * 128, pad columns 128; `start`, `step` fp32 [ld], pad columns 0;
-    document n = start + codes[n] * step.  `normalized`: the rows were L2-normalised before quantisation (cosine scores) or not (dot
-    scores).  Built by Context.scalar_quantize_corpus / util.quantize_embeddings(precision="uint8")."""
-
-    def __init__(self, codes: torch.Tensor, start: torch.Tensor, step: torch.Tensor, normalized: bool = True, dim: Optional[int] = None):
-        if codes.dim() != 2 or codes.dtype != torch.uint8 or codes.shape[1] == 0 or codes.shape[1] % 128:
-            raise ValueError(f"Uint8Corpus: codes are uint8 [N, ld] with ld % 128 == 0, got {codes.dtype} {tuple(codes.shape)}")
-        ld = int(codes.shape[1])
-        dim = ld if dim is None else int(dim)
-        if dim < 1 or dim > ld or (dim + 127) // 128 * 128 != ld:
-            raise ValueError(f"Uint8Corpus: {ld} bytes per row do not hold dim = {dim} (ld = ceil(dim / 128) * 128)")
-        if tuple(start.shape) != (ld,) or tuple(step.shape) != (ld,):
-            raise ValueError(f"Uint8Corpus: start and step must be [{ld}], got {tuple(start.shape)} and {tuple(step.shape)}")
-        self.codes, self.start, self.step, self.normalized, self.dim = codes, start, step, bool(normalized), dim
-
-    def __len__(self) -> int:
-        return int(self.codes.shape[0])
-
-    @property
-    def nbytes(self) -> int:
-        return self.codes.numel() + self.start.numel() * self.start.element_size() + self.step.numel() * self.step.element_size()
-
-    def dequantize(self, dtype=torch.float32) -> torch.Tensor:
-        """The rows the scorer stands for, start + codes * step (product and sum each rounded once in fp32, then to `dtype`), on the
-        device.  As wide as `codes` (zero columns behind `dim` included)."""
-        return get_context(self.codes.device).u8_dequantize_rows(self.codes, self.start, self.step, out_dtype=dtype)
-
-    def codes_int8(self) -> torch.Tensor:
-        """sentence-transformers' "int8" view of the same levels: codes - 128 as int8 [N, dim]."""
-        return (self.codes[:, :self.dim].to(torch.int16) - 128).to(torch.int8)
-
-
-RESCORE_MODES = {"none": 0, "sign": 1, "fp8": 2}      # the modes of sgpt_score_topk_bits; "uint8" is an entry of its own (_bits_u8)
 
 _contexts = {}
 
@@ -138,7 +40,10 @@ def get_context(device=None) -> "Context":
     return _contexts[idx]
 
 
-class Context:
+class Context(CorpusBuilders):
+    """(The corpus builders and the row conversions under them -- quantize_corpus, scalar_quantize_corpus, binarize_corpus, u8_*,
+    pack_sign_bits, rescore_u8 -- are inherited from corpus.py.)"""
+
     def __init__(self, device_index: int):
         self.lib = _lib.load()
         self.device = torch.device("cuda", device_index)
@@ -165,6 +70,19 @@ class Context:
         if a.dim() == 1:
             a = a.unsqueeze(0)
         return a.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _run_list(self, run, nq: int, k: int) -> Tuple[torch.Tensor, torch.Tensor, int]:
+        """The running list of a score + top-k call, (values fp32 [nq, k], indices int64 [nq, k], entries so far): the caller's `run`,
+        or a fresh one."""
+        if run is not None:
+            return run
+        return (torch.empty((nq, k), dtype=torch.float32, device=self.device),
+                torch.empty((nq, k), dtype=torch.int64, device=self.device), 0)
+
+    def _u8_operands(self, corpus: Uint8Corpus) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(codes, start, step) of a Uint8Corpus as the C entries take them: on this device, contiguous, the ranges fp32."""
+        return (corpus.codes.to(self.device).contiguous(), corpus.start.to(device=self.device, dtype=torch.float32).contiguous(),
+                corpus.step.to(device=self.device, dtype=torch.float32).contiguous())
 
     # ---- a4: stand-alone pooling ----
     def pool(self, hidden: torch.Tensor, mask: torch.Tensor, mode: str = "weightedmean",
@@ -308,308 +226,6 @@ class Context:
                                                     DT_CODE[out_dtype],
                                                     _stream_ptr(self.device)), "sgpt_fp8_dequantize_rows")
         return out
-
-    def quantize_corpus(self, emb, normalize: bool = True, block_rows: int = 65536) -> QuantizedCorpus:
-        """Embeddings [N, d] -> QuantizedCorpus (d padded with zero columns to a multiple of 8): rows L2-normalised (normalize=True, cosine search) or taken as they are
-        (dot scores), then sgpt_fp8_quantize_rows.  Works in blocks of `block_rows` rows, so the fp32 (normalised) copy of a large
-        corpus never exists whole on the device; `emb` may live on the host."""
-        if not isinstance(emb, torch.Tensor):
-            emb = torch.as_tensor(np.asarray(emb))
-        if emb.dim() != 2 or emb.shape[0] == 0 or emb.shape[1] == 0:
-            raise ValueError(f"quantize_corpus needs a non-empty [N, d] matrix, got {tuple(emb.shape)}")
-        N, d0 = emb.shape
-        d = (d0 + 7) // 8 * 8          # the scorer takes d % 8 == 0: zero columns (zero codes) change no score
-        codes = torch.empty((N, d), dtype=torch.uint8, device=self.device)
-        scale = torch.empty((N,), dtype=torch.float32, device=self.device)
-        for r0 in range(0, N, block_rows):
-            n = min(block_rows, N - r0)
-            blk = self._dev_f32(emb[r0:r0 + n])
-            if normalize:
-                blk = self.l2_normalize(blk)
-            if d != d0:
-                blk = torch.nn.functional.pad(blk, (0, d - d0))
-            self._chk(self.lib.sgpt_fp8_quantize_rows(self.handle, _p(blk), n, d, _p(codes[r0:r0 + n]), _p(scale[r0:r0 + n]),
-                                                      _stream_ptr(self.device)), "sgpt_fp8_quantize_rows")
-        return QuantizedCorpus(codes, scale, bool(normalize), d0)
-
-    # ---- uint8 corpus: scalar quantisation with one range per dimension ----
-    def u8_col_minmax(self, x, run: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Column min / max of fp32 rows [n, d] (NaN-propagating); run = (min, max) of earlier blocks of rows, updated in place."""
-        x = self._dev_f32(x)
-        n, d = x.shape
-        if n == 0 or d == 0:
-            raise ValueError(f"u8_col_minmax needs a non-empty [n, d] matrix, got {tuple(x.shape)}")
-        if run is None:
-            mn = torch.empty((d,), dtype=torch.float32, device=self.device)
-            mx = torch.empty((d,), dtype=torch.float32, device=self.device)
-        else:
-            mn, mx = run
-        self._chk(self.lib.sgpt_u8_col_minmax(self.handle, _p(x), n, d, 0 if run is None else 1, _p(mn), _p(mx),
-                                              _stream_ptr(self.device)), "sgpt_u8_col_minmax")
-        return mn, mx
-
-    def u8_quantize_rows(self, x, start: torch.Tensor, step: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """fp32 rows [n, d] -> uint8 [n, ld] by the rule of include/sgpt_hip.h; start / step fp32 [ld], ld = ceil(d / 128) * 128."""
-        x = self._dev_f32(x)
-        n, d = x.shape
-        ld = int(start.shape[0])
-        if out is None:
-            out = torch.empty((n, ld), dtype=torch.uint8, device=self.device)
-        self._chk(self.lib.sgpt_u8_quantize_rows(self.handle, _p(x), n, d, ld, _p(start), _p(step), _p(out),
-                                                 _stream_ptr(self.device)), "sgpt_u8_quantize_rows")
-        return out
-
-    def u8_dequantize_rows(self, codes: torch.Tensor, start: torch.Tensor, step: torch.Tensor, out_dtype=torch.float32) -> torch.Tensor:
-        codes = codes.to(device=self.device, dtype=torch.uint8).contiguous()
-        start = start.to(device=self.device, dtype=torch.float32).contiguous()
-        step = step.to(device=self.device, dtype=torch.float32).contiguous()
-        n, ld = codes.shape
-        out = torch.empty((n, ld), dtype=out_dtype, device=self.device)
-        self._chk(self.lib.sgpt_u8_dequantize_rows(self.handle, _p(codes), n, ld, _p(start), _p(step), _p(out), DT_CODE[out_dtype],
-                                                   _stream_ptr(self.device)), "sgpt_u8_dequantize_rows")
-        return out
-
-    def u8_prepare_queries(self, q, start: torch.Tensor, step: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """The scorer's query prologue on its own (tests): q fp32 [nq <= 64, d] -> (q'' f16 [64, ld], qscale fp32 [64], qbias fp32 [64])."""
-        q = self._dev_f32(q)
-        nq, d = q.shape
-        ld = int(start.shape[0])
-        qpad = torch.empty((64, ld), dtype=torch.float16, device=self.device)
-        qscale = torch.empty((64,), dtype=torch.float32, device=self.device)
-        qbias = torch.empty((64,), dtype=torch.float32, device=self.device)
-        self._chk(self.lib.sgpt_u8_prepare_queries(self.handle, _p(q), _p(start), _p(step), nq, d, ld, _p(qpad), _p(qscale), _p(qbias),
-                                                   _stream_ptr(self.device)), "sgpt_u8_prepare_queries")
-        return qpad, qscale, qbias
-
-    def scalar_quantize_corpus(self, emb, normalize: bool = True, ranges=None, calibration_embeddings=None,
-                               block_rows: int = 65536) -> Uint8Corpus:
-        """Embeddings [N, d] -> Uint8Corpus: rows L2-normalised (normalize=True, cosine search) or taken as they are (dot scores), then
-        quantised to 256 levels between each column's min and max.  The ranges are `ranges` ([2, d]: min row, max row -- the layout of
-        sentence-transformers), or those of `calibration_embeddings` (normalised like the corpus), or the corpus's own; elements outside
-        them clamp.  Non-finite ranges (a NaN or inf in the rows they come from) raise ValueError.  Works in blocks of `block_rows` rows,
-        as quantize_corpus does; `emb` may live on the host."""
-        if not isinstance(emb, torch.Tensor):
-            emb = torch.as_tensor(np.asarray(emb))
-        if emb.dim() != 2 or emb.shape[0] == 0 or emb.shape[1] == 0:
-            raise ValueError(f"scalar_quantize_corpus needs a non-empty [N, d] matrix, got {tuple(emb.shape)}")
-        N, d = emb.shape
-        start, step = self._u8_ranges(emb, normalize, ranges, calibration_embeddings, block_rows)
-        codes = torch.empty((N, start.shape[0]), dtype=torch.uint8, device=self.device)
-        for r0 in range(0, N, block_rows):
-            blk = self._dev_f32(emb[r0:r0 + block_rows])
-            self.u8_quantize_rows(self.l2_normalize(blk) if normalize else blk, start, step, out=codes[r0:r0 + block_rows])
-        return Uint8Corpus(codes, start, step, bool(normalize), d)
-
-    def _u8_ranges(self, emb: torch.Tensor, normalize: bool, ranges, calibration_embeddings, block_rows: int):
-        """(start, step) fp32 [ld] of scalar_quantize_corpus's rule for the rows of emb [N, d]: from `ranges`, from
-        `calibration_embeddings`, or from emb itself."""
-        if ranges is not None and calibration_embeddings is not None:
-            raise ValueError("scalar_quantize_corpus: give ranges or calibration_embeddings, not both")
-        N, d = emb.shape
-        ld = (d + 127) // 128 * 128
-
-        def rows(src, r0):
-            blk = self._dev_f32(src[r0:r0 + block_rows])
-            return self.l2_normalize(blk) if normalize else blk
-        if ranges is not None:
-            ranges = torch.as_tensor(np.asarray(ranges.cpu() if isinstance(ranges, torch.Tensor) else ranges)).to(torch.float32)
-            if tuple(ranges.shape) != (2, d):
-                raise ValueError(f"scalar_quantize_corpus: ranges must be [2, {d}] (min row, max row), got {tuple(ranges.shape)}")
-            mn, mx = ranges[0].to(self.device).contiguous(), ranges[1].to(self.device).contiguous()
-        else:
-            src = emb if calibration_embeddings is None else calibration_embeddings
-            if not isinstance(src, torch.Tensor):
-                src = torch.as_tensor(np.asarray(src))
-            if src.dim() != 2 or src.shape[0] == 0 or src.shape[1] != d:
-                raise ValueError(f"scalar_quantize_corpus: calibration_embeddings must be a non-empty [n, {d}] matrix, got {tuple(src.shape)}")
-            run = None
-            for r0 in range(0, src.shape[0], block_rows):
-                run = self.u8_col_minmax(rows(src, r0), run)
-            mn, mx = run
-        if not bool(torch.isfinite(mn).all()) or not bool(torch.isfinite(mx).all()) or bool((mx < mn).any()):
-            raise ValueError("scalar_quantize_corpus: the ranges are not finite, or a max lies below its min (a NaN or inf in the rows they "
-                             "come from)")
-        start = torch.zeros((ld,), dtype=torch.float32, device=self.device)
-        step = torch.zeros((ld,), dtype=torch.float32, device=self.device)
-        start[:d] = mn
-        step[:d] = (mx - mn) / torch.full_like(mx, 255.0)      # (a tensor divisor: one IEEE division per column, not a multiplication by 1 / 255)
-        if not bool(torch.isfinite(step).all()):
-            raise ValueError("scalar_quantize_corpus: max - min overflows fp32")
-        return start, step
-
-    def _score_topk_u8(self, q, corpus: Uint8Corpus, k: int, idx_base: int, run, dtype):
-        if dtype is not None:
-            raise ValueError(f"a Uint8Corpus is scored from fp32 queries (the kernel pre-scales them itself): dtype must be None, got {dtype}")
-        if q.dim() != 2 or q.shape[1] != corpus.dim:
-            raise ValueError(f"embedding dims differ: {tuple(q.shape)[-1]} vs {corpus.dim}")
-        q = self._dev_f32(q)
-        codes = corpus.codes.to(self.device).contiguous()
-        start = corpus.start.to(device=self.device, dtype=torch.float32).contiguous()
-        step = corpus.step.to(device=self.device, dtype=torch.float32).contiguous()
-        nq, d = q.shape
-        N, ld = codes.shape
-        if run is None:
-            val = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-            idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-            n_run = 0
-        else:
-            val, idx, n_run = run
-        n_out = C.c_int32(0)
-        # groups of 64 queries, each re-streaming the codes (the pass is HBM-bound there); the running list is chained per group
-        for g0 in range(0, nq, 64):
-            gn = min(64, nq - g0)
-            self._chk(self.lib.sgpt_score_topk_u8(self.handle, _p(q[g0:g0 + gn]), _p(codes), _p(start), _p(step), gn, N, d, ld, k, idx_base,
-                                                  _p(val[g0:g0 + gn]), _p(idx[g0:g0 + gn]), n_run, C.byref(n_out),
-                                                  _stream_ptr(self.device)), "sgpt_score_topk_u8")
-        return val, idx, int(n_out.value)
-
-    # ---- binary (1-bit) corpus: packed sign bits ----
-    def pack_sign_bits(self, x, center: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """fp32 rows [n, d] -> uint8 [n, 4 * ceil(d / 32)]: the sign bits of x - center (center None: of x) in numpy.packbits order, pad
-        bits zero (include/sgpt_hip.h::sgpt_pack_sign_bits)."""
-        x = self._dev_f32(x)
-        n, d = x.shape
-        if n == 0 or d == 0:
-            raise ValueError(f"pack_sign_bits needs a non-empty [n, d] matrix, got {tuple(x.shape)}")
-        ldb = 4 * ((d + 31) // 32)
-        if center is not None:
-            center = center.to(device=self.device, dtype=torch.float32).contiguous()
-            if tuple(center.shape) != (d,):
-                raise ValueError(f"pack_sign_bits: center must be [{d}], got {tuple(center.shape)}")
-        if out is None:
-            out = torch.empty((n, ldb), dtype=torch.uint8, device=self.device)
-        elif (out.dtype != torch.uint8 or tuple(out.shape) != (n, ldb) or out.device != self.device or not out.is_contiguous()):
-            raise ValueError(f"pack_sign_bits: out must be a contiguous uint8 [{n}, {ldb}] tensor on {self.device}, got {out.dtype} "
-                             f"{tuple(out.shape)} on {out.device}")
-        self._chk(self.lib.sgpt_pack_sign_bits(self.handle, _p(x), n, d, _p(center), _p(out), ldb, _stream_ptr(self.device)),
-                  "sgpt_pack_sign_bits")
-        return out
-
-    def binarize_corpus(self, emb, normalize: bool = True, center=None, keep_fp8: bool = False,
-                        block_rows: int = 65536, keep_uint8: bool = False, ranges=None, calibration_embeddings=None) -> BinaryCorpus:
-        """Embeddings [N, d] -> BinaryCorpus: rows L2-normalised, the centre subtracted, signs packed.  center: None | "mean" (the mean of
-        the normalised rows, kept on the corpus so that queries get the same shift) | a [d] tensor.  keep_fp8: the same normalised,
-        uncentred rows also go through quantize_corpus (re-scoring with rescore="fp8").  keep_uint8: the same normalised, uncentred
-        rows are also quantised by scalar_quantize_corpus's rule (its `ranges` / `calibration_embeddings`), block by block beside the
-        bits (re-scoring with rescore="uint8", with or without a centre).  Works in blocks of `block_rows` rows, as
-        quantize_corpus does; `emb` may live on the host.  Sign bits carry no norms: normalize=False is refused."""
-        if not keep_uint8 and (ranges is not None or calibration_embeddings is not None):
-            raise ValueError("binarize_corpus: ranges / calibration_embeddings belong to keep_uint8=True")
-        if keep_fp8 and center is not None:
-            raise ValueError("binarize_corpus: keep_fp8 with a centre is refused -- fp8 re-scoring needs the raw query, the centred bits "
-                             "q - center, and the search call takes one query matrix (score_topk)")
-        if not normalize:
-            raise ValueError("binarize_corpus: normalize=False is refused -- sign bits carry no norms, the search is a cosine search")
-        if not isinstance(emb, torch.Tensor):
-            emb = torch.as_tensor(np.asarray(emb))
-        if emb.dim() != 2 or emb.shape[0] == 0 or emb.shape[1] == 0:
-            raise ValueError(f"binarize_corpus needs a non-empty [N, d] matrix, got {tuple(emb.shape)}")
-        N, d = emb.shape
-        if isinstance(center, str):
-            if center != "mean":
-                raise ValueError(f"binarize_corpus: center must be None, 'mean' or a [d] tensor, got {center!r}")
-            acc = torch.zeros((d,), dtype=torch.float64, device=self.device)
-            for r0 in range(0, N, block_rows):
-                acc += self.l2_normalize(self._dev_f32(emb[r0:r0 + block_rows])).sum(dim=0, dtype=torch.float64)
-            center = (acc / N).to(torch.float32)
-        elif center is not None:
-            center = torch.as_tensor(center).to(device=self.device, dtype=torch.float32).contiguous()
-            if tuple(center.shape) != (d,):
-                raise ValueError(f"binarize_corpus: center must be [{d}], got {tuple(center.shape)}")
-        bits = torch.empty((N, 4 * ((d + 31) // 32)), dtype=torch.uint8, device=self.device)
-        start = step = codes = None
-        if keep_uint8:
-            start, step = self._u8_ranges(emb, True, ranges, calibration_embeddings, block_rows)
-            codes = torch.empty((N, start.shape[0]), dtype=torch.uint8, device=self.device)
-        for r0 in range(0, N, block_rows):
-            n = min(block_rows, N - r0)
-            rows = self.l2_normalize(self._dev_f32(emb[r0:r0 + n]))
-            self.pack_sign_bits(rows, center, out=bits[r0:r0 + n])
-            if keep_uint8:
-                self.u8_quantize_rows(rows, start, step, out=codes[r0:r0 + n])
-        fp8 = self.quantize_corpus(emb, normalize=True, block_rows=block_rows) if keep_fp8 else None
-        u8 = Uint8Corpus(codes, start, step, True, d) if keep_uint8 else None
-        return BinaryCorpus(bits, d, center, fp8, u8)
-
-    def _score_topk_bits(self, q, corpus: BinaryCorpus, k: int, idx_base: int, run, rescore: str, rescore_multiplier):
-        if rescore not in RESCORE_MODES and rescore != "uint8":
-            raise ValueError(f"score_topk: rescore must be 'sign', 'none', 'fp8' or 'uint8', got {rescore!r}")
-        if rescore == "fp8" and corpus.fp8 is None:
-            raise ValueError("score_topk: rescore='fp8' needs a BinaryCorpus built with keep_fp8=True (corpus.fp8 is None)")
-        if rescore == "uint8" and corpus.u8 is None:
-            raise ValueError("score_topk: rescore='uint8' needs a BinaryCorpus built with keep_uint8=True (corpus.u8 is None)")
-        if k < 1 or k > 1024:
-            raise ValueError(f"score_topk over a BinaryCorpus takes 1 <= k <= 1024, got {k}")
-        mode = RESCORE_MODES.get(rescore)
-        kp = k if mode == 0 else min(1024, max(k, int(round(k * rescore_multiplier))))
-        q = self._dev_f32(q)
-        nq, d = q.shape
-        if d != corpus.dim:
-            raise ValueError(f"embedding dims differ: {d} vs {corpus.dim}")
-        if rescore == "uint8":
-            # an entry of its own: it takes the RAW q and the centre, packs the stage-1 bits of q - center and re-scores with q
-            u8 = corpus.u8
-            bits = corpus.bits.to(self.device).contiguous()
-            codes = u8.codes.to(self.device).contiguous()
-            start = u8.start.to(device=self.device, dtype=torch.float32).contiguous()
-            step = u8.step.to(device=self.device, dtype=torch.float32).contiguous()
-            center = None if corpus.center is None else corpus.center.to(device=self.device, dtype=torch.float32).contiguous()
-            if run is None:
-                val = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-                idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-                n_run = 0
-            else:
-                val, idx, n_run = run
-            n_out = C.c_int32(0)
-            self._chk(self.lib.sgpt_score_topk_bits_u8(self.handle, _p(q), _p(center), _p(bits), bits.shape[1], _p(codes), _p(start), _p(step),
-                                                       codes.shape[1], nq, bits.shape[0], d, k, kp, idx_base, _p(val), _p(idx), n_run,
-                                                       C.byref(n_out), _stream_ptr(self.device)), "sgpt_score_topk_bits_u8")
-            return val, idx, int(n_out.value)
-        # The C call takes ONE query matrix: it packs the stage-1 bits from it and re-scores with it.  A centred corpus needs the bits of
-        # q - center, its fp8 copy the raw q: no single matrix serves both, and the raw one would search sign(q) against sign(x - center).
-        if corpus.center is not None and mode == 2:
-            raise ValueError("score_topk: rescore='fp8' is refused on a centred BinaryCorpus -- the stage-1 bits need q - center, the fp8 "
-                             "rows the raw q, and sgpt_score_topk_bits takes one query matrix; use rescore='sign', or an uncentred corpus")
-        if corpus.center is not None:
-            q = q - corpus.center.to(self.device)
-        bits = corpus.bits.to(self.device).contiguous()
-        codes = scale = None
-        if mode == 2:
-            codes = corpus.fp8.codes.to(self.device).contiguous()
-            scale = corpus.fp8.scale.to(device=self.device, dtype=torch.float32).contiguous()
-        if run is None:
-            val = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-            idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-            n_run = 0
-        else:
-            val, idx, n_run = run
-        n_out = C.c_int32(0)
-        self._chk(self.lib.sgpt_score_topk_bits(self.handle, _p(q), _p(bits), bits.shape[1], nq, bits.shape[0], d, k, kp, mode, _p(codes),
-                                                _p(scale), idx_base, _p(val), _p(idx), n_run, C.byref(n_out),
-                                                _stream_ptr(self.device)), "sgpt_score_topk_bits")
-        return val, idx, int(n_out.value)
-
-    def rescore_u8(self, q, corpus_u8: Uint8Corpus, idx: torch.Tensor, idx_base: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
-        """The values <q_i, document idx[i][j]> of candidate lists against a Uint8Corpus (include/sgpt_hip.h::sgpt_u8_rescore): q [nq, dim]
-        (upcast to fp32), idx int64 [nq, m] of document indices idx_base + n -> (values fp32 [nq, m], indices int64 [nq, m]), slot for
-        slot and unsorted; a slot with idx < 0 or idx - idx_base outside [0, N) gives (-inf, -1).  The candidates may come from any
-        first stage."""
-        q = self._dev_f32(q)
-        if q.dim() != 2 or q.shape[1] != corpus_u8.dim:
-            raise ValueError(f"embedding dims differ: {tuple(q.shape)[-1]} vs {corpus_u8.dim}")
-        if idx.dim() != 2 or idx.shape[0] != q.shape[0] or idx.shape[1] == 0 or idx.dtype != torch.int64:
-            raise ValueError(f"rescore_u8: idx must be int64 [{q.shape[0]}, m], got {idx.dtype} {tuple(idx.shape)}")
-        idx = idx.to(self.device).contiguous()
-        codes = corpus_u8.codes.to(self.device).contiguous()
-        start = corpus_u8.start.to(device=self.device, dtype=torch.float32).contiguous()
-        step = corpus_u8.step.to(device=self.device, dtype=torch.float32).contiguous()
-        nq, d = q.shape
-        m = int(idx.shape[1])
-        val = torch.empty((nq, m), dtype=torch.float32, device=self.device)
-        out = torch.empty((nq, m), dtype=torch.int64, device=self.device)
-        self._chk(self.lib.sgpt_u8_rescore(self.handle, _p(q), _p(codes), _p(start), _p(step), nq, codes.shape[0], d, codes.shape[1], _p(idx), m,
-                                           m, idx_base, _p(val), _p(out), _stream_ptr(self.device)), "sgpt_u8_rescore")
-        return val, out
 
     def score_overflow_count(self) -> Tuple[int, int]:
         """(filtered chunks, chunks whose candidate lists overflowed and took the fallback) of the last score_topk pass on this
@@ -953,34 +569,9 @@ class Context:
         rows need the raw q); rescore="uint8" serves a centred corpus too (its entry takes the raw q and the centre: the bits come from
         q - center, the values from q).  1 <= k <= 1024.  `rescore` / `rescore_multiplier` belong to a BinaryCorpus: any other corpus with
         non-default values of them raises ValueError."""
-        if isinstance(corpus, BinaryCorpus):
-            return self._score_topk_bits(q, corpus, k, idx_base, run, rescore, rescore_multiplier)
-        if rescore != "sign" or rescore_multiplier != 4:
-            raise ValueError("score_topk: rescore / rescore_multiplier apply to a BinaryCorpus only")
-        if isinstance(corpus, Uint8Corpus):
-            return self._score_topk_u8(q, corpus, k, idx_base, run, dtype)
-        if isinstance(corpus, QuantizedCorpus):
-            if dtype not in (None, torch.float16):
-                raise ValueError(f"a QuantizedCorpus is scored with f16 queries: dtype must be None or torch.float16, got {dtype}")
-            if q.shape[1] != corpus.codes.shape[1] and q.shape[1] == corpus.dim:
-                q = torch.nn.functional.pad(q, (0, corpus.codes.shape[1] - q.shape[1]))
-            q = self._operand(q, torch.float16)
-            codes = corpus.codes.to(self.device).contiguous()
-            scale = corpus.scale.to(device=self.device, dtype=torch.float32).contiguous()
-            nq, d = q.shape
-            N, d2 = codes.shape
-            if d != d2:
-                raise ValueError(f"embedding dims differ: {d} vs {d2}")
-            if run is None:
-                val = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-                idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-                n_run = 0
-            else:
-                val, idx, n_run = run
-            n_out = C.c_int32(0)
-            self._chk(self.lib.sgpt_score_topk_q8(self.handle, _p(q), _p(codes), _p(scale), nq, N, d, k, idx_base, _p(val), _p(idx),
-                                                  n_run, C.byref(n_out), _stream_ptr(self.device)), "sgpt_score_topk_q8")
-            return val, idx, int(n_out.value)
+        if isinstance(corpus, CORPUS_KINDS):
+            return corpus.score_topk(self, q, k, idx_base, run, dtype, rescore, rescore_multiplier)
+        _no_rescore(rescore, rescore_multiplier)
         if dtype is None:
             dtype = corpus.dtype if corpus.dtype in DT_CODE else torch.float32
         q, corpus = self._operand(q, dtype), self._operand(corpus, dtype)
@@ -988,12 +579,7 @@ class Context:
         N, d2 = corpus.shape
         if d != d2:
             raise ValueError(f"embedding dims differ: {d} vs {d2}")
-        if run is None:
-            val = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-            idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-            n_run = 0
-        else:
-            val, idx, n_run = run
+        val, idx, n_run = self._run_list(run, nq, k)
         n_out = C.c_int32(0)
         self._chk(self.lib.sgpt_score_topk(self.handle, _p(q), _p(corpus), DT_CODE[dtype], nq, N, d, k,
                                            idx_base, _p(val), _p(idx), n_run, C.byref(n_out),
@@ -1020,12 +606,7 @@ class Context:
             margin = self.REFINE_MARGIN_UNIT_F16
         nq, d = q.shape
         N = corpus32.shape[0]
-        if run is None:
-            val = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-            idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-            n_run = 0
-        else:
-            val, idx, n_run = run
+        val, idx, n_run = self._run_list(run, nq, k)
         n_out, fb = C.c_int32(0), C.c_int32(0)
         self._chk(self.lib.sgpt_score_topk_refined(self.handle, _p(q), _p(corpus32), _p(corpus16), DT_CODE[corpus16.dtype], nq, N, d, k,
                                                    idx_base, float(margin), _p(val), _p(idx), n_run, C.byref(n_out),

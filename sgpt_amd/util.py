@@ -6,7 +6,8 @@ from typing import Callable, List
 import numpy as np
 import torch
 
-from .runtime import BinaryCorpus, QuantizedCorpus, Uint8Corpus, get_context
+from .corpus import CORPUS_KINDS, BinaryCorpus
+from .runtime import get_context
 
 
 def _ctx_for(*xs):
@@ -123,55 +124,10 @@ def quantize_embeddings(embeddings, precision: str = "fp8", normalize: bool = Tr
 
 
 def _binary_rescore(corpus: BinaryCorpus) -> str:
-    """What semantic_search re-scores a BinaryCorpus with: its uint8 copy where it has one (centred or not); else its fp8 copy where it
-    has one and is not centred (a centred corpus needs q - center for the bits and the raw q for the fp8 rows; that search call takes
-    one matrix); the sign bits otherwise."""
-    if corpus.u8 is not None:
-        return "uint8"
-    return "fp8" if corpus.fp8 is not None and corpus.center is None else "sign"
+    return corpus.default_rescore
 
 
-def _search_binary(q, corpus: BinaryCorpus, top_k: int, score_function) -> List[List[dict]]:
-    if score_function not in (cos_sim, pytorch_cos_sim):
-        raise ValueError("semantic_search over a BinaryCorpus scores with cos_sim only: sign bits carry no norms, so dot_score and "
-                         "arbitrary score functions cannot be computed from them")
-    if min(top_k, len(corpus)) > 1024:
-        raise ValueError(f"semantic_search over a BinaryCorpus takes top_k <= 1024 (the candidate lists of the Hamming stage), got {top_k}")
-    ctx, _ = _ctx_for(corpus.bits, q)
-    k = min(top_k, len(corpus))
-    val, idx, n = ctx.score_topk(ctx.l2_normalize(q), corpus, k, rescore=_binary_rescore(corpus))
-    val, idx = val.cpu().tolist(), idx.cpu().tolist()
-    return [[{"corpus_id": j, "score": s} for j, s in zip(ii[:n], vv[:n])] for vv, ii in zip(val, idx)]
-
-
-def _search_quantized(q, corpus: QuantizedCorpus, top_k: int, score_function) -> List[List[dict]]:
-    cosine = score_function in (cos_sim, pytorch_cos_sim)
-    if not cosine and score_function is not dot_score:
-        raise ValueError("semantic_search over a QuantizedCorpus scores with cos_sim or dot_score; an arbitrary score function needs "
-                         "the de-quantised rows (corpus.dequantize())")
-    if cosine != bool(corpus.normalized):
-        raise ValueError("semantic_search: cos_sim needs a corpus quantised with normalize=True, dot_score one with normalize=False "
-                         f"(this one has normalize={bool(corpus.normalized)})")
-    ctx, _ = _ctx_for(corpus.codes, q)
-    qd = ctx.l2_normalize(q) if cosine else ctx._dev_f32(q)
-    k = min(top_k, len(corpus))
-    val, idx, n = ctx.score_topk(qd, corpus, k)
-    val, idx = val.cpu().tolist(), idx.cpu().tolist()
-    return [[{"corpus_id": j, "score": s} for j, s in zip(ii[:n], vv[:n])] for vv, ii in zip(val, idx)]
-
-
-def _search_uint8(q, corpus: Uint8Corpus, top_k: int, score_function) -> List[List[dict]]:
-    cosine = score_function in (cos_sim, pytorch_cos_sim)
-    if not cosine and score_function is not dot_score:
-        raise ValueError("semantic_search over a Uint8Corpus scores with cos_sim or dot_score; an arbitrary score function needs "
-                         "the de-quantised rows (corpus.dequantize())")
-    if cosine != bool(corpus.normalized):
-        raise ValueError("semantic_search: cos_sim needs a corpus quantised with normalize=True, dot_score one with normalize=False "
-                         f"(this one has normalize={bool(corpus.normalized)})")
-    ctx, _ = _ctx_for(corpus.codes, q)
-    qd = ctx.l2_normalize(q) if cosine else ctx._dev_f32(q)
-    k = min(top_k, len(corpus))
-    val, idx, n = ctx.score_topk(qd, corpus, k)
+def _hits(val: torch.Tensor, idx: torch.Tensor, n: int) -> List[List[dict]]:
     val, idx = val.cpu().tolist(), idx.cpu().tolist()
     return [[{"corpus_id": j, "score": s} for j, s in zip(ii[:n], vv[:n])] for vv, ii in zip(val, idx)]
 
@@ -186,12 +142,12 @@ def semantic_search(query_embeddings, corpus_embeddings, query_chunk_size: int =
     fp8 copy when it has one and is not centred, with its sign bits otherwise."""
     if isinstance(query_embeddings, list):
         query_embeddings = torch.stack(query_embeddings)
-    if isinstance(corpus_embeddings, QuantizedCorpus):     # fp8 corpus (quantize_embeddings): one fused pass over the codes
-        return _search_quantized(_wrap(query_embeddings), corpus_embeddings, top_k, score_function)
-    if isinstance(corpus_embeddings, Uint8Corpus):         # uint8 codes, one range per dimension: one fused pass per 64 queries
-        return _search_uint8(_wrap(query_embeddings), corpus_embeddings, top_k, score_function)
-    if isinstance(corpus_embeddings, BinaryCorpus):        # packed sign bits: Hamming search + re-scoring of the over-fetched list
-        return _search_binary(_wrap(query_embeddings), corpus_embeddings, top_k, score_function)
+    if isinstance(corpus_embeddings, CORPUS_KINDS):        # fp8 codes, uint8 codes or packed sign bits (corpus.py, quantize_embeddings)
+        corpus, q = corpus_embeddings, _wrap(query_embeddings)
+        cosine = corpus.check_search(score_function, top_k)           # (refusals come before anything reaches for the device)
+        ctx, _ = _ctx_for(corpus.data, q)
+        qd = ctx.l2_normalize(q) if cosine else ctx._dev_f32(q)
+        return _hits(*ctx.score_topk(qd, corpus, min(top_k, len(corpus)), rescore=corpus.default_rescore))
     if isinstance(corpus_embeddings, list):
         corpus_embeddings = torch.stack(corpus_embeddings)
     q, c = _wrap(query_embeddings), _wrap(corpus_embeddings)
@@ -209,7 +165,4 @@ def semantic_search(query_embeddings, corpus_embeddings, query_chunk_size: int =
                 for r, (vv, ii) in enumerate(zip(v.cpu().tolist(), i.cpu().tolist())):
                     out[qs + r] += [{"corpus_id": j, "score": s} for j, s in zip(ii, vv)]
         return [sorted(o, key=lambda x: x["score"], reverse=True)[:top_k] for o in out]
-    k = min(top_k, len(c))
-    val, idx, n = ctx.score_topk(qd, cd, k)
-    val, idx = val.cpu().tolist(), idx.cpu().tolist()
-    return [[{"corpus_id": j, "score": s} for j, s in zip(ii[:n], vv[:n])] for vv, ii in zip(val, idx)]
+    return _hits(*ctx.score_topk(qd, cd, min(top_k, len(c))))

@@ -312,6 +312,10 @@ def test_semantic_search_over_a_binary_corpus(ctx):
     c8 = util.quantize_embeddings(docs, precision="ubinary", keep_fp8=True)
     assert c8.fp8 is not None and c8.fp8.codes.shape == (1000, 104) and c8.nbytes == 16000 + 1000 * 104 + 4000
     assert torch.equal(c8.bits, corpus.bits)
+    # the copy comes from the rows of the bits' own block loop: bit for bit quantize_corpus's, over three blocks with a ragged last one
+    e44 = docs[:300, :44].contiguous()
+    blk8, want8 = ctx.binarize_corpus(e44, keep_fp8=True, block_rows=128).fp8, ctx.quantize_corpus(e44, normalize=True, block_rows=128)
+    assert blk8.codes.shape == (300, 48) and torch.equal(blk8.codes, want8.codes) and torch.equal(blk8.scale, want8.scale)
     h8 = util.semantic_search(q, c8, top_k=10)
     v8 = np.array([[e["score"] for e in h] for h in h8], dtype=np.float32)
     i8 = np.array([[e["corpus_id"] for e in h] for h in h8], dtype=np.int64)
