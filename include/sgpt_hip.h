@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 21
+#define SGPT_ABI_VERSION 22
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -230,6 +230,16 @@ sgpt_status sgpt_encode(sgpt_model* model, const int32_t* ids, const int32_t* po
                         int32_t B, int32_t T_pad, int32_t max_alloc_len,
                         int32_t pool_mode, int32_t n_layers_run, int32_t apply_final_ln,
                         int32_t normalize, float* out, float* hidden_out, void* stream);
+
+/* sgpt_encode with the sequence starts of the layout in HOST memory as well (ABI v22): seq_off_host int32[B + 1] holds the values
+ * of seq_off[] -- the library trusts that and cannot check it.  Knowing where the sequences start without reading the device,
+ * the call may run its forward as two chains of whole sequences (sgpt_ctx_set_encode_chains below); NULL, or a layout the
+ * conditions there refuse, is sgpt_encode itself.  Same results bit for bit either way. */
+sgpt_status sgpt_encode_host_layout(sgpt_model* model, const int32_t* ids, const int32_t* pos,
+                                    const int32_t* seq_off, const int32_t* seq_len, const int32_t* pad_left,
+                                    int32_t B, int32_t T_pad, int32_t max_alloc_len,
+                                    int32_t pool_mode, int32_t n_layers_run, int32_t apply_final_ln,
+                                    int32_t normalize, float* out, float* hidden_out, const int32_t* seq_off_host, void* stream);
 
 /* All L+1 hidden states pooled in ONE forward: the `meanmean` / `lasttokenmean` methods
  * (beir_dense_retriever.py:243-257, 284-301; useb_dense_retriever.py:219-302) average the pooled vector of
@@ -980,6 +990,23 @@ sgpt_status sgpt_prof_read(sgpt_ctx* ctx, int64_t* launches, double* ms, double*
  *   the prologue, LDS) is the entry's "not served" SGPT_ERR_INVALID with nothing launched.  0 (default) = the launcher chooses.
  *   Read by sgpt_linear_query alone: sgpt_encode's launches do not see it.  Identical bits whichever tile runs.  Returns the
  *   previous value; k outside 0 .. 7 changes nothing and returns -1. */
+/* sgpt_ctx_set_encode_chains (ABI v22): a bulk sgpt_encode_host_layout call as two chains of whole sequences, A = token rows [0, r)
+ *   on the caller's stream and B = [r, T_pad) on a stream the context owns, so that one chain's LayerNorm / attention / embedding
+ *   launches and the ramps of its projection launches fall into the other's k-loops.  Chain B starts half a block behind chain A.
+ *   Fork and join are events on the caller's stream: work issued on it after the call is ordered behind both chains, the host
+ *   never waits.  Weights and workspace are shared (the chains own disjoint row ranges), every kernel computes a row or a sequence
+ *   independently of the rest of its launch: identical bits.
+ *   n: 0 = the library's default (two chains: +2.1 % on the 1024 x 128-token calls of bench.py) | 1 = one chain |
+ *   2 = two chains; two chains run wherever ALL of these hold: a GPT-Neo / GPT-J / BLOOM model with bf16 or f16 operands (no fp8 mode, no split-precision plan, no
+ *   calibration or precision probe riding on the call); pooled embeddings only (no hidden_out); T_pad >= min_rows (0 = 131072, the
+ *   measured call) and a multiple of 256; r = the sequence start nearest T_pad / 2 that is a multiple of 256 rows and lies in
+ *   [T_pad / 3, 2 T_pad / 3] exists; both halves take the 256x256 kernel on all projections; the caller's stream is not
+ *   capturing (a captured graph never gets parallel branches: the call is recorded as one chain).
+ *   With sgpt_prof_enable on, event pairs are recorded on the stream of their launch: the summed milliseconds of two overlapping
+ *   chains may exceed wall time.  Returns the previous n (-1 and no change: bad arguments).
+ * sgpt_ctx_encode_chain_calls: how many calls on this context ran as two chains so far. */
+int32_t sgpt_ctx_set_encode_chains(sgpt_ctx* ctx, int32_t n, int32_t min_rows);
+int64_t sgpt_ctx_encode_chain_calls(const sgpt_ctx* ctx);
 int32_t sgpt_ctx_set_gemm_cu_cap(sgpt_ctx* ctx, int32_t n);
 int32_t sgpt_ctx_set_low_latency(sgpt_ctx* ctx, int32_t on);
 int32_t sgpt_ctx_set_tile_policy(sgpt_ctx* ctx, int32_t policy);

@@ -342,6 +342,7 @@ bool launch_qgemm(int dtype, int epi, int out_dtype, const QGemmArgs& a, hipStre
 bool gemm_qkv_one_launch(int M, int n_split, bool force256);   // 16-bit operands: does EPI_QKV apply (query-sized batch)?
 bool gemm_score_tail_foldable(int M, long N, int K);   // scorer: may the < 256 trailing documents ride in the 256x256 launch (GemmArgs.n_valid)?
 bool gemm_qkv_bulk(int M, int N, int K, int n_split, bool force256);   // 16-bit operands: EPI_QKV on the 256x256 kernel (bulk batch)?
+bool gemm_bulk_256(int M, int N, int K, int epi, bool force256);       // 16-bit operands: does this projection launch take the 256x256 kernel?
 #ifdef SGPT_EXPERIMENTS        // A/B knobs of the measurement scripts (libsgpt_hip_exp.so only)
 int set_gemm_skew(int cycles);  // start-up stagger of the persistent 256^2 kernel (shader cycles per phase); returns the previous value
 int set_gemm_use_w(int on);     // 1: the 32x32x16-MFMA re-tiling of the 256^2 kernel (gemm256w.hip); returns the previous value

@@ -28,6 +28,14 @@ struct sgpt_ctx {
     int no_qpath = 0;                               // tile policy 2: query- / mid-sized layouts keep the bulk path's small-tile kernels (A/B, tests)
     int cu_cap = 0;                                 // persistent 256x256 GEMM: workgroups per launch at most (0 = one per CU; sgpt_ctx_set_gemm_cu_cap)
     int qtile = 0;                                  // sgpt_linear_query only: k > 0 = the k-th candidate tile of qgemm.hip (0 = the launcher's choice; sgpt_ctx_set_query_tile)
+    // a bulk encode call as two chains of whole sequences (encode.hip; sgpt_ctx_set_encode_chains): 0 = the library's default,
+    // 1 = one chain, 2 = two wherever the conditions hold; chain_min_rows > 0 replaces the row threshold.  Chain A runs on the
+    // caller's stream, chain B on chain_stream (non-blocking); chain_ev = fork, chain B's start, join.  Created by the first
+    // call that is cut (chain_init), destroyed with the context.
+    int chains = 0, chain_min_rows = 0;
+    hipStream_t chain_stream = nullptr;
+    hipEvent_t chain_ev[3] = {nullptr, nullptr, nullptr};
+    int64_t chain_calls = 0;                        // calls that ran as two chains (sgpt_ctx_encode_chain_calls)
     // GEMM profiling (bench.py roofline)
     bool prof = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;

@@ -63,6 +63,8 @@ void sgpt_ctx_destroy(sgpt_ctx* c) {
     if (c->ws6) (void)hipFree(c->ws6);
     if (c->range_flag) (void)hipFree(c->range_flag);
     for (auto& e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    for (hipEvent_t e : c->chain_ev) if (e) (void)hipEventDestroy(e);
+    if (c->chain_stream) (void)hipStreamDestroy(c->chain_stream);
     delete c;
 }
 
@@ -134,6 +136,14 @@ int32_t sgpt_ctx_set_tile_policy(sgpt_ctx* c, int32_t policy) {
     c->no_qpath = policy == 2 ? 1 : 0;
     return old;
 }
+int32_t sgpt_ctx_set_encode_chains(sgpt_ctx* c, int32_t n, int32_t min_rows) {
+    if (!c || n < 0 || n > 2 || min_rows < 0) return -1;
+    const int old = c->chains;
+    c->chains = n;
+    c->chain_min_rows = min_rows;
+    return old;
+}
+int64_t sgpt_ctx_encode_chain_calls(const sgpt_ctx* c) { return c ? c->chain_calls : 0; }
 int32_t sgpt_ctx_set_query_tile(sgpt_ctx* c, int32_t k) {
     if (!c || k < 0 || k > 7) return -1;           // (7 plain candidates, 3 with the LayerNorm prologue: a k the kernel family lacks is "not served")
     const int old = c->qtile;

@@ -1,6 +1,7 @@
 // C ABI (include/sgpt_hip.h): the forward -- one block function per arithmetic (16-bit, fp32, fp8 MFMA) under encode_impl -- and the LM head.
 // Host-side C++ only -- every device op is one of the hand-written kernels in this directory.
 #include "host.h"
+#include "encode_split.h"
 
 namespace {
 
@@ -26,6 +27,12 @@ struct Fwd {
     void* gu;             // SGPT_ARCH_LLAMA: fc1 output [T][2 ffn] = gate | up columns, the input of the SwiGLU row kernel
     void* a8; float* sa;  // fp8-MFMA block: LayerNorm output as e4m3 codes + one scale per row
     long att_lo;
+    long ldvt;            // row length of V^T: the token rows of the CALL
+    // One of the two chains of a call (chain_of): the chain owns rows [row0, row0 + T) = sequences [b0, b0 + B) of the call's buffers.
+    // pos / seq_off / seq_len / x / a / ctx / qkv / h start at its first row or sequence, vt at its first column; seq_off[] keeps
+    // counting from the call's first row.  0, 0: the whole call.
+    long row0; int b0;
+    hipEvent_t half_ev;   // block_16 records it behind the out-projection when set (the other chain's start, half a block behind)
 };
 
 // Descriptor of one projection, out[T][N] = (resid +) A[T][K] . W[N][K]^T (+ bias), from the per-call base.  Built for one launch: the
@@ -53,7 +60,7 @@ void proj_qk_vt(const Fwd& f, const GemmArgs& g, int n_qk, int n_v, const void* 
     gemm(f.c, f.dt, EPI_STORE, f.dt, qk, f.s);
     if (p_ln1 == 2) split_w(v, (const bf16_t*)W3 + (size_t)n_qk * 3 * g.K, g.K);
     else v.W = (const bf16_t*)g.W + (size_t)n_qk * g.K;
-    v.N = n_v; v.out = f.vt; v.ldo = f.T; v.bias = g.bias ? g.bias + n_qk : nullptr;
+    v.N = n_v; v.out = f.vt; v.ldo = f.ldvt; v.bias = g.bias ? g.bias + n_qk : nullptr;
     gemm(f.c, f.dt, EPI_VT, f.dt, v, f.s);
 }
 
@@ -68,8 +75,12 @@ AttnArgs attn_base(const Fwd& f, const LayerW& l, int k_qkv) {
     at.scale = d.attn_scale * pow2f(2 * k_qkv);      // q and k are both stored down-shifted
     at.max_alloc_len = f.max_alloc; at.ctx = f.ctx; at.ldo = dq; at.alibi = f.m->alibi;
     at.q = f.qkv; at.kv_group = d.n_heads / d.n_kv_heads;
-    if (f.vt) { at.k = (bf16_t*)f.qkv + dq; at.v = f.vt; at.ldq = dq + f.d_kv; at.ldvt = f.T; }
+    if (f.vt) { at.k = (bf16_t*)f.qkv + dq; at.v = f.vt; at.ldq = dq + f.d_kv; at.ldvt = f.ldvt; }
     else { at.k = (float*)f.qkv + dq; at.v = (float*)f.qkv + dq + f.d_kv; at.ldq = dq + 2 * f.d_kv; }
+    if (f.row0) {        // a chain (16-bit, ctx rows of d_q elements): the kernel indexes rows by seq_off[], from the call's first row
+        at.ctx = (bf16_t*)f.ctx - f.row0 * dq; at.q = (bf16_t*)f.qkv - f.row0 * at.ldq; at.k = (const bf16_t*)at.q + dq;
+        at.v = (bf16_t*)f.vt - f.row0;
+    }
     return at;
 }
 
@@ -104,7 +115,7 @@ sgpt_status block_bert16(const Fwd& f, const LayerW& l, int) {
     const int dm = d.d_model, ffn = d.d_ffn, T = f.T, dt = f.dt;
     GemmArgs q = proj(f, f.a, dm, l.w_qkv, 3 * dm, dm, f.qkv, 2 * dm, l.b_qkv);
     if (gemm_qkv_one_launch(T, 2 * dm, f.c->force256 != 0)) {        // query-sized batch: q | k and V^T from one launch
-        q.n_split = 2 * dm; q.out2 = f.vt; q.ldo2 = T;
+        q.n_split = 2 * dm; q.out2 = f.vt; q.ldo2 = f.ldvt;
         gemm(f.c, dt, EPI_QKV, dt, q, f.s);
     } else proj_qk_vt(f, q, 2 * dm, dm);
     launch_attn_bf16(attn_bidir(f, l), f.s);
@@ -266,7 +277,7 @@ sgpt_status block_16(const Fwd& f, const LayerW& l, int li) {
         if (f.qpath || ((p_ln1 == 0 || p_ln1 == 2) && gemm_qkv_one_launch(T, 2 * dm, c->force256 != 0)) ||
             (p_ln1 == 0 && !p_att && l.b_qkv == nullptr && gemm_qkv_bulk(T, 3 * dm, dm, 2 * dm, c->force256 != 0))) {
             if (p_ln1 == 2) split_w(q.g, l.w_qkv3, dm);
-            q.g.n_split = 2 * dm; q.g.out2 = f.vt; q.g.ldo2 = T;
+            q.g.n_split = 2 * dm; q.g.out2 = f.vt; q.g.ldo2 = f.ldvt;
             if ((st = launch16(f, EPI_QKV, dt, q, "QKV projection")) != SGPT_OK) return st;
         } else {
             // Q | K (split: K' = 3d, or 2d for p_ln1 == 3), then V from the hi block alone unless the plan splits it too (p_ln1 == 2)
@@ -288,6 +299,7 @@ sgpt_status block_16(const Fwd& f, const LayerW& l, int li) {
         q.g.in_mul = pow2f(k_qkv);
         if ((st = launch16(f, EPI_BIAS_RESID, SGPT_F32, q, "out-projection")) != SGPT_OK) return st;
     }
+    if (f.half_ev) HIPC(c, hipEventRecord(f.half_ev, s));
     {   // GPT-Neo: x += MLP(LN2(x));  GPT-J (parallel block, HF:gptj:400-411): x += MLP(LN1(x_old)), `a` still holds it
         QGemmArgs q{};
         q.g = proj(f, f.a, lda2, l.w_fc, ffn, dm, f.h, ldh, l.b_fc);
@@ -408,6 +420,7 @@ sgpt_status plan(Fwd& f, int n_layers_run, float** lp) {
     if (f.mlp8) { f.a8 = base + o_a8; f.sa = (float*)(base + o_sa); }
     if (lp) *lp = (float*)(base + o_lp);
     f.att_lo = (long)(qkv_bytes / 2);      // element distance of the lo halves of q | k and of V^T (x3 attention)
+    f.ldvt = T;
     return SGPT_OK;
 }
 
@@ -433,6 +446,78 @@ sgpt_status zero_overread(const Fwd& f) {
     return SGPT_OK;
 }
 
+// ---- a bulk call as two chains of whole sequences (include/sgpt_hip.h: sgpt_ctx_set_encode_chains) ----
+// Chain A = rows [0, r) on the caller's stream, chain B = [r, T) on the context's stream.  Same buffers, same weights: each launch of a
+// chain covers its row range (row kernels, projections: M = its rows) or its sequences (attention, pool).  Every kernel computes a
+// row / a sequence from that row / sequence alone, and the projections stay on the 256x256 kernel: identical bits.
+
+// what sgpt_ctx_set_encode_chains(n = 0) means: 1 = one chain | 2 = two (measured; -DSGPT_CHAINS_DEFAULT=1 / 2: same-box A/B builds)
+#ifndef SGPT_CHAINS_DEFAULT
+#define SGPT_CHAINS_DEFAULT 2
+#endif
+constexpr int CHAINS_DEFAULT = SGPT_CHAINS_DEFAULT;
+constexpr int CHAINS_AUTO_ROWS = 131072;      // row threshold unless the caller gave one: the measured call (1024 x 128 tokens)
+// How far chain B starts behind chain A, in half blocks: 0 = together | 1 = behind A's first out-projection | 2 = behind A's first
+// block.  Out of phase, one chain's LayerNorm / attention / epilogue-heavy launches meet the other's k-loops instead of their twins.
+// Measured: profiles/encode_two_chains_ab.txt.
+#ifndef SGPT_CHAIN_PHASE
+#define SGPT_CHAIN_PHASE 1
+#endif
+constexpr int CHAIN_PHASE = SGPT_CHAIN_PHASE;
+
+// Where this call is cut, or row == 0: the conditions of the header, cheapest first.  f: after plan().
+EncodeSplit chain_cut(const Fwd& f, BlockFn block, const int32_t* seq_off_host, bool pooled_only) {
+    sgpt_model* m = f.m; sgpt_ctx* c = f.c;
+    const EncodeSplit none{0, 0};
+    const int mode = c->chains ? c->chains : CHAINS_DEFAULT;
+    const int dm = m->d.d_model, ffn = m->d.d_ffn;
+    if (mode != 2 || !seq_off_host || !pooled_only || block != block_16) return none;
+    if (f.qpath || f.fp8 || f.mlp8 || f.split || m->calibrating || m->probing) return none;
+    if (f.T < (c->chain_min_rows > 0 ? c->chain_min_rows : CHAINS_AUTO_ROWS) || f.T % ENCODE_SPLIT_TILE != 0) return none;
+    const EncodeSplit cut = encode_split_point(seq_off_host, f.B, f.T);
+    if (cut.row == 0) return none;
+    const bool f256 = c->force256 != 0;
+    for (int rows : {cut.row, f.T - cut.row})
+        if (!gemm_bulk_256(rows, 2 * dm, dm, EPI_STORE, f256) || !gemm_bulk_256(rows, dm, dm, EPI_VT, f256) ||
+            !gemm_bulk_256(rows, dm, dm, EPI_BIAS_RESID, f256) || !gemm_bulk_256(rows, ffn, dm, EPI_BIAS_GELU, f256) ||
+            !gemm_bulk_256(rows, dm, ffn, EPI_BIAS_RESID, f256))
+            return none;
+    // a capturing stream records the call as one chain: a captured graph never gets parallel branches (a failed query counts as capturing)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(f.s, &cap) != hipSuccess) { (void)hipGetLastError(); return none; }
+    return cap == hipStreamCaptureStatusNone ? cut : none;
+}
+
+// the context's stream and events, on the first call that is cut
+sgpt_status chain_init(sgpt_ctx* c) {
+    if (!c->chain_stream) HIPC(c, hipStreamCreateWithFlags(&c->chain_stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : c->chain_ev)
+        if (!e) HIPC(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return SGPT_OK;
+}
+
+// The chain of call `f` that owns rows [row0, row0 + rows) = sequences [b0, b0 + nb), on stream s (16-bit block_16 families: the
+// LayerNorm output, the context and q, k, v all have d_model columns)
+Fwd chain_of(const Fwd& f, int row0, int rows, int b0, int nb, hipStream_t s) {
+    const size_t dm = f.m->d.d_model, ffn = f.m->d.d_ffn, r = row0;
+    Fwd h = f;
+    h.s = s; h.row0 = row0; h.b0 = b0; h.T = rows; h.B = nb;
+    h.pos += r; h.seq_off += b0; h.seq_len += b0;
+    h.x += r * dm;
+    h.a = (bf16_t*)f.a + r * dm; h.ctx = (bf16_t*)f.ctx + r * dm; h.qkv = (bf16_t*)f.qkv + r * 2 * dm; h.vt = (bf16_t*)f.vt + r;
+    h.h = (bf16_t*)f.h + r * ffn;
+    return h;
+}
+
+// Before the chains part: chain A's last sequences load keys (up to 63 rows) and query fragments (up to 255 rows) past their end, in
+// chain B's rows -- masked, but 0 * NaN = NaN, and in the first block chain B may not have written them yet in this call.
+sgpt_status zero_cut_overread(const Fwd& f, int r) {
+    const size_t dm = f.m->d.d_model;
+    HIPC(f.c, hipMemsetAsync((bf16_t*)f.qkv + (size_t)r * 2 * dm, 0, (size_t)256 * 2 * dm * 2, f.s));
+    HIPC(f.c, hipMemset2DAsync((bf16_t*)f.vt + r, (size_t)f.ldvt * 2, 0, SLACK * 2, dm, f.s));
+    return SGPT_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -441,7 +526,8 @@ sgpt_status zero_overread(const Fwd& f) {
 static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t* pos, const int32_t* seq_off,
                                const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t T, int32_t max_alloc,
                                int32_t pool_mode, int32_t n_layers_run, int32_t apply_final_ln, int32_t normalize,
-                               float* out, float* hidden_out, float* layer_out, float* layer_mean, void* stream) {
+                               float* out, float* hidden_out, float* layer_out, float* layer_mean, void* stream,
+                               const int32_t* seq_off_host = nullptr) {
     if (!m) return SGPT_ERR_INVALID;
     sgpt_ctx* c = m->ctx;
     const Family& F = family(m->d.arch);
@@ -459,10 +545,46 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
         launch_lnf_pool(x, m->lnf_g, m->lnf_b, seq_off, seq_len, pad_left, B, dm, m->d.ln_eps, final_ln, pool_mode, normalize, m->pool_w,
                         m->pool_w_n, dst, s, range_flag, F.norm_kind);
     };
-    launch_embed(ids, pos, m->wte, m->wpe, x, T, dm, m->d.vocab, m->d.max_pos, s);
-    if (F.post_ln && f.vt) launch_layernorm_writeback(x, m->emb_ln_g, m->emb_ln_b, f.a, dt, T, dm, m->d.ln_eps, f.range_flag, s);   // x and its 16-bit copy
-    else if (m->emb_ln_g) launch_layernorm(x, m->emb_ln_g, m->emb_ln_b, x, SGPT_F32, T, dm, m->d.ln_eps, s);   // BLOOM :499
+    // the embedding (and its LayerNorm) of the rows of g: the call, or one of its chains
+    auto embed = [&](const Fwd& g) {
+        launch_embed(ids + g.row0, g.pos, m->wte, m->wpe, g.x, g.T, dm, m->d.vocab, m->d.max_pos, g.s);
+        if (F.post_ln && g.vt) launch_layernorm_writeback(g.x, m->emb_ln_g, m->emb_ln_b, g.a, dt, g.T, dm, m->d.ln_eps, g.range_flag, g.s);   // x and its 16-bit copy
+        else if (m->emb_ln_g) launch_layernorm(g.x, m->emb_ln_g, m->emb_ln_b, g.x, SGPT_F32, g.T, dm, m->d.ln_eps, g.s);   // BLOOM :499
+    };
     const BlockFn block = pick_block(f);
+    const EncodeSplit cut = chain_cut(f, block, seq_off_host, out && !hidden_out && !layer_out && !layer_mean);
+    if (cut.row) {
+        // Two chains.  Fork: chain B's stream waits for what the caller's stream holds so far; each chain pools its own sequences;
+        // join: the caller's stream waits for chain B.  No host or device-wide wait.
+        if ((st = chain_init(c)) != SGPT_OK || (st = zero_cut_overread(f, cut.row)) != SGPT_OK) return st;
+        hipStream_t sb = c->chain_stream;
+        const Fwd fa = chain_of(f, 0, cut.row, 0, cut.seq, s), fb = chain_of(f, cut.row, T - cut.row, cut.seq, B - cut.seq, sb);
+        HIPC(c, hipEventRecord(c->chain_ev[0], s));
+        HIPC(c, hipStreamWaitEvent(sb, c->chain_ev[0], 0));
+        embed(fa);
+        if (CHAIN_PHASE == 0 || n_layers_run == 0) embed(fb);
+        for (int li = 0; li < n_layers_run; ++li) {
+            Fwd a = fa;
+            if (li == 0 && CHAIN_PHASE == 1) a.half_ev = c->chain_ev[1];
+            if ((st = block(a, m->L[li], li)) != SGPT_OK) return st;
+            if (li == 0 && CHAIN_PHASE != 0) {
+                if (CHAIN_PHASE == 2) HIPC(c, hipEventRecord(c->chain_ev[1], s));
+                HIPC(c, hipStreamWaitEvent(sb, c->chain_ev[1], 0));
+                embed(fb);
+            }
+            if ((st = block(fb, m->L[li], li)) != SGPT_OK) return st;
+        }
+        int* rf = m->d.compute_dtype == SGPT_F16 ? (int*)m->range_dev : nullptr;
+        for (const Fwd* g : {&fa, &fb})
+            launch_lnf_pool(x, m->lnf_g, m->lnf_b, g->seq_off, g->seq_len, pad_left ? pad_left + g->b0 : nullptr, g->B, dm, m->d.ln_eps,
+                            apply_final_ln, pool_mode, normalize, m->pool_w, m->pool_w_n, out + (size_t)g->b0 * dm, g->s, rf, F.norm_kind);
+        HIPC(c, hipEventRecord(c->chain_ev[2], sb));
+        HIPC(c, hipStreamWaitEvent(s, c->chain_ev[2], 0));
+        c->chain_calls++;
+        HIPC(c, hipGetLastError());
+        return SGPT_OK;
+    }
+    embed(f);
     for (int li = 0; li < n_layers_run; ++li) {
         LayerW l = m->L[li];
         if (layer_out) pool(0, layer_out + (size_t)li * B * dm, nullptr);   // hidden_states[li] = input of block li (HF:gpt_neo:475-478)
@@ -495,6 +617,14 @@ sgpt_status sgpt_encode(sgpt_model* m, const int32_t* ids, const int32_t* pos, c
                         float* out, float* hidden_out, void* stream) {
     return encode_impl(m, ids, pos, seq_off, seq_len, pad_left, B, T, max_alloc, pool_mode, n_layers_run,
                        apply_final_ln, normalize, out, hidden_out, nullptr, nullptr, stream);
+}
+
+sgpt_status sgpt_encode_host_layout(sgpt_model* m, const int32_t* ids, const int32_t* pos, const int32_t* seq_off,
+                                    const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t T, int32_t max_alloc,
+                                    int32_t pool_mode, int32_t n_layers_run, int32_t apply_final_ln, int32_t normalize,
+                                    float* out, float* hidden_out, const int32_t* seq_off_host, void* stream) {
+    return encode_impl(m, ids, pos, seq_off, seq_len, pad_left, B, T, max_alloc, pool_mode, n_layers_run,
+                       apply_final_ln, normalize, out, hidden_out, nullptr, nullptr, stream, seq_off_host);
 }
 
 sgpt_status sgpt_encode_layers(sgpt_model* m, const int32_t* ids, const int32_t* pos, const int32_t* seq_off,

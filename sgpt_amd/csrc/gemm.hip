@@ -1087,6 +1087,16 @@ bool gemm_qkv_bulk(int M, int N, int K, int n_split, bool force256) {
     return M % 256 == 0 && N % 256 == 0 && n_split % 256 == 0 && n_split < N && K % 64 == 0 && K >= 128 &&
            (long)(M / 256) * (n_split / 256) > SGPT_FEW_TILES;
 }
+// Does a 16-bit projection launch of M x N x K with this epilogue (not EPI_QKV, no scorer) take the 256x256 LDS-DMA kernel?  The
+// shape and few-tiles rule of launch_gemm16 above, for callers that decide something from it before they launch (encode.hip: a call
+// is cut into two chains only while both halves stay on this kernel).
+bool gemm_bulk_256(int M, int N, int K, int epi, bool force256) {
+    if (exp_env("SGPT_GEMM128") != nullptr) return false;
+    const bool small_tiles = exp_env("SGPT_NO_SMALL_TILE") == nullptr;
+    const long few_limit = epi_is_gelu(epi) ? 255 : SGPT_FEW_TILES;
+    const bool few = small_tiles && !force256 && (long)(M / 256) * (N / 256) <= few_limit;
+    return M > 0 && M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && K >= 128 && !few;
+}
 // THE predicate of the folded ragged tail (the scorer's planner asks its shape arithmetic before folding; launch_gemm16 re-checks it): a scorer launch of M padded
 // query rows against N = (whole 256-document tiles + 256) documents of width K takes the 256x256 kernel with the documents as its
 // streamed operand -- the only kernel that honours GemmArgs.n_valid.

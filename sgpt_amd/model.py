@@ -65,6 +65,7 @@ class PackedBatch:
     max_pos: int = 0  # largest position id (pad_left + len - 1): bounds the learntmean weight table
     arena: Optional[torch.Tensor] = None  # the one int32 device buffer the five views above slice (graph replays refill it in one copy)
     n_real: int = 0  # sequences that are the caller's (B minus the bucket's filler sequences)
+    off_host: Optional[np.ndarray] = None  # host int32[B + 1] copy of seq_off: lets the library cut a bulk call into two chains without reading the device
 
 
 def _flatten(seqs, total: int) -> np.ndarray:
@@ -590,13 +591,14 @@ class SGPTModel:
         dev = into.arena if into is not None else torch.empty(n_int, dtype=torch.int32, device=self.device)
         dev.copy_(host[:n_int], non_blocking=True)
         self._staging.release(slot)
+        off_host = np.ascontiguousarray(lay["off"], dtype=np.int32)
         if into is not None:
-            into.n_tokens, into.max_pos, into.n_real = lay["n_tokens"], lay["max_pos"], lay["n_real"]
+            into.n_tokens, into.max_pos, into.n_real, into.off_host = lay["n_tokens"], lay["max_pos"], lay["n_real"], off_host
             return into
         o = 2 * T
         return PackedBatch(dev[:T], dev[T:o], dev[o: o + B + 1], dev[o + B + 1: o + 2 * B + 1],
                            dev[o + 2 * B + 1: o + 3 * B + 1], B, T, lay["max_alloc"], lay["n_tokens"], lay["max_pos"],
-                           arena=dev, n_real=lay["n_real"])
+                           arena=dev, n_real=lay["n_real"], off_host=off_host)
 
     # ---- one C call: forward + pool ----
     def encode_packed(self, pb: PackedBatch, mode: str = "weightedmean", normalize: bool = False,
@@ -615,10 +617,11 @@ class SGPTModel:
         if out is None:
             out = torch.empty((pb.B, d), dtype=torch.float32, device=self.device)
         hidden = torch.empty((pb.T_pad, d), dtype=torch.float32, device=self.device) if return_hidden else None
-        st = self.ctx.lib.sgpt_encode(self.handle, _p(pb.ids), _p(pb.pos), _p(pb.seq_off), _p(pb.seq_len),
-                                      _p(pb.pad_left), pb.B, pb.T_pad, pb.max_alloc, POOL_MODES[mode], n_run,
-                                      final_ln, 1 if normalize else 0, _p(out), _p(hidden),
-                                      _stream_ptr(self.device))
+        off_host = pb.off_host.ctypes.data if pb.off_host is not None and pb.off_host.size == pb.B + 1 else None
+        st = self.ctx.lib.sgpt_encode_host_layout(self.handle, _p(pb.ids), _p(pb.pos), _p(pb.seq_off), _p(pb.seq_len),
+                                                  _p(pb.pad_left), pb.B, pb.T_pad, pb.max_alloc, POOL_MODES[mode], n_run,
+                                                  final_ln, 1 if normalize else 0, _p(out), _p(hidden), off_host,
+                                                  _stream_ptr(self.device))
         _lib.check(self.ctx.handle, st, "sgpt_encode")
         return (out, hidden) if return_hidden else out
 

@@ -204,6 +204,19 @@ class Context(CorpusBuilders):
         it (include/sgpt_hip.h::sgpt_ctx_set_query_tile).  Returns the previous value; -1 (nothing changed) for k outside 0 .. 7."""
         return int(self.lib.sgpt_ctx_set_query_tile(self.handle, int(k)))
 
+    def set_encode_chains(self, n: int, min_rows: int = 0) -> int:
+        """Per context: a bulk encode call as two chains of whole sequences on two streams (include/sgpt_hip.h::
+        sgpt_ctx_set_encode_chains): n = 0 the library's default, 1 one chain, 2 two chains wherever the conditions hold;
+        min_rows > 0 replaces the row threshold.  Identical bits either way.  Returns the previous n."""
+        old = int(self.lib.sgpt_ctx_set_encode_chains(self.handle, int(n), int(min_rows)))
+        if old < 0:
+            raise ValueError("set_encode_chains: n in (0, 1, 2), min_rows >= 0")
+        return old
+
+    def encode_chain_calls(self) -> int:
+        """Encode calls on this context that ran as two chains so far."""
+        return int(self.lib.sgpt_ctx_encode_chain_calls(self.handle))
+
     def reserve(self, encode_bytes: int = 0, score_bytes: int = 0) -> None:
         self._chk(self.lib.sgpt_ctx_reserve(self.handle, encode_bytes, score_bytes), "sgpt_ctx_reserve")
 
