@@ -34,7 +34,14 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 22
+#define SGPT_ABI_VERSION 23
+
+/* The longest sequence (ABI v23): the token rows one sequence may own in the packed layout of sgpt_encode*, sgpt_attention_ex and
+ * sgpt_attention_gqa (max_alloc_len <= SGPT_MAX_SEQ_LEN; a larger value is SGPT_ERR_INVALID, nothing launched).  32 768 is the
+ * context of Qwen3-Embedding; up to ABI v22 the bound was 2048, the position table of the SGPT checkpoints.  A model's own bound is
+ * its descriptor's max_pos (positions at or above it are clamped by the kernels and refused by the Python host); the descriptor
+ * and the rotary tables hold min(max_position_embeddings, SGPT_MAX_SEQ_LEN) rows.  The plain sgpt_attention entry keeps 2048. */
+#define SGPT_MAX_SEQ_LEN 32768
 
 typedef int sgpt_status;
 #define SGPT_OK 0
@@ -838,7 +845,11 @@ sgpt_status sgpt_linear_qkv(sgpt_ctx* ctx, int32_t dtype, const void* A, const v
  *   out rows of the allocations [seq_off[b], seq_off[b+1]) are written.
  * SGPT_ERR_INVALID (nothing launched) for: head_dim other than 64 | 128 | 256, T % 32, max_alloc_len odd or above 2048,
  *   out_fp8 with f16 / fp32 operands or with a split-precision mode, x3 at head_dim 256, split modes with fp32 operands,
- *   misaligned pointers / leading dimensions. */
+ *   misaligned pointers / leading dimensions.
+ * This entry keeps the bound of ABI <= v22, max_alloc_len <= 2048, and its message; sgpt_attention_ex (causal = 1) and
+ *   sgpt_attention_gqa are the same kernels up to SGPT_MAX_SEQ_LEN rows per sequence.  fp32 above 2048 rows: a second kernel takes
+ *   the keys in chunks of 2048 with an online softmax across chunks; a row that sees at most 2048 keys keeps the bits of the
+ *   one-chunk kernel. */
 sgpt_status sgpt_attention(sgpt_ctx* ctx, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
                            void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t dh,
                            int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
@@ -850,7 +861,8 @@ sgpt_status sgpt_attention(sgpt_ctx* ctx, int32_t dtype, const void* q, const vo
  *   causal = 0: every query row of sequence b sees keys j in [0, seq_len[b]) of that sequence -- seq_len device int32[B], clamped
  *     into [0, seq_off[b+1] - seq_off[b]]; NULL = the whole allocation -- and nothing of its neighbours on the packed axis.  A
  *     sequence of no keys gives zero rows.  window = 0 and alibi = NULL; out_fp8, x3 and the split context are refused
- *     (SGPT_ERR_INVALID), as is 16-bit head_dim 256.  Over-read contract as sgpt_attention. */
+ *     (SGPT_ERR_INVALID), as is 16-bit head_dim 256.  Over-read contract as sgpt_attention.
+ *   max_alloc_len even, in [2, SGPT_MAX_SEQ_LEN] (ABI v23; sgpt_attention_gqa too). */
 sgpt_status sgpt_attention_ex(sgpt_ctx* ctx, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
                               void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t dh,
                               int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,

@@ -19,7 +19,7 @@ import torch
 
 from .model import SGPTModel
 from .runtime import get_context
-from .families import family_of
+from .families import family_of, max_seq_len_of
 from .tokenization import TextPipeline, load_tokenizer
 
 logger = logging.getLogger(__name__)
@@ -42,7 +42,7 @@ class CustomEmbedder:
         self.device = torch.device(device)
         self.model = model if model is not None else SGPTModel.from_pretrained(model_name, device=device, dtype=dtype)
         self.tokenizer = tokenizer if tokenizer is not None else load_tokenizer(model_name)
-        self.max_token_len = maxseqlen if maxseqlen else self.model.cfg.max_position_embeddings   # :128
+        self.max_token_len = maxseqlen if maxseqlen else max_seq_len_of(self.model)   # :128, never beyond what the model encodes
         self.pipe = TextPipeline(self.tokenizer, self.max_token_len, specb=specb, family=family_of(self.model), frame=frame)   # frame: TextPipeline's
         self.max_token_len = self.pipe.max_token_len
         self.batch_size = batch_size

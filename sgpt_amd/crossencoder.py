@@ -9,6 +9,7 @@ from typing import List, Sequence, Tuple
 import numpy as np
 import torch
 
+from .families import max_seq_len_of
 from .model import ALIGN, SGPTModel
 
 
@@ -89,7 +90,7 @@ class GPTRanker:
     def __init__(self, model: SGPTModel, tokenizer, max_length: int = None, use_prompt: bool = True,
                  prompt_doc: str = "{}\n", prompt_doc_start: str = "{}\n{}\n", fewshots=""):
         self.model, self.tokenizer = model, tokenizer
-        self.max_length = max_length if max_length else model.cfg.max_position_embeddings
+        self.max_length = max_length if max_length else max_seq_len_of(model)
         self.use_prompt, self.prompt_doc = use_prompt, prompt_doc
         n_tok = lambda text: len(tokenizer.tokenize(text))  # noqa: E731
         self.fewshots = prompt_doc_start.format(fewshots[0], fewshots[1]) if fewshots else ""   # one formatted block

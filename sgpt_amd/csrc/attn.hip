@@ -15,7 +15,8 @@
 //   Online softmax (running max m, running sum l) over 64-key tiles; masked scores are -inf and
 //   m starts at -1e30 so a fully masked step contributes exp(-inf) = 0 without NaN.
 //
-// fp32 path (attn_f32_kernel): exact-fp32 VALU kernel for the parity gate, one wave per query row.
+// fp32 path (attn_f32_kernel): exact-fp32 VALU kernel for the parity gate, one wave per query row; calls with an allocation of more
+// than 2048 rows take attn_f32_long_kernel, the same row in chunks of 2048 keys.
 #include <cstdlib>
 
 #include "common.h"
@@ -619,6 +620,91 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnArgs p) {
     }
 }
 
+// Exact fp32 for calls whose longest allocation exceeds F32_MAXKEYS rows (up to SGPT_MAX_SEQ_LEN): one wave per query row as above, the
+// row's keys taken in chunks of at most F32_MAXKEYS through the same 32 KiB of LDS, and an online softmax ACROSS chunks -- running max
+// m, running sum l, and the lane's output columns (at most 4: head_dim <= 256) carried in registers, rescaled by exp(m_old - m_new)
+// when a chunk raises the max.  Inside a chunk the arithmetic is attn_f32_kernel's, expression for expression and in its order: the
+// scores, the wave max, exp(s - m), the lane-strided sum, the serial fma chain over the chunk's keys.  The first chunk starts its
+// chains from 0 and takes m = its own max, so a row that sees at most F32_MAXKEYS keys (a short sequence packed beside a long one, the
+// head of the long one, any row of a window layer) is ONE chunk and leaves with the bits attn_f32_kernel gives it -- the
+// batch-invariance rule.  Rows of several chunks differ from a one-pass softmax by the rescales: one rounding of exp and one multiply
+// per chunk on l and on every output column.
+template <bool CAUSAL>
+__global__ __launch_bounds__(256) void attn_f32_long_kernel(const AttnArgs p) {
+    __shared__ float sc[4][F32_MAXKEYS];
+    __shared__ float qs[4][256];
+    const int sq = blockIdx.z, head = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int s0 = p.seq_off[sq];
+    const int alloc = p.seq_off[sq + 1] - s0;
+    const int qi = blockIdx.x * 4 + wave;
+    if (qi >= alloc) return;
+    const int dh = p.dh;
+    const float* __restrict__ qb = static_cast<const float*>(p.q) + (long)head * dh;
+    const int kvh = p.kv_group > 1 ? head / p.kv_group : head;      // grouped K / V: see attn16_lds_kernel
+    const float* __restrict__ kb = static_cast<const float*>(p.k) + (long)kvh * dh;
+    const float* __restrict__ vb = static_cast<const float*>(p.v) + (long)kvh * dh;
+    for (int c = lane; c < dh; c += 64) qs[wave][c] = qb[(long)(s0 + qi) * p.ldq + c];
+    int lo = 0;
+    if (p.window > 0) { lo = qi - p.window + 1; lo = lo < 0 ? 0 : lo; }
+    int nkeys = qi - lo + 1;
+    if constexpr (!CAUSAL) {        // bidirectional: keys [0, seq_len) of the sequence
+        nkeys = p.seq_len ? p.seq_len[sq] : alloc;
+        nkeys = nkeys < 0 ? 0 : (nkeys > alloc ? alloc : nkeys);
+        lo = 0;
+    }
+    const float slope = p.alibi ? p.alibi[head] : 0.f;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};            // output column lane + 64 ci, un-normalised
+    float m_run = -INFINITY, l_run = 0.f;
+    for (int k0 = 0; k0 < nkeys; k0 += F32_MAXKEYS) {   // (wave-uniform trip count)
+        const int nk = nkeys - k0 < F32_MAXKEYS ? nkeys - k0 : F32_MAXKEYS;
+        const int klo = lo + k0;                     // first key of the chunk, counted from the sequence start
+        const bool first = k0 == 0;
+        float mx = -INFINITY;
+        for (int jj = lane; jj < nk; jj += 64) {
+            const float* kr = kb + (long)(s0 + klo + jj) * p.ldq;
+            float a = 0.f;
+            for (int c = 0; c < dh; c += 4) {
+                const float4 kv = *reinterpret_cast<const float4*>(kr + c);
+                a = fmaf(qs[wave][c], kv.x, a); a = fmaf(qs[wave][c + 1], kv.y, a);
+                a = fmaf(qs[wave][c + 2], kv.z, a); a = fmaf(qs[wave][c + 3], kv.w, a);
+            }
+            a = a * p.scale + slope * (float)(klo + jj);
+            sc[wave][jj] = a;
+            mx = fmaxf(mx, a);
+        }
+        mx = wave_max(mx);
+        const float m_new = first ? mx : fmaxf(m_run, mx);
+        float sum = 0.f;
+        for (int jj = lane; jj < nk; jj += 64) {
+            const float e = expf(sc[wave][jj] - m_new);
+            sc[wave][jj] = e;
+            sum += e;
+        }
+        sum = wave_sum(sum);
+        const float alpha = first ? 0.f : expf(m_run - m_new);   // (every chunk holds a key: m_run is finite from the first one on)
+        l_run = first ? sum : l_run * alpha + sum;
+        m_run = m_new;
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) {
+            const int c = lane + 64 * ci;
+            if (c < dh) {
+                float a = first ? 0.f : acc[ci] * alpha;
+                for (int jj = 0; jj < nk; ++jj) a = fmaf(sc[wave][jj], vb[(long)(s0 + klo + jj) * p.ldq + c], a);
+                acc[ci] = a;
+            }
+        }
+    }
+    float inv = 1.0f / l_run;
+    if constexpr (!CAUSAL) inv = l_run > 0.f ? inv : 0.f;       // a sequence of no tokens has no keys: zero rows, not 0 / 0
+    float* orow = static_cast<float*>(p.ctx) + (long)(s0 + qi) * p.ldo + (long)head * dh;
+#pragma unroll
+    for (int ci = 0; ci < 4; ++ci) {
+        const int c = lane + 64 * ci;
+        if (c < dh) orow[c] = acc[ci] * inv;
+    }
+}
+
 }  // namespace
 
 void launch_attn_bf16(const AttnArgs& a, hipStream_t s) {
@@ -722,6 +808,11 @@ void launch_attn_bf16(const AttnArgs& a, hipStream_t s) {
 
 void launch_attn_f32(const AttnArgs& a, hipStream_t s) {
     dim3 grid((a.max_alloc_len + 3) / 4, a.H, a.B);
+    if (a.max_alloc_len > F32_MAXKEYS) {     // a row may see more keys than the score slice holds: the chunked kernel, and only then
+        if (a.noncausal) hipLaunchKernelGGL(attn_f32_long_kernel<false>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(attn_f32_long_kernel<true>, grid, dim3(256), 0, s, a);
+        return;
+    }
     if (a.noncausal) hipLaunchKernelGGL(attn_f32_kernel<false>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(attn_f32_kernel<true>, grid, dim3(256), 0, s, a);
 }

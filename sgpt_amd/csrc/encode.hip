@@ -348,7 +348,8 @@ sgpt_status check_call(sgpt_model* m, const int32_t* const (&layout)[4], const i
         if (!pad_left && max_alloc - 7 > m->pool_w_n)
             return fail(c, SGPT_ERR_INVALID, "sgpt_encode: fewer learnt position weights than the longest sequence");
     }
-    if (max_alloc > 2048) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: sequence longer than 2048 tokens");
+    if (max_alloc > SGPT_MAX_SEQ_LEN)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_encode: sequence longer than " + std::to_string(SGPT_MAX_SEQ_LEN) + " tokens (SGPT_MAX_SEQ_LEN)");
     if (!pooled && !hidden_out) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: no output requested");
     return SGPT_OK;
 }

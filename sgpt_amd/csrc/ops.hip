@@ -218,7 +218,9 @@ static sgpt_status attention_impl(sgpt_ctx* c, int32_t dtype, const void* q, con
                               void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t dh,
                               int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
                               float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
-                              int64_t ctx_lo_delta, int64_t ctx_hi2_delta, int32_t causal, const int32_t* seq_len, int32_t kv_group, const char* who, void* stream) {
+                              int64_t ctx_lo_delta, int64_t ctx_hi2_delta, int32_t causal, const int32_t* seq_len, int32_t kv_group, int32_t max_seq,
+                              const char* who, void* stream) {
+    // max_seq: the longest allocation the entry takes -- SGPT_MAX_SEQ_LEN, but 2048 (the bound and the message of ABI <= v22) for sgpt_attention
     const std::string w = std::string(who) + ": ";   // the entry the caller used: its name leads every refusal
     if (causal != 0 && causal != 1) return fail(c, SGPT_ERR_INVALID, w + "causal 0 | 1");
     if (causal && seq_len) return fail(c, SGPT_ERR_INVALID, w + "seq_len belongs to the bidirectional mode (causal = 0)");
@@ -236,8 +238,8 @@ static sgpt_status attention_impl(sgpt_ctx* c, int32_t dtype, const void* q, con
     if (!in16 && dtype != SGPT_F32) return fail(c, SGPT_ERR_INVALID, w + "dtype SGPT_F32 | SGPT_BF16 | SGPT_F16");
     if (dh != 64 && dh != 128 && dh != 256) return fail(c, SGPT_ERR_INVALID, w + "head_dim 64, 128 or 256");
     if (T % 32) return fail(c, SGPT_ERR_INVALID, w + "T % 32 == 0");
-    if (max_alloc_len <= 0 || max_alloc_len > 2048 || max_alloc_len % 2)
-        return fail(c, SGPT_ERR_INVALID, w + "max_alloc_len even, in [2, 2048]");
+    if (max_alloc_len <= 0 || max_alloc_len > max_seq || max_alloc_len % 2)
+        return fail(c, SGPT_ERR_INVALID, w + "max_alloc_len even, in [2, " + std::to_string(max_seq) + "]");
     const long d = (long)H * dh;
     if (ldq < d || ldo < d) return fail(c, SGPT_ERR_INVALID, w + "ldq, ldo >= H * head_dim");
     const bool split_ctx = ctx_lo_delta != 0;
@@ -284,7 +286,7 @@ sgpt_status sgpt_attention_ex(sgpt_ctx* c, int32_t dtype, const void* q, const v
                               float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
                               int64_t ctx_lo_delta, int64_t ctx_hi2_delta, int32_t causal, const int32_t* seq_len, void* stream) {
     return attention_impl(c, dtype, q, k, v, ldq, ldvt, out, ldo, seq_off, B, T, H, dh, window, scale, alibi, max_alloc_len, out_fp8,
-                          out_scale, range_flag, x3, qk_lo_delta, v_lo_delta, ctx_lo_delta, ctx_hi2_delta, causal, seq_len, 1, "sgpt_attention_ex", stream);
+                          out_scale, range_flag, x3, qk_lo_delta, v_lo_delta, ctx_lo_delta, ctx_hi2_delta, causal, seq_len, 1, SGPT_MAX_SEQ_LEN, "sgpt_attention_ex", stream);
 }
 
 sgpt_status sgpt_attention_gqa(sgpt_ctx* c, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
@@ -298,7 +300,7 @@ sgpt_status sgpt_attention_gqa(sgpt_ctx* c, int32_t dtype, const void* q, const 
         return fail(c, SGPT_ERR_INVALID, "sgpt_attention_gqa: out_fp8 and the split-precision modes are not available with grouped K / V");
     if (dtype != SGPT_F32 && dh != 64 && dh != 128) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_gqa: 16-bit grouped attention serves head_dim 64 | 128");
     return attention_impl(c, dtype, q, k, v, ldq, ldvt, out, ldo, seq_off, B, T, H, dh, window, scale, nullptr, max_alloc_len, 0,
-                          out_scale, range_flag, 0, qk_lo_delta, v_lo_delta, 0, 0, 1, nullptr, H / n_kv_heads, "sgpt_attention_gqa", stream);
+                          out_scale, range_flag, 0, qk_lo_delta, v_lo_delta, 0, 0, 1, nullptr, H / n_kv_heads, SGPT_MAX_SEQ_LEN, "sgpt_attention_gqa", stream);
 }
 
 sgpt_status sgpt_attention(sgpt_ctx* c, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
@@ -307,7 +309,7 @@ sgpt_status sgpt_attention(sgpt_ctx* c, int32_t dtype, const void* q, const void
                            float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
                            int64_t ctx_lo_delta, int64_t ctx_hi2_delta, void* stream) {
     return attention_impl(c, dtype, q, k, v, ldq, ldvt, out, ldo, seq_off, B, T, H, dh, window, scale, alibi, max_alloc_len, out_fp8,
-                          out_scale, range_flag, x3, qk_lo_delta, v_lo_delta, ctx_lo_delta, ctx_hi2_delta, 1, nullptr, 1, "sgpt_attention", stream);
+                          out_scale, range_flag, x3, qk_lo_delta, v_lo_delta, ctx_lo_delta, ctx_hi2_delta, 1, nullptr, 1, 2048, "sgpt_attention", stream);
 }
 
 // ---- the encoder's row kernels stand-alone (elementwise.hip; tests/test_gpu_rowops.py): every argument a launch would index or

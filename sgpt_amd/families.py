@@ -8,7 +8,10 @@ import torch
 
 from . import _lib
 
-MAX_SEQ_LEN = 2048   # tokens per sequence sgpt_encode takes (include/sgpt_hip.h)
+MAX_SEQ_LEN = _lib.SGPT_MAX_SEQ_LEN   # tokens per sequence sgpt_encode takes (include/sgpt_hip.h): 32 768
+# Mistral: a sliding_window of at least this many tokens (or of the whole position table) is folded away -- the rule the window kernels
+# were accepted under when 2048 was the longest sequence; the fold then caps the positions at the window (see _parse_llama)
+WINDOW_FOLD = 2048
 
 
 @dataclass
@@ -45,6 +48,12 @@ class SGPTConfig:
             if mt in fam.hf_model_types:
                 return fam.parse_config(c)
         raise NotImplementedError(f"model_type {mt!r}: GPT-Neo, GPT-J, BLOOM, BERT and Llama / Mistral are the families built here")
+
+
+def table_rows(cfg: SGPTConfig) -> int:
+    """Rows of the descriptor's max_pos and of the host rotary tables: positions past MAX_SEQ_LEN cannot be reached (gte-Qwen2's 131 072
+    would be a 67 MB table of them).  Also the longest sequence a model takes: SGPTModel.max_seq_len."""
+    return min(cfg.max_position_embeddings, MAX_SEQ_LEN)
 
 
 def head_dim(cfg: SGPTConfig) -> int:
@@ -120,14 +129,19 @@ def _parse_llama(c: dict) -> SGPTConfig:
     if theta is None and isinstance(c.get("rope_parameters"), dict):
         theta = c["rope_parameters"].get("rope_theta")
     # Mistral: key j is visible to query i iff j > i - sliding_window (HF sliding_window_overlay) -- the window rule of the
-    # GPT-Neo local layers, on every layer.  A window that no sequence here can reach is no window: the longest sequence is
-    # min(max_position_embeddings, MAX_SEQ_LEN) tokens (Mistral-7B-v0.1's 4096 folds to 0: the no-window kernels).  A missing
-    # key is HF MistralConfig's default, 4096
+    # GPT-Neo local layers, on every layer.  A window of min(max_position_embeddings, WINDOW_FOLD) tokens or more is folded to 0, the
+    # no-window kernels (Mistral-7B-v0.1's 4096) -- and a model whose window was folded away takes sequences of at most sliding_window
+    # tokens, inside which the window hides nothing: its max_position_embeddings is capped there, so that pack() refuses a longer
+    # sequence with the ordinary message (Mistral-7B-v0.1 / e5-mistral: 4096 tokens).  `sliding_window: null` (v0.2 on): no window, the
+    # whole table.  A missing key is HF MistralConfig's default, 4096
     sw = c.get("sliding_window", 4096) if mt == "mistral" else None
-    window = 0 if (sw is None or sw >= min(c["max_position_embeddings"], MAX_SEQ_LEN)) else int(sw)
+    max_pos = c["max_position_embeddings"]
+    window = 0 if (sw is None or sw >= min(max_pos, WINDOW_FOLD)) else int(sw)
     if window < 0:
         raise NotImplementedError(f"{mt}: sliding_window {sw!r}")
-    return SGPTConfig(vocab_size=c["vocab_size"], max_position_embeddings=c["max_position_embeddings"], hidden_size=d, num_layers=L,
+    if sw is not None and window == 0:
+        max_pos = min(max_pos, int(sw))
+    return SGPTConfig(vocab_size=c["vocab_size"], max_position_embeddings=max_pos, hidden_size=d, num_layers=L,
                       num_heads=H, intermediate_size=c["intermediate_size"], layer_norm_epsilon=c.get("rms_norm_eps", 1e-6),
                       model_type="llama", window_size=window, attention_layers=["local" if window else "global"] * L,
                       num_kv_heads=c.get("num_key_value_heads") or H, rope_theta=float(theta if theta is not None else 10000.0),
@@ -264,14 +278,14 @@ _ROTARY = ("rotary.sin", "rotary.cos")
 FAMILIES = (
     Family("gpt_neo", ("gpt_neo",), _lib.SGPT_ARCH_GPTNEO, "GPT-Neo", _parse_gpt_neo, scaled_logits=False),
     Family("gptj", ("gptj",), _lib.SGPT_ARCH_GPTJ, "GPT-J", _parse_gptj, rotary_dim="config", keeps_lm_head=True, parallel_block=True,
-           prepare_weights=lambda c, w: dict(w, **dict(zip(_ROTARY, rotary_tables(c.max_position_embeddings, c.rotary_dim))))),
+           prepare_weights=lambda c, w: dict(w, **dict(zip(_ROTARY, rotary_tables(table_rows(c), c.rotary_dim))))),
     Family("bloom", ("bloom",), _lib.SGPT_ARCH_BLOOM, "BLOOM", _parse_bloom,
            prepare_weights=lambda c, w: dict(w, **{"alibi.slopes": alibi_slopes(c.num_heads)})),
     Family("bert", ("bert",), _lib.SGPT_ARCH_BERT, "BERT", _parse_bert, prepare_weights=lambda c, w: bert_state_dict(w), sgpt_modes=False,
            framing="cls_sep", dtype_advice="'f16', 'bf16' or 'fp32'", no_lm_head="lm_logprobs: a BERT model carries no causal LM head"),
     Family("llama", ("llama", "mistral", "qwen2", "qwen3"), _lib.SGPT_ARCH_LLAMA, "Llama / Mistral", _parse_llama, rotary_dim="head_dim", grouped_kv=True,
            prepare_weights=lambda c, w: dict(llama_state_dict(w), **dict(zip(_ROTARY, rotary_tables_half(
-               c.max_position_embeddings, head_dim(c), c.rope_theta)))),
+               table_rows(c), head_dim(c), c.rope_theta)))),
            sgpt_modes=False, framing="bos_eos", dtype_advice="'bf16', 'f16' or 'fp32'",
            no_lm_head="lm_logprobs is not built for Llama / Mistral models (their LM head is not loaded)"),
 )
@@ -289,6 +303,13 @@ def family(model_type: str) -> Family:
 def family_of(model) -> Family:
     """The row of a model object (SGPTModel, or a stand-in with a `cfg`; one without, or without a model_type, is a GPT model)."""
     return family(getattr(getattr(model, "cfg", None), "model_type", FAMILIES[0].model_type))
+
+
+def max_seq_len_of(model) -> Optional[int]:
+    """SGPTModel.max_seq_len of a model object or a stand-in with a `cfg`: the longest sequence it encodes, min(max_position_embeddings,
+    MAX_SEQ_LEN).  None where the object names no position range (nothing to clamp to)."""
+    cfg = getattr(model, "cfg", None)
+    return table_rows(cfg) if getattr(cfg, "max_position_embeddings", None) else None
 
 
 # ---- seeded random-init weights under HF state-dict names (fixtures, benches: no checkpoints exist offline) ----

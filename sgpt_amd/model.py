@@ -18,7 +18,7 @@ from . import _lib
 from ._lib import (ModelDesc, TensorView, POOL_MODES, SGPT_BF16, SGPT_F16, SGPT_F32, SGPT_FP8M, SGPT_FP8W, SgptRangeError,
                    SGPT_PREC_CLASSES, PC_LN1, PC_ATT, PC_CTX, PC_LN2, PC_H)
 from .families import (MAX_SEQ_LEN, SGPTConfig, alibi_slopes, bert_state_dict, family, head_dim, llama_state_dict, rotary_tables,  # noqa: F401
-                       rotary_tables_half, synthetic_bert_weights, synthetic_llama_weights, synthetic_qwen_weights, synthetic_weights)
+                       rotary_tables_half, table_rows, synthetic_bert_weights, synthetic_llama_weights, synthetic_qwen_weights, synthetic_weights)
 from .runtime import Context, get_context, _p, _stream_ptr
 
 # Precision probe thresholds: crest factor max|v| / rms(v) of an operand row above which 11-bit operands are not trusted.
@@ -268,7 +268,7 @@ def model_desc(cfg: SGPTConfig, dtype: str, precise_qk, precision: str):
     dh = head_dim(cfg)
     ln1, _, ctx = PRECISE_QK_PLANS[precise_qk] if precise_qk else (0, 0, 0)
     return ModelDesc(arch=fam.arch, n_layers=cfg.num_layers, d_model=cfg.hidden_size, n_heads=cfg.num_heads, d_ffn=cfg.intermediate_size,
-                     vocab=cfg.vocab_size, max_pos=cfg.max_position_embeddings, window=cfg.window_size, ln_eps=cfg.layer_norm_epsilon,
+                     vocab=cfg.vocab_size, max_pos=table_rows(cfg), window=cfg.window_size, ln_eps=cfg.layer_norm_epsilon,
                      attn_scale=float(1.0 / np.sqrt(np.float32(dh))) if fam.scaled_logits else 1.0,
                      compute_dtype={"f16": SGPT_F16, "bf16": SGPT_BF16, "fp32": SGPT_F32, "fp8": SGPT_FP8W, "fp8mfma": SGPT_FP8M}[dtype],
                      layer_is_local=C.cast(local, C.POINTER(C.c_uint8)),
@@ -287,7 +287,11 @@ def load_tensors(cfg: SGPTConfig, weights) -> List[Tuple[str, torch.Tensor]]:
         if (k2 == "position_weights" or k2.endswith(("attn.attention.bias", "attn.bias", "masked_bias", "embed_positions"))
                 or (k.startswith("lm_head") and not fam.keeps_lm_head)):
             continue
-        out.append((k2, v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))))
+        v = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))
+        if (k2 in ("wpe.weight", "embeddings.position_embeddings.weight") and cfg.max_position_embeddings > MAX_SEQ_LEN
+                and v.shape[0] == cfg.max_position_embeddings):
+            v = v[:MAX_SEQ_LEN]           # a learned position table beyond MAX_SEQ_LEN: the descriptor's max_pos rows are loaded
+        out.append((k2, v))
     return out
 
 
@@ -359,6 +363,12 @@ class SGPTModel:
             if self._plan_pending:
                 S = min(64, cfg.max_position_embeddings)
                 self._auto_precision(np.random.default_rng(4321).integers(0, cfg.vocab_size, size=(64, S), dtype=np.int64), None, final=False)
+
+    @property
+    def max_seq_len(self) -> int:
+        """The longest sequence (tokens, framing included) this model encodes: min(cfg.max_position_embeddings, MAX_SEQ_LEN).  What
+        the adapters default and clamp their max_seq_length to."""
+        return table_rows(self.cfg)
 
     def _call(self, fn: str, *args) -> None:
         """sgpt_model_<fn>(this model, *args); a failure raises with the library's message."""
@@ -577,7 +587,10 @@ class SGPTModel:
         bucket: pad the layout to a capacity (pack_layout); into: refill that batch's device arena (same bucket) instead of
         allocating a new one -- the form hipGraph replays use, whose kernels hold the arena's addresses."""
         lay = pack_layout(seqs, pad_left, bucket, self.row_tile)
-        if lay["max_alloc"] > 2048 or lay["max_pos"] >= self.cfg.max_position_embeddings:
+        # two refusals: the library's limit (SGPT_MAX_SEQ_LEN, include/sgpt_hip.h) and the model's own position range
+        if int(lay["lens"][: lay["n_real"]].max()) > MAX_SEQ_LEN:
+            raise ValueError(f"sequence longer than {MAX_SEQ_LEN} tokens, the longest the library encodes (SGPT_MAX_SEQ_LEN)")
+        if lay["max_pos"] >= self.cfg.max_position_embeddings:
             raise ValueError("sequence longer than max_position_embeddings")
         n_int = arena_ints(lay)
         B, T = lay["B"], lay["T_pad"]

@@ -11,7 +11,7 @@ import torch
 from .dist import balanced_cuts, get_comm, is_distributed, shard_sizes  # noqa: F401  (shard_sizes: re-exported)
 from .model import ALIGN, SGPTModel
 from .runtime import get_context  # noqa: F401
-from .families import family_of
+from .families import family_of, max_seq_len_of
 from .tokenization import TextPipeline
 
 
@@ -19,8 +19,17 @@ class SentenceTransformerSGPT:
     """Transformer + Pooling(weightedmean) [+ Normalize] as one module
     (the assembly of training_nli_v2.py:85-123 / modules.json)."""
 
-    def __init__(self, model: SGPTModel, tokenizer, max_seq_length: int = 300, pooling_mode: str = "weightedmean",
+    def __init__(self, model: SGPTModel, tokenizer, max_seq_length: Optional[int] = None, pooling_mode: str = "weightedmean",
                  specb: bool = False, normalize: bool = False, frame=None):
+        """max_seq_length: tokens per text, framing included; longer texts are truncated by the tokeniser, as in sentence-transformers.
+        None = 300, or the model's longest sequence (SGPTModel.max_seq_len) where that is shorter; a value beyond what the model
+        encodes is refused here and not at the first long text."""
+        limit = max_seq_len_of(model)
+        if max_seq_length is None:
+            max_seq_length = 300 if limit is None else min(300, limit)
+        elif limit is not None and max_seq_length > limit:
+            raise ValueError(f"max_seq_length {max_seq_length} exceeds the {limit} tokens this model encodes "
+                             "(min(max_position_embeddings, SGPT_MAX_SEQ_LEN))")
         self.model = model
         self.tokenizer = tokenizer
         self.max_seq_length = max_seq_length
@@ -43,7 +52,8 @@ class SentenceTransformerSGPT:
         if spec.position_weights_file:
             model.set_position_weights(torch.load(spec.position_weights_file, map_location="cpu", weights_only=True)["position_weights"])
         tok = tokenizer if tokenizer is not None else load_tokenizer(spec.transformer_dirs[""])
-        return cls(model, tok, max_seq_length=spec.max_seq_length or model.cfg.max_position_embeddings,
+        # the folder's max_seq_length, else the model's longest sequence; never beyond it (over-long text is truncated, not refused)
+        return cls(model, tok, max_seq_length=min(spec.max_seq_length or model.max_seq_len, model.max_seq_len),
                    pooling_mode=spec.pooling_mode, specb=specb, normalize=spec.normalize, frame=frame)
 
     def get_sentence_embedding_dimension(self) -> int:

@@ -7,7 +7,7 @@ import torch
 
 from .beir import ALL_LAYER_METHODS, SINGLE_LAYER_METHODS
 from .model import SGPTModel
-from .families import family_of
+from .families import family_of, max_seq_len_of
 from .tokenization import TextPipeline
 
 
@@ -23,7 +23,7 @@ class CustomEmbedder:
         self.model = model
         self.layeridx = layeridx
         self.method = method
-        self.pipe = TextPipeline(tokenizer, maxseqlen or model.cfg.max_position_embeddings, specb=specb,
+        self.pipe = TextPipeline(tokenizer, maxseqlen or max_seq_len_of(model), specb=specb,
                                  family=family_of(model), frame=frame)
 
     def encode_device(self, sentences: List[str], is_query: bool = True) -> torch.Tensor:
