@@ -994,7 +994,8 @@ sgpt_status sgpt_prof_read(sgpt_ctx* ctx, int64_t* launches, double* ms, double*
  /* sgpt_ctx_set_gemm_cu_cap: n > 0 = the persistent 256x256 projection kernel launches at most n workgroups (rounded down to
  *   a multiple of 8; 0 = one per CU, the default) -- for two contexts that run their calls half a block out of phase on two
  *   streams, so that one pipeline's LayerNorm / attention / embed kernels find free CUs while the other is in its k-loops
- *   (scripts/dual_stream_probe.py).  Results do not depend on it.  Returns the previous value. */
+ *   (scripts/dual_stream_probe.py).  The fp8 projection kernel (sgpt_linear_fp8, SGPT_FP8M blocks) honours it
+ *   in the same way.  Results do not depend on it.  Returns the previous value. */
  /* sgpt_ctx_set_query_tile (kernel tests): k > 0 = sgpt_linear_query launches the k-th candidate tile of csrc/qgemm.hip instead of
  *   the one its cost rule picks from the CU count -- plain kernels k = 1 .. 7 = 32x16 (256-element stages), 32x32, 32x64, 64x32,
  *   64x64, 128x64, 128x128; with the LayerNorm prologue k = 1 .. 3 = 32x32, 32x64, 64x64.  A tile that does not serve the shape

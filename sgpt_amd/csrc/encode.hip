@@ -196,7 +196,11 @@ sgpt_status block_fp8(const Fwd& f, const LayerW& l, int li) {
     const int dm = d.d_model, ffn = d.d_ffn, T = f.T;
     const bool gptj = d.arch == SGPT_ARCH_GPTJ;
     const float s_h = f.m->act_scale[li], s_c = f.m->act_scale[d.n_layers + li];     // scales of the GELU output's / the context's codes
-    auto launch = [&](int epi, int out_dtype, const GemmArgs& q) { Prof pr(f.c, f.s, 2.0 * T * (double)q.N * q.K); launch_gemm_fp8(epi, out_dtype, q, f.s); };
+    auto launch = [&](int epi, int out_dtype, GemmArgs q) {
+        Prof pr(f.c, f.s, 2.0 * T * (double)q.N * q.K);
+        q.cu_cap = f.c->cu_cap;                        // per-ctx workgroup cap (sgpt_ctx_set_gemm_cu_cap), as gemm() sets it for the 16-bit launches
+        launch_gemm_fp8(epi, out_dtype, q, f.s);
+    };
     // attention projections: a8 = e4m3(LN1(x) / sa[row]) feeds Q, K (row-major 16-bit) and V^T
     launch_layernorm_q8(f.x, l.ln1_g, l.ln1_b, f.a8, f.sa, T, dm, d.ln_eps, f.s);
     GemmArgs qk = proj(f, f.a8, dm, l.w_qkv, 2 * dm, dm, f.qkv, 2 * dm, l.b_qkv);

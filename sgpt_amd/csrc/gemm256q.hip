@@ -18,6 +18,7 @@
 //     sgpt_fp8_quantize_rows).  Both factor out of the k-sum and are applied to the accumulators in the epilogue.
 //   * epilogues: bias + gelu_new -> fp8 codes under a per-tensor output scale (saturating at +-448; a saturated value
 //     raises bit 1 of the context's range flag), and bias + residual in fp32 (in place).
+// The launch honours the per-ctx workgroup cap (GemmArgs::cu_cap, sgpt_ctx_set_gemm_cu_cap) exactly as launch256d does.
 #include <cstdlib>
 #include <type_traits>
 
@@ -343,7 +344,8 @@ void launch256q(const GemmArgs& a, hipStream_t s) {
     GemmArgs b = a;
     const int gm = b.gm > 0 ? b.gm : 4;
     const int tiles_pad = ((AT + 7) / 8 + gm - 1) / gm * gm * 8 * BT;
-    const int grid = tiles_pad < ncu ? tiles_pad : ncu;
+    const int cus = (a.cu_cap >= 8 && a.cu_cap < ncu) ? a.cu_cap / 8 * 8 : ncu;     // per-ctx workgroup cap, as in launch256d (gemm.hip)
+    const int grid = tiles_pad < cus ? tiles_pad : cus;
     if (a.M >= a.N) hipLaunchKernelGGL((gemm256q_kernel<EPI, OutT, SWAP, true>), dim3(grid), dim3(512), 0, s, b);
     else hipLaunchKernelGGL((gemm256q_kernel<EPI, OutT, SWAP, false>), dim3(grid), dim3(512), 0, s, b);
 }

@@ -93,7 +93,7 @@ sgpt_status sgpt_linear_fp8(sgpt_ctx* c, int32_t epi, int32_t out_dtype, const u
     GemmArgs q{};
     q.A = A; q.lda = K; q.W = W; q.ldw = K; q.M = M; q.m_valid = M; q.N = N; q.K = K; q.out = out; q.ldo = epi == EPI_VT ? M : N;
     q.bias = bias; q.resid = resid; q.a_scale = a_scale; q.a_scalar = a_scalar; q.w_scale = w_scale; q.out_scale = out_scale;
-    q.range_flag = c->range_flag;
+    q.range_flag = c->range_flag; q.cu_cap = c->cu_cap;
     { Prof pr(c, (hipStream_t)stream, 2.0 * M * (double)N * K); launch_gemm_fp8(epi, out_dtype, q, (hipStream_t)stream); }
     HIPC(c, hipGetLastError());
     return SGPT_OK;

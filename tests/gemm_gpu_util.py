@@ -1,5 +1,5 @@
-"""Shared by the GPU tests of sgpt_linear (tests/test_gpu_linear_edges.py, tests/test_gpu_linear_256.py; not a test module): outputs
-inside guarded buffers of NaN sentinels, the twice-called entry, and the tolerance of a result against the float64 reference of
+"""Shared by the GPU tests of sgpt_linear and sgpt_linear_fp8 (tests/test_gpu_linear_edges.py, tests/test_gpu_linear_256.py,
+tests/test_gpu_linear_fp8.py; not a test module): outputs inside guarded buffers of NaN sentinels, the twice-called entry, and the tolerance of a result against the float64 reference of
 tests/gemm_ref.py.
 
 Tolerances: `bound` ((K + 4) 2^-23 (|a| |w|^T + |bias| + |resid|), gemm_ref.bound) for fp32 outputs; + u16 |ref| (2^-8 bf16 /
@@ -15,13 +15,20 @@ import gemm_ref as G
 DEV = "cuda"
 GUARD = 64                                             # elements in front of and behind every output (keeps 16-byte alignment)
 SENT32, SENT16 = 0x7FC12345, 0x7FC1                    # NaN bit patterns (fp32; bf16 and f16 alike), compared as integers
+SENT8 = 0x7F                                           # the NaN code of e4m3fn: no finite input makes the fp8 epilogue store it
 TORCH = {"bf16": torch.bfloat16, "f16": torch.float16, "fp32": torch.float32}
 CODE = {"fp32": 0, "bf16": 1, "f16": 3}                # SGPT_F32 / SGPT_BF16 / SGPT_F16
 
 
+def _sentinel(ity):
+    return {torch.int32: SENT32, torch.int16: SENT16, torch.uint8: SENT8}[ity]
+
+
 def guarded(n, out_t, init=None):
-    """[GUARD | n elements | GUARD] as integers, everything the sentinel; the middle also as a view of the output type."""
-    ity, sent = (torch.int32, SENT32) if out_t == torch.float32 else (torch.int16, SENT16)
+    """[GUARD | n elements | GUARD] as integers, everything the sentinel; the middle also as a view of the output type (fp32, a
+    16-bit float, or uint8 for e4m3 codes)."""
+    ity = torch.int32 if out_t == torch.float32 else torch.uint8 if out_t == torch.uint8 else torch.int16
+    sent = _sentinel(ity)
     buf = torch.full((n + 2 * GUARD,), sent, dtype=ity, device=DEV)
     body = buf[GUARD:GUARD + n].view(out_t)
     if init is not None:
@@ -30,7 +37,7 @@ def guarded(n, out_t, init=None):
 
 
 def check_guards(buf, n, what):
-    sent = SENT32 if buf.dtype == torch.int32 else SENT16
+    sent = _sentinel(buf.dtype)
     assert bool((buf[:GUARD] == sent).all()), f"{what}: a store in front of the output"
     assert bool((buf[GUARD + n:] == sent).all()), f"{what}: a store behind the output"
     assert not bool((buf[GUARD:GUARD + n] == sent).any()), f"{what}: an element of the output was left unwritten"

@@ -1,7 +1,8 @@
 """Test infrastructure: the projection GEMM with its fused epilogues (include/sgpt_hip.h::sgpt_linear / sgpt_linear_split) in
 float64 numpy, a derived error bound for any fp32 accumulation of the same products, a Python mirror of the launch rule of
-csrc/gemm.hip and of the tile walk of its persistent 256x256 kernel, a mirror of the launcher and workgroup list of the query-sized
-kernels (csrc/qgemm.hip), and the shape tables of tests/test_gpu_linear_edges.py, tests/test_gpu_linear_256.py and
+csrc/gemm.hip and of the tile walk of its persistent 256x256 kernel, the same for the fp8 MFMA kernel (csrc/gemm256q.hip) with
+operands whose sums are exact, a mirror of the launcher and workgroup list of the query-sized kernels (csrc/qgemm.hip), and the
+shape tables of tests/test_gpu_linear_edges.py, tests/test_gpu_linear_256.py, tests/test_gpu_linear_fp8.py and
 tests/test_gpu_linear_query.py.  Checked without a GPU by tests/test_gemm_ref.py.
 
 Operands are the exact values of the already rounded inputs (16-bit x 16-bit and fp32 x fp32 products are taken as the float64
@@ -210,12 +211,13 @@ Launch256 = namedtuple("Launch256", "balanced m_major deep_a AT BT tiles_total g
 
 
 @functools.lru_cache(maxsize=8)
-def _tile_list256(MT, NT, ncu, gm, gn):
-    """tile_coords of gemm256d_kernel for every tile index below tiles_total: (m0, n0), or None where it returns false."""
+def _tile_list256(MT, NT, ncu, gm, gn, may_balance=True):
+    """tile_coords of gemm256d_kernel for every tile index below tiles_total: (m0, n0), or None where it returns false.
+    may_balance=False: tile_coords of gemm256q_kernel (csrc/gemm256q.hip), which has the supertile branch alone."""
     m_major = MT >= NT
     AT, BT = (MT, NT) if m_major else (NT, MT)
     GM, GN = (gm if gm > 0 else 4), (gn if gn > 0 else 8)
-    balanced = AT * BT <= 4 * ncu                              # launch256d
+    balanced = may_balance and AT * BT <= 4 * ncu              # launch256d
     R = AT * BT
     c0, rem = R >> 3, R & 7
     tiles_total = 8 * ((R + 7) >> 3) if balanced else ((AT + 7) // 8 + GM - 1) // GM * GM * 8 * BT
@@ -285,6 +287,152 @@ SUPER_ROWS = ("super-m", "super-n", "super-3")
 
 def launch_of(c, ncu=NCU256, cu_cap=None):
     return tiles256(c.M, c.N, ncu, c.cu_cap if cu_cap is None else cu_cap)
+
+
+# ---------------------------------------------------------------- the fp8 MFMA kernel: launch256q and its tile_coords ------------
+def tiles256q(M, N, ncu, cu_cap=0, gm=4, gn=8):
+    """The same mirror for launch256q<> and tile_coords of gemm256q_kernel (csrc/gemm256q.hip): the supertile walk (GM 4 / GN 8) at
+    every size -- the kernel has no balanced branch -- under the per-ctx workgroup cap; deep_a = M >= N (launch256q)."""
+    ncu = ncu // 8 * 8
+    balanced, m_major, AT, BT, coords = _tile_list256(M // 256, N // 256, ncu, gm, gn, False)
+    tiles_total = len(coords)
+    cus = cu_cap // 8 * 8 if 8 <= cu_cap < ncu else ncu
+    grid = tiles_total if tiles_total < cus else cus
+    runs = [[c for c in coords[b::grid] if c is not None] for b in range(grid)]
+    return Launch256(balanced, m_major, M >= N, AT, BT, tiles_total, grid, sum(c is None for c in coords), runs)
+
+
+def slots256q(M, N, ncu, cu_cap=0):
+    """Per workgroup, the slots it looks at in order -- (m0, n0), or None for a slot tile_coords refuses (the walk of tiles256q
+    with the refused slots kept: a None between two tiles is a skipped slot in the interior of a run)."""
+    L = tiles256q(M, N, ncu, cu_cap)
+    coords = _tile_list256(M // 256, N // 256, ncu // 8 * 8, 4, 8, False)[4]
+    return [list(coords[b::L.grid]) for b in range(L.grid)]
+
+
+# ---------------------------------------------------------------- shapes of tests/test_gpu_linear_fp8.py -------------------------
+# fp8 (e4m3) operands, every K a multiple of 256; nk = K / 128 k-steps.  A workgroup carries the deep ring position sd (mod 3)
+# from tile to tile: tile i of a run starts from sd = i nk mod 3.  tag: 'ring' (24 tiles on 8 workgroups, runs of 3: with
+# nk % 3 = 2, 1, 0 the tiles of a run start from every sd), 'uneven' (three of eight workgroups without a tile), 'single',
+# 'groups' (BT = 9 > GN: a second column group of width 1, skipped slots between the valid tiles of a run), 'cap' (bit invariance
+# under the cap), 'grid' (no cap: 288 slots on a device of 256 CUs, runs of 2 and 1 -- the only rows that depend on the CU count).
+Case256Q = namedtuple("Case256Q", "name M N K cu_cap tag")
+RINGQ_K = (256, 512, 768)
+CAPQ = (0, 8, 24, 100)                                 # 100 rounds down to 96
+CASES256Q = (
+    [Case256Q(f"q8-ringA-k{K}", 2048, 768, K, 8, "ring") for K in RINGQ_K]          # deep A (M >= N)
+    + [Case256Q(f"q8-ringW-k{K}", 768, 2048, K, 8, "ring") for K in RINGQ_K]        # deep W
+    + [
+        Case256Q("q8-uneven", 1280, 1024, 256, 8, "uneven"),
+        Case256Q("q8-single", 256, 256, 256, 0, "single"),
+        Case256Q("q8-groups", 2304, 2304, 256, 8, "groups"),
+        Case256Q("q8-cap", 2048, 768, 512, 0, "cap"),
+        Case256Q("q8-grid-m", 8192, 2304, 512, 0, "grid"),
+        Case256Q("q8-grid-n", 2304, 8192, 512, 0, "grid"),
+    ]
+)
+
+
+def launch_of_q8(c, ncu=NCU256, cu_cap=None):
+    return tiles256q(c.M, c.N, ncu, c.cu_cap if cu_cap is None else cu_cap)
+
+
+# Exact operands.  Small-integer e4m3 codes: every product is an integer and every sum of them is exact in fp32 whatever its order,
+# so the output of the kernel is ONE value per element and a k-step taken from a stale ring slot or from another tile fails
+# torch.equal with certainty.  |a| <= 4, |w| <= 6: |acc| <= 24 K <= 18 432 (K <= 768) for any such codes; the pattern below keeps
+# |acc| <= EXACT_ACC_MAX = 2^11 (tests/test_gemm_ref.py computes it for every case).  Row scales 2^-4 .. 2^2, channel scales
+# 2^-3 .. 2^1, a_scalar 1 or 2^-2: every scaled value is at most 8 EXACT_ACC_MAX = 2^14 < 2^15 -- the threshold of the f16 range
+# tracker -- and a multiple of 2^-9 with at most 11 + 9 significant bits; with the integer bias and residual added (|.| <= 13)
+# it still has fewer than 24: every intermediate of every epilogue is exact in fp32, and the 16-bit stores round an exact value once.
+# The pattern is a multiplicative hash of (row, k) folded to -4 .. 4 (a) and -6 .. 6 (w).  The periodic pattern of
+# test_gpu_fp8mfma.py::test_linear_fp8_layout_probe, (5 m + 3 k) % 9 - 4 and (7 n + 11 k) % 13 - 6, does not serve here: its
+# 256 x 128-byte slabs repeat -- A after 3 k-steps and after 9 row tiles, and the slab of (row tile 3, k-step 0) is that of (row
+# tile 0, k-step 1) -- so a k-step read from the ring slot of three steps earlier would go unseen.  Linear patterns whose
+# strides depend on the tile and the k-step have distinct slabs but resonate (|acc| up to 3 000 at K = 768); the hash has
+# distinct slabs and accumulators of about six standard deviations of a random sum at most.
+EXACT_ACC_MAX = 2048
+
+
+def _hash_codes(R, K, p, q, mod):
+    r, k = np.arange(R, dtype=np.uint64)[:, None], np.arange(K, dtype=np.uint64)[None, :]
+    h = (((r * np.uint64(p)) ^ (k * np.uint64(q))) * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)
+    return ((h >> np.uint64(16)) % np.uint64(mod)).astype(np.int64) - mod // 2
+
+
+def exact_codes(M, N, K):
+    """(a [M, K] in -4 .. 4, w [N, K] in -6 .. 6) as int64 numpy: the small integers above."""
+    return _hash_codes(M, K, 73856093, 19349663, 9), _hash_codes(N, K, 83492791, 50331653, 13)
+
+
+def exact_scales(M, N):
+    """Row scales 2^((m % 7) - 4) and channel scales 2^((n % 5) - 3), float64."""
+    return 2.0 ** ((np.arange(M) % 7) - 4), 2.0 ** ((np.arange(N) % 5) - 3)
+
+
+def exact_bias_resid(M, N):
+    """Integer bias [N] (period 11, -5 .. 5) and residual [M, N] (period 17 along both axes, -8 .. 8), float64."""
+    m, n = np.arange(M)[:, None], np.arange(N)[None, :]
+    return (np.arange(N) % 11 - 5).astype(np.float64), ((3 * m + 5 * n) % 17 - 8).astype(np.float64)
+
+
+SCALE_VARIANTS = {"row": (True, 1.0), "scalar": (False, 0.25), "both": (True, 0.25)}      # (a_scale per row?, a_scalar)
+
+
+@functools.lru_cache(maxsize=2)
+def exact_case(name):
+    """The exact operands of a CASES256Q row and their integer product acc [M, N] in float64 (computed once per case)."""
+    c = case(name)
+    a, w = exact_codes(c.M, c.N, c.K)
+    sa, sw = exact_scales(c.M, c.N)
+    bias, resid = exact_bias_resid(c.M, c.N)
+    return dict(c=c, a=a, w=w, sa=sa, sw=sw, bias=bias, resid=resid, acc=product(a, w))
+
+
+def exact_scaled(x, variant):
+    """acc sa[m] a_scalar sw[n] of a scale variant, float64 (exact: powers of two)."""
+    rows, a_scalar = SCALE_VARIANTS[variant]
+    v = x["acc"] * (x["sw"] * a_scalar)[None, :]
+    return v * x["sa"][:, None] if rows else v
+
+
+def e4m3_values():
+    """The 127 non-negative finite e4m3fn values, ascending."""
+    import torch
+    return torch.arange(127, dtype=torch.uint8).view(torch.float8_e4m3fn).double().numpy()
+
+
+def e4m3_tie_distance(v):
+    """|v - the nearest rounding boundary of e4m3fn| / |v| for 0 < v <= 448 (float64 array): how far, relatively, a value is from
+    the point where a last-bit difference of the epilogue's arithmetic could move its code."""
+    vals = e4m3_values()
+    ties = 0.5 * (vals[1:] + vals[:-1])
+    i = np.clip(np.searchsorted(ties, v), 1, len(ties) - 1)
+    return np.minimum(np.abs(v - ties[i - 1]), np.abs(v - ties[i])) / np.abs(v)
+
+
+GELU_EXACT_MARGIN = 2.0 ** -19                          # 16 fp32 ulps
+
+
+def gelu_exact_setup(acc, sa, sw, a_scalar):
+    """Bias [N] and out_scale for the exact test of the gelu -> e4m3 epilogue on the integer product acc [M, N] under row scales sa
+    (None = 1), channel scales sw and a_scalar.  With s[n] = sw[n] a_scalar: bias[n] = s[n] (C[n] + 2^-5), C[n] an integer, so that
+    u = acc sa sw a_scalar + bias = s[n] t,  t = acc sa[m] + C[n] + 2^-5  >= 512:
+      * u >= 16: z of gelu_new_fast is below -300, exp2 gives 0 and gelu_new(u) = u but for the last bit of rcp(1.0);
+      * t is an odd multiple of 2^-5 in [2^9, 2^14) (while |acc sa| < 7 900; the tests compute the distance): it has at least 15 significant bits, a rounding
+        boundary of e4m3 has 5, and the nearest one is at least 2^-5 away: 2^-19 relative = GELU_EXACT_MARGIN, 16 ulps of fp32 --
+        no last-bit difference of rcp or exp2 moves a code;
+      * u is exact in fp32 (19 bits) and u / out_scale <= 448 with out_scale the smallest such power of two.
+    A bias per COLUMN cannot make every u / out_scale exactly representable in e4m3 (3 mantissa bits: the product would have to
+    take 16 values); the distance to the boundaries is the property that protects the codes, and tests check the computed one.
+    Returns (bias float64 [N], out_scale, u float64 [M, N])."""
+    v = acc * (1.0 if sa is None else sa[:, None])
+    vmax = float(np.abs(v).max())
+    C = 512 + math.ceil(vmax) + 16 * (np.arange(acc.shape[1]) % 3)
+    s = sw * a_scalar
+    bias = s * (C + 2.0 ** -5)
+    u = (v + (C + 2.0 ** -5)[None, :]) * s[None, :]
+    out_scale = 2.0 ** math.ceil(math.log2(float(u.max()) / 448.0))
+    return bias, out_scale, u
 
 
 # ---------------------------------------------------------------- the query-sized kernels: the launcher of csrc/qgemm.hip --------
@@ -535,11 +683,11 @@ def launch_q(c, epi=None, ncu=NCU256):
 
 
 def case(name):
-    return next(c for c in CASES + CASES256 + CASESQ if c.name == name)
+    return next(c for c in CASES + CASES256 + CASES256Q + CASESQ if c.name == name)
 
 
 def case_k(c, dtype):
-    if isinstance(c, (Case256, CaseQ)):
+    if isinstance(c, (Case256, Case256Q, CaseQ)):
         return c.K
     return c.K32 if dtype == "fp32" else c.K16
 

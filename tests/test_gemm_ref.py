@@ -447,3 +447,155 @@ def test_q_workgroup_list_covers_every_tile_group_once():
                     NG = R // MT
                     for NT in {NG * group, NG * group - (group - 1)}:
                         _covers_once(MT * 32, NT * 32, 32, 32, group)
+
+
+# ---------------------------------------------------------------- the fp8 MFMA kernel: tile walk, case table, exact operands ------
+
+Q8IDS = dict(ids=lambda c: c.name)
+Q8_SMALL = [c for c in G.CASES256Q if c.tag != "grid"]
+# the ring positions a tile can start from: tile i of a run starts at sd = i nk mod 3, so nk % 3 == 0 always starts from 0
+Q8_RING_STATES = {(0, 0), (0, 1), (1, 1), (2, 1), (0, 2), (2, 2), (1, 2)}         # (sd at the start of a tile, nk % 3)
+
+
+def test_tiles256q_visits_every_tile_exactly_once():
+    """launch256q / tile_coords of gemm256q_kernel: the supertile walk at every size, never the balanced one; the union of the
+    workgroups' runs is every tile exactly once for every AT x BT in 1..40 x 1..12, both orientations, every cap."""
+    shapes = {(at, bt) for at in range(1, 41) for bt in range(1, 13)} | {(c.M // 256, c.N // 256) for c in G.CASES256Q}
+    shapes |= {(b, a) for a, b in shapes}
+    for mt, nt in sorted(shapes):
+        for cap in G.CAPQ + (96,):
+            L = G.tiles256q(mt * 256, nt * 256, G.NCU256, cap)
+            seen = [t for run in L.runs for t in run]
+            assert not L.balanced and len(seen) == mt * nt == len(set(seen)), (mt, nt, cap)
+            assert all(0 <= m0 < mt * 256 and 0 <= n0 < nt * 256 for m0, n0 in seen)
+            assert L.skipped == L.tiles_total - mt * nt and L.grid % 8 == 0 and L.grid <= (cap // 8 * 8 if 8 <= cap < G.NCU256 else G.NCU256)
+            assert L.deep_a == (mt >= nt) == L.m_major
+            slots = G.slots256q(mt * 256, nt * 256, G.NCU256, cap)
+            assert [[s for s in r if s is not None] for r in slots] == L.runs
+
+
+def test_tiles256q_pins():
+    """The mirror against values worked out by hand from launch256q."""
+    L = G.tiles256q(2048, 768, 256, 8)                 # AT 8, BT 3: one band of 4 x 8 x 3 = 96 slots; XCD b's first three are (b, 0 .. 2)
+    assert (L.tiles_total, L.grid, L.skipped) == (96, 8, 72) and L.runs[1] == [(256, 0), (256, 256), (256, 512)]
+    L = G.tiles256q(768, 2048, 256, 8)
+    assert not L.m_major and not L.deep_a and L.runs[1] == [(0, 256), (256, 256), (512, 256)]
+    assert [G.tiles256q(2048, 768, 256, cap).grid for cap in G.CAPQ] == [96, 8, 24, 96]
+    L = G.tiles256q(256, 256, 256)                     # 32 slots for one tile
+    assert (L.tiles_total, L.grid) == (32, 32) and [len(r) for r in L.runs] == [1] + [0] * 31
+    L = G.tiles256q(2304, 2304, 256, 8)                # BT 9: column groups of 8 and 1; A-tile 8 belongs to XCD 0
+    assert L.tiles_total == 288 and [len(r) for r in L.runs] == [18] + [9] * 7
+    assert L.runs[0] == [(0, 256 * j) for j in range(8)] + [(2048, 256 * j) for j in range(8)] + [(0, 2048), (2048, 2048)]
+    assert L.runs[3] == [(768, 256 * j) for j in range(9)]
+    L = G.tiles256q(8192, 2304, 256)
+    assert (L.tiles_total, L.grid, L.skipped) == (288, 256, 0) and sorted(len(r) for r in L.runs) == [1] * 224 + [2] * 32
+
+
+def test_cases256q_reach_every_branch_of_the_tile_walk():
+    launches = {c.name: G.launch_of_q8(c) for c in G.CASES256Q}
+    for deep_a in (True, False):
+        states = set()
+        for c in G.CASES256Q:
+            L = launches[c.name]
+            if c.tag == "ring" and L.deep_a == deep_a:
+                nk = c.K // 128
+                assert c.K % 256 == 0 and L.grid == 8 and all(len(r) == 3 for r in L.runs)
+                states |= {((i * nk) % 3, nk % 3) for r in L.runs for i in range(len(r))}
+        assert states == Q8_RING_STATES, (deep_a, states)
+    assert {(L.deep_a, L.m_major) for L in launches.values()} == {(True, True), (False, False)}
+    for tag in ("ring", "grid"):
+        assert {launches[c.name].deep_a for c in G.CASES256Q if c.tag == tag} == {True, False}
+    L = launches["q8-uneven"]
+    assert sorted(len(r) for r in L.runs) == [0, 0, 0, 4, 4, 4, 4, 4]                  # three of eight workgroups exit at once
+    assert [len(r) for r in launches["q8-single"].runs].count(1) == 1 and sum(map(len, launches["q8-single"].runs)) == 1
+    c = G.case("q8-groups")
+    slots = G.slots256q(c.M, c.N, G.NCU256, c.cu_cap)
+    def interior_gap(r):
+        live = [i for i, s in enumerate(r) if s is not None]
+        return any(s is None for s in r[live[0]:live[-1]])
+    assert all(interior_gap(r) for r in slots) and launches["q8-groups"].BT == 9       # a skipped slot between two tiles of a run
+    # the look-up of the tile after the next one runs past the end: in every run of two tiles or more, at its last but one tile
+    assert all(len(r) >= 2 for c in G.CASES256Q if c.tag in ("ring", "groups") for r in launches[c.name].runs)
+    assert {tuple(sorted({len(r) for r in launches[n].runs})) for n in ("q8-grid-m", "q8-grid-n")} == {(1, 2)}
+    assert [G.launch_of_q8(G.case("q8-cap"), cu_cap=cap).grid for cap in G.CAPQ] == [96, 8, 24, 96]
+    assert all(c.K % 256 == 0 and c.M % 256 == 0 and c.N % 256 == 0 for c in G.CASES256Q)
+    assert len({c.name for c in G.CASES + G.CASES256 + G.CASES256Q + G.CASESQ}) == len(G.CASES + G.CASES256 + G.CASES256Q + G.CASESQ)
+
+
+@pytest.mark.parametrize("c", G.CASES256Q, **Q8IDS)
+def test_exact_operands_have_distinct_slabs_and_small_sums(c):
+    """Per operand, the 256 x 128-byte slabs of any two different (row tile, k-step) pairs differ -- so do the (A slab, W slab)
+    pairs of any two (tile, k-step) -- the codes are integers e4m3 holds exactly, and |acc| <= EXACT_ACC_MAX."""
+    a, w = G.exact_codes(c.M, c.N, c.K)
+    assert a.min() == -4 and a.max() == 4 and w.min() == -6 and w.max() == 6
+    for x in (a, w):
+        back = torch.from_numpy(x.astype(np.float32)).to(torch.float8_e4m3fn).float().numpy()
+        assert np.array_equal(back, x)
+    for x, rows in ((a, c.M), (w, c.N)):
+        slabs = {x[r0:r0 + 256, k0:k0 + 128].astype(np.int8).tobytes() for r0 in range(0, rows, 256) for k0 in range(0, c.K, 128)}
+        assert len(slabs) == (rows // 256) * (c.K // 128)
+    acc = a.astype(np.float32) @ w.astype(np.float32).T                              # integers below 2^24: exact in fp32 too
+    assert float(np.abs(acc).max()) <= G.EXACT_ACC_MAX and 24 * c.K <= 18432
+    assert 8 * G.EXACT_ACC_MAX < 2 ** 15
+    if c.tag != "grid":
+        assert np.array_equal(acc.astype(np.float64), G.exact_case(c.name)["acc"])
+
+
+@pytest.mark.parametrize("c", Q8_SMALL, **Q8IDS)
+def test_exact_epilogue_values_are_exact_in_fp32(c):
+    """Every intermediate the epilogues form from the exact operands is an fp32 number: the scaled accumulator, with the bias, and
+    with bias + residual, for every scale variant; the gelu set-up keeps u >= 16, u / out_scale <= 448 and at GELU_EXACT_MARGIN
+    from every rounding boundary of e4m3, and gelu_new(u) = u in float64."""
+    x = G.exact_case(c.name)
+    f32 = lambda v: np.array_equal(v.astype(np.float32).astype(np.float64), v)
+    for variant, (rows, a_scalar) in G.SCALE_VARIANTS.items():
+        v = G.exact_scaled(x, variant)
+        assert float(np.abs(v).max()) < 2 ** 15 - 16
+        assert f32(v) and f32(v + x["bias"][None, :]) and f32(x["bias"][None, :] + x["resid"]) and f32(v + (x["bias"][None, :] + x["resid"]))
+        bias, out_scale, u = G.gelu_exact_setup(x["acc"], x["sa"] if rows else None, x["sw"], a_scalar)
+        assert f32(bias) and f32(u) and np.array_equal(v + bias[None, :], u)
+        assert float(u.min()) >= 16.0 and float(u.max()) <= 448.0 * out_scale and math.log2(out_scale) == round(math.log2(out_scale))
+        assert np.array_equal(G.gelu_new(u), u)
+        margin = float(G.e4m3_tie_distance(u / out_scale).min())
+        print(f"{c.name} {variant}: u in [{u.min():.4g}, {u.max():.4g}], out_scale {out_scale:g}, distance to a rounding boundary >= 2^{math.log2(margin):.2f}")
+        assert margin >= G.GELU_EXACT_MARGIN
+
+
+def test_e4m3_tie_distance():
+    v = np.array([1.0, 1.0625, 1.125, 17.0, 18.0, 448.0, 2.0 ** -9, 1.5 * 2.0 ** -9])
+    assert np.allclose(G.e4m3_tie_distance(v), [0.03125, 0.0, 0.0625 / 1.125, 0.0, 1.0 / 18.0, 16.0 / 448.0, 0.5, 0.0])
+    assert len(G.e4m3_values()) == 127 and G.e4m3_values()[-1] == 448.0
+
+
+@pytest.mark.parametrize("c", [c for c in G.CASES256Q if c.tag in ("ring", "uneven", "groups", "grid")], **Q8IDS)
+def test_a_slab_from_the_wrong_tile_or_a_stale_slot_changes_the_exact_result(c):
+    """What the carry-over between the tiles of a run can get wrong, as integers, for every pair of consecutive tiles of two
+    workgroups' runs and every k-step of the later tile: (1) the A slab or (2) the W slab of that k-step comes from the previous
+    tile of the run; (3) the deep operand's slab is the one its ring slot held three global k-steps earlier (a slot the run-ahead
+    DMA did not refill: for the first k-steps of a tile a slab of the PREVIOUS tile).  Each changes more than nine tenths of the
+    tile's integer sums -- the condition under which torch.equal on the GPU sees the fault with certainty."""
+    a, w = G.exact_codes(c.M, c.N, c.K)
+    L = G.launch_of_q8(c)
+    nk = c.K // 128
+    runs = [r for r in L.runs if len(r) >= 2]
+    assert runs
+    for run in (runs[0], runs[-1]):
+        for i in range(1, len(run)):
+            (pm0, pn0), (m0, n0) = run[i - 1], run[i]
+            A1, W1, A0, W0 = a[m0:m0 + 256], w[n0:n0 + 256], a[pm0:pm0 + 256], w[pn0:pn0 + 256]
+            for kt in range(nk):
+                ks = slice(kt * 128, kt * 128 + 128)
+                moved = {"A from the previous tile": (A0[:, ks] - A1[:, ks]) @ W1[:, ks].T,
+                         "W from the previous tile": A1[:, ks] @ (W0[:, ks] - W1[:, ks]).T}
+                g = i * nk + kt - 3                     # global k-step of the run whose deep slab the ring slot held before
+                D_old = (A0, W0)[not L.deep_a] if g < i * nk else (A1, W1)[not L.deep_a]
+                go = slice((g % nk) * 128, (g % nk) * 128 + 128)
+                if L.deep_a:
+                    moved["stale deep slot"] = (D_old[:, go] - A1[:, ks]) @ W1[:, ks].T
+                else:
+                    moved["stale deep slot"] = A1[:, ks] @ (D_old[:, go] - W1[:, ks]).T
+                for what, d in moved.items():
+                    if (pm0 == m0 and what.startswith("A")) or (pn0 == n0 and what.startswith("W")):
+                        continue                        # the neighbour shares this operand's rows: the same slab
+                    frac = float((d != 0).mean())
+                    assert frac > 0.9, f"{c.name} tile {i} of a run, k-step {kt}, {what}: only {frac:.3f} of the sums change"

@@ -33,8 +33,11 @@ def dq(codes, scale):
     return codes.view(torch.float8_e4m3fn).float() * scale[:, None]
 
 
-@pytest.mark.parametrize("M,N,K", [(4096, 3072, 768), (4096, 768, 3072), (256, 256, 256), (512, 2048, 256), (2048, 256, 512)])
+@pytest.mark.parametrize("M,N,K", [(256, 256, 256), (512, 2048, 256), (2048, 256, 512)])
 def test_linear_fp8_equals_fp32_product_of_dequantised_operands(ctx, M, N, K):
+    """(Launches of more tiles than workgroups -- runs of two tiles per workgroup on the default grid, both orientations -- are
+    tests/test_gpu_linear_fp8.py::test_default_grid_is_exact, bit for bit; runs of three and more, every epilogue and random
+    operands against float64 are in that file too.)"""
     g = torch.Generator(device="cuda").manual_seed(M + N + K)
     a = torch.randn((M, K), generator=g, device="cuda") * torch.exp(torch.randn((M, 1), generator=g, device="cuda"))
     w = torch.randn((N, K), generator=g, device="cuda") / math.sqrt(K)
