@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 23
+#define SGPT_ABI_VERSION 24
 
 /* The longest sequence (ABI v23): the token rows one sequence may own in the packed layout of sgpt_encode*, sgpt_attention_ex and
  * sgpt_attention_gqa (max_alloc_len <= SGPT_MAX_SEQ_LEN; a larger value is SGPT_ERR_INVALID, nothing launched).  32 768 is the
@@ -73,7 +73,7 @@ enum { SGPT_ARCH_GPTNEO = 0, SGPT_ARCH_GPTJ = 1, SGPT_ARCH_BLOOM = 2, SGPT_ARCH_
  *   sgpt_model_set_range_shifts refuse -- a flagged model is reloaded as SGPT_BF16 / SGPT_F32.  16-bit head_dim 64 | 128.
  *   Every layout (T_pad % 32) runs the bulk projection kernels: the query-sized kernels' LayerNorm prologues assume pre-LN. */
 /* SGPT_ARCH_LLAMA (ABI v15): HF LlamaModel and MistralModel (HF:llama/modeling_llama.py, HF:mistral/modeling_mistral.py) -- the two differ
- * only in the window.  Pre-norm causal decoder, no bias anywhere, x the fp32 residual stream:
+ * only in the window.  Pre-norm decoder, causal unless sgpt_model_set_attention says otherwise (ABI v24, below), no bias anywhere, x the fp32 residual stream:
  *   a = RMSNorm_1(x);  q | k | v = a W^T with n_heads query heads and n_kv_heads key / value heads (grouped K / V: query head h reads
  *   key / value head h / (n_heads / n_kv_heads));  q, k <- half-split rotary (rotate_half: x[i] pairs with x[i + head_dim / 2]);
  *   x += softmax(q.k^T / sqrt(dh), causal, window) v Wo^T;  a = RMSNorm_2(x);  x += (silu(a Wgate^T) * (a Wup^T)) Wdown^T;
@@ -96,7 +96,12 @@ enum { SGPT_ARCH_GPTNEO = 0, SGPT_ARCH_GPTJ = 1, SGPT_ARCH_BLOOM = 2, SGPT_ARCH_
  *   q / k norm (Qwen3): when "layers.N.self_attn.q_norm.weight" and "layers.N.self_attn.k_norm.weight" fp32 [head_dim] are given, every
  *   query and key head is RMS-normalised over head_dim (ln_eps, the gain shared by the heads) before the rotary -- one fused row
  *   kernel, sgpt_qknorm_rope_half.  Presence is decided on layer 0 and holds for every layer; one gain without the other, or a layer
- *   that disagrees with layer 0, is SGPT_ERR_MISSING by name. */
+ *   that disagrees with layer 0, is SGPT_ERR_MISSING by name.
+ *   ABI v24 -- the bidirectional embedders built on these backbones (GritLM, gte-Qwen2-instruct, LLM2Vec: `is_causal: false`) are this
+ *   family with one property set AFTER load, sgpt_model_set_attention(model, 0): in every layer every query row of a sequence sees
+ *   keys [0, seq_len[b]) of that sequence (the non-causal kernels of SGPT_ARCH_BERT with grouped K / V); rotary, the q / k norm, the
+ *   bias and the projections are untouched.  Not a descriptor field: the descriptor of a model is the same in both modes.  Such
+ *   models usually pool the tokens behind an instruction prompt: sgpt_encode_pool_from. */
 enum { SGPT_POOL_WEIGHTEDMEAN = 0, SGPT_POOL_MEAN = 1, SGPT_POOL_LASTTOKEN = 2, SGPT_POOL_LEARNTMEAN = 3,
        SGPT_POOL_CLS = 4 };   /* ABI v13: the first token row of each sequence (Pooling.py:103-105 `pooling_mode_cls_token`); sgpt_encode*, sgpt_pool */
 enum { SGPT_COS = 0, SGPT_DOT = 1, SGPT_NEG_L2 = 2 };   /* SGPT_NEG_L2 (ABI v11): -||x - y||_2, sgpt_eval_groups only */
@@ -248,6 +253,28 @@ sgpt_status sgpt_encode_host_layout(sgpt_model* model, const int32_t* ids, const
                                     int32_t pool_mode, int32_t n_layers_run, int32_t apply_final_ln,
                                     int32_t normalize, float* out, float* hidden_out, const int32_t* seq_off_host, void* stream);
 
+/* sgpt_encode_host_layout with the pooled rows starting behind a prefix (ABI v24): pool_lo device int32[B] (NULL = zeros = the call
+ * above exactly, bit for bit) -- sequence b is pooled over its token rows t in [min(max(pool_lo[b], 0), seq_len[b]), seq_len[b]): the
+ * tokens behind an instruction prompt (sentence-transformers `include_prompt: false`, GritLM, LLM2Vec).  mean: over that range.
+ * weightedmean: the weight of row t stays pad_left[b] + t + 1, the PADDED position index (Pooling.py) -- the weights do not restart
+ * behind the prompt.  lasttoken: row seq_len[b] - 1 whatever pool_lo says.  An empty range is a zero row (the clamped denominator),
+ * not NaN.  SGPT_POOL_CLS and SGPT_POOL_LEARNTMEAN with a non-NULL pool_lo are SGPT_ERR_INVALID.  seq_off_host may be NULL; in a call
+ * that runs as two chains each chain reads its own sequences' entries. */
+sgpt_status sgpt_encode_pool_from(sgpt_model* model, const int32_t* ids, const int32_t* pos,
+                                  const int32_t* seq_off, const int32_t* seq_len, const int32_t* pad_left,
+                                  int32_t B, int32_t T_pad, int32_t max_alloc_len,
+                                  int32_t pool_mode, int32_t n_layers_run, int32_t apply_final_ln,
+                                  int32_t normalize, float* out, float* hidden_out, const int32_t* seq_off_host,
+                                  const int32_t* pool_lo, void* stream);
+
+/* The attention mode of an SGPT_ARCH_LLAMA model (ABI v24), set after load.  causal = 1: the default, today's path bit for bit.
+ * causal = 0: bidirectional -- see SGPT_ARCH_LLAMA above.  SGPT_ERR_INVALID, by name: for every other arch (SGPT_ARCH_BERT is
+ * bidirectional by architecture, the GPT families stay causal), and with causal = 0 for a model whose descriptor applies a sliding
+ * window on any layer (window > 0 on a layer layer_is_local marks; a Mistral window the loader of the caller folded away is not in
+ * the descriptor, and inside a folded window the window hides nothing in either direction).  Graphs captured before a change are
+ * stale (sgpt_ctx_generation moves). */
+sgpt_status sgpt_model_set_attention(sgpt_model* model, int32_t causal);
+
 /* All L+1 hidden states pooled in ONE forward: the `meanmean` / `lasttokenmean` methods
  * (beir_dense_retriever.py:243-257, 284-301; useb_dense_retriever.py:219-302) average the pooled vector of
  * every entry of `all_hidden_states`.  Entry i < L is the input of block i (raw residual stream), entry L is
@@ -258,6 +285,12 @@ sgpt_status sgpt_encode_layers(sgpt_model* model, const int32_t* ids, const int3
                                const int32_t* seq_off, const int32_t* seq_len, const int32_t* pad_left,
                                int32_t B, int32_t T_pad, int32_t max_alloc_len, int32_t pool_mode,
                                int32_t normalize, float* out_layers, float* out_mean, void* stream);
+
+/* sgpt_encode_layers with pool_lo (ABI v24; see sgpt_encode_pool_from): every one of the L + 1 hidden states is pooled over the same range. */
+sgpt_status sgpt_encode_layers_pool_from(sgpt_model* model, const int32_t* ids, const int32_t* pos,
+                                         const int32_t* seq_off, const int32_t* seq_len, const int32_t* pad_left,
+                                         int32_t B, int32_t T_pad, int32_t max_alloc_len, int32_t pool_mode,
+                                         int32_t normalize, float* out_layers, float* out_mean, const int32_t* pool_lo, void* stream);
 
 /* Trained position weights for SGPT_POOL_LEARNTMEAN: `position_weights` of
  * models/WeightedMeanPooling.py:21-39 (the reference reads them from 1_WeightedMeanPooling/pytorch_model.bin,
@@ -880,6 +913,17 @@ sgpt_status sgpt_attention_gqa(sgpt_ctx* ctx, int32_t dtype, const void* q, cons
                                float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
                                int64_t ctx_lo_delta, int64_t ctx_hi2_delta, void* stream);
 
+/* sgpt_attention_gqa_ex (ABI v24): sgpt_attention_gqa with the trailing causal / seq_len of sgpt_attention_ex, same meaning: causal = 1
+ *   and seq_len = NULL is sgpt_attention_gqa exactly; causal = 0 is the bidirectional attention of an SGPT_ARCH_LLAMA model after
+ *   sgpt_model_set_attention(0) -- bit for bit sgpt_attention_ex(causal = 0) on explicitly replicated K / V^T, at any length up to
+ *   SGPT_MAX_SEQ_LEN (16-bit: the same 64-key tile loop, run to the sequence end; fp32 above 2048 rows: the chunked kernel).  causal = 0
+ *   refuses window, alibi, out_fp8, x3, the split context and 16-bit head_dim 256.  max_alloc_len even, in [2, SGPT_MAX_SEQ_LEN]. */
+sgpt_status sgpt_attention_gqa_ex(sgpt_ctx* ctx, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
+                                  void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t n_kv_heads,
+                                  int32_t dh, int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
+                                  float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
+                                  int64_t ctx_lo_delta, int64_t ctx_hi2_delta, int32_t causal, const int32_t* seq_len, void* stream);
+
 /* The encoder's row kernels, stand-alone (ABI v12; kernel-level tests: tests/test_gpu_rowops.py compares each with a float64
  * restatement of the same operation).  These are the launches sgpt_encode / sgpt_lm_logprobs make between their GEMMs, on
  * caller-owned device buffers.  Every entry returns SGPT_ERR_INVALID, with nothing launched, for a null pointer, a row width
@@ -913,6 +957,9 @@ sgpt_status sgpt_attention_gqa(sgpt_ctx* ctx, int32_t dtype, const void* q, cons
  *   sgpt_range_check.
  * sgpt_lnf_pool_ex (ABI v15): sgpt_lnf_pool with a trailing norm_kind: 0 = LayerNorm (sgpt_lnf_pool exactly), 1 = RMSNorm(gamma)
  *   (beta is not read).
+ * sgpt_lnf_pool_range (ABI v24): sgpt_lnf_pool_ex with pool_lo device int32[B] (NULL = zeros = sgpt_lnf_pool_ex exactly): the pooled
+ *   rows of sequence i are t in [min(max(pool_lo[i], 0), seq_len[i]), seq_len[i]) -- see sgpt_encode_pool_from.  A non-NULL pool_lo
+ *   with SGPT_POOL_LEARNTMEAN is refused.
  * sgpt_lnf_pool: the final LayerNorm fused with the pooling of a packed batch (layout of sgpt_encode: sequence i holds rows
  *   [seq_off[i], seq_off[i] + seq_len[i]) of x fp32[T_pad, d]; rows outside are never read).  apply_ln: ln_f (HF:gpt_neo:492)
  *   on every row first.  mode SGPT_POOL_*: weightedmean sum_t (P + t + 1) h_t / max(sum_t (P + t + 1), 1e-9) with P =
@@ -948,6 +995,10 @@ sgpt_status sgpt_lnf_pool_ex(sgpt_ctx* ctx, const float* x, const float* gamma, 
                              const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
                              int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,
                              int32_t* nonfinite_flag, int32_t norm_kind, void* stream);
+sgpt_status sgpt_lnf_pool_range(sgpt_ctx* ctx, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
+                                const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
+                                int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,
+                                int32_t* nonfinite_flag, int32_t norm_kind, const int32_t* pool_lo, void* stream);
 sgpt_status sgpt_lnf_pool(sgpt_ctx* ctx, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
                           const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
                           int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,

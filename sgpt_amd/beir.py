@@ -36,14 +36,19 @@ class CustomEmbedder:
 
     def __init__(self, model_name="EleutherAI/gpt-neo-1.3B", batch_size=250, device="cuda:0", save_emb=False,
                  reinit=False, layeridx=-1, method="mean", dataset="scifact", specb=False, maxseqlen=None,
-                 model: Optional[SGPTModel] = None, tokenizer=None, dtype="f16", frame=None, **kwargs):
+                 model: Optional[SGPTModel] = None, tokenizer=None, dtype="f16", frame=None, prompt: str = None,
+                 include_prompt: bool = True, **kwargs):
+        """prompt / include_prompt: TextPipeline's -- an instruction in front of every text (queries and documents alike) that
+        include_prompt=False leaves out of the pooling (GritLM, LLM2Vec); single-layer methods 'mean', 'weightedmean', 'lasttoken'
+        and the all-layer methods take it."""
         if reinit:
             raise NotImplementedError("reinit (random re-initialisation ablation) is not part of the hot path")
         self.device = torch.device(device)
         self.model = model if model is not None else SGPTModel.from_pretrained(model_name, device=device, dtype=dtype)
         self.tokenizer = tokenizer if tokenizer is not None else load_tokenizer(model_name)
         self.max_token_len = maxseqlen if maxseqlen else max_seq_len_of(self.model)   # :128, never beyond what the model encodes
-        self.pipe = TextPipeline(self.tokenizer, self.max_token_len, specb=specb, family=family_of(self.model), frame=frame)   # frame: TextPipeline's
+        self.pipe = TextPipeline(self.tokenizer, self.max_token_len, specb=specb, family=family_of(self.model), frame=frame,   # frame: TextPipeline's
+                                 prompt=prompt, include_prompt=include_prompt)
         self.max_token_len = self.pipe.max_token_len
         self.batch_size = batch_size
         self.save_emb = save_emb
@@ -78,12 +83,14 @@ class CustomEmbedder:
         L = self.model.cfg.num_layers
         if abs(self.layeridx) > L + 1:
             raise ValueError(f"Layer Idx {self.layeridx} is larger than the {L + 1} hidden states")   # :234-235
+        pf = self.pipe.pool_from()
+        pf = {} if pf is None else {"pool_from": pf}        # (a model stand-in without the argument keeps working while no prompt is left out)
         if self.method in SINGLE_LAYER_METHODS:
-            return self.model.encode_ids(seqs, mode=self.method, normalize=normalize, layer_idx=self.layeridx)
+            return self.model.encode_ids(seqs, mode=self.method, normalize=normalize, layer_idx=self.layeridx, **pf)
         # meanmean / lasttokenmean (:243-257, 284-301): average of the per-layer pooled vectors over all
         # L+1 hidden states (equal token counts per layer make the two formulations identical) -- pooled on
         # the way through ONE forward (sgpt_encode_layers) instead of copying L+1 hidden states to the host
-        acc = self.model.encode_ids_all_layers(seqs, mode=ALL_LAYER_METHODS[self.method])
+        acc = self.model.encode_ids_all_layers(seqs, mode=ALL_LAYER_METHODS[self.method], **pf)
         return get_context(self.model.device).l2_normalize(acc) if normalize else acc
 
     # -- reference surface -------------------------------------------------------------------

@@ -459,7 +459,8 @@ void launch_lnf_pool(const float* x, const float* g, const float* b, const int* 
                      const int* pad_left, int B, int d, float eps, int apply_ln, int mode, int normalize,
                      const float* pos_weights, int pos_weights_n, float* out, hipStream_t s,
                      int* nonfinite_flag = nullptr,    // f16 models: raised (bit 0) when a pooled row is not finite
-                     int norm_kind = 0);               // apply_ln: 0 = LayerNorm(g, b), 1 = RMSNorm(g) (b is not read)
+                     int norm_kind = 0,                // apply_ln: 0 = LayerNorm(g, b), 1 = RMSNorm(g) (b is not read)
+                     const int* pool_lo = nullptr);    // first pooled row per sequence (null = 0), clamped into [0, len]; not for cls
 void launch_pool(const void* hidden, int dtype, const int* mask, int B, int S, int d, int mode,
                  const float* pos_weights, float* out, hipStream_t s);
 // fp8 e4m3fn weight storage, one power-of-two scale per row (output channel)

@@ -145,11 +145,15 @@ __global__ __launch_bounds__(256) void layernorm_q8_kernel(const float* __restri
 // mean: Pooling.py:117-125 / beir_dense_retriever.py:238-242;  lasttoken: :271-282 (index len-1)
 // learntmean (mode 3): w_t = position_weights[P+t], clamp 1e-9 (WeightedMeanPooling.py:21-39)
 // Norm: RowLayerNorm<true>, or RowRMSNorm<true> for the final norm of the Llama family (g alone; b is not read).
+// pool_lo (or null = zeros): the first pooled row of every sequence, clamped into [0, len] -- weightedmean / mean / learntmean run over
+//   rows [lo, len) (the tokens behind an instruction prompt); the weight of row t stays P + t + 1, the PADDED position index, and does not
+//   restart behind the prompt (GritLM, Pooling.py with include_prompt = false).  lasttoken is row len - 1 whatever lo is.  An empty range
+//   leaves a zero numerator over the clamped denominator: a zero row.
 template <int NV, typename Norm>
 __global__ __launch_bounds__(256) void lnf_pool_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                        const float* __restrict__ b, const int* __restrict__ seq_off,
                                                        const int* __restrict__ seq_len,
-                                                       const int* __restrict__ pad_left, int d, float eps,
+                                                       const int* __restrict__ pad_left, const int* __restrict__ pool_lo, int d, float eps,
                                                        int apply_ln, int mode, int normalize,
                                                        const float* __restrict__ pw, int pw_n, float* __restrict__ out,
                                                        int* __restrict__ nonfinite_flag) {
@@ -163,9 +167,11 @@ __global__ __launch_bounds__(256) void lnf_pool_kernel(const float* __restrict__
 #pragma unroll
     for (int i = 0; i < NV; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     float den = 0.f;
-    const int t_lo = mode == 2 ? (len > 0 ? len - 1 : 0) : 0;
+    int lo = pool_lo ? pool_lo[sq] : 0;
+    lo = lo < 0 ? 0 : (lo > len ? len : lo);
+    const int t_lo = mode == 2 ? (len > 0 ? len - 1 : 0) : lo;
     const int t_hi = mode == 4 ? (len > 0 ? 1 : 0) : len;        // cls (mode 4): the first row alone (Pooling.py:103-105)
-    // A wave's rows t = wave, wave + 4, ... are accumulated in that order; their LOADS go out LPB rows at a time (round 6: one
+    // A wave's rows t = t_lo + wave, t_lo + wave + 4, ... are accumulated in that order; their LOADS go out LPB rows at a time (round 6: one
     // sequence of 30 tokens is eight dependent load -> normalise -> accumulate round trips per wave otherwise -- 14 us of a
     // 0.43 ms single-query encode; a bulk call has thousands of workgroups to hide the latency behind).  Same sums, same bits.
     constexpr int LPB = NV <= 4 ? 4 : 2;
@@ -817,12 +823,13 @@ void launch_absmax16(const void* in, long numel, int dtype, unsigned* out_bits, 
 
 void launch_lnf_pool(const float* x, const float* g, const float* b, const int* seq_off, const int* seq_len,
                      const int* pad_left, int B, int d, float eps, int apply_ln, int mode, int normalize,
-                     const float* pos_weights, int pos_weights_n, float* out, hipStream_t s, int* nonfinite_flag, int norm_kind) {
+                     const float* pos_weights, int pos_weights_n, float* out, hipStream_t s, int* nonfinite_flag, int norm_kind,
+                     const int* pool_lo) {
     const size_t sm = (size_t)(4 * d + 8) * sizeof(float);
     for_row_width(d, [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
         const auto kernel = norm_kind == 1 ? lnf_pool_kernel<NV, RowRMSNorm<true>> : lnf_pool_kernel<NV, RowLayerNorm<true>>;
-        hipLaunchKernelGGL(kernel, dim3(B), dim3(256), sm, s, x, g, b, seq_off, seq_len, pad_left, d, eps, apply_ln, mode, normalize,
+        hipLaunchKernelGGL(kernel, dim3(B), dim3(256), sm, s, x, g, b, seq_off, seq_len, pad_left, pool_lo, d, eps, apply_ln, mode, normalize,
                            pos_weights, pos_weights_n, out, nonfinite_flag);
     });
 }

@@ -94,6 +94,10 @@ AttnArgs attn_bidir(const Fwd& f, const LayerW& l) {
     return at;
 }
 
+// the attention of a Llama-family block: causal with the model's window, or -- sgpt_model_set_attention(0) -- that of attn_bidir with
+// kv_group query heads per key / value head (no window on any layer then: the setter refuses it)
+AttnArgs attn_llama(const Fwd& f, const LayerW& l) { return f.m->bidir ? attn_bidir(f, l) : attn_base(f, l, 0); }
+
 // fp32: the projections read the residual stream itself
 sgpt_status block_bert_f32(const Fwd& f, const LayerW& l, int) {
     const sgpt_model_desc& d = f.m->d;
@@ -148,7 +152,7 @@ sgpt_status block_llama_f32(const Fwd& f, const LayerW& l, int) {
     launch_rmsnorm(f.x, l.ln1_g, f.a, SGPT_F32, T, dm, d.ln_eps, nullptr, f.s);
     gemm(f.c, SGPT_F32, EPI_STORE, SGPT_F32, proj(f, f.a, dm, l.w_qkv, dq + 2 * dkv, dm, f.qkv, dq + 2 * dkv, l.b_qkv), f.s);
     rope_llama(f, l, SGPT_F32, dq + 2 * dkv, dh);
-    launch_attn_f32(attn_base(f, l, 0), f.s);
+    launch_attn_f32(attn_llama(f, l), f.s);
     gemm(f.c, SGPT_F32, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dq, l.w_o, dm, dq, f.x, dm, l.b_o, f.x), f.s);
     launch_rmsnorm(f.x, l.ln2_g, f.a, SGPT_F32, T, dm, d.ln_eps, nullptr, f.s);
     gemm(f.c, SGPT_F32, EPI_STORE, SGPT_F32, proj(f, f.a, dm, l.w_fc, 2 * ffn, dm, f.gu, 2 * ffn, nullptr), f.s);
@@ -164,7 +168,7 @@ sgpt_status block_llama16(const Fwd& f, const LayerW& l, int) {
     launch_rmsnorm(f.x, l.ln1_g, f.a, dt, T, dm, d.ln_eps, f.range_flag, f.s);
     proj_qk_vt(f, proj(f, f.a, dm, l.w_qkv, dq + dkv, dm, f.qkv, dq + dkv, l.b_qkv), dq + dkv, dkv);
     rope_llama(f, l, dt, dq + dkv, dh);
-    launch_attn_bf16(attn_base(f, l, 0), f.s);
+    launch_attn_bf16(attn_llama(f, l), f.s);
     gemm(f.c, dt, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dq, l.w_o, dm, dq, f.x, dm, l.b_o, f.x), f.s);
     launch_rmsnorm(f.x, l.ln2_g, f.a, dt, T, dm, d.ln_eps, f.range_flag, f.s);
     gemm(f.c, dt, EPI_STORE, dt, proj(f, f.a, dm, l.w_fc, 2 * ffn, dm, f.gu, 2 * ffn, nullptr), f.s);
@@ -333,8 +337,8 @@ BlockFn pick_block(const Fwd& f) {
 
 // The argument and pooling refusals of a forward.  layout: ids, pos, seq_off, seq_len; pooled: the outputs that go through the pool
 // (out, layer_out, layer_mean).
-sgpt_status check_call(sgpt_model* m, const int32_t* const (&layout)[4], const int32_t* pad_left, int B, int T, int max_alloc, int pool_mode,
-                       int n_layers_run, bool pooled, const float* hidden_out) {
+sgpt_status check_call(sgpt_model* m, const int32_t* const (&layout)[4], const int32_t* pad_left, const int32_t* pool_lo, int B, int T, int max_alloc,
+                       int pool_mode, int n_layers_run, bool pooled, const float* hidden_out) {
     sgpt_ctx* c = m->ctx;
     const Family& F = family(m->d.arch);
     if (!layout[0] || !layout[1] || !layout[2] || !layout[3] || B <= 0 || T <= 0 || T % 32 != 0 || max_alloc <= 0 || max_alloc % 2 != 0)
@@ -344,6 +348,8 @@ sgpt_status check_call(sgpt_model* m, const int32_t* const (&layout)[4], const i
     if (pool_mode == SGPT_POOL_LEARNTMEAN && !F.learntmean)
         return fail(c, SGPT_ERR_INVALID, std::string("sgpt_encode: learntmean pooling (trained position weights of the SGPT checkpoints) is not available for ") + F.name);
     if (pool_mode == SGPT_POOL_CLS && !F.cls) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: cls pooling belongs to SGPT_ARCH_BERT");
+    if (pool_lo && (pool_mode == SGPT_POOL_CLS || pool_mode == SGPT_POOL_LEARNTMEAN))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_encode: pool_lo (pooling from a row on) serves weightedmean, mean and lasttoken, not cls or learntmean");
     if (pool_mode == SGPT_POOL_LEARNTMEAN && pooled) {
         if (!m->pool_w) return fail(c, SGPT_ERR_MISSING, "sgpt_encode: learntmean needs sgpt_model_set_pool_weights first");
         // with pad_left on the device the longest padded position is not known here: the kernel clamps the table index,
@@ -532,11 +538,11 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
                                const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t T, int32_t max_alloc,
                                int32_t pool_mode, int32_t n_layers_run, int32_t apply_final_ln, int32_t normalize,
                                float* out, float* hidden_out, float* layer_out, float* layer_mean, void* stream,
-                               const int32_t* seq_off_host = nullptr) {
+                               const int32_t* seq_off_host = nullptr, const int32_t* pool_lo = nullptr) {
     if (!m) return SGPT_ERR_INVALID;
     sgpt_ctx* c = m->ctx;
     const Family& F = family(m->d.arch);
-    sgpt_status st = check_call(m, {ids, pos, seq_off, seq_len}, pad_left, B, T, max_alloc, pool_mode, n_layers_run, out || layer_out || layer_mean, hidden_out);
+    sgpt_status st = check_call(m, {ids, pos, seq_off, seq_len}, pad_left, pool_lo, B, T, max_alloc, pool_mode, n_layers_run, out || layer_out || layer_mean, hidden_out);
     if (st != SGPT_OK) return st;
     if (!F.lnf) apply_final_ln = 0;    // no final norm in this family: the last block's LayerNorm output is hidden_states[-1]
     HIPC(c, hipSetDevice(c->device));
@@ -548,7 +554,7 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
     const int dm = m->d.d_model, ffn = m->d.d_ffn, dt = f.dt; float* x = f.x;
     auto pool = [&](int final_ln, float* dst, int* range_flag) {
         launch_lnf_pool(x, m->lnf_g, m->lnf_b, seq_off, seq_len, pad_left, B, dm, m->d.ln_eps, final_ln, pool_mode, normalize, m->pool_w,
-                        m->pool_w_n, dst, s, range_flag, F.norm_kind);
+                        m->pool_w_n, dst, s, range_flag, F.norm_kind, pool_lo);
     };
     // the embedding (and its LayerNorm) of the rows of g: the call, or one of its chains
     auto embed = [&](const Fwd& g) {
@@ -582,7 +588,8 @@ static sgpt_status encode_impl(sgpt_model* m, const int32_t* ids, const int32_t*
         int* rf = m->d.compute_dtype == SGPT_F16 ? (int*)m->range_dev : nullptr;
         for (const Fwd* g : {&fa, &fb})
             launch_lnf_pool(x, m->lnf_g, m->lnf_b, g->seq_off, g->seq_len, pad_left ? pad_left + g->b0 : nullptr, g->B, dm, m->d.ln_eps,
-                            apply_final_ln, pool_mode, normalize, m->pool_w, m->pool_w_n, out + (size_t)g->b0 * dm, g->s, rf, F.norm_kind);
+                            apply_final_ln, pool_mode, normalize, m->pool_w, m->pool_w_n, out + (size_t)g->b0 * dm, g->s, rf, F.norm_kind,
+                            pool_lo ? pool_lo + g->b0 : nullptr);
         HIPC(c, hipEventRecord(c->chain_ev[2], sb));
         HIPC(c, hipStreamWaitEvent(s, c->chain_ev[2], 0));
         c->chain_calls++;
@@ -630,6 +637,24 @@ sgpt_status sgpt_encode_host_layout(sgpt_model* m, const int32_t* ids, const int
                                     float* out, float* hidden_out, const int32_t* seq_off_host, void* stream) {
     return encode_impl(m, ids, pos, seq_off, seq_len, pad_left, B, T, max_alloc, pool_mode, n_layers_run,
                        apply_final_ln, normalize, out, hidden_out, nullptr, nullptr, stream, seq_off_host);
+}
+
+sgpt_status sgpt_encode_pool_from(sgpt_model* m, const int32_t* ids, const int32_t* pos, const int32_t* seq_off,
+                                  const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t T, int32_t max_alloc,
+                                  int32_t pool_mode, int32_t n_layers_run, int32_t apply_final_ln, int32_t normalize,
+                                  float* out, float* hidden_out, const int32_t* seq_off_host, const int32_t* pool_lo, void* stream) {
+    return encode_impl(m, ids, pos, seq_off, seq_len, pad_left, B, T, max_alloc, pool_mode, n_layers_run,
+                       apply_final_ln, normalize, out, hidden_out, nullptr, nullptr, stream, seq_off_host, pool_lo);
+}
+
+sgpt_status sgpt_encode_layers_pool_from(sgpt_model* m, const int32_t* ids, const int32_t* pos, const int32_t* seq_off,
+                                         const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t T, int32_t max_alloc,
+                                         int32_t pool_mode, int32_t normalize, float* out_layers, float* out_mean, const int32_t* pool_lo,
+                                         void* stream) {
+    if (!m) return SGPT_ERR_INVALID;
+    if (!out_layers && !out_mean) return fail(m->ctx, SGPT_ERR_INVALID, "sgpt_encode_layers: no output requested");
+    return encode_impl(m, ids, pos, seq_off, seq_len, pad_left, B, T, max_alloc, pool_mode, m->d.n_layers, 1, normalize,
+                       nullptr, nullptr, out_layers, out_mean, stream, nullptr, pool_lo);
 }
 
 sgpt_status sgpt_encode_layers(sgpt_model* m, const int32_t* ids, const int32_t* pos, const int32_t* seq_off,

@@ -63,6 +63,7 @@ struct sgpt_model {
     int qkv3_rows = 0;                 // row blocks of w_qkv3: 2 (q, k: qk_split alone) | 3 (q, k, v: split_weights) | 0 (none)
     unsigned* crest_dev = nullptr;
     bool probing = false;
+    bool bidir = false;                // SGPT_ARCH_LLAMA: every query sees every key of its sequence (sgpt_model_set_attention(0))
     std::vector<void*> allocs;
 };
 
@@ -119,17 +120,20 @@ struct Family {
     // is the family's refusal of anything else, and dh_all: it holds for SGPT_F32 models too.  window: WIN_*.  gqa: n_kv_heads may
     // differ from n_heads.
     bool dh256; const char* dh_rule; bool dh_all; int window; bool gqa;
+    // sgpt_model_set_attention: why the family's attention mode is not the caller's to set (null: it is -- causal or bidirectional)
+    const char* attn_fixed;
 };
 constexpr Family FAMILIES[] = {
     // name, prefix, wte, lnf, norm_kind | post_ln, swiglu, slack_f32 | fp8, split, shifts, probe, qpath, learntmean, cls | no_lm |
-    // dh256, dh_rule, dh_all, window, gqa          (the bools of a row are grouped as in this line: 3, then 7, then dh256)
-    {"SGPT_ARCH_GPTNEO", "h.", "wte.weight", "ln_f", 0, false, false, true,  true, true, true, true, true, true, true,  nullptr, true, nullptr, false, WIN_ANY, false},
-    {"SGPT_ARCH_GPTJ", "h.", "wte.weight", "ln_f", 0, false, false, true,  true, true, true, true, true, true, true,  nullptr, true, nullptr, false, WIN_ANY, false},
-    {"SGPT_ARCH_BLOOM", "h.", "word_embeddings.weight", "ln_f", 0, false, false, true,  true, true, true, true, true, true, true,  nullptr, true, nullptr, false, WIN_ANY, false},
+    // dh256, dh_rule, dh_all, window, gqa | attn_fixed     (the bools of a row are grouped as in this line: 3, then 7, then dh256)
+    {"SGPT_ARCH_GPTNEO", "h.", "wte.weight", "ln_f", 0, false, false, true,  true, true, true, true, true, true, true,  nullptr, true, nullptr, false, WIN_ANY, false, "stays causal"},
+    {"SGPT_ARCH_GPTJ", "h.", "wte.weight", "ln_f", 0, false, false, true,  true, true, true, true, true, true, true,  nullptr, true, nullptr, false, WIN_ANY, false, "stays causal"},
+    {"SGPT_ARCH_BLOOM", "h.", "word_embeddings.weight", "ln_f", 0, false, false, true,  true, true, true, true, true, true, true,  nullptr, true, nullptr, false, WIN_ANY, false, "stays causal"},
     {"SGPT_ARCH_BERT", "encoder.layer.", "embeddings.word_embeddings.weight", nullptr, 0, true, false, true,  false, false, false, false, false, false, true,
-     "SGPT_ARCH_BERT carries no causal LM head", false, "16-bit bidirectional attention supports head_dim 64 or 128", false, WIN_ZERO, false},
+     "SGPT_ARCH_BERT carries no causal LM head", false, "16-bit bidirectional attention supports head_dim 64 or 128", false, WIN_ZERO, false,
+     "is bidirectional by architecture"},
     {"SGPT_ARCH_LLAMA", "layers.", "embed_tokens.weight", "norm", 1, false, true, false,  false, false, false, false, false, false, false,
-     "not built for SGPT_ARCH_LLAMA (the LM head of this family is not loaded)", false, "head_dim 64 or 128", true, WIN_NONNEG, true},
+     "not built for SGPT_ARCH_LLAMA (the LM head of this family is not loaded)", false, "head_dim 64 or 128", true, WIN_NONNEG, true, nullptr},
 };
 constexpr int N_FAMILIES = sizeof(FAMILIES) / sizeof(FAMILIES[0]);
 static_assert(SGPT_ARCH_GPTNEO == 0 && SGPT_ARCH_GPTJ == 1 && SGPT_ARCH_BLOOM == 2 && SGPT_ARCH_BERT == 3 && SGPT_ARCH_LLAMA == 4 && N_FAMILIES == 5, "FAMILIES is indexed by SGPT_ARCH_*");

@@ -381,6 +381,25 @@ sgpt_status sgpt_model_set_pool_weights(sgpt_model* m, const float* w, int32_t n
     return SGPT_OK;
 }
 
+// The attention mode of a loaded model (not a descriptor field: the descriptor of a model does not change with it).  The family's row
+// says whose it is to set; the block functions read m->bidir (encode.hip: attn_llama).
+sgpt_status sgpt_model_set_attention(sgpt_model* m, int32_t causal) {
+    if (!m) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    const Family& F = family(m->d.arch);
+    if (causal != 0 && causal != 1) return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_attention: causal 0 | 1");
+    if (F.attn_fixed)
+        return fail(c, SGPT_ERR_INVALID, std::string("sgpt_model_set_attention: the attention mode belongs to SGPT_ARCH_LLAMA models; ") + F.name + " " + F.attn_fixed);
+    if (!causal && m->d.window > 0)
+        for (const LayerW& l : m->L)
+            if (l.is_local)
+                return fail(c, SGPT_ERR_INVALID, "sgpt_model_set_attention: bidirectional attention with an applied sliding window (window " +
+                            std::to_string(m->d.window) + " on a layer of this model) is not built");
+    if (m->bidir != (causal == 0)) c->generation++;       // captured graphs carry the old attention launches
+    m->bidir = causal == 0;
+    return SGPT_OK;
+}
+
 sgpt_status sgpt_model_calibrate_begin(sgpt_model* m) {
     if (!m) return SGPT_ERR_INVALID;
     sgpt_ctx* c = m->ctx;

@@ -303,6 +303,21 @@ sgpt_status sgpt_attention_gqa(sgpt_ctx* c, int32_t dtype, const void* q, const 
                           out_scale, range_flag, 0, qk_lo_delta, v_lo_delta, 0, 0, 1, nullptr, H / n_kv_heads, SGPT_MAX_SEQ_LEN, "sgpt_attention_gqa", stream);
 }
 
+sgpt_status sgpt_attention_gqa_ex(sgpt_ctx* c, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
+                                  void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t n_kv_heads,
+                                  int32_t dh, int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
+                                  float out_scale, int32_t* range_flag, int32_t x3, int64_t qk_lo_delta, int64_t v_lo_delta,
+                                  int64_t ctx_lo_delta, int64_t ctx_hi2_delta, int32_t causal, const int32_t* seq_len, void* stream) {
+    if (H <= 0 || n_kv_heads <= 0 || H % n_kv_heads) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_gqa_ex: n_heads % n_kv_heads == 0, both > 0");
+    if (alibi != nullptr) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_gqa_ex: no ALiBi with grouped K / V");
+    if (out_fp8 || x3 || ctx_lo_delta != 0 || ctx_hi2_delta != 0)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_attention_gqa_ex: out_fp8 and the split-precision modes are not available with grouped K / V");
+    if (dtype != SGPT_F32 && dh != 64 && dh != 128) return fail(c, SGPT_ERR_INVALID, "sgpt_attention_gqa_ex: 16-bit grouped attention serves head_dim 64 | 128");
+    // (causal = 0 with a window: refused by attention_impl, as for sgpt_attention_ex)
+    return attention_impl(c, dtype, q, k, v, ldq, ldvt, out, ldo, seq_off, B, T, H, dh, window, scale, nullptr, max_alloc_len, 0,
+                          out_scale, range_flag, 0, qk_lo_delta, v_lo_delta, 0, 0, causal, seq_len, H / n_kv_heads, SGPT_MAX_SEQ_LEN, "sgpt_attention_gqa_ex", stream);
+}
+
 sgpt_status sgpt_attention(sgpt_ctx* c, int32_t dtype, const void* q, const void* k, const void* v, int64_t ldq, int64_t ldvt,
                            void* out, int64_t ldo, const int32_t* seq_off, int32_t B, int32_t T, int32_t H, int32_t dh,
                            int32_t window, float scale, const float* alibi, int32_t max_alloc_len, int32_t out_fp8,
@@ -395,14 +410,14 @@ sgpt_status sgpt_swiglu(sgpt_ctx* c, const void* gu, int32_t dtype, int32_t T, i
 static sgpt_status lnf_pool_impl(sgpt_ctx* c, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
                                  const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
                                  int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,
-                                 int32_t* nonfinite_flag, int32_t norm_kind, void* stream);
+                                 int32_t* nonfinite_flag, int32_t norm_kind, const int32_t* pool_lo, void* stream);
 
 sgpt_status sgpt_lnf_pool(sgpt_ctx* c, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
                           const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
                           int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,
                           int32_t* nonfinite_flag, void* stream) {
     return lnf_pool_impl(c, x, gamma, beta, seq_off, seq_len, pad_left, B, d, eps, apply_ln, mode, normalize, pos_weights, n_weights, out,
-                         nonfinite_flag, 0, stream);
+                         nonfinite_flag, 0, nullptr, stream);
 }
 
 sgpt_status sgpt_lnf_pool_ex(sgpt_ctx* c, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
@@ -411,13 +426,24 @@ sgpt_status sgpt_lnf_pool_ex(sgpt_ctx* c, const float* x, const float* gamma, co
                              int32_t* nonfinite_flag, int32_t norm_kind, void* stream) {
     if (norm_kind != 0 && norm_kind != 1) return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool_ex: norm_kind 0 (LayerNorm) | 1 (RMSNorm)");
     return lnf_pool_impl(c, x, gamma, beta, seq_off, seq_len, pad_left, B, d, eps, apply_ln, mode, normalize, pos_weights, n_weights, out,
-                         nonfinite_flag, norm_kind, stream);
+                         nonfinite_flag, norm_kind, nullptr, stream);
+}
+
+sgpt_status sgpt_lnf_pool_range(sgpt_ctx* c, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
+                                const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
+                                int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,
+                                int32_t* nonfinite_flag, int32_t norm_kind, const int32_t* pool_lo, void* stream) {
+    if (norm_kind != 0 && norm_kind != 1) return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool_range: norm_kind 0 (LayerNorm) | 1 (RMSNorm)");
+    if (pool_lo && (mode == SGPT_POOL_CLS || mode == SGPT_POOL_LEARNTMEAN))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool_range: pool_lo serves weightedmean, mean and lasttoken, not cls or learntmean");
+    return lnf_pool_impl(c, x, gamma, beta, seq_off, seq_len, pad_left, B, d, eps, apply_ln, mode, normalize, pos_weights, n_weights, out,
+                         nonfinite_flag, norm_kind, pool_lo, stream);
 }
 
 static sgpt_status lnf_pool_impl(sgpt_ctx* c, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
                                  const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
                                  int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,
-                                 int32_t* nonfinite_flag, int32_t norm_kind, void* stream) {
+                                 int32_t* nonfinite_flag, int32_t norm_kind, const int32_t* pool_lo, void* stream) {
     if (!c || !x || !seq_off || !seq_len || !out || B <= 0 || !row_width_ok(d))
         return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool: bad arguments (d % 4 == 0, d <= 4096)");
     if (mode < SGPT_POOL_WEIGHTEDMEAN || mode > SGPT_POOL_LEARNTMEAN) return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool: mode 0 .. 3");
@@ -428,7 +454,7 @@ static sgpt_status lnf_pool_impl(sgpt_ctx* c, const float* x, const float* gamma
     if (mis(x, 16) || mis(gamma, 16) || mis(beta, 16)) return fail(c, SGPT_ERR_INVALID, "sgpt_lnf_pool: 16-byte aligned x / gamma / beta");
     HIPC(c, hipSetDevice(c->device));
     launch_lnf_pool(x, gamma, beta, seq_off, seq_len, pad_left, B, d, eps, apply_ln ? 1 : 0, mode, normalize ? 1 : 0, pos_weights,
-                    n_weights, out, (hipStream_t)stream, nonfinite_flag, norm_kind);
+                    n_weights, out, (hipStream_t)stream, nonfinite_flag, norm_kind, pool_lo);
     HIPC(c, hipGetLastError());
     return SGPT_OK;
 }

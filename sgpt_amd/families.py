@@ -270,6 +270,10 @@ class Family:
     dtype_advice: str = ""                # the dtypes the fp8 refusal advises, in the family's order
     parallel_block: bool = False          # one LayerNorm feeds attention and MLP: LayerNorm-2 follows LayerNorm-1 in a per-class plan
     no_lm_head: Optional[str] = None      # the refusal of lm_logprobs where the family has no LM head
+    # attention: the mode the family runs, and whether SGPTModel(attention=) may choose the other one (sgpt_model_set_attention,
+    # include/sgpt_hip.h: the Llama family alone -- the bidirectional embedders built on its backbones)
+    native_attention: str = "causal"
+    attention_switch: bool = False
     # tokenizer
     framing: str = "brackets"             # "brackets" (specb / speca allowed, nothing added) | "cls_sep" | "bos_eos"
 
@@ -282,11 +286,11 @@ FAMILIES = (
     Family("bloom", ("bloom",), _lib.SGPT_ARCH_BLOOM, "BLOOM", _parse_bloom,
            prepare_weights=lambda c, w: dict(w, **{"alibi.slopes": alibi_slopes(c.num_heads)})),
     Family("bert", ("bert",), _lib.SGPT_ARCH_BERT, "BERT", _parse_bert, prepare_weights=lambda c, w: bert_state_dict(w), sgpt_modes=False,
-           framing="cls_sep", dtype_advice="'f16', 'bf16' or 'fp32'", no_lm_head="lm_logprobs: a BERT model carries no causal LM head"),
+           native_attention="bidirectional", framing="cls_sep", dtype_advice="'f16', 'bf16' or 'fp32'", no_lm_head="lm_logprobs: a BERT model carries no causal LM head"),
     Family("llama", ("llama", "mistral", "qwen2", "qwen3"), _lib.SGPT_ARCH_LLAMA, "Llama / Mistral", _parse_llama, rotary_dim="head_dim", grouped_kv=True,
            prepare_weights=lambda c, w: dict(llama_state_dict(w), **dict(zip(_ROTARY, rotary_tables_half(
                table_rows(c), head_dim(c), c.rope_theta)))),
-           sgpt_modes=False, framing="bos_eos", dtype_advice="'bf16', 'f16' or 'fp32'",
+           sgpt_modes=False, attention_switch=True, framing="bos_eos", dtype_advice="'bf16', 'f16' or 'fp32'",
            no_lm_head="lm_logprobs is not built for Llama / Mistral models (their LM head is not loaded)"),
 )
 FRAMED = {"cls_sep": "is framed [CLS] ... [SEP]", "bos_eos": "takes its tokenizer's BOS / EOS"}   # Family.framing, as a refusal of the brackets puts it
@@ -298,6 +302,32 @@ def family(model_type: str) -> Family:
         if fam.model_type == model_type:
             return fam
     raise ValueError(f"model_type {model_type!r}: SGPTConfig.model_type is one of {[f.model_type for f in FAMILIES]}")
+
+
+ATTENTION_MODES = ("causal", "bidirectional")
+
+
+def check_attention(cfg: SGPTConfig, attention: str) -> str:
+    """SGPTModel's attention= argument, or its refusal: 'bidirectional' is the Llama family's to choose, and not over an applied window."""
+    fam = family(cfg.model_type)
+    if attention not in ATTENTION_MODES:
+        raise ValueError(f"attention must be 'causal' or 'bidirectional', not {attention!r}")
+    if attention == "bidirectional" and not fam.attention_switch:
+        fixed = "is bidirectional by architecture" if fam.native_attention == "bidirectional" else "stays causal"
+        raise ValueError(f"attention='bidirectional' is a mode of the Llama / Mistral / Qwen family: a {fam.name} model {fixed}")
+    if attention == "bidirectional" and cfg.window_size > 0 and "local" in cfg.attention_layers:
+        raise ValueError(f"attention='bidirectional' over an applied sliding window (window_size {cfg.window_size}) is not built: "
+                         "only a window the config parser folded away (at least min(max_position_embeddings, "
+                         f"{WINDOW_FOLD}) tokens) runs bidirectionally")
+    return attention
+
+
+def attention_from_hf_dict(c: dict, attention: Optional[str] = None) -> str:
+    """from_pretrained's attention=None: 'bidirectional' iff the folder's raw config.json says `is_causal: false` (GritLM, gte-Qwen2,
+    LLM2Vec checkpoints), else 'causal'; an explicit argument wins.  The key stays out of SGPTConfig."""
+    if attention is not None:
+        return attention
+    return "bidirectional" if c.get("is_causal", True) is False else "causal"
 
 
 def family_of(model) -> Family:

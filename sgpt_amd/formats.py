@@ -36,6 +36,7 @@ class STFolder:
     pooling_mode: str = "mean"
     position_weights_file: Optional[str] = None   # learntmean: <dir>/pytorch_model.bin holding `position_weights`
     normalize: bool = False
+    include_prompt: Optional[bool] = None     # 1_Pooling/config.json `include_prompt` where the folder has the field (None: it has not)
     modules: List[dict] = field(default_factory=list)
 
     @property
@@ -95,7 +96,10 @@ def read_st_folder(path: str) -> STFolder:
                 out.max_seq_length = tc.get("max_seq_length", out.max_seq_length)
                 out.do_lower_case = bool(tc.get("do_lower_case", out.do_lower_case))
         elif kind == "Pooling":
-            out.pooling_mode = pooling_mode_from_config(_read_json(os.path.join(folder, "config.json")))
+            pc = _read_json(os.path.join(folder, "config.json"))
+            out.pooling_mode = pooling_mode_from_config(pc)
+            if "include_prompt" in pc:
+                out.include_prompt = bool(pc["include_prompt"])
         elif kind == "WeightedMeanPooling":
             out.pooling_mode = "learntmean"
             out.position_weights_file = os.path.join(folder, "pytorch_model.bin")

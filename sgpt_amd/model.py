@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from ._lib import (ModelDesc, TensorView, POOL_MODES, SGPT_BF16, SGPT_F16, SGPT_F32, SGPT_FP8M, SGPT_FP8W, SgptRangeError,
                    SGPT_PREC_CLASSES, PC_LN1, PC_ATT, PC_CTX, PC_LN2, PC_H)
-from .families import (MAX_SEQ_LEN, SGPTConfig, alibi_slopes, bert_state_dict, family, head_dim, llama_state_dict, rotary_tables,  # noqa: F401
+from .families import (MAX_SEQ_LEN, SGPTConfig, attention_from_hf_dict, check_attention, alibi_slopes, bert_state_dict, family, head_dim, llama_state_dict, rotary_tables,  # noqa: F401
                        rotary_tables_half, table_rows, synthetic_bert_weights, synthetic_llama_weights, synthetic_qwen_weights, synthetic_weights)
 from .runtime import Context, get_context, _p, _stream_ptr
 
@@ -66,6 +66,7 @@ class PackedBatch:
     arena: Optional[torch.Tensor] = None  # the one int32 device buffer the five views above slice (graph replays refill it in one copy)
     n_real: int = 0  # sequences that are the caller's (B minus the bucket's filler sequences)
     off_host: Optional[np.ndarray] = None  # host int32[B + 1] copy of seq_off: lets the library cut a bulk call into two chains without reading the device
+    pool_lo: Optional[torch.Tensor] = None  # int32[B] first pooled token of every sequence (pack(pool_from=)); None: every token is pooled
 
 
 def _flatten(seqs, total: int) -> np.ndarray:
@@ -88,11 +89,13 @@ def _to_i32(a: np.ndarray) -> np.ndarray:
 
 
 def pack_layout(seqs, pad_left: Optional[Sequence[int]] = None, bucket: Optional[Tuple[int, int, int]] = None,
-                row_tile: Optional[int] = None) -> dict:
+                row_tile: Optional[int] = None, pool_from=None) -> dict:
     """Sizes and offsets of the packed layout (no token data yet).
     bucket = (B_cap, T_cap, A_cap): pad the layout to that capacity -- B_cap - B one-token filler sequences behind the real
     ones, T_pad = T_cap, max_alloc = A_cap -- so that every batch of the bucket launches the same grids (hipGraph replay).
-    The filler rows are computed and dropped; `n_real` says how many output rows are the caller's."""
+    The filler rows are computed and dropped; `n_real` says how many output rows are the caller's.
+    pool_from: one int, or one per sequence -- the first pooled token, counted from the sequence start with its frame (BOS, [CLS])
+    included: the tokens of an instruction prompt in front of it are encoded and not pooled.  None: no such array in the layout."""
     B = len(seqs)
     if isinstance(seqs, np.ndarray) and seqs.ndim == 2:
         lens = np.full(B, seqs.shape[1], dtype=np.int64)
@@ -101,6 +104,15 @@ def pack_layout(seqs, pad_left: Optional[Sequence[int]] = None, bucket: Optional
     if B == 0 or (lens <= 0).any():
         raise ValueError("Empty items should be cleaned prior to running")  # beir_dense_retriever.py:180-181
     pl = np.zeros(B, dtype=np.int32) if pad_left is None else np.asarray(pad_left, dtype=np.int32)
+    pf = None
+    if pool_from is not None:
+        pf = np.asarray(pool_from)
+        if pf.dtype.kind not in "iu" or pf.ndim > 1 or (pf.ndim == 1 and pf.shape[0] != B):
+            raise ValueError("pool_from: one int, or one int per sequence")
+        pf = np.full(B, int(pf), dtype=np.int64) if pf.ndim == 0 else pf.astype(np.int64)
+        if (pf < 0).any():
+            raise ValueError("pool_from counts tokens from the sequence start: it cannot be negative")
+        pf = np.minimum(pf, lens).astype(np.int32)          # (the kernel clamps too: an empty range is a zero row)
     n_real, n_tokens = B, int(lens.sum())
     max_pos = int((lens + pl.astype(np.int64)).max()) - 1
     if bucket is not None:
@@ -110,6 +122,8 @@ def pack_layout(seqs, pad_left: Optional[Sequence[int]] = None, bucket: Optional
                              f"{QUERY_ROWS} rows; A_cap % {ALIGN})")
         lens = np.concatenate([lens, np.ones(B_cap - B, dtype=np.int64)])
         pl = np.concatenate([pl, np.zeros(B_cap - B, dtype=np.int32)])
+        if pf is not None:
+            pf = np.concatenate([pf, np.zeros(B_cap - B, dtype=np.int32)])
         B = B_cap
     alloc = (lens + ALIGN - 1) // ALIGN * ALIGN
     off = np.zeros(B + 1, dtype=np.int64)
@@ -121,12 +135,13 @@ def pack_layout(seqs, pad_left: Optional[Sequence[int]] = None, bucket: Optional
             raise ValueError(f"packed layout (T_pad {T_pad}, max_alloc {max_alloc}) does not fit bucket {bucket}")
         T_pad, max_alloc = bucket[1], bucket[2]
     return dict(B=B, lens=lens, alloc=alloc, off=off, T_pad=T_pad, pl=pl, n_tokens=n_tokens, n_real=n_real,
-                max_alloc=max_alloc, max_pos=max_pos)
+                max_alloc=max_alloc, max_pos=max_pos, pool_lo=pf)
 
 
 def arena_ints(lay: dict) -> int:
-    """int32 words of the one-buffer host/device image: [ids T_pad | pos T_pad | seq_off B+1 | seq_len B | pad_left B]."""
-    return 2 * lay["T_pad"] + 3 * lay["B"] + 1
+    """int32 words of the one-buffer host/device image: [ids T_pad | pos T_pad | seq_off B+1 | seq_len B | pad_left B], and behind them
+    [pool_lo B] where the layout has one (pack_layout(pool_from=))."""
+    return 2 * lay["T_pad"] + (3 if lay.get("pool_lo") is None else 4) * lay["B"] + 1
 
 
 def fill_arena(seqs, lay: dict, arena: np.ndarray):
@@ -156,20 +171,23 @@ def fill_arena(seqs, lay: dict, arena: np.ndarray):
     arena[o: o + B + 1] = off
     arena[o + B + 1: o + 2 * B + 1] = lens
     arena[o + 2 * B + 1: o + 3 * B + 1] = pl
+    if lay.get("pool_lo") is not None:
+        arena[o + 3 * B + 1: o + 4 * B + 1] = lay["pool_lo"]
     return hi_lo
 
 
 def pack_host(seqs: Sequence[Sequence[int]], pad_left: Optional[Sequence[int]] = None,
-              bucket: Optional[Tuple[int, int, int]] = None):
+              bucket: Optional[Tuple[int, int, int]] = None, pool_from=None):
     """Token lists -> numpy arrays of the packed layout (host side; the dict form used by tests)."""
-    lay = pack_layout(seqs, pad_left, bucket)
+    lay = pack_layout(seqs, pad_left, bucket, pool_from=pool_from)
     arena = np.empty(arena_ints(lay), dtype=np.int32)
     fill_arena(seqs, lay, arena)
     B, T_pad = lay["B"], lay["T_pad"]
     o = 2 * T_pad
     return dict(ids=arena[:T_pad], pos=arena[T_pad:o], seq_off=arena[o: o + B + 1], seq_len=arena[o + B + 1: o + 2 * B + 1],
                 pad_left=arena[o + 2 * B + 1: o + 3 * B + 1], B=B, T_pad=T_pad, max_alloc=lay["max_alloc"],
-                n_tokens=lay["n_tokens"], max_pos=lay["max_pos"], n_real=lay["n_real"], arena=arena)
+                n_tokens=lay["n_tokens"], max_pos=lay["max_pos"], n_real=lay["n_real"], arena=arena,
+                pool_lo=None if lay["pool_lo"] is None else arena[o + 3 * B + 1: o + 4 * B + 1])
 
 
 class _Staging:
@@ -300,8 +318,11 @@ class SGPTModel:
 
     def __init__(self, cfg: SGPTConfig, weights: Dict[str, "np.ndarray | torch.Tensor"], device=None,
                  dtype: str = "f16", ctx: Optional[Context] = None, max_tokens_per_call: int = 131072,
-                 calibrate: bool = True, precise_qk=None, precision: Optional[str] = None):
-        """precision (dtype 'f16' / 'bf16'): how operands enter the MFMAs (include/sgpt_hip.h::sgpt_model_set_precision).
+                 calibrate: bool = True, precise_qk=None, precision: Optional[str] = None, attention: str = "causal"):
+        """attention: 'causal' (default) | 'bidirectional' -- Llama / Mistral / Qwen models only, set after load
+        (sgpt_model_set_attention): in every layer every token sees every token of its sequence, what GritLM, gte-Qwen2-instruct and the
+        LLM2Vec checkpoints were trained with.  Refused for the other families and over an applied (unfolded) sliding window.
+        precision (dtype 'f16' / 'bf16'): how operands enter the MFMAs (include/sgpt_hip.h::sgpt_model_set_precision).
           'plain'  16-bit operands everywhere (plus the structural rule below);
           'x3'     every operand class of every block as a hi + lo pair of 16-bit values (the "f16x3" mode: embeddings within
                    ~1e-5 of the fp32 reference on ANY checkpoint the f16 range guard accepts, a third of the 16-bit MFMA
@@ -326,6 +347,7 @@ class SGPTModel:
         LayerNorm-1 output split against plain weights (+17 % FLOPs); 'full+logits'; 'qkv+logits' (the V projection split as
         well); 'attn' (the whole attention sub-block: Q / K / V projection, attention, out-projection)."""
         dtype, precise_qk, precision = check_args(cfg, dtype, precise_qk, precision)
+        attention = check_attention(cfg, attention)
         self.cfg = cfg
         self.ctx = ctx or get_context(device)
         self.device = self.ctx.device
@@ -347,6 +369,9 @@ class SGPTModel:
         _lib.check(self.ctx.handle, self.ctx.lib.sgpt_model_load(self.ctx.handle, C.byref(desc), views, len(keep), C.byref(self.handle)),
                    "sgpt_model_load")
         del keep  # the library now owns packed copies
+        self._attention = family(cfg.model_type).native_attention     # (a family without the switch runs its own mode whatever the default says)
+        if family(cfg.model_type).attention_switch and attention != self._attention:
+            self.set_attention(attention)
         self._staging = _Staging(self.device)
         self.act_scales = None
         if dtype == "fp8mfma" and calibrate:
@@ -369,6 +394,18 @@ class SGPTModel:
         """The longest sequence (tokens, framing included) this model encodes: min(cfg.max_position_embeddings, MAX_SEQ_LEN).  What
         the adapters default and clamp their max_seq_length to."""
         return table_rows(self.cfg)
+
+    @property
+    def attention(self) -> str:
+        """'causal' | 'bidirectional': what every layer's attention shows a token."""
+        return self._attention
+
+    def set_attention(self, attention: str) -> None:
+        """Switch a Llama-family model between causal and bidirectional attention (the library refuses the other families)."""
+        if attention not in ("causal", "bidirectional"):
+            raise ValueError(f"attention must be 'causal' or 'bidirectional', not {attention!r}")
+        self._call("set_attention", 1 if attention == "causal" else 0)
+        self._attention = attention
 
     def _call(self, fn: str, *args) -> None:
         """sgpt_model_<fn>(this model, *args); a failure raises with the library's message."""
@@ -565,16 +602,18 @@ class SGPTModel:
 
     # ---- loading real checkpoints (HF folder / sentence-transformers folder layout) ----
     @classmethod
-    def from_pretrained(cls, path: str, **kw) -> "SGPTModel":
+    def from_pretrained(cls, path: str, attention: Optional[str] = None, **kw) -> "SGPTModel":
         """Reads config.json + model.safetensors / pytorch_model.bin of an SGPT checkpoint folder
         (AutoModel.from_pretrained at beir_dense_retriever.py:123; ST folder layout
-        SentenceTransformer.py:903-936 keeps the transformer either at the root or in 0_Transformer/)."""
+        SentenceTransformer.py:903-936 keeps the transformer either at the root or in 0_Transformer/).
+        attention=None: 'bidirectional' iff config.json says `is_causal: false`, else 'causal' (families.attention_from_hf_dict)."""
         root = path
         if not os.path.exists(os.path.join(root, "config.json")) and os.path.exists(os.path.join(root, "0_Transformer")):
             root = os.path.join(root, "0_Transformer")
         with open(os.path.join(root, "config.json")) as f:
-            cfg = SGPTConfig.from_hf_dict(json.load(f))
-        model = cls(cfg, load_state_dict(root), **kw)
+            raw = json.load(f)
+        cfg = SGPTConfig.from_hf_dict(raw)
+        model = cls(cfg, load_state_dict(root), attention=attention_from_hf_dict(raw, attention), **kw)
         wmp = os.path.join(path, "1_WeightedMeanPooling", "pytorch_model.bin")
         if os.path.exists(wmp):
             model.set_position_weights(torch.load(wmp, map_location="cpu", weights_only=True)["position_weights"])
@@ -582,11 +621,13 @@ class SGPTModel:
 
     # ---- packing ----
     def pack(self, seqs: Sequence[Sequence[int]], pad_left: Optional[Sequence[int]] = None,
-             bucket: Optional[Tuple[int, int, int]] = None, into: Optional[PackedBatch] = None) -> PackedBatch:
+             bucket: Optional[Tuple[int, int, int]] = None, into: Optional[PackedBatch] = None, pool_from=None) -> PackedBatch:
         """Token lists -> device-resident packed batch: ONE pinned, non-blocking H2D copy of the whole layout.
         bucket: pad the layout to a capacity (pack_layout); into: refill that batch's device arena (same bucket) instead of
-        allocating a new one -- the form hipGraph replays use, whose kernels hold the arena's addresses."""
-        lay = pack_layout(seqs, pad_left, bucket, self.row_tile)
+        allocating a new one -- the form hipGraph replays use, whose kernels hold the arena's addresses.
+        pool_from: one int or one per sequence (pack_layout): the batch is pooled from that token on -- mean and weightedmean over the
+        tokens behind it, lasttoken unchanged; it travels in the same arena and is refused with 'cls' / 'learntmean' by the encode calls."""
+        lay = pack_layout(seqs, pad_left, bucket, self.row_tile, pool_from)
         # two refusals: the library's limit (SGPT_MAX_SEQ_LEN, include/sgpt_hip.h) and the model's own position range
         if int(lay["lens"][: lay["n_real"]].max()) > MAX_SEQ_LEN:
             raise ValueError(f"sequence longer than {MAX_SEQ_LEN} tokens, the longest the library encodes (SGPT_MAX_SEQ_LEN)")
@@ -597,6 +638,8 @@ class SGPTModel:
         if into is not None and (into.arena is None or (into.B, into.T_pad, into.max_alloc) != (B, T, lay["max_alloc"])):
             raise ValueError(f"packed layout {(B, T, lay['max_alloc'])} does not match the batch being refilled "
                              f"{(into.B, into.T_pad, into.max_alloc)}")
+        if into is not None and (into.pool_lo is None) != (lay["pool_lo"] is None):
+            raise ValueError("the batch being refilled was packed " + ("without" if into.pool_lo is None else "with") + " pool_from")
         slot, host = self._staging.acquire(n_int)
         hi, lo = fill_arena(seqs, lay, host.numpy())
         if lo < 0 or hi >= self.cfg.vocab_size:
@@ -611,7 +654,8 @@ class SGPTModel:
         o = 2 * T
         return PackedBatch(dev[:T], dev[T:o], dev[o: o + B + 1], dev[o + B + 1: o + 2 * B + 1],
                            dev[o + 2 * B + 1: o + 3 * B + 1], B, T, lay["max_alloc"], lay["n_tokens"], lay["max_pos"],
-                           arena=dev, n_real=lay["n_real"], off_host=off_host)
+                           arena=dev, n_real=lay["n_real"], off_host=off_host,
+                           pool_lo=None if lay["pool_lo"] is None else dev[o + 3 * B + 1: o + 4 * B + 1])
 
     # ---- one C call: forward + pool ----
     def encode_packed(self, pb: PackedBatch, mode: str = "weightedmean", normalize: bool = False,
@@ -626,17 +670,25 @@ class SGPTModel:
             raise ValueError(f"Layer Idx {layer_idx} is larger than the {L + 1} hidden states")
         n_run, final_ln = (L, 1) if li == L else (li, 0)
         self._check_learnt(mode, pb)
+        self._check_pool_from(mode, pb)
         d = self.cfg.hidden_size
         if out is None:
             out = torch.empty((pb.B, d), dtype=torch.float32, device=self.device)
         hidden = torch.empty((pb.T_pad, d), dtype=torch.float32, device=self.device) if return_hidden else None
         off_host = pb.off_host.ctypes.data if pb.off_host is not None and pb.off_host.size == pb.B + 1 else None
-        st = self.ctx.lib.sgpt_encode_host_layout(self.handle, _p(pb.ids), _p(pb.pos), _p(pb.seq_off), _p(pb.seq_len),
-                                                  _p(pb.pad_left), pb.B, pb.T_pad, pb.max_alloc, POOL_MODES[mode], n_run,
-                                                  final_ln, 1 if normalize else 0, _p(out), _p(hidden), off_host,
-                                                  _stream_ptr(self.device))
+        args = (self.handle, _p(pb.ids), _p(pb.pos), _p(pb.seq_off), _p(pb.seq_len), _p(pb.pad_left), pb.B, pb.T_pad, pb.max_alloc,
+                POOL_MODES[mode], n_run, final_ln, 1 if normalize else 0, _p(out), _p(hidden), off_host)
+        if pb.pool_lo is None:
+            st = self.ctx.lib.sgpt_encode_host_layout(*args, _stream_ptr(self.device))
+        else:
+            st = self.ctx.lib.sgpt_encode_pool_from(*args, _p(pb.pool_lo), _stream_ptr(self.device))
         _lib.check(self.ctx.handle, st, "sgpt_encode")
         return (out, hidden) if return_hidden else out
+
+    @staticmethod
+    def _check_pool_from(mode: str, pb: PackedBatch) -> None:
+        if pb.pool_lo is not None and mode in ("cls", "learntmean"):
+            raise ValueError(f"pool_from (pooling the tokens behind a prompt) serves 'mean', 'weightedmean' and 'lasttoken', not {mode!r}")
 
     def _check_learnt(self, mode: str, pb: PackedBatch) -> None:
         if mode != "learntmean":
@@ -656,12 +708,16 @@ class SGPTModel:
         if mode not in POOL_MODES:
             raise ValueError(f"unknown pooling mode {mode}")
         self._check_learnt(mode, pb)
+        self._check_pool_from(mode, pb)
         d, L1 = self.cfg.hidden_size, self.cfg.num_layers + 1
         layers = torch.empty((L1, pb.B, d), dtype=torch.float32, device=self.device) if per_layer else None
         mean = torch.empty((pb.B, d), dtype=torch.float32, device=self.device)
-        st = self.ctx.lib.sgpt_encode_layers(self.handle, _p(pb.ids), _p(pb.pos), _p(pb.seq_off), _p(pb.seq_len),
-                                             _p(pb.pad_left), pb.B, pb.T_pad, pb.max_alloc, POOL_MODES[mode],
-                                             1 if normalize else 0, _p(layers), _p(mean), _stream_ptr(self.device))
+        args = (self.handle, _p(pb.ids), _p(pb.pos), _p(pb.seq_off), _p(pb.seq_len), _p(pb.pad_left), pb.B, pb.T_pad, pb.max_alloc,
+                POOL_MODES[mode], 1 if normalize else 0, _p(layers), _p(mean))
+        if pb.pool_lo is None:
+            st = self.ctx.lib.sgpt_encode_layers(*args, _stream_ptr(self.device))
+        else:
+            st = self.ctx.lib.sgpt_encode_layers_pool_from(*args, _p(pb.pool_lo), _stream_ptr(self.device))
         _lib.check(self.ctx.handle, st, "sgpt_encode_layers")
         return (layers, mean) if per_layer else mean
 
@@ -834,7 +890,7 @@ class SGPTModel:
                 return out
         raise SgptRangeError("dtype='f16': the range shifts did not converge; this checkpoint needs dtype='bf16'")
 
-    def _batched(self, seqs, pad_left, run) -> torch.Tensor:
+    def _batched(self, seqs, pad_left, run, pool_from=None) -> torch.Tensor:
         """Length-sorted token-budget batches -> `run(pb, out_rows)` per batch -> rows back in input order."""
         n = len(seqs)
         d = self.cfg.hidden_size
@@ -844,22 +900,25 @@ class SGPTModel:
         if (lens <= 0).any():
             raise ValueError("Empty items should be cleaned prior to running")
         self.ensure_precision_plan(seqs, pad_left)
-        return self.guarded(lambda: self._batched_once(seqs, pad_left, run, lens))
+        if pool_from is not None and np.ndim(pool_from) == 1 and len(pool_from) != n:
+            raise ValueError("pool_from: one int, or one int per sequence")
+        return self.guarded(lambda: self._batched_once(seqs, pad_left, run, lens, pool_from))
 
-    def _batched_once(self, seqs, pad_left, run, lens) -> torch.Tensor:
+    def _batched_once(self, seqs, pad_left, run, lens, pool_from=None) -> torch.Tensor:
         n, d = len(seqs), self.cfg.hidden_size
         # everything fits one call: the packed layout has no padding to the longest sequence, so the length sort of the
         # reference (SentenceTransformer.py:148-149) buys nothing -- pack in input order, no un-sort pass
         alloc_total = int(((lens + ALIGN - 1) // ALIGN * ALIGN).sum())
         if alloc_total <= self.max_tokens_per_call:
             res = torch.empty((n, d), dtype=torch.float32, device=self.device)
-            run(self.pack(seqs, pad_left), res)
+            run(self.pack(seqs, pad_left, pool_from=pool_from), res)
             return res
         plan = self.plan_batches(lens)
         sorted_rows = torch.empty((n, d), dtype=torch.float32, device=self.device)
         o = 0
         for sel in plan:
-            pb = self.pack([seqs[i] for i in sel], None if pad_left is None else [pad_left[i] for i in sel])
+            pb = self.pack([seqs[i] for i in sel], None if pad_left is None else [pad_left[i] for i in sel],
+                           pool_from=pool_from if pool_from is None or np.ndim(pool_from) == 0 else [pool_from[i] for i in sel])
             run(pb, sorted_rows[o: o + pb.B])
             o += pb.B
         order = torch.from_numpy(np.concatenate(plan)).pin_memory().to(self.device, non_blocking=True)
@@ -868,16 +927,18 @@ class SGPTModel:
         return res
 
     def encode_ids_all_layers(self, seqs: Sequence[Sequence[int]], mode: str = "mean",
-                              pad_left: Optional[Sequence[int]] = None) -> torch.Tensor:
+                              pad_left: Optional[Sequence[int]] = None, pool_from=None) -> torch.Tensor:
         """n token lists -> fp32[n,d]: the per-layer pooled vectors of all L+1 hidden states, averaged
-        (`meanmean` with mode='mean', `lasttokenmean` with mode='lasttoken'), one forward per batch."""
-        return self._batched(seqs, pad_left, lambda pb, out: out.copy_(self.encode_packed_layers(pb, mode)))
+        (`meanmean` with mode='mean', `lasttokenmean` with mode='lasttoken'), one forward per batch.  pool_from: as encode_ids."""
+        return self._batched(seqs, pad_left, lambda pb, out: out.copy_(self.encode_packed_layers(pb, mode)), pool_from)
 
     def encode_ids(self, seqs: Sequence[Sequence[int]], mode: str = "weightedmean", normalize: bool = False,
                    layer_idx: int = -1, pad_left: Optional[Sequence[int]] = None,
-                   out_dtype=torch.float32) -> torch.Tensor:
-        """n token lists -> fp32[n,d] embeddings on the GPU, row-aligned with the input order."""
-        return self._batched(seqs, pad_left, lambda pb, out: self.encode_packed(pb, mode, normalize, layer_idx, out=out))
+                   out_dtype=torch.float32, pool_from=None) -> torch.Tensor:
+        """n token lists -> fp32[n,d] embeddings on the GPU, row-aligned with the input order.
+        pool_from: one int or one per sequence -- pool from that token on (counted from the sequence start, frame included): the tokens
+        of an instruction prompt in front are encoded, not pooled (pack())."""
+        return self._batched(seqs, pad_left, lambda pb, out: self.encode_packed(pb, mode, normalize, layer_idx, out=out), pool_from)
 
     def token_embeddings(self, seqs: Sequence[Sequence[int]], layer_idx: int = -1,
                          pad_left: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
@@ -916,7 +977,12 @@ class EncodeGraph:
 
     def __init__(self, model: "SGPTModel", seqs: Sequence[Sequence[int]], mode: str = "weightedmean",
                  normalize: bool = False, layer_idx: int = -1, pad_left: Optional[Sequence[int]] = None,
-                 bucket: Optional[Tuple[int, int, int]] = None):
+                 bucket: Optional[Tuple[int, int, int]] = None, pool_from=None):
+        # (out of scope, refused loudly: a captured graph of the bidirectional mode or of a ranged pool has not been built or tested)
+        if family(model.cfg.model_type).attention_switch and getattr(model, "attention", "causal") != "causal":
+            raise ValueError("EncodeGraph: a model with attention='bidirectional' is not captured (encode it eagerly: encode_ids / encode_packed)")
+        if pool_from is not None:
+            raise ValueError("EncodeGraph: pool_from is not captured (encode eagerly: encode_ids(pool_from=) / pack(pool_from=))")
         self.model, self.mode, self.normalize, self.layer_idx = model, mode, normalize, layer_idx
         model.ensure_precision_plan(seqs, pad_left)        # (a later plan change would only force a re-capture)
         self.capacity = bucket               # None: exact layouts only; else batches are padded to this capacity

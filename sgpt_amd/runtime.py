@@ -335,7 +335,8 @@ class Context(CorpusBuilders):
         (fp32); out [T, ...] in q's dtype, or uint8 (e4m3 codes of ctx / out_scale, bf16 operands).  Deltas in elements.
         causal None: the sgpt_attention entry.  True / False: sgpt_attention_ex -- False is the bidirectional mode of the BERT family,
         every query of a sequence sees its keys [0, seq_len[b]) (seq_len int32 [B]; None = the whole allocation).
-        n_kv_heads: sgpt_attention_gqa -- k and v hold n_kv_heads heads, query head h reads head h // (H // n_kv_heads) (causal)."""
+        n_kv_heads: sgpt_attention_gqa -- k and v hold n_kv_heads heads, query head h reads head h // (H // n_kv_heads) (causal;
+        attention_gqa_ex below is the entry with both grouped K / V and the bidirectional mode)."""
         T = q.shape[0]
         out_fp8 = out.dtype == torch.uint8
         if q.dtype not in DT_CODE:
@@ -371,6 +372,34 @@ class Context(CorpusBuilders):
                                           out.stride(0), _p(so), so.numel() - 1, T, H, dh, window, scale, _p(al), max_alloc_len,
                                           1 if out_fp8 else 0, out_scale, _p(range_flag), 1 if x3 else 0, qk_lo_delta,
                                           v_lo_delta, ctx_lo_delta, ctx_hi2_delta, _stream_ptr(self.device)), "sgpt_attention")
+        return out
+
+    def attention_gqa_ex(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, seq_off: torch.Tensor, H: int,
+                         n_kv_heads: int, dh: int, max_alloc_len: int, causal: bool, seq_len: Optional[torch.Tensor] = None, window: int = 0,
+                         scale: float = 1.0, alibi: Optional[torch.Tensor] = None, out_scale: float = 0.0, x3: bool = False,
+                         qk_lo_delta: int = 0, v_lo_delta: int = 0, ctx_lo_delta: int = 0, ctx_hi2_delta: int = 0) -> torch.Tensor:
+        """include/sgpt_hip.h::sgpt_attention_gqa_ex: grouped K / V (as attention(n_kv_heads=)) with the causal / seq_len arguments of
+        sgpt_attention_ex -- causal=False is the bidirectional attention of a Llama-family model, every query of sequence b sees its
+        keys [0, seq_len[b]) (None = the whole allocation).  Buffers as attention(); the library checks the rest."""
+        if q.dtype not in DT_CODE:
+            raise ValueError(f"attention_gqa_ex: operands are fp32, bf16 or f16, got {q.dtype}")
+        if k.stride(0) != q.stride(0) or q.stride(1) != 1 or k.stride(1) != 1 or v.stride(1) != 1 or out.stride(1) != 1:
+            raise ValueError("attention_gqa_ex: q and k share one leading dimension; unit column strides")
+        if k.dtype != q.dtype or v.dtype != q.dtype:
+            raise ValueError("attention_gqa_ex: q, k and v have one dtype")
+        out_fp8 = out.dtype == torch.uint8
+        if out.dtype != q.dtype and not out_fp8:
+            raise ValueError("attention_gqa_ex: out has q's dtype")
+        if q.dtype == torch.float32 and v.stride(0) != q.stride(0):
+            raise ValueError("attention_gqa_ex: fp32 v rows share q's leading dimension (the fp32 kernel reads v with ldq)")
+        so = seq_off.to(device=self.device, dtype=torch.int32).contiguous()
+        sl = None if seq_len is None else seq_len.to(device=self.device, dtype=torch.int32).contiguous()
+        al = None if alibi is None else alibi.to(device=self.device, dtype=torch.float32).contiguous()
+        self._chk(self.lib.sgpt_attention_gqa_ex(self.handle, DT_CODE[q.dtype], _p(q), _p(k), _p(v), q.stride(0), v.stride(0), _p(out),
+                                                 out.stride(0), _p(so), so.numel() - 1, q.shape[0], H, int(n_kv_heads), dh, window, scale,
+                                                 _p(al), max_alloc_len, 1 if out_fp8 else 0, out_scale, None, 1 if x3 else 0, qk_lo_delta,
+                                                 v_lo_delta, ctx_lo_delta, ctx_hi2_delta, 1 if causal else 0, _p(sl),
+                                                 _stream_ptr(self.device)), "sgpt_attention_gqa_ex")
         return out
 
     # ---- the encoder's row kernels stand-alone (kernel-level tests): include/sgpt_hip.h::sgpt_embed ... sgpt_logprob_rows ----
@@ -497,6 +526,25 @@ class Context(CorpusBuilders):
         self._chk(self.lib.sgpt_lnf_pool(self.handle, _p(x), _p(g), _p(b), _p(seq_off), _p(seq_len), _p(pad_left), B, d, eps,
                                          0 if ln is None else 1, POOL_MODES[mode], 1 if normalize else 0, _p(pw), n_w, _p(out),
                                          _p(nonfinite_flag), _stream_ptr(self.device)), "sgpt_lnf_pool")
+        return out
+
+    def lnf_pool_range(self, x: torch.Tensor, seq_off: torch.Tensor, seq_len: torch.Tensor, pool_lo: Optional[torch.Tensor],
+                       pad_left: Optional[torch.Tensor] = None, ln=None, rms=None, mode: str = "weightedmean",
+                       normalize: bool = False) -> torch.Tensor:
+        """lnf_pool over the rows [pool_lo[b], seq_len[b]) of every sequence (include/sgpt_hip.h::sgpt_lnf_pool_range): pool_lo int32 [B]
+        on the device, clamped by the kernel; None = every row.  ln = (gamma, beta, eps) | rms = (gamma, eps) | neither (pool x as it is)."""
+        if ln is not None and rms is not None:
+            raise ValueError("lnf_pool_range: ln or rms, not both")
+        if mode not in POOL_MODES:
+            raise ValueError(f"unknown pooling mode {mode}")
+        B, d = seq_len.numel(), x.shape[1]
+        g, b, eps = (self._f32c(ln[0]), self._f32c(ln[1]), float(ln[2])) if ln is not None else (
+            (self._f32c(rms[0]), None, float(rms[1])) if rms is not None else (None, None, 0.0))
+        out = torch.empty((B, d), dtype=torch.float32, device=self.device)
+        self._chk(self.lib.sgpt_lnf_pool_range(self.handle, _p(x), _p(g), _p(b), _p(seq_off), _p(seq_len), _p(pad_left), B, d, eps,
+                                               0 if (ln is None and rms is None) else 1, POOL_MODES[mode], 1 if normalize else 0, None, 0,
+                                               _p(out), None, 1 if rms is not None else 0, _p(pool_lo), _stream_ptr(self.device)),
+                  "sgpt_lnf_pool_range")
         return out
 
     def rope(self, buf: torch.Tensor, pos: torch.Tensor, sin: torch.Tensor, cos: torch.Tensor, H: int, head_dim: int,

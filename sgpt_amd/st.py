@@ -15,15 +15,26 @@ from .families import family_of, max_seq_len_of
 from .tokenization import TextPipeline
 
 
+def resolve_include_prompt(explicit: Optional[bool], folder: Optional[bool]) -> bool:
+    """include_prompt of a model loaded from a folder: the caller's argument, else the folder's 1_Pooling field, else True."""
+    return bool(explicit) if explicit is not None else (True if folder is None else bool(folder))
+
+
+def _pf(pool_from: Optional[int]) -> dict:
+    """(a model stand-in without the argument keeps working while no prompt is left out)"""
+    return {} if pool_from is None else {"pool_from": pool_from}
+
+
 class SentenceTransformerSGPT:
     """Transformer + Pooling(weightedmean) [+ Normalize] as one module
     (the assembly of training_nli_v2.py:85-123 / modules.json)."""
 
     def __init__(self, model: SGPTModel, tokenizer, max_seq_length: Optional[int] = None, pooling_mode: str = "weightedmean",
-                 specb: bool = False, normalize: bool = False, frame=None):
+                 specb: bool = False, normalize: bool = False, frame=None, prompt: str = None, include_prompt: bool = True):
         """max_seq_length: tokens per text, framing included; longer texts are truncated by the tokeniser, as in sentence-transformers.
         None = 300, or the model's longest sequence (SGPTModel.max_seq_len) where that is shorter; a value beyond what the model
-        encodes is refused here and not at the first long text."""
+        encodes is refused here and not at the first long text.
+        prompt / include_prompt: TextPipeline's -- the defaults of encode(prompt=, include_prompt=)."""
         limit = max_seq_len_of(model)
         if max_seq_length is None:
             max_seq_length = 300 if limit is None else min(300, limit)
@@ -36,13 +47,15 @@ class SentenceTransformerSGPT:
         self.pooling_mode = pooling_mode
         self.specb = specb
         self.normalize = normalize          # a Normalize module in modules.json (models/Normalize.py)
-        self.pipe = TextPipeline(tokenizer, max_seq_length, specb=specb, family=family_of(model), frame=frame)   # frame: TextPipeline's
+        self.pipe = TextPipeline(tokenizer, max_seq_length, specb=specb, family=family_of(model), frame=frame,   # frame: TextPipeline's
+                                 prompt=prompt, include_prompt=include_prompt)
 
     @classmethod
     def from_pretrained(cls, path: str, tokenizer=None, device=None, dtype: str = "f16", specb: bool = False, frame=None,
-                        **model_kw) -> "SentenceTransformerSGPT":
+                        prompt: str = None, include_prompt: Optional[bool] = None, **model_kw) -> "SentenceTransformerSGPT":
         """SentenceTransformer(model_path) for an SGPT folder (SentenceTransformer._load_sbert_model, :903-936):
-        modules.json -> Transformer weights, Pooling / WeightedMeanPooling mode, optional Normalize."""
+        modules.json -> Transformer weights, Pooling / WeightedMeanPooling mode, optional Normalize.  include_prompt: None = the
+        `include_prompt` field of 1_Pooling/config.json where the folder has one (else True); an explicit argument wins."""
         from .formats import read_st_folder
         from .tokenization import load_tokenizer
         spec = read_st_folder(path)
@@ -54,7 +67,8 @@ class SentenceTransformerSGPT:
         tok = tokenizer if tokenizer is not None else load_tokenizer(spec.transformer_dirs[""])
         # the folder's max_seq_length, else the model's longest sequence; never beyond it (over-long text is truncated, not refused)
         return cls(model, tok, max_seq_length=min(spec.max_seq_length or model.max_seq_len, model.max_seq_len),
-                   pooling_mode=spec.pooling_mode, specb=specb, normalize=spec.normalize, frame=frame)
+                   pooling_mode=spec.pooling_mode, specb=specb, normalize=spec.normalize, frame=frame, prompt=prompt,
+                   include_prompt=resolve_include_prompt(include_prompt, spec.include_prompt))
 
     def get_sentence_embedding_dimension(self) -> int:
         return self.model.cfg.hidden_size
@@ -62,7 +76,7 @@ class SentenceTransformerSGPT:
     def encode(self, sentences: Union[str, List[str]], batch_size: int = 32, show_progress_bar: bool = None,
                output_value: str = "sentence_embedding", convert_to_numpy: bool = True,
                convert_to_tensor: bool = False, device: str = None, normalize_embeddings: bool = False,
-               num_proc=None, is_query: bool = True):
+               num_proc=None, is_query: bool = True, prompt: str = None, include_prompt: Optional[bool] = None):
         """SentenceTransformer.encode (SentenceTransformer.py:107-215), same arguments and return-type rules:
           output_value 'sentence_embedding' -> ndarray [n, d] (convert_to_numpy, the default) | Tensor [n, d] (convert_to_tensor)
                         | list of Tensors; 'token_embeddings' -> list of [len_i, d] Tensors (:233-241); None -> list of dicts
@@ -76,6 +90,8 @@ class SentenceTransformerSGPT:
                         device handle cannot be pickled, so that form is refused with a pointer to the equivalents
                         (start_multi_process_pool(model_factory) / encode_multi_process, or torchrun + this method);
           batch_size / show_progress_bar are accepted for signature compatibility (batches are cut by token budget).
+          prompt / include_prompt  (None: the module's) the text encoded is `prompt + sentence`, tokenised as one string;
+                        include_prompt=False pools the tokens behind the prompt only (SGPTModel.encode_ids(pool_from=)).
         A single string returns a single vector / dict (:143-146, 212-213)."""
         if device is not None:
             dev, mine = torch.device(device), torch.device(self.model.device)
@@ -95,14 +111,15 @@ class SentenceTransformerSGPT:
         if isinstance(sentences, str) or not hasattr(sentences, "__len__"):     # :143-146
             sentences = [sentences]
             input_was_string = True
-        seqs = self.pipe.batch([str(s).strip() for s in sentences], is_query)
+        seqs = self.pipe.batch([str(s).strip() for s in sentences], is_query, prompt)
+        pool_from = self.pipe.pool_from(prompt, include_prompt)
 
         if output_value == "token_embeddings":                                  # :233-241
             embs = self.model.token_embeddings(seqs)
             return embs[0] if input_was_string else embs
         if output_value is None:                                                # :242-246: every output of the module chain
             toks = self.model.token_embeddings(seqs)
-            sent = self.model.encode_ids(seqs, mode=self.pooling_mode, normalize=self.normalize)
+            sent = self.model.encode_ids(seqs, mode=self.pooling_mode, normalize=self.normalize, **_pf(pool_from))
             rows = [{"input_ids": torch.tensor(s, dtype=torch.int64, device=t.device),
                      "attention_mask": torch.ones(len(s), dtype=torch.int64, device=t.device),
                      "token_embeddings": t, "sentence_embedding": e} for s, t, e in zip(seqs, toks, sent)]
@@ -111,9 +128,9 @@ class SentenceTransformerSGPT:
             raise ValueError("output_value must be 'sentence_embedding', 'token_embeddings' or None")
 
         if is_distributed():
-            emb = self.encode_ids_distributed(seqs, normalize_embeddings)
+            emb = self.encode_ids_distributed(seqs, normalize_embeddings, pool_from=pool_from)
         else:
-            emb = self.model.encode_ids(seqs, mode=self.pooling_mode, normalize=normalize_embeddings)
+            emb = self.model.encode_ids(seqs, mode=self.pooling_mode, normalize=normalize_embeddings, **_pf(pool_from))
 
         if convert_to_numpy:
             emb = emb.cpu().numpy()
@@ -123,7 +140,7 @@ class SentenceTransformerSGPT:
             emb = emb[0]
         return emb
 
-    def encode_ids_distributed(self, seqs, normalize_embeddings: bool = False, group=None) -> torch.Tensor:
+    def encode_ids_distributed(self, seqs, normalize_embeddings: bool = False, group=None, pool_from: Optional[int] = None) -> torch.Tensor:
         """The torch.distributed data-parallel branch of SentenceTransformer.encode (:153-175): every rank sorts the
         SAME list by length (longest first, :148-149 -- appendix A.10: the un-sort below relies on all ranks agreeing
         on this order, so the sort is stable and keyed on the token count only) and encodes one CONTIGUOUS shard of the
@@ -141,7 +158,7 @@ class SentenceTransformerSGPT:
         mine = [seqs[i] for i in order[cuts[comm.rank]: cuts[comm.rank + 1]]]
         d = self.get_sentence_embedding_dimension()
         if mine:
-            local = self.model.encode_ids(mine, mode=self.pooling_mode, normalize=normalize_embeddings)
+            local = self.model.encode_ids(mine, mode=self.pooling_mode, normalize=normalize_embeddings, **_pf(pool_from))
         else:                                                     # more ranks than sentences
             local = torch.empty((0, d), dtype=torch.float32, device=getattr(self.model, "device", "cpu"))
         gathered = comm.all_gather_rows(local, counts)

@@ -79,12 +79,20 @@ class TextPipeline:
     frame: an explicit (front_ids, back_ids) pair in place of what `framing` would resolve from the tokenizer, for a tokenizer whose
            attributes do not say what its model was trained with: the Qwen tokenizers carry no BOS, and Qwen3-Embedding closes every
            input with EOS -- frame=([], [tok.eos_token_id]).  The content is cut to max_token_len minus its length.  Not together with
-           specb / speca."""
+           specb / speca.
+    prompt: an instruction put in front of every text (sentence-transformers `encode(prompt=...)`, GritLM): the text encoded is
+           `prompt + text`, tokenised as ONE string.  include_prompt=False: the prompt's tokens are encoded but not pooled --
+           pool_from(prompt) is the number of ids the front frame plus the tokenised prompt ALONE give (no back frame), the
+           `pool_from=` of SGPTModel.encode_ids (sentence-transformers' `include_prompt: false`, which counts the prompt's tokens the
+           same way).  ids() / batch() take a prompt of their own in place of the pipeline's.  Not together with specb / speca."""
 
     def __init__(self, tokenizer, max_token_len: int, specb: bool = False, speca: bool = False, st_path: bool = False, family=None,
-                 frame=None):
+                 frame=None, prompt: str = None, include_prompt: bool = True):
         if speca and specb:
             raise ValueError("speca and specb are mutually exclusive")
+        if (specb or speca) and (prompt is not None or not include_prompt):
+            raise ValueError("prompt / include_prompt do not go together with specb / speca brackets (the brackets would sit in front of the prompt)")
+        self.prompt, self.include_prompt = prompt, include_prompt
         if frame is not None and (specb or speca):
             raise ValueError("frame replaces the family's framing of the content: it does not go together with specb / speca brackets")
         fam = family if isinstance(family, Family) else (FAMILIES[0] if family is None else family_row(family))
@@ -125,7 +133,26 @@ class TextPipeline:
             self.bos_q, self.eos_q, self.bos_d, self.eos_d = enc
         self.docs_truncated = self.toks_truncated = 0
 
-    def ids(self, txt: str, is_query: bool) -> List[int]:
+    def pool_from(self, prompt: str = None, include_prompt: bool = None):
+        """The first pooled token of a sequence encoded with `prompt` / `include_prompt` (None: the pipeline's): None when the prompt is
+        pooled too (include_prompt, or no prompt), else len(front frame) + the ids of the prompt tokenised alone."""
+        prompt = self.prompt if prompt is None else prompt
+        if (self.include_prompt if include_prompt is None else include_prompt) or not prompt:
+            return None
+        if self.specb or self.speca:
+            raise ValueError("prompt / include_prompt do not go together with specb / speca brackets")
+        if not self.st_path:
+            prompt = prompt.replace("\n", " ")
+        return (len(self.frame[0]) if self.frame else 0) + len(self.tok.convert_tokens_to_ids(self.tok.tokenize(prompt)))
+
+    def _with_prompt(self, prompt):
+        prompt = self.prompt if prompt is None else prompt
+        if prompt and (self.specb or self.speca):
+            raise ValueError("prompt / include_prompt do not go together with specb / speca brackets")
+        return prompt or ""
+
+    def ids(self, txt: str, is_query: bool, prompt: str = None) -> List[int]:
+        txt = self._with_prompt(prompt) + txt
         if not self.st_path:                                                    # the ST path hands the text to the
             txt = txt.replace("\n", " ")                                       # tokenizer untouched; raw path: :169
         tokens = self.tok.convert_tokens_to_ids(self.tok.tokenize(txt))        # :172-173
@@ -142,13 +169,15 @@ class TextPipeline:
             tokens = self.frame[0] + tokens + self.frame[1]
         return tokens
 
-    def batch(self, texts: Sequence[str], is_query: bool) -> List[List[int]]:
+    def batch(self, texts: Sequence[str], is_query: bool, prompt: str = None) -> List[List[int]]:
         """All texts of a call at once.  A HF *fast* tokenizer takes the whole list in ONE call (its Rust core
         tokenises the batch in parallel and returns the ids directly: the id sequence of
         `convert_tokens_to_ids(tokenize(t))`, beir_dense_retriever.py:172-173); truncation and brackets are then list
         slices.  Any other tokenizer object (slow HF tokenizers, SyntheticTokenizer) goes through the per-text calls."""
         if not getattr(self.tok, "is_fast", False) or len(texts) < 2:
-            return [self.ids(t, is_query) for t in texts]
+            return [self.ids(t, is_query, prompt) for t in texts]
+        if self._with_prompt(prompt):
+            texts = [self._with_prompt(prompt) + t for t in texts]
         if not self.st_path:
             texts = [t.replace("\n", " ") for t in texts]                        # :169
         enc = self.tok(list(texts), add_special_tokens=False, padding=False, truncation=False,
