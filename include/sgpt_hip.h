@@ -311,7 +311,8 @@ sgpt_status sgpt_lm_logprobs(sgpt_model* model, const float* hidden, const int32
 /* Stand-alone pooling over caller-supplied hidden states (USEB layer sweeps, parity tests).
  * Replaces Pooling.forward (sentence_transformers/models/Pooling.py:99-125,129-164) and
  * CustomEmbedder.embed_batcher's pooling branch (beir_dense_retriever.py:238-282).
- *   hidden device [B,S,d] (fp32 or bf16), mask device int32[B,S] (0/1, any padding side);
+ *   hidden device [B,S,d], fp32, bf16 or f16 (hidden_dtype SGPT_F32 | SGPT_BF16 | SGPT_F16; any other
+ *   code is SGPT_ERR_INVALID); mask device int32[B,S] (0/1, any padding side);
  *   weights follow the padded index t+1; weight sum clamped at 1e-9 (Pooling.py:122).
  *   pool_mode SGPT_POOL_WEIGHTEDMEAN | _MEAN | _LASTTOKEN | _CLS (row 0 of every sequence, whatever the mask: Pooling.py:103-105). */
 sgpt_status sgpt_pool(sgpt_ctx* ctx, const void* hidden, int32_t hidden_dtype, const int32_t* mask,
@@ -321,7 +322,9 @@ sgpt_status sgpt_pool_learnt(sgpt_ctx* ctx, const void* hidden, int32_t hidden_d
                              int32_t B, int32_t S, int32_t d, const float* pos_weights, float* out, void* stream);
 
 /* Row-wise x / max(||x||_2, 1e-12): torch.nn.functional.normalize(p=2, dim=1)
- * (sentence_transformers/util.py:41-42, 66-70).  out may alias in when out_dtype == SGPT_F32. */
+ * (sentence_transformers/util.py:41-42, 66-70).  out_dtype SGPT_F32 | SGPT_BF16 | SGPT_F16 (any other code
+ * is SGPT_ERR_INVALID); the 16-bit outputs are the fp32 result rounded once (RNE).  out may alias in when
+ * out_dtype == SGPT_F32. */
 sgpt_status sgpt_l2_normalize(sgpt_ctx* ctx, const float* in, int64_t n, int32_t d,
                               void* out, int32_t out_dtype, void* stream);
 

@@ -6,8 +6,9 @@ extern "C" {
 
 sgpt_status sgpt_pool(sgpt_ctx* c, const void* hidden, int32_t dtype, const int32_t* mask, int32_t B, int32_t S,
                       int32_t d, int32_t mode, float* out, void* stream) {
-    if (!c || !hidden || !mask || !out || B <= 0 || S <= 0 || d <= 0 || d % 4 || mode < 0 || (mode > 2 && mode != SGPT_POOL_CLS))
-        return fail(c, SGPT_ERR_INVALID, "sgpt_pool: bad arguments (d % 4 == 0 required; mode 0 | 1 | 2 | 4)");
+    if (!c || !hidden || !mask || !out || B <= 0 || S <= 0 || d <= 0 || d % 4 || mode < 0 || (mode > 2 && mode != SGPT_POOL_CLS) ||
+        (dtype != SGPT_F32 && dtype != SGPT_BF16 && dtype != SGPT_F16))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_pool: bad arguments (d % 4 == 0 required; mode 0 | 1 | 2 | 4; hidden fp32, bf16 or f16)");
     HIPC(c, hipSetDevice(c->device));
     launch_pool(hidden, dtype, mask, B, S, d, mode, nullptr, out, (hipStream_t)stream);
     HIPC(c, hipGetLastError());
@@ -16,8 +17,9 @@ sgpt_status sgpt_pool(sgpt_ctx* c, const void* hidden, int32_t dtype, const int3
 
 sgpt_status sgpt_pool_learnt(sgpt_ctx* c, const void* hidden, int32_t dtype, const int32_t* mask, int32_t B, int32_t S,
                              int32_t d, const float* pos_weights, float* out, void* stream) {
-    if (!c || !hidden || !mask || !out || !pos_weights || B <= 0 || S <= 0 || d <= 0 || d % 4)
-        return fail(c, SGPT_ERR_INVALID, "sgpt_pool_learnt: bad arguments (d % 4 == 0 required)");
+    if (!c || !hidden || !mask || !out || !pos_weights || B <= 0 || S <= 0 || d <= 0 || d % 4 ||
+        (dtype != SGPT_F32 && dtype != SGPT_BF16 && dtype != SGPT_F16))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_pool_learnt: bad arguments (d % 4 == 0 required; hidden fp32, bf16 or f16)");
     HIPC(c, hipSetDevice(c->device));
     launch_pool(hidden, dtype, mask, B, S, d, SGPT_POOL_LEARNTMEAN, pos_weights, out, (hipStream_t)stream);
     HIPC(c, hipGetLastError());

@@ -9,7 +9,8 @@ extern "C" {
 
 sgpt_status sgpt_l2_normalize(sgpt_ctx* c, const float* in, int64_t n, int32_t d, void* out, int32_t out_dtype,
                               void* stream) {
-    if (!c || !in || !out || n <= 0 || d <= 0) return fail(c, SGPT_ERR_INVALID, "sgpt_l2_normalize: bad arguments");
+    if (!c || !in || !out || n <= 0 || d <= 0 || (out_dtype != SGPT_F32 && out_dtype != SGPT_BF16 && out_dtype != SGPT_F16))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_l2_normalize: bad arguments (out fp32, bf16 or f16)");
     HIPC(c, hipSetDevice(c->device));
     launch_l2norm(in, n, d, out, out_dtype, (hipStream_t)stream);
     HIPC(c, hipGetLastError());
