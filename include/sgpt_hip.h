@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 24
+#define SGPT_ABI_VERSION 25
 
 /* The longest sequence (ABI v23): the token rows one sequence may own in the packed layout of sgpt_encode*, sgpt_attention_ex and
  * sgpt_attention_gqa (max_alloc_len <= SGPT_MAX_SEQ_LEN; a larger value is SGPT_ERR_INVALID, nothing launched).  32 768 is the
@@ -101,7 +101,10 @@ enum { SGPT_ARCH_GPTNEO = 0, SGPT_ARCH_GPTJ = 1, SGPT_ARCH_BLOOM = 2, SGPT_ARCH_
  *   family with one property set AFTER load, sgpt_model_set_attention(model, 0): in every layer every query row of a sequence sees
  *   keys [0, seq_len[b]) of that sequence (the non-causal kernels of SGPT_ARCH_BERT with grouped K / V); rotary, the q / k norm, the
  *   bias and the projections are untouched.  Not a descriptor field: the descriptor of a model is the same in both modes.  Such
- *   models usually pool the tokens behind an instruction prompt: sgpt_encode_pool_from. */
+ *   models usually pool the tokens behind an instruction prompt: sgpt_encode_pool_from.
+ *   ABI v25 -- fp8 projections, a second property set AFTER load on an SGPT_BF16 model, sgpt_model_set_projections(model, 1, ..): the
+ *   Q | K | V, gate | up and down projections on the e4m3 MFMA with dynamic per-token activation scales and per-channel weight scales,
+ *   no calibration; the out-projection, the attention and everything else as above.  Composes with both attention modes and pool_lo. */
 enum { SGPT_POOL_WEIGHTEDMEAN = 0, SGPT_POOL_MEAN = 1, SGPT_POOL_LASTTOKEN = 2, SGPT_POOL_LEARNTMEAN = 3,
        SGPT_POOL_CLS = 4 };   /* ABI v13: the first token row of each sequence (Pooling.py:103-105 `pooling_mode_cls_token`); sgpt_encode*, sgpt_pool */
 enum { SGPT_COS = 0, SGPT_DOT = 1, SGPT_NEG_L2 = 2 };   /* SGPT_NEG_L2 (ABI v11): -||x - y||_2, sgpt_eval_groups only */
@@ -274,6 +277,22 @@ sgpt_status sgpt_encode_pool_from(sgpt_model* model, const int32_t* ids, const i
  * the descriptor, and inside a folded window the window hides nothing in either direction).  Graphs captured before a change are
  * stale (sgpt_ctx_generation moves). */
 sgpt_status sgpt_model_set_attention(sgpt_model* model, int32_t causal);
+
+/* The arithmetic of an SGPT_ARCH_LLAMA model's projections (ABI v25), set after load; no compute dtype, no descriptor field, no
+ * calibration pass.  kind 0: 16-bit, the model as loaded (legal only on a model never converted: a no-op).  kind 1: fp8 -- layer by
+ * layer w_qkv [d_q + 2 d_kv, d], w_fc [2 ffn, d] and w_proj [d, ffn] become e4m3fn codes with one power-of-two fp32 scale per output
+ * row (sgpt_fp8_quantize_rows' rule and RNE codes, taken from the bf16 values the model holds), and each 16-bit allocation is freed as
+ * its layer is done.  *bytes_freed (or NULL): the 16-bit bytes of the three matrices minus codes and scales, over all layers.  ONE-WAY.
+ * The forward of a converted model: RMSNorm and SwiGLU write e4m3fn codes under one DYNAMIC power-of-two scale per token row
+ * (sgpt_rmsnorm_fp8, sgpt_swiglu_fp8); q | k, V^T, gate | up and the down-projection run on the fp8 MFMA (sgpt_linear_fp8 epi 0 / 4 /
+ * 0 / 2 with a_scale = the row scales); rotary, the q / k norm, the attention in either mode, pooling and the out-projection are the
+ * 16-bit model's -- w_o stays 16-bit, its operand (the attention context) has no row scale.  sgpt_encode* then takes layouts of
+ * T_pad % 256 == 0 only (SGPT_ERR_INVALID otherwise: no other path is left).  Graphs captured before the call are stale.
+ * SGPT_ERR_INVALID, each by its own message: any arch but SGPT_ARCH_LLAMA; a compute dtype other than SGPT_BF16; d_model, d_q + d_kv,
+ * d_kv or d_ffn not a multiple of 256; kind outside 0 | 1; kind 0 after a conversion; a second conversion.
+ * sgpt_model_get_projections: *kind = 0 | 1. */
+sgpt_status sgpt_model_set_projections(sgpt_model* model, int32_t kind, int64_t* bytes_freed);
+sgpt_status sgpt_model_get_projections(sgpt_model* model, int32_t* kind);
 
 /* All L+1 hidden states pooled in ONE forward: the `meanmean` / `lasttokenmean` methods
  * (beir_dense_retriever.py:243-257, 284-301; useb_dense_retriever.py:219-302) average the pooled vector of
@@ -1024,6 +1043,17 @@ sgpt_status sgpt_layernorm_fp8(sgpt_ctx* ctx, const float* x, const float* gamma
 sgpt_status sgpt_linear_fp8(sgpt_ctx* ctx, int32_t epi, int32_t out_dtype, const uint8_t* A, const float* a_scale,
                             float a_scalar, const uint8_t* W, const float* w_scale, const float* bias, const float* resid,
                             void* out, float out_scale, int32_t M, int32_t N, int32_t K, void* stream);
+/* The two quantising row kernels of the fp8 projections of SGPT_ARCH_LLAMA (ABI v25; sgpt_model_set_projections), stand-alone.
+ * sgpt_rmsnorm_fp8: sgpt_rmsnorm's fp32 row (x * rsqrt(mean(x^2) + eps) * gamma) -> e4m3fn codes [T, d] + one power-of-two scale per
+ *   row, exactly as sgpt_layernorm_fp8 quantises: scale = the smallest 2^k with max|row| / 2^k <= 448 (1 for a zero row), codes =
+ *   RNE e4m3fn(value / scale), true value = code * scale.  d % 4 == 0, d <= 4096; x / gamma 16-byte aligned.
+ * sgpt_swiglu_fp8:  gu [T, 2 ffn] of dtype SGPT_BF16 | SGPT_F16 (gate columns, then up columns) -> codes [T, ffn] + row_scale [T] of
+ *   h = silu(gate) * up, computed in fp32 with sgpt_swiglu's expression and NOT rounded to 16 bits in between; one scale per row by the
+ *   same rule.  ffn % 16 == 0; gu and codes 16-byte aligned, codes a buffer of its own.  A row of zeros: scale 1, zero codes. */
+sgpt_status sgpt_rmsnorm_fp8(sgpt_ctx* ctx, const float* x, const float* gamma, int32_t T, int32_t d, float eps, uint8_t* codes,
+                             float* row_scale, void* stream);
+sgpt_status sgpt_swiglu_fp8(sgpt_ctx* ctx, const void* gu, int32_t dtype, int32_t T, int32_t ffn, uint8_t* codes, float* row_scale,
+                            void* stream);
 
 /* -- measurement ----------------------------------------------------------------------- */
 /* bench.py's live roofline: when enabled, every GEMM launched by sgpt_encode /

@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGPT_HIP_LIB") or os.path.join(HERE, "lib", "libsgpt_hip.so")   # env: A/B builds of the same ABI
 
 SGPT_F32, SGPT_BF16, SGPT_FP8W, SGPT_F16, SGPT_FP8M = 0, 1, 2, 3, 4
-SGPT_ABI_VERSION = 24
+SGPT_ABI_VERSION = 25
 SGPT_MAX_SEQ_LEN = 32768                   # tokens per sequence of sgpt_encode*, sgpt_attention_ex / _gqa (include/sgpt_hip.h)
 SGPT_PREC_CLASSES = 5                      # precision-plan classes per block: LN1, ATT, CTX, LN2, H (include/sgpt_hip.h)
 PC_LN1, PC_ATT, PC_CTX, PC_LN2, PC_H = 0, 1, 2, 3, 4
@@ -61,6 +61,10 @@ SIGNATURES = {
                                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p]),
     "sgpt_model_set_attention": (C.c_int, [C.c_void_p, C.c_int32]),
+    "sgpt_model_set_projections": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "sgpt_model_get_projections": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "sgpt_rmsnorm_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sgpt_swiglu_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sgpt_model_set_pool_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "sgpt_pool_learnt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),

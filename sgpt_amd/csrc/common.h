@@ -454,6 +454,10 @@ void launch_crest16(const void* in, int T, int cols, long ld, int dtype, unsigne
 void launch_split16_rows(const float* in, long n, int d, int layout, void* out, int out_dtype, hipStream_t s);
 // LayerNorm -> e4m3fn codes q[T,d] + one power-of-two scale per row
 void launch_layernorm_q8(const float* x, const float* g, const float* b, void* q, float* scale, int T, int d, float eps, hipStream_t s);
+// RMSNorm -> the same (fp8 projections of SGPT_ARCH_LLAMA)
+void launch_rmsnorm_q8(const float* x, const float* g, void* q, float* scale, int T, int d, float eps, hipStream_t s);
+// SwiGLU of 16-bit gu [T][2 ffn] -> e4m3fn codes q[T, ffn] of the fp32 product + one power-of-two scale per row; ffn % 16 == 0
+void launch_swiglu_q8(const void* gu, int dtype, void* q, float* scale, int T, int ffn, hipStream_t s);
 void launch_absmax16(const void* in, long numel, int dtype, unsigned* out_bits, hipStream_t s);   // max|x| of a bf16 / f16 array
 void launch_lnf_pool(const float* x, const float* g, const float* b, const int* seq_off, const int* seq_len,
                      const int* pad_left, int B, int d, float eps, int apply_ln, int mode, int normalize,
@@ -465,6 +469,7 @@ void launch_pool(const void* hidden, int dtype, const int* mask, int B, int S, i
                  const float* pos_weights, float* out, hipStream_t s);
 // fp8 e4m3fn weight storage, one power-of-two scale per row (output channel)
 void launch_fp8_quant_rows(const float* w, long rows, long cols, void* q, float* scale, hipStream_t s);
+void launch_fp8_quant_rows_bf16(const void* w, long rows, long cols, void* q, float* scale, hipStream_t s);   // bf16 rows, cols % 2 == 0
 void launch_fp8_dequant_rows(const void* q, const float* scale, long rows, long cols, void* out, int out_dtype,
                              hipStream_t s);
 void launch_l2norm(const float* in, long n, int d, void* out, int out_dtype, hipStream_t s);

@@ -1,10 +1,11 @@
 // The HBM-bound kernels around the GEMMs and the attention, and their launchers:
-//   row normalisation (one wave per row, rowln.h): LayerNorm to fp32 / 16 bit, with write-back, as [hi | lo | hi], as fp8 codes; RMSNorm;
+//   row normalisation (one wave per row, rowln.h): LayerNorm to fp32 / 16 bit, with write-back, as [hi | lo | hi], as fp8 codes; RMSNorm, to 16 bit / fp32 and as fp8 codes;
 //     the fused final norm + pooling + L2 normalise (one workgroup per sequence, LDS for its cross-wave combine only);
 //   other row kernels: embedding gather-add, stand-alone pooling, L2 normalise, pairwise scores, row gather, log-prob of a logits row,
 //     crest factor;
+//   SwiGLU as fp8 codes under one scale per row (one workgroup per row);
 //   element maps: SwiGLU, the three rotary embeddings (GPT-J pairs, half-split, half-split behind a per-head RMSNorm);
-//   formats: fp8 row quantise / de-quantise, split-precision rows and weights, sign bits, fp32 -> 16 bit, BLOOM's QKV re-ordering;
+//   formats: fp8 row quantise (from fp32 and from bf16 rows) / de-quantise, split-precision rows and weights, sign bits, fp32 -> 16 bit, BLOOM's QKV re-ordering;
 //   small tools: abs-max (fp32, 16 bit), mean over axis 0, fill, pseudo-random fill.
 #include <type_traits>
 
@@ -137,6 +138,78 @@ __global__ __launch_bounds__(256) void layernorm_q8_kernel(const float* __restri
                                                            const float* __restrict__ b, uint8_t* __restrict__ q,
                                                            float* __restrict__ scale, int T, int d, float eps) {
     rownorm_row<NV>(x, T, d, RowLayerNorm<>(g, b, eps), RowStoreFp8{q, scale});
+}
+
+// RMSNorm whose output feeds an fp8-MFMA GEMM (fp8 projections of the Llama family): rmsnorm_kernel's arithmetic, layernorm_q8_kernel's sink
+template <int NV>
+__global__ __launch_bounds__(256) void rmsnorm_q8_kernel(const float* __restrict__ x, const float* __restrict__ g, uint8_t* __restrict__ q,
+                                                         float* __restrict__ scale, int T, int d, float eps) {
+    rownorm_row<NV>(x, T, d, RowRMSNorm<>(g, nullptr, eps), RowStoreFp8{q, scale});
+}
+
+// SwiGLU whose output feeds an fp8-MFMA GEMM (the down-projection of a converted Llama model): h = silu_mul(gate, up) in fp32 from the
+// 16-bit gu [T][2 ffn] -- the expression of swiglu_kernel, NOT rounded to 16 bits -- then e4m3fn codes of h / scale under ONE scale per
+// row, fp8_pow2_scale(max|h_row|), as RowStoreFp8 writes them.  A row is up to 28 672 columns (Qwen2.5-72B; 14 336 at Mistral-7B): more
+// than a wave holds, so one 256-thread workgroup per row, 16 columns per thread and step (four 16-byte loads, one 16-byte store), the row
+// maximum through the wave butterfly and four LDS words.
+// NIT > 0: the row's h stays in registers between the two passes (NIT steps of 16 fp32 values per thread, ffn <= NIT * 4096).  Chosen
+// over a second read of the row from the compiler's report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): no scratch and no spill
+// in any variant, 38 / 58 / 80 / 143 VGPRs at NIT = 1 / 2 / 4 / 7 (14 336 columns run NIT = 4), and the second pass would compute
+// expf and the IEEE divide of every element again -- the kernel moves 5 bytes per element and is near the VALU's rate already.
+// NIT == 0 (ffn > 28 672): any width, the second pass reads the row again (at 4 bytes per column it sits in L2) and recomputes h.
+template <typename T, int NIT>
+__global__ __launch_bounds__(256) void swiglu_q8_kernel(const T* __restrict__ gu, uint8_t* __restrict__ q, float* __restrict__ scale,
+                                                        int ffn) {
+    __shared__ float red[4];
+    const long row = blockIdx.x;
+    const int t = threadIdx.x, nchunk = ffn / 16;
+    const T* grow = gu + row * 2 * (long)ffn;
+    uint8_t* qrow = q + row * (long)ffn;
+    // h of columns 16 c .. 16 c + 15, and the largest |h| among them folded into amax
+    auto chunk = [&](int c, float (&h)[16], float& amax) {
+        const T* gp = grow + (long)c * 16;
+        const uint4 a0 = *reinterpret_cast<const uint4*>(gp), a1 = *reinterpret_cast<const uint4*>(gp + 8);
+        const uint4 b0 = *reinterpret_cast<const uint4*>(gp + ffn), b1 = *reinterpret_cast<const uint4*>(gp + ffn + 8);
+        const uint32_t aw[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w}, bw[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+        for (int w = 0; w < 8; ++w) {
+            h[2 * w] = silu_mul(Half<T>::lo(aw[w]), Half<T>::lo(bw[w]));
+            h[2 * w + 1] = silu_mul(Half<T>::hi(aw[w]), Half<T>::hi(bw[w]));
+            amax = fmaxf(amax, fmaxf(fabsf(h[2 * w]), fabsf(h[2 * w + 1])));
+        }
+    };
+    auto store = [&](int c, const float (&h)[16], float inv) {
+        uint32_t w[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            int p = __builtin_amdgcn_cvt_pk_fp8_f32(h[4 * u] * inv, h[4 * u + 1] * inv, 0, false);
+            p = __builtin_amdgcn_cvt_pk_fp8_f32(h[4 * u + 2] * inv, h[4 * u + 3] * inv, p, true);
+            w[u] = (uint32_t)p;
+        }
+        *reinterpret_cast<uint4*>(qrow + (long)c * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+    };
+    float amax = 0.f;
+    float hr[NIT > 0 ? NIT : 1][16];
+    if constexpr (NIT > 0) {
+#pragma unroll
+        for (int i = 0; i < NIT; ++i)
+            if (i * 256 + t < nchunk) chunk(i * 256 + t, hr[i], amax);
+    } else {
+        for (int c = t; c < nchunk; c += 256) chunk(c, hr[0], amax);
+    }
+    amax = wave_max(amax);
+    if ((t & 63) == 0) red[t >> 6] = amax;
+    __syncthreads();
+    const float sc = fp8_pow2_scale(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
+    if (t == 0) scale[row] = sc;
+    const float inv = 1.0f / sc;                                      // exact: power of two
+    if constexpr (NIT > 0) {
+#pragma unroll
+        for (int i = 0; i < NIT; ++i)
+            if (i * 256 + t < nchunk) store(i * 256 + t, hr[i], inv);
+    } else {
+        for (int c = t; c < nchunk; c += 256) { float unused = 0.f; chunk(c, hr[0], unused); store(c, hr[0], inv); }
+    }
 }
 
 // ---- ln_f + pooling + optional L2 normalise, one workgroup (4 waves) per sequence ----
@@ -503,6 +576,27 @@ __global__ __launch_bounds__(256) void fp8_quant_rows_kernel(const float* __rest
     for (long c = lane; c < cols; c += 64) q[row * cols + c] = (uint8_t)e4m3fn_encode(wr[c] * inv);
 }
 
+// the same from bf16 rows (sgpt_model_set_projections: the loader has dropped the fp32 source): same scale rule, same RNE codes -- the
+// codes of fp8_quant_rows_kernel on the bf16 values widened to fp32.  cols % 2 == 0: two columns per lane and step.
+__global__ __launch_bounds__(256) void fp8_quant_rows_bf16_kernel(const uint32_t* __restrict__ w2, long rows, long cols,
+                                                                  uint8_t* __restrict__ q, float* __restrict__ scale) {
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const long c2 = cols / 2;
+    const uint32_t* wr = w2 + row * c2;
+    float amax = 0.f;
+    for (long c = lane; c < c2; c += 64) { const uint32_t u = wr[c]; amax = fmaxf(amax, fmaxf(fabsf(Half<bf16_t>::lo(u)), fabsf(Half<bf16_t>::hi(u)))); }
+    const float sc = fp8_pow2_scale(wave_max(amax));
+    if (lane == 0) scale[row] = sc;
+    const float inv = 1.0f / sc;                                      // exact: power of two
+    uint16_t* qr = reinterpret_cast<uint16_t*>(q + row * cols);
+    for (long c = lane; c < c2; c += 64) {
+        const uint32_t u = wr[c];
+        qr[c] = (uint16_t)(e4m3fn_encode(Half<bf16_t>::lo(u) * inv) | (e4m3fn_encode(Half<bf16_t>::hi(u) * inv) << 8));
+    }
+}
+
 // Sign bits of the rows x - center (center null: x), packed in the order of numpy.packbits: dimension i is bit 7 - i % 8 of byte i / 8,
 // set exactly when the element is > 0 (NaN, +0, -0: clear); bits d .. 8 ldb - 1 are zero.  One thread per output byte.  The test is
 // taken on the bit pattern (0 < bits <= +inf's), so a subnormal element counts as positive whatever the denormal mode of the compare.
@@ -812,6 +906,26 @@ void launch_layernorm_q8(const float* x, const float* g, const float* b, void* q
     for_row_width(d, [&](auto nv) {
         hipLaunchKernelGGL(layernorm_q8_kernel<decltype(nv)::value>, row_grid(T), dim3(256), 0, s, x, g, b, (uint8_t*)q, scale, T, d, eps);
     });
+}
+
+void launch_rmsnorm_q8(const float* x, const float* g, void* q, float* scale, int T, int d, float eps, hipStream_t s) {
+    for_row_width(d, [&](auto nv) {
+        hipLaunchKernelGGL(rmsnorm_q8_kernel<decltype(nv)::value>, row_grid(T), dim3(256), 0, s, x, g, (uint8_t*)q, scale, T, d, eps);
+    });
+}
+
+// ffn % 16 == 0; the register steps of a row: 1, 2, 4 or 7 x 4096 columns, beyond that the re-reading variant
+void launch_swiglu_q8(const void* gu, int dtype, void* q, float* scale, int T, int ffn, hipStream_t s) {
+    for_dtype16(dtype, [&](auto e) {
+        using E = decltype(e);
+        const auto kernel = ffn <= 4096 ? swiglu_q8_kernel<E, 1> : ffn <= 8192 ? swiglu_q8_kernel<E, 2> : ffn <= 16384 ? swiglu_q8_kernel<E, 4>
+                          : ffn <= 28672 ? swiglu_q8_kernel<E, 7> : swiglu_q8_kernel<E, 0>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)T), dim3(256), 0, s, (const E*)gu, (uint8_t*)q, scale, ffn);
+    });
+}
+
+void launch_fp8_quant_rows_bf16(const void* w, long rows, long cols, void* q, float* scale, hipStream_t s) {
+    hipLaunchKernelGGL(fp8_quant_rows_bf16_kernel, row_grid(rows), dim3(256), 0, s, (const uint32_t*)w, rows, cols, (uint8_t*)q, scale);
 }
 
 void launch_absmax16(const void* in, long numel, int dtype, unsigned* out_bits, hipStream_t s) {

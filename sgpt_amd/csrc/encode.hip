@@ -26,6 +26,9 @@ struct Fwd {
     void *a, *ctx, *qkv, *vt, *h;
     void* gu;             // SGPT_ARCH_LLAMA: fc1 output [T][2 ffn] = gate | up columns, the input of the SwiGLU row kernel
     void* a8; float* sa;  // fp8-MFMA block: LayerNorm output as e4m3 codes + one scale per row
+    // q8: a converted SGPT_ARCH_LLAMA model (sgpt_model_set_projections: block_llama_q8) -- a8 / sa hold the RMSNorm output, h the SwiGLU
+    // output as e4m3 codes [T][ffn] with sh, one scale per row
+    bool q8; float* sh;
     long att_lo;
     long ldvt;            // row length of V^T: the token rows of the CALL
     // One of the two chains of a call (chain_of): the chain owns rows [row0, row0 + T) = sequences [b0, b0 + B) of the call's buffers.
@@ -174,6 +177,35 @@ sgpt_status block_llama16(const Fwd& f, const LayerW& l, int) {
     gemm(f.c, dt, EPI_STORE, dt, proj(f, f.a, dm, l.w_fc, 2 * ffn, dm, f.gu, 2 * ffn, nullptr), f.s);
     launch_swiglu(f.gu, f.h, dt, T, ffn, f.range_flag, f.s);
     gemm(f.c, dt, EPI_BIAS_RESID, SGPT_F32, proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x), f.s);
+    return SGPT_OK;
+}
+
+// fp8 projections (sgpt_model_set_projections(1); SGPT_BF16 models, T % 256 == 0): no calibration -- every A operand carries one dynamic
+// power-of-two scale per token row, written by the row kernel in front of the projection, every weight one per output channel:
+//   a8, sa = e4m3(RMS1(x)) ; q | k = bf16((a8 . Wqk8^T) sa s_w (+ b)) ; V^T alike ; rope, attention, out-projection + residual as block_llama16
+//   (w_o is 16-bit: the context has no row scale) ; a8, sa = e4m3(RMS2(x)) ; gu = bf16((a8 . Wgu8^T) sa s_w) ; h8, sh = e4m3(silu(gate) * up) ;
+//   x += (h8 . Wdown8^T) sh s_w
+// `a` is written by no norm on this path: it holds the context alone (zero_overread).
+sgpt_status block_llama_q8(const Fwd& f, const LayerW& l, int) {
+    const sgpt_model_desc& d = f.m->d;
+    const int dm = d.d_model, ffn = d.d_ffn, T = f.T, dt = f.dt, dq = f.d_q, dh = dq / d.n_heads, dkv = f.d_kv;
+    auto launch = [&](int epi, int out_dtype, GemmArgs q, const float* a_scale, const float* w_scale) {
+        Prof pr(f.c, f.s, 2.0 * T * (double)q.N * q.K);
+        q.a_scale = a_scale; q.a_scalar = 1.0f; q.w_scale = w_scale;
+        q.cu_cap = f.c->cu_cap;                        // per-ctx workgroup cap, as gemm() sets it for the 16-bit launches
+        launch_gemm_fp8(epi, out_dtype, q, f.s);
+    };
+    launch_rmsnorm_q8(f.x, l.ln1_g, f.a8, f.sa, T, dm, d.ln_eps, f.s);
+    launch(EPI_STORE, dt, proj(f, f.a8, dm, l.w_qkv, dq + dkv, dm, f.qkv, dq + dkv, l.b_qkv), f.sa, l.s_qkv);
+    launch(EPI_VT, dt, proj(f, f.a8, dm, (const uint8_t*)l.w_qkv + (size_t)(dq + dkv) * dm, dkv, dm, f.vt, f.ldvt, l.b_qkv ? l.b_qkv + dq + dkv : nullptr),
+           f.sa, l.s_qkv + dq + dkv);
+    rope_llama(f, l, dt, dq + dkv, dh);
+    launch_attn_bf16(attn_llama(f, l), f.s);
+    gemm(f.c, dt, EPI_BIAS_RESID, SGPT_F32, proj(f, f.ctx, dq, l.w_o, dm, dq, f.x, dm, l.b_o, f.x), f.s);
+    launch_rmsnorm_q8(f.x, l.ln2_g, f.a8, f.sa, T, dm, d.ln_eps, f.s);
+    launch(EPI_STORE, dt, proj(f, f.a8, dm, l.w_fc, 2 * ffn, dm, f.gu, 2 * ffn, nullptr), f.sa, l.s_fc);
+    launch_swiglu_q8(f.gu, dt, f.h, f.sh, T, ffn, f.s);
+    launch(EPI_BIAS_RESID, 0, proj(f, f.h, ffn, l.w_proj, dm, ffn, f.x, dm, l.b_proj, f.x), f.sh, l.s_proj);
     return SGPT_OK;
 }
 
@@ -331,7 +363,7 @@ using BlockFn = sgpt_status (*)(const Fwd&, const LayerW&, int);
 BlockFn pick_block(const Fwd& f) {
     const bool bf = f.dt != SGPT_F32;
     if (f.m->d.arch == SGPT_ARCH_BERT) return bf ? block_bert16 : block_bert_f32;
-    if (f.m->d.arch == SGPT_ARCH_LLAMA) return bf ? block_llama16 : block_llama_f32;
+    if (f.m->d.arch == SGPT_ARCH_LLAMA) return f.q8 ? block_llama_q8 : (bf ? block_llama16 : block_llama_f32);
     return f.mlp8 ? block_fp8 : (bf ? block_16 : block_f32);
 }
 
@@ -395,6 +427,12 @@ sgpt_status plan(Fwd& f, int n_layers_run, float** lp) {
         for (int li = 0; li < n_layers_run; ++li)
             if (!(m->act_scale[li] > 0.f) || !(m->act_scale[m->d.n_layers + li] > 0.f))
                 return fail(c, SGPT_ERR_INVALID, "SGPT_FP8M: activation scales are not set (sgpt_model_calibrate_begin / _end, or sgpt_model_set_act_scales)");
+    // fp8 projections of a converted Llama-family model: the 16-bit weights are gone, so a layout the fp8 MFMA kernel does not take is
+    // refused, not served another way
+    if (m->proj8 < 0) return fail(c, SGPT_ERR_INVALID, "sgpt_encode: sgpt_model_set_projections failed part of the way on this model; load it again");
+    f.q8 = m->proj8 == 1;
+    if (f.q8 && T % 256 != 0)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_encode: a model with fp8 projections takes layouts of T_pad % 256 == 0 token rows (T_pad = " + std::to_string(T) + ")");
     // Query-sized batches (round 6; qgemm.hip): at most QGEMM_MAX_ROWS token rows, plain 16-bit operands, no probe / calibration
     // pass riding on the forward.  Every projection takes the register-staged deep-prefetch kernel; at d = 512 / 768 / 1024 the two
     // LayerNorms of a sequential block (GPT-Neo, BLOOM) run inside the prologues of the projections they feed: five launches per block
@@ -416,10 +454,12 @@ sgpt_status plan(Fwd& f, int n_layers_run, float** lp) {
     if (bf && ((size_t)T + 256) * (dq + dkv) > qkv_elems) qkv_elems = ((size_t)T + 256) * (dq + dkv);
     const size_t qkv_bytes = qkv_elems * esz;
     const size_t o_qkv = carve(qkv_bytes * (f.any_att ? 2 : 1));         // 16-bit: q | k rows + V^T (x3 attention: the lo halves behind); fp32: q | k | v rows
-    const size_t o_h = carve((size_t)T * ffn * esz * (f.any_h ? 3 : 1));                   // MLP hidden (FP8M: e4m3 codes in the same region)
+    // MLP hidden (FP8M: e4m3 codes in the same region; fp8 projections: codes alone, the 16-bit h is never written)
+    const size_t o_h = carve(f.q8 ? (size_t)T * ffn : (size_t)T * ffn * esz * (f.any_h ? 3 : 1));
     const size_t o_gu = f.F->swiglu ? carve((size_t)T * 2 * ffn * esz) : 0;                     // SGPT_ARCH_LLAMA: fc1 output, gate | up columns
-    const size_t o_a8 = f.mlp8 ? carve((size_t)T * dm) : 0;              // FP8M: LayerNorm output as e4m3 codes
-    const size_t o_sa = f.mlp8 ? carve((size_t)T * 4) : 0;               //       + one scale per row
+    const size_t o_a8 = (f.mlp8 || f.q8) ? carve((size_t)T * dm) : 0;    // FP8M / fp8 projections: norm output as e4m3 codes
+    const size_t o_sa = (f.mlp8 || f.q8) ? carve((size_t)T * 4) : 0;     //       + one scale per row
+    const size_t o_sh = f.q8 ? carve((size_t)T * 4) : 0;                 // fp8 projections: one scale per row of the SwiGLU codes
     const size_t o_lp = lp ? carve((size_t)(m->d.n_layers + 1) * f.B * dm * 4) : 0;
     sgpt_status st = ensure(c, &c->ws, &c->ws_bytes, off);
     if (st != SGPT_OK) return st;
@@ -428,7 +468,8 @@ sgpt_status plan(Fwd& f, int n_layers_run, float** lp) {
     f.x = (float*)(base + o_x); f.a = base + o_a; f.ctx = base + o_c; f.qkv = base + o_qkv; f.h = base + o_h;
     if (f.F->swiglu) f.gu = base + o_gu;
     f.vt = bf ? (void*)((bf16_t*)f.qkv + ((size_t)T + SLACK) * (dq + dkv)) : nullptr;
-    if (f.mlp8) { f.a8 = base + o_a8; f.sa = (float*)(base + o_sa); }
+    if (f.mlp8 || f.q8) { f.a8 = base + o_a8; f.sa = (float*)(base + o_sa); }
+    if (f.q8) f.sh = (float*)(base + o_sh);
     if (lp) *lp = (float*)(base + o_lp);
     f.att_lo = (long)(qkv_bytes / 2);      // element distance of the lo halves of q | k and of V^T (x3 attention)
     f.ldvt = T;
@@ -451,6 +492,8 @@ sgpt_status zero_overread(const Fwd& f) {
     // (post-LN family in fp32: no LayerNorm ever writes the buffer the context lives in)
     if (f.m->d.arch == SGPT_ARCH_GPTJ || f.mlp8 || f.split || f.qln || (f.F->post_ln && !f.vt))
         HIPC(c, hipMemsetAsync(f.ctx, 0, T * dm * esz * (f.any_ctx ? 3 : 1), f.s));   // (fp8: stale bytes would decode to NaN codes)
+    // (fp8 projections: the norms write a8, so nothing fills the buffer the context [T][d_q] lives in -- its filler rows feed the out-projection)
+    else if (f.q8) HIPC(c, hipMemsetAsync(f.ctx, 0, T * dq * esz, f.s));
     // (a context wider than the norm output it shares the buffer with: the norm fills T * d elements, and the filler rows of the rest
     // feed the out-projection -- stale bytes there would raise the f16 range word from rows that belong to no sequence)
     else if (dq > dm) HIPC(c, hipMemsetAsync(f.ctx, 0, T * dq * esz, f.s));

@@ -28,7 +28,8 @@ struct LayerW {
     float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *b_o, *b_fc, *b_proj;
     float* b_qkv = nullptr;  // BLOOM: [3d] de-interleaved (q | k | v) projection bias; SGPT_ARCH_LLAMA: [d_q + 2 d_kv] when the model has one (Qwen2)
     float *qn_g = nullptr, *kn_g = nullptr;   // SGPT_ARCH_LLAMA: per-head RMSNorm gains of q and k [head_dim] when the model has them (Qwen3)
-    // SGPT_FP8W: w_* hold e4m3fn codes, s_* the per-output-channel power-of-two scales
+    // SGPT_FP8W: w_* hold e4m3fn codes, s_* the per-output-channel power-of-two scales (a converted SGPT_ARCH_LLAMA model,
+    // sgpt_model.proj8: all but w_o / s_o)
     float *s_qkv = nullptr, *s_o = nullptr, *s_fc = nullptr, *s_proj = nullptr;
     int is_local = 0;
 };
@@ -64,6 +65,9 @@ struct sgpt_model {
     unsigned* crest_dev = nullptr;
     bool probing = false;
     bool bidir = false;                // SGPT_ARCH_LLAMA: every query sees every key of its sequence (sgpt_model_set_attention(0))
+    // SGPT_ARCH_LLAMA, SGPT_BF16: 1 once sgpt_model_set_projections(1) has turned w_qkv / w_fc / w_proj of every layer into e4m3fn codes with
+    // s_qkv / s_fc / s_proj (w_o stays 16-bit); the forward then runs block_llama_q8 (encode.hip).  One-way.
+    int proj8 = 0;
     std::vector<void*> allocs;
 };
 

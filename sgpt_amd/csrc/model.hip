@@ -1,5 +1,5 @@
 // C ABI (include/sgpt_hip.h): packed weights (load / free), learnt pooling weights, FP8M calibration, the f16 range guard and
-// the precision plan of a model.
+// the precision plan of a model, the attention mode and the fp8 projections of a Llama-family model.
 // Host-side C++ only -- every device op is one of the hand-written kernels in this directory.
 #include "host.h"
 
@@ -598,6 +598,75 @@ sgpt_status sgpt_model_release_split_weights(sgpt_model* m, int64_t* bytes_freed
     m->split_all = false;
     c->generation++;
     if (bytes_freed) *bytes_freed = freed;
+    return SGPT_OK;
+}
+
+// The arithmetic of a loaded Llama-family model's projections (not a descriptor field, not a compute dtype: sgpt_model_set_attention is
+// the model for this).  kind 1: layer by layer, the bf16 rows of w_qkv, w_fc and w_proj become e4m3fn codes + one power-of-two scale per
+// output row (the rule and the RNE codes of sgpt_fp8_quantize_rows on the bf16 values), and the 16-bit allocation goes back to the
+// device as its layer is done -- the peak is one layer's codes on top of the model.  w_o stays 16-bit: its operand, the attention
+// context, has no per-row scale.  The block functions read m->proj8 (encode.hip: pick_block).
+sgpt_status sgpt_model_set_projections(sgpt_model* m, int32_t kind, int64_t* bytes_freed) {
+    if (!m) return SGPT_ERR_INVALID;
+    sgpt_ctx* c = m->ctx;
+    if (bytes_freed) *bytes_freed = 0;
+    const sgpt_model_desc& d = m->d;
+    const char* who = "sgpt_model_set_projections: ";
+    if (d.arch != SGPT_ARCH_LLAMA)
+        return fail(c, SGPT_ERR_INVALID, std::string(who) + "fp8 projections belong to SGPT_ARCH_LLAMA models (" + family(d.arch).name + " has its fp8 compute dtypes or none)");
+    if (d.compute_dtype != SGPT_BF16) return fail(c, SGPT_ERR_INVALID, std::string(who) + "the model must be loaded with SGPT_BF16");
+    const int dh = head_dim(d), dq = d.n_heads * dh, dkv = d.n_kv_heads * dh;
+    const std::pair<const char*, int> widths[] = {{"d_model", d.d_model}, {"d_q + d_kv", dq + dkv}, {"d_kv", dkv}, {"d_ffn", d.d_ffn}};
+    for (const auto& w : widths)
+        if (w.second % 256)
+            return fail(c, SGPT_ERR_INVALID, std::string(who) + w.first + " = " + std::to_string(w.second) + " is not a multiple of 256 (the fp8 MFMA kernel's tile)");
+    if (kind != 0 && kind != 1) return fail(c, SGPT_ERR_INVALID, std::string(who) + "kind 0 (16-bit) | 1 (fp8)");
+    if (kind == 0 && m->proj8 != 0) return fail(c, SGPT_ERR_INVALID, std::string(who) + "the conversion is one-way: the 16-bit weights are gone (load the model again)");
+    if (kind == 1 && m->proj8 != 0) return fail(c, SGPT_ERR_INVALID, std::string(who) + "the model is converted already");
+    if (kind == 0) return SGPT_OK;
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipDeviceSynchronize());      // an in-flight encode still reads the 16-bit weights
+    int64_t freed = 0;
+    bool oom = false;
+    // one matrix [rows, cols]: codes + scales allocated, quantised from the bf16 rows, the pointers swapped; the old allocation is `old`
+    auto convert = [&](void*& w, float*& sc, size_t rows, size_t cols, void*& old) {
+        void* q = nullptr; float* s = nullptr;
+        if (hipMalloc(&q, rows * cols) != hipSuccess || hipMalloc((void**)&s, rows * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            if (q) (void)hipFree(q);
+            oom = true;
+            return;
+        }
+        m->allocs.push_back(q); m->allocs.push_back(s);
+        launch_fp8_quant_rows_bf16(w, (long)rows, (long)cols, q, s, 0);
+        old = w; w = q; sc = s;
+        freed += (int64_t)(rows * cols * 2) - (int64_t)(rows * cols + rows * 4);
+    };
+    m->proj8 = -1;                        // (until every layer is done: a model converted in part encodes nothing, plan() refuses it)
+    c->generation++;                      // captured graphs carry the 16-bit launches and pointers
+    for (LayerW& l : m->L) {
+        void* old[3] = {nullptr, nullptr, nullptr};
+        convert(l.w_qkv, l.s_qkv, (size_t)dq + 2 * dkv, d.d_model, old[0]);
+        if (!oom) convert(l.w_fc, l.s_fc, (size_t)2 * d.d_ffn, d.d_model, old[1]);
+        if (!oom) convert(l.w_proj, l.s_proj, d.d_model, d.d_ffn, old[2]);
+        HIPC(c, hipDeviceSynchronize());  // the quantiser has read the rows that go back now
+        for (void* p : old) {
+            if (!p) continue;
+            for (size_t i = 0; i < m->allocs.size(); ++i)
+                if (m->allocs[i] == p) { m->allocs[i] = m->allocs.back(); m->allocs.pop_back(); break; }
+            (void)hipFree(p);
+        }
+        if (oom) return fail(c, SGPT_ERR_OOM, std::string(who) + "hipMalloc failed part of the way: the model is unusable, free it and load it again");
+    }
+    HIPC(c, hipGetLastError());
+    m->proj8 = 1;
+    if (bytes_freed) *bytes_freed = freed;
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_model_get_projections(sgpt_model* m, int32_t* kind) {
+    if (!m || !kind) return m ? fail(m->ctx, SGPT_ERR_INVALID, "sgpt_model_get_projections: kind is NULL") : SGPT_ERR_INVALID;
+    *kind = m->proj8 == 1 ? 1 : 0;
     return SGPT_OK;
 }
 

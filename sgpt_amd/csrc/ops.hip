@@ -409,6 +409,31 @@ sgpt_status sgpt_swiglu(sgpt_ctx* c, const void* gu, int32_t dtype, int32_t T, i
     return SGPT_OK;
 }
 
+sgpt_status sgpt_rmsnorm_fp8(sgpt_ctx* c, const float* x, const float* gamma, int32_t T, int32_t d, float eps, uint8_t* codes,
+                             float* row_scale, void* stream) {
+    if (!c || !x || !gamma || !codes || !row_scale || T <= 0 || !row_width_ok(d) || !(eps >= 0.f) || !std::isfinite(eps))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_rmsnorm_fp8: bad arguments (d % 4 == 0, d <= 4096)");
+    if (mis(x, 16) || mis(gamma, 16) || mis(codes, 4) || mis(row_scale, 4))
+        return fail(c, SGPT_ERR_INVALID, "sgpt_rmsnorm_fp8: 16-byte aligned x / gamma, 4-byte aligned codes / row_scale");
+    HIPC(c, hipSetDevice(c->device));
+    launch_rmsnorm_q8(x, gamma, codes, row_scale, T, d, eps, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
+sgpt_status sgpt_swiglu_fp8(sgpt_ctx* c, const void* gu, int32_t dtype, int32_t T, int32_t ffn, uint8_t* codes, float* row_scale,
+                            void* stream) {
+    if (!c || !gu || !codes || !row_scale || T <= 0 || ffn <= 0) return fail(c, SGPT_ERR_INVALID, "sgpt_swiglu_fp8: bad arguments");
+    if (dtype != SGPT_BF16 && dtype != SGPT_F16) return fail(c, SGPT_ERR_INVALID, "sgpt_swiglu_fp8: dtype SGPT_BF16 | SGPT_F16");
+    // a thread moves 16 columns of a row per step: two 16-byte words of the gate half, two of the up half, one of codes
+    if (ffn % 16 || mis(gu, 16) || mis(codes, 16) || mis(row_scale, 4) || gu == (const void*)codes)
+        return fail(c, SGPT_ERR_INVALID, "sgpt_swiglu_fp8: ffn % 16; 16-byte aligned gu / codes; codes is a buffer of its own");
+    HIPC(c, hipSetDevice(c->device));
+    launch_swiglu_q8(gu, dtype, codes, row_scale, T, ffn, (hipStream_t)stream);
+    HIPC(c, hipGetLastError());
+    return SGPT_OK;
+}
+
 static sgpt_status lnf_pool_impl(sgpt_ctx* c, const float* x, const float* gamma, const float* beta, const int32_t* seq_off,
                                  const int32_t* seq_len, const int32_t* pad_left, int32_t B, int32_t d, float eps, int32_t apply_ln,
                                  int32_t mode, int32_t normalize, const float* pos_weights, int32_t n_weights, float* out,

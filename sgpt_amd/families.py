@@ -274,6 +274,7 @@ class Family:
     # include/sgpt_hip.h: the Llama family alone -- the bidirectional embedders built on its backbones)
     native_attention: str = "causal"
     attention_switch: bool = False
+    fp8_projections: bool = False         # SGPTModel(projections='fp8'): calibration-free fp8 projections, set after load (sgpt_model_set_projections)
     # tokenizer
     framing: str = "brackets"             # "brackets" (specb / speca allowed, nothing added) | "cls_sep" | "bos_eos"
 
@@ -290,7 +291,7 @@ FAMILIES = (
     Family("llama", ("llama", "mistral", "qwen2", "qwen3"), _lib.SGPT_ARCH_LLAMA, "Llama / Mistral", _parse_llama, rotary_dim="head_dim", grouped_kv=True,
            prepare_weights=lambda c, w: dict(llama_state_dict(w), **dict(zip(_ROTARY, rotary_tables_half(
                table_rows(c), head_dim(c), c.rope_theta)))),
-           sgpt_modes=False, attention_switch=True, framing="bos_eos", dtype_advice="'bf16', 'f16' or 'fp32'",
+           sgpt_modes=False, attention_switch=True, fp8_projections=True, framing="bos_eos", dtype_advice="'bf16', 'f16' or 'fp32'",
            no_lm_head="lm_logprobs is not built for Llama / Mistral models (their LM head is not loaded)"),
 )
 FRAMED = {"cls_sep": "is framed [CLS] ... [SEP]", "bos_eos": "takes its tokenizer's BOS / EOS"}   # Family.framing, as a refusal of the brackets puts it
@@ -320,6 +321,32 @@ def check_attention(cfg: SGPTConfig, attention: str) -> str:
                          "only a window the config parser folded away (at least min(max_position_embeddings, "
                          f"{WINDOW_FOLD}) tokens) runs bidirectionally")
     return attention
+
+
+PROJECTION_MODES = (None, "fp8")
+PROJECTION_TILE = 256          # the fp8 MFMA kernel's tile: every projection width of a converted model is a multiple of it
+
+
+def check_projections(cfg: SGPTConfig, dtype: str, projections: Optional[str]) -> Optional[str]:
+    """SGPTModel's projections= argument, or its refusal: 'fp8' (sgpt_model_set_projections) is the Llama family's, on a 'bf16' model
+    whose projection widths are multiples of 256."""
+    fam = family(cfg.model_type)
+    if projections not in PROJECTION_MODES:
+        raise ValueError(f"projections must be None or 'fp8', not {projections!r}")
+    if projections is None:
+        return None
+    if not fam.fp8_projections:
+        raise ValueError(f"projections='fp8' is a mode of the Llama / Mistral / Qwen family: a {fam.name} model has "
+                         + ("dtype 'fp8' / 'fp8mfma'" if fam.sgpt_modes else "no fp8 mode"))
+    if dtype != "bf16":
+        raise ValueError(f"projections='fp8' converts a dtype='bf16' model, not dtype={dtype!r}")
+    dh = head_dim(cfg)
+    widths = (("hidden_size", cfg.hidden_size), ("num_heads * head_dim", cfg.num_heads * dh),
+              ("num_kv_heads * head_dim", cfg.num_kv_heads * dh), ("intermediate_size", cfg.intermediate_size))
+    for name, w in widths:
+        if w % PROJECTION_TILE:
+            raise ValueError(f"projections='fp8' needs {name} to be a multiple of {PROJECTION_TILE}: this model has {name} = {w}")
+    return projections
 
 
 def attention_from_hf_dict(c: dict, attention: Optional[str] = None) -> str:

@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from ._lib import (ModelDesc, TensorView, POOL_MODES, SGPT_BF16, SGPT_F16, SGPT_F32, SGPT_FP8M, SGPT_FP8W, SgptRangeError,
                    SGPT_PREC_CLASSES, PC_LN1, PC_ATT, PC_CTX, PC_LN2, PC_H)
-from .families import (MAX_SEQ_LEN, SGPTConfig, attention_from_hf_dict, check_attention, alibi_slopes, bert_state_dict, family, head_dim, llama_state_dict, rotary_tables,  # noqa: F401
+from .families import (MAX_SEQ_LEN, SGPTConfig, attention_from_hf_dict, check_attention, check_projections, alibi_slopes, bert_state_dict, family, head_dim, llama_state_dict, rotary_tables,  # noqa: F401
                        rotary_tables_half, table_rows, synthetic_bert_weights, synthetic_llama_weights, synthetic_qwen_weights, synthetic_weights)
 from .runtime import Context, get_context, _p, _stream_ptr
 
@@ -318,8 +318,14 @@ class SGPTModel:
 
     def __init__(self, cfg: SGPTConfig, weights: Dict[str, "np.ndarray | torch.Tensor"], device=None,
                  dtype: str = "f16", ctx: Optional[Context] = None, max_tokens_per_call: int = 131072,
-                 calibrate: bool = True, precise_qk=None, precision: Optional[str] = None, attention: str = "causal"):
-        """attention: 'causal' (default) | 'bidirectional' -- Llama / Mistral / Qwen models only, set after load
+                 calibrate: bool = True, precise_qk=None, precision: Optional[str] = None, attention: str = "causal",
+                 projections: Optional[str] = None):
+        """projections: None (default) | 'fp8' -- Llama / Mistral / Qwen models of dtype 'bf16' only, set after load
+        (sgpt_model_set_projections): the Q | K | V, gate | up and down projections run on the e4m3 MFMA with one dynamic power-of-two
+        scale per token row and one per weight row -- no calibration pass -- and their weights take half the bytes; the out-projection
+        stays bf16.  hidden_size, num_heads * head_dim, num_kv_heads * head_dim and intermediate_size must be multiples of 256; layouts
+        are padded to 256 token rows.  One-way; refused for EncodeGraph.  Quality and speed as measured: README.
+        attention: 'causal' (default) | 'bidirectional' -- Llama / Mistral / Qwen models only, set after load
         (sgpt_model_set_attention): in every layer every token sees every token of its sequence, what GritLM, gte-Qwen2-instruct and the
         LLM2Vec checkpoints were trained with.  Refused for the other families and over an applied (unfolded) sliding window.
         precision (dtype 'f16' / 'bf16'): how operands enter the MFMAs (include/sgpt_hip.h::sgpt_model_set_precision).
@@ -348,11 +354,12 @@ class SGPTModel:
         well); 'attn' (the whole attention sub-block: Q / K / V projection, attention, out-projection)."""
         dtype, precise_qk, precision = check_args(cfg, dtype, precise_qk, precision)
         attention = check_attention(cfg, attention)
+        projections = check_projections(cfg, dtype, projections)
         self.cfg = cfg
         self.ctx = ctx or get_context(device)
         self.device = self.ctx.device
         self.dtype = dtype
-        self.row_tile = TOKEN_TILE if dtype == "fp8mfma" else None      # pack(): rows per layout tile (pad_rows)
+        self.row_tile = TOKEN_TILE if (dtype == "fp8mfma" or projections == "fp8") else None      # pack(): rows per layout tile (pad_rows)
         # token rows per sgpt_encode call: 131 072 = 6 / 12 / 24 full rounds of 256x256 tiles on 256 CUs for the 125M
         # projections (measured: 1000 TFLOP/s there, 864-890 at 49 k rows, 754 at 25 k); activations ~2.5 GB (125M) to
         # ~13 GB (bloom-7b1) of the 288 GB
@@ -372,6 +379,11 @@ class SGPTModel:
         self._attention = family(cfg.model_type).native_attention     # (a family without the switch runs its own mode whatever the default says)
         if family(cfg.model_type).attention_switch and attention != self._attention:
             self.set_attention(attention)
+        self._projections, self.projection_bytes_freed = None, 0
+        if projections == "fp8":
+            freed = C.c_int64(0)
+            self._call("set_projections", 1, C.byref(freed))
+            self._projections, self.projection_bytes_freed = "fp8", int(freed.value)
         self._staging = _Staging(self.device)
         self.act_scales = None
         if dtype == "fp8mfma" and calibrate:
@@ -399,6 +411,11 @@ class SGPTModel:
     def attention(self) -> str:
         """'causal' | 'bidirectional': what every layer's attention shows a token."""
         return self._attention
+
+    @property
+    def projections(self) -> Optional[str]:
+        """None | 'fp8': the arithmetic of the Q | K | V, gate | up and down projections (SGPTModel(projections=))."""
+        return self._projections
 
     def set_attention(self, attention: str) -> None:
         """Switch a Llama-family model between causal and bidirectional attention (the library refuses the other families)."""
@@ -602,7 +619,7 @@ class SGPTModel:
 
     # ---- loading real checkpoints (HF folder / sentence-transformers folder layout) ----
     @classmethod
-    def from_pretrained(cls, path: str, attention: Optional[str] = None, **kw) -> "SGPTModel":
+    def from_pretrained(cls, path: str, attention: Optional[str] = None, projections: Optional[str] = None, **kw) -> "SGPTModel":
         """Reads config.json + model.safetensors / pytorch_model.bin of an SGPT checkpoint folder
         (AutoModel.from_pretrained at beir_dense_retriever.py:123; ST folder layout
         SentenceTransformer.py:903-936 keeps the transformer either at the root or in 0_Transformer/).
@@ -613,7 +630,7 @@ class SGPTModel:
         with open(os.path.join(root, "config.json")) as f:
             raw = json.load(f)
         cfg = SGPTConfig.from_hf_dict(raw)
-        model = cls(cfg, load_state_dict(root), attention=attention_from_hf_dict(raw, attention), **kw)
+        model = cls(cfg, load_state_dict(root), attention=attention_from_hf_dict(raw, attention), projections=projections, **kw)
         wmp = os.path.join(path, "1_WeightedMeanPooling", "pytorch_model.bin")
         if os.path.exists(wmp):
             model.set_position_weights(torch.load(wmp, map_location="cpu", weights_only=True)["position_weights"])
@@ -981,6 +998,8 @@ class EncodeGraph:
         # (out of scope, refused loudly: a captured graph of the bidirectional mode or of a ranged pool has not been built or tested)
         if family(model.cfg.model_type).attention_switch and getattr(model, "attention", "causal") != "causal":
             raise ValueError("EncodeGraph: a model with attention='bidirectional' is not captured (encode it eagerly: encode_ids / encode_packed)")
+        if getattr(model, "projections", None) is not None:
+            raise ValueError("EncodeGraph: a model with projections='fp8' is not captured (encode it eagerly: encode_ids / encode_packed)")
         if pool_from is not None:
             raise ValueError("EncodeGraph: pool_from is not captured (encode eagerly: encode_ids(pool_from=) / pack(pool_from=))")
         self.model, self.mode, self.normalize, self.layer_idx = model, mode, normalize, layer_idx

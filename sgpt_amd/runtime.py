@@ -584,6 +584,30 @@ class Context(CorpusBuilders):
                                               _stream_ptr(self.device)), "sgpt_layernorm_fp8")
         return codes, scale
 
+    # ---- the quantising row kernels of the fp8 projections of the Llama family (SGPTModel(projections='fp8')) ----
+    def rmsnorm_fp8(self, x: torch.Tensor, gamma: torch.Tensor, eps: float = 1e-6):
+        """RMSNorm rows of x fp32 [T, d] -> (e4m3fn codes uint8 [T, d], power-of-two scale fp32 [T]); value = code * scale
+        (include/sgpt_hip.h::sgpt_rmsnorm_fp8)."""
+        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        T, d = x.shape
+        codes = torch.empty((T, d), dtype=torch.uint8, device=self.device)
+        scale = torch.empty((T,), dtype=torch.float32, device=self.device)
+        self._chk(self.lib.sgpt_rmsnorm_fp8(self.handle, _p(x), _p(self._f32c(gamma)), T, d, float(eps), _p(codes), _p(scale),
+                                            _stream_ptr(self.device)), "sgpt_rmsnorm_fp8")
+        return codes, scale
+
+    def swiglu_fp8(self, gu: torch.Tensor):
+        """silu(gu[:, :ffn]) * gu[:, ffn:] of gu [T, 2 ffn] (bf16 or f16, contiguous), in fp32, -> (e4m3fn codes uint8 [T, ffn],
+        power-of-two scale fp32 [T]) (include/sgpt_hip.h::sgpt_swiglu_fp8)."""
+        if gu.dtype not in (torch.bfloat16, torch.float16) or not gu.is_contiguous() or gu.shape[1] % 2:
+            raise ValueError("swiglu_fp8: gu is a contiguous bf16 / f16 [T, 2 ffn] tensor")
+        T, ffn = gu.shape[0], gu.shape[1] // 2
+        codes = torch.empty((T, ffn), dtype=torch.uint8, device=self.device)
+        scale = torch.empty((T,), dtype=torch.float32, device=self.device)
+        self._chk(self.lib.sgpt_swiglu_fp8(self.handle, _p(gu), DT_CODE[gu.dtype], T, ffn, _p(codes), _p(scale),
+                                           _stream_ptr(self.device)), "sgpt_swiglu_fp8")
+        return codes, scale
+
     def linear_fp8(self, a8: torch.Tensor, w8: torch.Tensor, w_scale: torch.Tensor, bias: torch.Tensor, epi: str,
                    a_scale: Optional[torch.Tensor] = None, a_scalar: float = 1.0, resid: Optional[torch.Tensor] = None,
                    out_scale: float = 1.0, out_dtype=None) -> torch.Tensor:
