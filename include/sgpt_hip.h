@@ -323,7 +323,22 @@ sgpt_status sgpt_model_set_pool_weights(sgpt_model* model, const float* weights,
  * fp32 [T_pad, d_model]); row_idx[i] = the token row whose next-token distribution is asked for, targets[i] the
  * token id to score.  The LM head is the embedding matrix (GPT-Neo, BLOOM: tied) or "lm_head.weight" /
  * "lm_head.bias" when those tensors were passed to sgpt_model_load (GPT-J).  Logits are computed in exact-fp32 MFMA.
- *   out_logprob device fp32[n]; out_greedy device int32[n] (argmax token, first maximum) or NULL. */
+ *   out_logprob device fp32[n]; out_greedy device int32[n] (argmax token, first maximum) or NULL.
+ * Contract (the entry has no row count of `hidden` and cannot check the first point):
+ *   - every row_idx[i] must lie in [0, T_pad): the gather reads row row_idx[i] of `hidden` and does NOT clamp -- an index outside
+ *     the allocation is an out-of-bounds read (SGPTModel.lm_logprobs checks the indices on the host before it uploads them);
+ *     targets[i] outside [0, vocab) is clamped to the nearest valid id (a bad target scores a wrong token);
+ *   - d_model % 4 == 0 (sgpt_model_load guarantees % 128) and `hidden` 16-byte aligned with row stride d_model: rows are
+ *     copied in 16-byte pieces;
+ *   - the n rows are processed in chunks of 1024: per chunk a gather into a staging buffer, the fp32 GEMM [rows, vocab] with
+ *     leading dimension roundup(vocab, 4) (+ bias), and the log-softmax.  Staging buffer and logits chunk live in the context's
+ *     scorer workspace (1024 x roundup(vocab, 4) x 4 bytes: 206 MB at vocab 50 257), which grows on demand (a growth
+ *     synchronises the device) and is reused by every call: calls on one context must be ordered on one stream, and the pad
+ *     columns [vocab, roundup(vocab, 4)) of the logits are never written nor read.  The call overwrites what the last score +
+ *     top-k pass left in that workspace: sgpt_score_overflow_count no longer describes that pass afterwards;
+ *   - a row's result does not depend on n, on the row's position in its chunk or on the order of row_idx (every tile of the
+ *     fp32 GEMM sums k ascending; the opt-in low-latency mode of a context, sgpt_ctx_set_low_latency, gives this up).
+ * SGPT_ERR_INVALID (nothing launched): null model / hidden / row_idx / targets / out_logprob, n <= 0, a family without LM head. */
 sgpt_status sgpt_lm_logprobs(sgpt_model* model, const float* hidden, const int32_t* row_idx, const int32_t* targets,
                              int32_t n, float* out_logprob, int32_t* out_greedy, void* stream);
 

@@ -740,11 +740,26 @@ class SGPTModel:
 
     def lm_logprobs(self, hidden: torch.Tensor, row_idx, targets, return_greedy: bool = False):
         """log P(targets[i] | prefix ending at token row row_idx[i]) from post-ln_f hidden states [T_pad, d]
-        (the log_softmax + gather of crossencoder/beir/sgptce.py:233-255) -> fp32[n] on the GPU."""
+        (the log_softmax + gather of crossencoder/beir/sgptce.py:233-255) -> fp32[n] on the GPU.
+        The arguments are checked here, on the host, before anything is uploaded: the C entry has no row count of `hidden` and
+        its gather does not clamp (include/sgpt_hip.h::sgpt_lm_logprobs)."""
         if refusal := family(self.cfg.model_type).no_lm_head:
             raise ValueError(refusal)
-        ri = torch.as_tensor(np.asarray(row_idx, dtype=np.int32)).to(self.device)
-        tg = torch.as_tensor(np.asarray(targets, dtype=np.int32)).to(self.device)
+        if not isinstance(hidden, torch.Tensor) or hidden.dtype != torch.float32 or hidden.dim() != 2:
+            raise ValueError("lm_logprobs: hidden must be an fp32 tensor [T_pad, d_model]")
+        if hidden.device != self.device:
+            raise ValueError(f"lm_logprobs: hidden is on {hidden.device}, the model on {self.device}")
+        if hidden.shape[1] != self.cfg.hidden_size:
+            raise ValueError(f"lm_logprobs: hidden has width {hidden.shape[1]}, d_model is {self.cfg.hidden_size}")
+        ri_host, tg_host = np.asarray(row_idx, dtype=np.int64).reshape(-1), np.asarray(targets, dtype=np.int64).reshape(-1)
+        if ri_host.size == 0:
+            raise ValueError("lm_logprobs: row_idx is empty")
+        if tg_host.size != ri_host.size:
+            raise ValueError(f"lm_logprobs: targets has {tg_host.size} entries, row_idx {ri_host.size}")
+        if int(ri_host.min()) < 0 or int(ri_host.max()) >= hidden.shape[0]:
+            raise ValueError(f"lm_logprobs: row_idx outside [0, {hidden.shape[0]}), the rows of hidden")
+        ri = torch.from_numpy(ri_host.astype(np.int32)).to(self.device)
+        tg = torch.from_numpy(tg_host.astype(np.int32)).to(self.device)
         n = int(ri.numel())
         out = torch.empty((n,), dtype=torch.float32, device=self.device)
         greedy = torch.empty((n,), dtype=torch.int32, device=self.device) if return_greedy else None

@@ -261,8 +261,8 @@ def test_learntmean_and_lm_head_refusals(mt):
     assert str(e.value) == (E_LEARNT_NONE if mt in DECODERS else E_LEARNT)
     with pytest.raises(Exception) as e:
         m.lm_logprobs(None, [0], [0])
-    if mt in DECODERS:
-        assert type(e.value) is AttributeError                          # past the refusal: the stand-in has no device
+    if mt in DECODERS:                                                  # past the family's refusal: the argument check answers
+        assert (type(e.value), str(e.value)) == (ValueError, "lm_logprobs: hidden must be an fp32 tensor [T_pad, d_model]")
     else:
         assert (type(e.value), str(e.value)) == (ValueError, E_LM[mt])
 
