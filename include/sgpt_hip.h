@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 25
+#define SGPT_ABI_VERSION 26
 
 /* The longest sequence (ABI v23): the token rows one sequence may own in the packed layout of sgpt_encode*, sgpt_attention_ex and
  * sgpt_attention_gqa (max_alloc_len <= SGPT_MAX_SEQ_LEN; a larger value is SGPT_ERR_INVALID, nothing launched).  32 768 is the
@@ -649,6 +649,75 @@ sgpt_status sgpt_score_topk_bits_u8(sgpt_ctx* ctx, const float* q, const float* 
                                     const uint8_t* codes, const float* start, const float* step, int32_t ld, int32_t nq, int64_t N, int32_t d,
                                     int32_t k, int32_t kp, int64_t idx_base, float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out,
                                     void* stream);
+
+/* IVF corpus (ABI v26; csrc/ivf.hip): an inverted-file index over f16 rows -- spherical k-means cuts the L2-normalised corpus into nlist
+ * lists, a query scores the centroids and scans only its nprobe best lists, with full-precision (f16 row, fp32 accumulate) scores for the
+ * rows it reads.  Cosine only.
+ *   format    centroids16 device f16 [nlist, d] (the f16 rounding of unit fp32 centroids); rows device f16 [N, d] in list-major order: list c
+ *             is rows[offsets[c] .. offsets[c + 1]); ids device int64 [N]: the original row number of every stored row, ascending inside
+ *             every list; offsets device int64 [nlist + 1], offsets[0] = 0, offsets[nlist] = N.
+ *   limits    d % 8 == 0, d <= SGPT_IVF_MAX_DIM, nlist <= SGPT_IVF_MAX_LISTS, N <= SGPT_IVF_MAX_ROWS.
+ *
+ * sgpt_ivf_lists: an assignment -> the lists.  assign device int64 [N] -> perm device int64 [N], the STABLE argsort of assign (rows of a
+ *   list in ascending row number), and offsets device int64 [nlist + 1], the exclusive prefix of the list sizes.  Integer arithmetic only
+ *   (a device sort of the unique keys list << 32 | row): the result is the one exact answer.  An assignment outside [0, nlist) is clamped
+ *   to the nearest end (memory-safe; the row lands in list 0 or nlist - 1).
+ *   SGPT_ERR_INVALID: null pointers, N <= 0 or > SGPT_IVF_MAX_ROWS, nlist <= 0 or > SGPT_IVF_MAX_LISTS.
+ *
+ * sgpt_ivf_centroids: out[c] = the sum of x[perm[p]] over offsets[c] <= p < offsets[c + 1]; with normalize != 0 divided by its L2 norm.
+ *   x         device [n_x, d], x_dtype SGPT_F32 | SGPT_F16 (f16 elements are widened exactly), 16-byte aligned; perm device int64 [n], offsets
+ *             device int64 [nlist + 1] inside [0, n]; prev device fp32 [nlist, d] or NULL; out device fp32 [nlist, d].
+ *   order     fixed by the list alone.  The list is cut into chunks of 256 rows counted from its own first row; a chunk's rows are added in
+ *             ascending order into a partial sum (fp32, one rounding per addition, no fused operation), the list's partials are added in
+ *             chunk order.  A long list is many chunks on many compute units.  No float atomics.  The bits of out[c] do not depend on
+ *             nlist, on where the list sits in perm, or on the launch shape.  normalize: the squared norm is summed columns t, t + 256, ...
+ *             ascending per thread t, the 256 threads in a fixed tree; one IEEE square root, one IEEE division per element.
+ *   fallback  an empty list -- and under normalize a sum whose squared norm is zero or not finite -- gives prev[c] (zeros if prev is NULL).
+ *             A perm entry outside [0, n_x) adds nothing; offsets that are no range inside [0, n] give an empty list.
+ *   SGPT_ERR_INVALID: null pointers (prev may be NULL), another x_dtype, d % 8, d > SGPT_IVF_MAX_DIM, n or n_x <= 0, n > SGPT_IVF_MAX_ROWS,
+ *   nlist <= 0 or > SGPT_IVF_MAX_LISTS, x or out not 16-byte aligned.
+ *
+ * sgpt_gather_rows: out[p] = RNE_f16(x[perm[p]]), p < n: x device [n_x, d] (SGPT_F32 | SGPT_F16), out device f16 [n, d], 16-byte loads and
+ *   stores (d % 8 == 0, both 16-byte aligned).  A perm entry outside [0, n_x) gives a zero row.  SGPT_ERR_INVALID: null pointers, another
+ *   x_dtype, d % 8, n or n_x <= 0, alignment.
+ *
+ * sgpt_ivf_search: the two-stage search.
+ *   q         device fp32 [nq, d], L2-normalised by the caller, 16-byte aligned.
+ *   stage 1   the probe set of a query is sgpt_score_topk(SGPT_F16) of RNE_f16(q) against centroids16 with k = nprobe: the same launches,
+ *             so the same bits and the same order (score descending, ties to the lowest list).  probe_out (device int64 [nq, nprobe] or
+ *             NULL) receives the probe sets.
+ *   stage 2   one work item per (query, probed list, chunk of SGPT_IVF_CHUNK rows of that list); items past a list's end exit at once.  The
+ *             grid comes from max_list (HOST: the longest list), so the call never synchronises; rows of a list beyond max_list are not
+ *             scanned.
+ *   value     sum_j q_j * float(row_j) in fp32: a wavefront walks the row in 16-byte pieces (8 elements), lane l owning pieces l, l + 64, ...;
+ *             per lane four accumulators (one per dword of a piece) take their two products by fma, low half first, pieces ascending;
+ *             s = (a0 + a1) + (a2 + a3); the 64 lanes are added in the xor butterfly 32, 16, .., 1.  The order depends on d alone: the same
+ *             (q, row) pair gives the same bits in any list, position, nq, nprobe or launch shape.  NaN -> -1.
+ *   error     |value - <q, row> in exact arithmetic| <= gamma_n sum_j |q_j row_j|, n = 2 ceil(d / 512) + 8, gamma_n = n u / (1 - n u),
+ *             u = 2^-24: a partial sum passes at most 2 ceil(d / 512) fmas, 2 joining and 6 butterfly additions.
+ *   select    every item keeps its min(k, SGPT_IVF_CHUNK) best by the library order (score descending, then original index ascending --
+ *             ids ascend inside a list); the items' pairs and the running list go through the select kernel of sgpt_topk_merge.
+ *   result    as sgpt_score_topk: rows sorted, tail (-inf, -1), indices ids[...] + idx_base, running list in/out.  *n_out = min(k, n_run + N):
+ *             the host cannot know how many rows were probed, so slots that found no row are (-inf, -1) inside that count.
+ *   shapes    any nq <= 65535 (in groups when the candidate workspace asks for it); speed is claimed for nq <= 64 only: a list probed by
+ *             several queries is streamed once per query.
+ * SGPT_ERR_INVALID (nothing launched, outputs untouched): null pointers (probe_out may be NULL); nq <= 0 or > 65535; N <= 0; d % 8 or
+ * d > SGPT_IVF_MAX_DIM; nlist <= 0 or > SGPT_IVF_MAX_LISTS; max_list < 0 or > N; nprobe <= 0, > nlist or > 1024; k <= 0 or > 1024; n_run < 0 or
+ * > k; q, centroids16 or rows not 16-byte aligned. */
+#define SGPT_IVF_CHUNK 256
+#define SGPT_IVF_MAX_DIM 4096
+#define SGPT_IVF_MAX_LISTS 65536
+#define SGPT_IVF_MAX_ROWS (1 << 30)
+sgpt_status sgpt_ivf_lists(sgpt_ctx* ctx, const int64_t* assign, int64_t N, int32_t nlist, int64_t* offsets, int64_t* perm, void* stream);
+sgpt_status sgpt_ivf_centroids(sgpt_ctx* ctx, const void* x, int32_t x_dtype, int64_t n_x, int32_t d, const int64_t* perm, int64_t n,
+                               const int64_t* offsets, int32_t nlist, const float* prev /* fp32[nlist, d] or NULL */, int32_t normalize,
+                               float* out, void* stream);
+sgpt_status sgpt_gather_rows(sgpt_ctx* ctx, const void* x, int32_t x_dtype, int64_t n_x, const int64_t* perm, int64_t n, int32_t d, void* out,
+                             void* stream);
+sgpt_status sgpt_ivf_search(sgpt_ctx* ctx, const float* q, const void* centroids16, const void* rows, const int64_t* ids,
+                            const int64_t* offsets, int32_t nq, int64_t N, int32_t d, int32_t nlist, int64_t max_list, int32_t nprobe,
+                            int32_t k, int64_t idx_base, float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out,
+                            int64_t* probe_out /* int64[nq, nprobe] or NULL */, void* stream);
 
 /* Diagnostics (ABI v19): of the filtered chunks of the LAST score + top-k pass on this context (sgpt_score_topk, _q8, _u8; _bits: its last
  * query group), how many overflowed their candidate lists and were recomputed by the predicated fallback.  Synchronises `stream`. */

@@ -13,7 +13,7 @@ LIBDIR = os.path.join(HERE, "lib")
 EXPERIMENTS = os.environ.get("SGPT_EXPERIMENTS") == "1"
 LIB = os.path.join(LIBDIR, "libsgpt_hip_exp.so" if EXPERIMENTS else "libsgpt_hip.so")
 SOURCES = ["gemm.hip", "qgemm.hip", "gemm256q.hip", "attn.hip", "elementwise.hip", "topk.hip", "eval.hip", "useb_eval.hip", "comm.hip",
-           "ctx.hip", "model.hip", "encode.hip", "score.hip", "score8.hip", "scoreu8.hip", "scorebits.hip", "ops.hip"]
+           "ctx.hip", "model.hip", "encode.hip", "score.hip", "score8.hip", "scoreu8.hip", "scorebits.hip", "ivf.hip", "ops.hip"]
 # the slower 32x32x16-MFMA re-tiling lives with the measurement scripts (scripts/micro/gemm256w.hip): experiment build only
 EXTRA_SOURCES = [os.path.join(HERE, "..", "scripts", "micro", "gemm256w.hip")] if EXPERIMENTS else []
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

@@ -1,9 +1,11 @@
-"""The corpus kinds a search can run against besides plain rows -- QuantizedCorpus (fp8), Uint8Corpus, BinaryCorpus -- in one place:
+"""The corpus kinds a search can run against besides plain rows -- QuantizedCorpus (fp8), Uint8Corpus, BinaryCorpus, IVFCorpus -- in one place:
 what each holds, what a search over it may ask (`check_search`, device-free), how it is scored (`score_topk`, the C entry of its
 format) and how it is built from embeddings (`CorpusBuilders`, the methods Context inherits).  util.semantic_search and
 Context.score_topk dispatch on CORPUS_KINDS once and know no kind by name.
 `_rt` is sgpt_amd.runtime, looked up at call time: get_context and _stream_ptr are what tests replace to keep a call off the device."""
+import copy
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -253,7 +255,114 @@ class BinaryCorpus:
         return val, idx, int(n_out.value)
 
 
-CORPUS_KINDS = (QuantizedCorpus, Uint8Corpus, BinaryCorpus)
+IVF_CHUNK, IVF_MAX_DIM, IVF_MAX_LISTS = 256, 4096, 65536      # SGPT_IVF_CHUNK, SGPT_IVF_MAX_DIM, SGPT_IVF_MAX_LISTS of include/sgpt_hip.h
+
+
+class IVFCorpus:
+    """A corpus held as inverted lists over spherical k-means centroids (include/sgpt_hip.h::sgpt_ivf_search): `centroids` fp32 [nlist, d]
+    unit rows and `centroids16`, their f16 rounding; `rows` f16 [N, d] in list-major order, list c = rows[offsets[c]:offsets[c + 1]];
+    `ids` int64 [N], the original row number of every stored row, ascending inside every list; `offsets` int64 [nlist + 1]; `max_list`, a
+    host int: the longest list (the launch geometry, so a search never synchronises); `nprobe`: how many lists a query scans.  A search
+    scores the centroids with the f16 scorer and scans the nprobe best lists with fp32 accumulation: cosine only, approximate -- a hit
+    outside the probed lists is missed, and slots that found no row come back as (-inf, -1).  Built by Context.ivf_index /
+    util.build_ivf_index."""
+    default_rescore = "sign"         # (score_topk's default: re-scoring belongs to a BinaryCorpus)
+
+    def __init__(self, centroids: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, max_list: int,
+                 nprobe: Optional[int] = None, centroids16: Optional[torch.Tensor] = None):
+        if centroids.dim() != 2 or centroids.dtype != torch.float32 or centroids.shape[0] == 0:
+            raise ValueError(f"IVFCorpus: centroids are fp32 [nlist, d], got {centroids.dtype} {tuple(centroids.shape)}")
+        nlist, d = (int(v) for v in centroids.shape)
+        if d == 0 or d % 8 or d > IVF_MAX_DIM or nlist > IVF_MAX_LISTS:
+            raise ValueError(f"IVFCorpus: d % 8 == 0, d <= {IVF_MAX_DIM} and nlist <= {IVF_MAX_LISTS} are required, got d = {d}, nlist = {nlist}")
+        if rows.dim() != 2 or rows.dtype != torch.float16 or rows.shape[0] == 0 or rows.shape[1] != d:
+            raise ValueError(f"IVFCorpus: rows are f16 [N, {d}] with N >= 1, got {rows.dtype} {tuple(rows.shape)}")
+        N = int(rows.shape[0])
+        if ids.dtype != torch.int64 or tuple(ids.shape) != (N,):
+            raise ValueError(f"IVFCorpus: ids must be int64 [{N}], got {ids.dtype} {tuple(ids.shape)}")
+        if offsets.dtype != torch.int64 or tuple(offsets.shape) != (nlist + 1,):
+            raise ValueError(f"IVFCorpus: offsets must be int64 [{nlist + 1}], got {offsets.dtype} {tuple(offsets.shape)}")
+        if centroids16 is None:
+            centroids16 = centroids.to(torch.float16)      # (a conversion: round-to-nearest-even, as sgpt_f32_to_16)
+        if centroids16.dtype != torch.float16 or tuple(centroids16.shape) != (nlist, d):
+            raise ValueError(f"IVFCorpus: centroids16 must be f16 [{nlist}, {d}], got {centroids16.dtype} {tuple(centroids16.shape)}")
+        max_list = int(max_list)
+        if max_list < 0 or max_list > N:
+            raise ValueError(f"IVFCorpus: max_list (the longest list) must lie in [0, {N}], got {max_list}")
+        self.centroids, self.centroids16, self.rows, self.ids, self.offsets, self.max_list = centroids, centroids16, rows, ids, offsets, max_list
+        self.nprobe = self._check_nprobe(min(nlist, 32) if nprobe is None else nprobe)
+
+    @property
+    def nlist(self) -> int:
+        return int(self.centroids.shape[0])
+
+    @property
+    def dim(self) -> int:
+        return int(self.centroids.shape[1])
+
+    def __len__(self) -> int:
+        return int(self.rows.shape[0])
+
+    @property
+    def data(self) -> torch.Tensor:
+        return self.rows
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.centroids, self.centroids16, self.rows, self.ids, self.offsets))
+
+    def _check_nprobe(self, nprobe) -> int:
+        top = min(self.nlist, 1024)
+        if isinstance(nprobe, bool) or not isinstance(nprobe, (int, np.integer)) or nprobe < 1 or nprobe > top:
+            raise ValueError(f"IVFCorpus: nprobe must be an integer in [1, {top}] (min(nlist, 1024)), got {nprobe!r}")
+        return int(nprobe)
+
+    def with_nprobe(self, nprobe: int) -> "IVFCorpus":
+        """The same index (shared tensors) probing `nprobe` lists per query."""
+        view = copy.copy(self)
+        view.nprobe = self._check_nprobe(nprobe)
+        return view
+
+    def check_search(self, score_function, top_k: int) -> bool:
+        """As _CodesCorpus.check_search: cos_sim only (the rows are normalised, k-means is spherical), top_k <= 1024, nprobe in range."""
+        if not _score_kind(score_function):
+            raise ValueError("semantic_search over an IVFCorpus scores with cos_sim only: the lists come from spherical k-means over "
+                             "L2-normalised rows, so dot_score and arbitrary score functions are not served")
+        if top_k > 1024:
+            raise ValueError(f"semantic_search over an IVFCorpus takes top_k <= 1024, got {top_k}")
+        self._check_nprobe(self.nprobe)
+        return True
+
+    def search(self, ctx, q, k: int, idx_base: int = 0, run=None, return_probes: bool = False):
+        """sgpt_ivf_search: q [nq, d] L2-normalised (upcast to fp32) -> (values fp32 [nq, k], indices int64 [nq, k], n_valid[, the probe
+        sets int64 [nq, nprobe]]); slots that found no row are (-inf, -1) inside n_valid."""
+        nprobe = self._check_nprobe(self.nprobe)
+        if k < 1 or k > 1024:
+            raise ValueError(f"score_topk over an IVFCorpus takes 1 <= k <= 1024, got {k}")
+        q = ctx._dev_f32(q)
+        nq, d = q.shape
+        if d != self.dim:
+            raise ValueError(f"embedding dims differ: {d} vs {self.dim}")
+        dev = dict(device=ctx.device)
+        c16, rows = self.centroids16.to(**dev).contiguous(), self.rows.to(**dev).contiguous()
+        ids, offsets = self.ids.to(**dev).contiguous(), self.offsets.to(**dev).contiguous()
+        val, idx, n_run = ctx._run_list(run, nq, k)
+        probes = torch.empty((nq, nprobe), dtype=torch.int64, device=ctx.device) if return_probes else None
+        n_out = C.c_int32(0)
+        ctx._chk(ctx.lib.sgpt_ivf_search(ctx.handle, _p(q), _p(c16), _p(rows), _p(ids), _p(offsets), nq, len(self), d, self.nlist, self.max_list,
+                                         nprobe, k, idx_base, _p(val), _p(idx), n_run, C.byref(n_out), _p(probes), _stream_ptr(ctx.device)),
+                 "sgpt_ivf_search")
+        return (val, idx, int(n_out.value), probes) if return_probes else (val, idx, int(n_out.value))
+
+    def score_topk(self, ctx, q, k, idx_base, run, dtype, rescore, rescore_multiplier):
+        _no_rescore(rescore, rescore_multiplier)
+        if dtype is not None:
+            raise ValueError(f"an IVFCorpus is scored from fp32 queries (the call rounds them to f16 for the centroids itself): dtype must be "
+                             f"None, got {dtype}")
+        return self.search(ctx, q, k, idx_base, run)
+
+
+CORPUS_KINDS = (QuantizedCorpus, Uint8Corpus, BinaryCorpus, IVFCorpus)
 
 
 def _matrix(emb, who: str) -> torch.Tensor:
@@ -479,6 +588,109 @@ class CorpusBuilders:
             if keep_fp8:
                 self._fp8_quantize_block(rows, fp8.codes[r0:r1], fp8.scale[r0:r1])
         return BinaryCorpus(bits, d, center, fp8, u8)
+
+
+    # ---- IVF corpus: spherical k-means lists (sgpt_ivf_lists, sgpt_ivf_centroids, sgpt_gather_rows) ----
+    def _ivf_rows(self, x: torch.Tensor, who: str) -> torch.Tensor:
+        if x.dtype not in (torch.float32, torch.float16):
+            x = x.to(torch.float32)
+        x = x.to(self.device).contiguous()
+        if x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0 or x.shape[1] % 8 or x.shape[1] > IVF_MAX_DIM:
+            raise ValueError(f"{who}: rows are [n, d] with d % 8 == 0 and d <= {IVF_MAX_DIM}, got {tuple(x.shape)}")
+        return x
+
+    def ivf_lists(self, assign: torch.Tensor, nlist: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """assign int64 [N] -> (offsets int64 [nlist + 1], perm int64 [N]): perm is the stable argsort of assign, offsets the exclusive
+        prefix of the list sizes; assignments outside [0, nlist) are clamped (include/sgpt_hip.h::sgpt_ivf_lists)."""
+        assign = assign.to(device=self.device, dtype=torch.int64).contiguous()
+        if assign.dim() != 1 or assign.shape[0] == 0:
+            raise ValueError(f"ivf_lists needs a non-empty [N] assignment, got {tuple(assign.shape)}")
+        N = int(assign.shape[0])
+        offsets = torch.empty((nlist + 1,), dtype=torch.int64, device=self.device)
+        perm = torch.empty((N,), dtype=torch.int64, device=self.device)
+        self._chk(self.lib.sgpt_ivf_lists(self.handle, _p(assign), N, nlist, _p(offsets), _p(perm), _stream_ptr(self.device)), "sgpt_ivf_lists")
+        return offsets, perm
+
+    def ivf_centroids(self, x: torch.Tensor, perm: torch.Tensor, offsets: torch.Tensor, prev: Optional[torch.Tensor] = None,
+                      normalize: bool = True) -> torch.Tensor:
+        """out[c] = sum of x[perm[p]] over list c (divided by its L2 norm with normalize), in the fixed order of
+        include/sgpt_hip.h::sgpt_ivf_centroids; x fp32 or f16 [n_x, d]; an empty list (or a zero / non-finite sum) gives prev[c] or zeros."""
+        x = self._ivf_rows(x, "ivf_centroids")
+        perm = perm.to(device=self.device, dtype=torch.int64).contiguous()
+        offsets = offsets.to(device=self.device, dtype=torch.int64).contiguous()
+        nlist, d = int(offsets.shape[0]) - 1, int(x.shape[1])
+        if prev is not None:
+            prev = prev.to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(prev.shape) != (nlist, d):
+                raise ValueError(f"ivf_centroids: prev must be [{nlist}, {d}], got {tuple(prev.shape)}")
+        out = torch.empty((nlist, d), dtype=torch.float32, device=self.device)
+        self._chk(self.lib.sgpt_ivf_centroids(self.handle, _p(x), _rt.DT_CODE[x.dtype], x.shape[0], d, _p(perm), perm.shape[0], _p(offsets), nlist,
+                                              _p(prev), 1 if normalize else 0, _p(out), _stream_ptr(self.device)), "sgpt_ivf_centroids")
+        return out
+
+    def gather_rows(self, x: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
+        """out[p] = RNE_f16(x[perm[p]]): x fp32 or f16 [n_x, d] -> f16 [len(perm), d] (include/sgpt_hip.h::sgpt_gather_rows)."""
+        x = self._ivf_rows(x, "gather_rows")
+        perm = perm.to(device=self.device, dtype=torch.int64).contiguous()
+        out = torch.empty((perm.shape[0], x.shape[1]), dtype=torch.float16, device=self.device)
+        self._chk(self.lib.sgpt_gather_rows(self.handle, _p(x), _rt.DT_CODE[x.dtype], x.shape[0], _p(perm), perm.shape[0], x.shape[1], _p(out),
+                                            _stream_ptr(self.device)), "sgpt_gather_rows")
+        return out
+
+    def ivf_assign(self, x16: torch.Tensor, centroids16: torch.Tensor, block_rows: int = 65536) -> torch.Tensor:
+        """The list of every row: the k = 1 result of the f16 scorer with the rows as queries against the centroids (ties to the lowest
+        list), in blocks of `block_rows` queries -> int64 [n]."""
+        assign = torch.empty((x16.shape[0],), dtype=torch.int64, device=self.device)
+        for r0 in range(0, x16.shape[0], block_rows):
+            _, idx, _ = self.score_topk(x16[r0:r0 + block_rows], centroids16, 1, dtype=torch.float16)
+            assign[r0:r0 + block_rows] = idx[:, 0]
+        return assign
+
+    def spherical_kmeans(self, x16: torch.Tensor, k: int, n_iter: int = 10, seed: int = 0, block_rows: int = 65536) -> torch.Tensor:
+        """Lloyd iterations over unit f16 rows [n, d] -> unit fp32 centroids [k, d], deterministic: the first centroids are the rows at a
+        seeded CPU randperm (sorted); every iteration assigns with the f16 scorer (ivf_assign), builds the lists (ivf_lists) and takes the
+        normalised list sums (ivf_centroids; an empty list keeps its centroid)."""
+        n = int(x16.shape[0])
+        if k < 1 or k > min(n, IVF_MAX_LISTS):
+            raise ValueError(f"spherical_kmeans: 1 <= k <= min(n, {IVF_MAX_LISTS}) is required, got k = {k}, n = {n}")
+        pick = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed)))[:k].sort().values.to(self.device)
+        centroids = self.ivf_centroids(x16, pick, torch.arange(k + 1, dtype=torch.int64, device=self.device))
+        for _ in range(int(n_iter)):
+            assign = self.ivf_assign(x16, self.to_16(centroids), block_rows)
+            offsets, perm = self.ivf_lists(assign, k)
+            centroids = self.ivf_centroids(x16, perm, offsets, prev=centroids)
+        return centroids
+
+    def ivf_index(self, emb, nlist: Optional[int] = None, n_iter: int = 10, train_size: Optional[int] = None, seed: int = 0,
+                  block_rows: int = 65536, nprobe: Optional[int] = None) -> IVFCorpus:
+        """Embeddings [N, d] (d % 8 == 0) -> IVFCorpus: rows L2-normalised and rounded to f16, spherical k-means (spherical_kmeans) on a
+        strided sample of `train_size` rows (default min(N, 256 nlist)), a final assignment of all N rows, the lists, the rows gathered in
+        list-major order.  nlist None: the power of two nearest 4 sqrt(N).  Works in blocks of `block_rows` rows: the fp32 copy of a large
+        corpus never exists whole on the device (its f16 copy does, twice while the rows are gathered); `emb` may live on the host.  torch
+        allocates and copies; every sum, score and sort is a kernel of this library."""
+        emb = _matrix(emb, "ivf_index")
+        N, d = emb.shape
+        if d % 8 or d > IVF_MAX_DIM:
+            raise ValueError(f"ivf_index: d % 8 == 0 and d <= {IVF_MAX_DIM} are required, got d = {d}")
+        if nlist is None:
+            nlist = 2 ** int(round(math.log2(4.0 * math.sqrt(N))))
+            nlist = max(1, min(nlist, N, IVF_MAX_LISTS))
+        if nlist < 1 or nlist > min(N, IVF_MAX_LISTS):
+            raise ValueError(f"ivf_index: 1 <= nlist <= min(N, {IVF_MAX_LISTS}) is required, got nlist = {nlist}, N = {N}")
+        x16 = torch.empty((N, d), dtype=torch.float16, device=self.device)
+        for r0 in range(0, N, block_rows):
+            x16[r0:r0 + block_rows] = self.l2_normalize(emb[r0:r0 + block_rows], out_dtype=torch.float16)
+        T = min(N, 256 * nlist) if train_size is None else int(train_size)
+        if T < nlist or T > N:
+            raise ValueError(f"ivf_index: nlist <= train_size <= N is required, got train_size = {T}")
+        step = N // T
+        train = x16 if step == 1 and T == N else x16[0:step * T:step].contiguous()
+        centroids = self.spherical_kmeans(train, nlist, n_iter, seed, block_rows)
+        centroids16 = self.to_16(centroids)
+        offsets, perm = self.ivf_lists(self.ivf_assign(x16, centroids16, block_rows), nlist)
+        rows = self.gather_rows(x16, perm)
+        sizes = offsets.cpu().numpy()
+        return IVFCorpus(centroids, rows, perm, offsets, int((sizes[1:] - sizes[:-1]).max()), nprobe, centroids16)
 
 
 from . import runtime as _rt  # noqa: E402  (last: runtime.py imports the names above, whichever of the two modules is loaded first)

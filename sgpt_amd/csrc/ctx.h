@@ -16,6 +16,7 @@ struct sgpt_ctx {
     void* ws4 = nullptr; size_t ws4_bytes = 0;      // refined / binary-corpus scorer: 16-bit or packed queries, stage-1 lists, candidate list, saved running list, flag
     void* ws5 = nullptr; size_t ws5_bytes = 0;      // evaluation (useb_eval.hip): sort keys, flag scan, block partials of sgpt_eval_pairs
     void* ws6 = nullptr; size_t ws6_bytes = 0;      // fp8 corpus (sgpt_score_topk_q8): f16 rows of the de-quantised block / ragged tail
+    void* ws7 = nullptr; size_t ws7_bytes = 0;      // IVF corpus (ivf.hip): sort keys, chunk partials; f16 queries, probe sets, candidate lists of sgpt_ivf_search
     size_t filt_flag_off = 0; int filt_chunks = 0;   // scorer: overflow flags (offset into ws2, which only grows) of the last pass's filtered chunks (sgpt_score_overflow_count)
     void* comm = nullptr;                         // ncclComm_t of this ctx (sgpt_comm_init), one per process / GPU
     int comm_rank = 0, comm_world = 0;

@@ -61,6 +61,7 @@ void sgpt_ctx_destroy(sgpt_ctx* c) {
     if (c->ws4) (void)hipFree(c->ws4);
     if (c->ws5) (void)hipFree(c->ws5);
     if (c->ws6) (void)hipFree(c->ws6);
+    if (c->ws7) (void)hipFree(c->ws7);
     if (c->range_flag) (void)hipFree(c->range_flag);
     for (auto& e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (hipEvent_t e : c->chain_ev) if (e) (void)hipEventDestroy(e);

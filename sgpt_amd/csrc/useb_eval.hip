@@ -15,8 +15,8 @@
 //     earlier chunks (exact), a chunk's 64 float terms are summed by the xor butterfly and the chunks added in ascending order.
 //
 // sgpt_eval_pairs -- TwitterPara: the global rank statistics of n scored pairs.
-//   * (score key, index) 64-bit keys are sorted ascending by a bitonic network: tiles of 2048 keys in LDS for the strides below
-//     2048, one global compare-exchange launch per stride above.  The keys are unique, so the result is the one sorted order.
+//   * (score key, index) 64-bit keys are sorted ascending by the bitonic network of sort64.h: tiles of 2048 keys in LDS for the strides
+//     below 2048, one global compare-exchange launch per stride above.  The keys are unique, so the result is the one sorted order.
 //   * A tie group is found from the sorted keys (neighbour compare, binary search only inside a group of equal scores):
 //     rank2 = first + last 1-based rank of the group = twice the averaged rank.
 //   * Positives and used rows at or above each threshold come from a three-launch inclusive scan of the (positive, used) flags
@@ -30,23 +30,17 @@
 #include "../../include/sgpt_hip.h"
 #include "common.h"
 #include "ctx.h"
+#include "sort64.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int GR_WAVES = 4;              // small groups per workgroup
 constexpr int GR_THREADS = GR_WAVES * WAVE;
 constexpr int GR_SMALL = WAVE;           // <= this: a wavefront per group
-constexpr int PR_TILE = 2048;            // keys sorted in LDS by one workgroup (16 KiB)
-constexpr int PR_THREADS = 256;
+constexpr int PR_TILE = S64_TILE;        // keys sorted in LDS by one workgroup (sort64.h)
+constexpr int PR_THREADS = S64_THREADS;
 constexpr int PR_SCAN = 1024;            // flags scanned by one workgroup (4 per thread)
 constexpr int PR_FLAG_WORD = 33;         // word of the ctx's 256-byte flag block that collects the NaN check (32: sgpt_eval_ranked)
-
-__device__ __forceinline__ uint32_t f2key(float f) {  // ascending uint order == ascending float order
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 __device__ __forceinline__ int popc_below_incl(u64 m, int lane) {   // set bits of m at lanes 0 .. lane
     return __popcll(m & (~0ull >> (63 - lane)));
@@ -255,43 +249,6 @@ __global__ __launch_bounds__(PR_THREADS) void pairs_keys_kernel(const float* __r
     if (__ballot(bad) && (threadIdx.x & (WAVE - 1)) == 0) atomicOr(flag, 1);
 }
 
-// one compare-exchange step of the ascending bitonic network on a tile in LDS whose first key is key `base` of the array
-__device__ __forceinline__ void tile_step(u64* s, int base, int size, int stride, int t) {
-    for (int p = t; p < PR_TILE / 2; p += PR_THREADS) {
-        const int i = ((p & ~(stride - 1)) << 1) | (p & (stride - 1)), j = i | stride;
-        const bool up = ((base + i) & size) == 0;
-        const u64 x = s[i], y = s[j];
-        if ((x > y) == up && x != y) { s[i] = y; s[j] = x; }
-    }
-    __syncthreads();
-}
-
-// FULL: every size 2 .. PR_TILE of the network (the first launch); else the strides below PR_TILE of one size > PR_TILE
-template <bool FULL>
-__global__ __launch_bounds__(PR_THREADS) void pairs_sort_tile_kernel(u64* __restrict__ keys, int size_outer) {
-    __shared__ u64 s[PR_TILE];
-    const int t = threadIdx.x;
-    const int base = blockIdx.x * PR_TILE;
-    for (int k = t; k < PR_TILE; k += PR_THREADS) s[k] = keys[base + k];
-    __syncthreads();
-    if (FULL) {
-        for (int size = 2; size <= PR_TILE; size <<= 1)
-            for (int stride = size >> 1; stride > 0; stride >>= 1) tile_step(s, base, size, stride, t);
-    } else {
-        for (int stride = PR_TILE >> 1; stride > 0; stride >>= 1) tile_step(s, base, size_outer, stride, t);
-    }
-    for (int k = t; k < PR_TILE; k += PR_THREADS) keys[base + k] = s[k];
-}
-
-__global__ __launch_bounds__(PR_THREADS) void pairs_sort_global_kernel(u64* __restrict__ keys, int np2, int size, int stride) {
-    const int p = blockIdx.x * PR_THREADS + threadIdx.x;
-    if (p >= (np2 >> 1)) return;
-    const int i = ((p & ~(stride - 1)) << 1) | (p & (stride - 1)), j = i | stride;
-    const bool up = (i & size) == 0;
-    const u64 x = keys[i], y = keys[j];
-    if ((x > y) == up && x != y) { keys[i] = y; keys[j] = x; }
-}
-
 // (positive << 32 | used) of sorted position p
 __device__ __forceinline__ u64 pair_flags(const u64* __restrict__ keys, const int* __restrict__ label, int n, int p) {
     if (p >= n) return 0ull;
@@ -348,18 +305,6 @@ __global__ __launch_bounds__(PR_THREADS) void pairs_scan_kernel(const u64* __res
     u64 total;
     const u64 before = block_scan_incl(v, sh, t, total) - v + bsum[blockIdx.x];
     for (int u = 0; u < 4; ++u) incl_out[p0 + u] = before + f[u];
-}
-
-// first p in [0, n) with keys[p] >= key (n if none)
-__device__ __forceinline__ int lower_bound_key(const u64* __restrict__ keys, int n, u64 key) {
-    int lo = 0, len = n;
-    while (len > 0) {
-        const int half = len >> 1;
-        const bool right = keys[lo + half] < key;
-        lo = right ? lo + half + 1 : lo;
-        len = right ? len - half - 1 : half;
-    }
-    return lo;
 }
 
 __global__ __launch_bounds__(PR_THREADS) void pairs_rank_kernel(const u64* __restrict__ keys, const u64* __restrict__ incl, int n,
@@ -510,12 +455,7 @@ extern "C" sgpt_status sgpt_eval_pairs(sgpt_ctx* c, const float* score, const in
     int* flag = c->range_flag + PR_FLAG_WORD;
     HIPC(c, hipMemsetAsync(flag, 0, sizeof(int), s));
     hipLaunchKernelGGL(pairs_keys_kernel, dim3(np2 / PR_THREADS), dim3(PR_THREADS), 0, s, score, n, np2, keys, flag);
-    hipLaunchKernelGGL(pairs_sort_tile_kernel<true>, dim3(np2 / PR_TILE), dim3(PR_THREADS), 0, s, keys, 0);
-    for (int size = PR_TILE * 2; size <= np2; size <<= 1) {
-        for (int stride = size >> 1; stride >= PR_TILE; stride >>= 1)
-            hipLaunchKernelGGL(pairs_sort_global_kernel, dim3(np2 / 2 / PR_THREADS), dim3(PR_THREADS), 0, s, keys, np2, size, stride);
-        hipLaunchKernelGGL(pairs_sort_tile_kernel<false>, dim3(np2 / PR_TILE), dim3(PR_THREADS), 0, s, keys, size);
-    }
+    launch_sort_u64(keys, np2, s);
     hipLaunchKernelGGL(pairs_block_sums_kernel, dim3(nblk), dim3(PR_THREADS), 0, s, keys, label, n, bsum);
     hipLaunchKernelGGL(pairs_scan_sums_kernel, dim3(1), dim3(PR_THREADS), 0, s, bsum, nblk);
     hipLaunchKernelGGL(pairs_scan_kernel, dim3(nblk), dim3(PR_THREADS), 0, s, keys, label, n, bsum, incl);

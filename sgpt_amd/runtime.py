@@ -9,7 +9,7 @@ import torch
 
 from . import _lib
 from ._lib import SGPT_BF16, SGPT_F16, SGPT_F32, POOL_MODES
-from .corpus import CORPUS_KINDS, RESCORE_MODES, BinaryCorpus, CorpusBuilders, QuantizedCorpus, Uint8Corpus, _no_rescore  # noqa: F401  (re-exported)
+from .corpus import CORPUS_KINDS, RESCORE_MODES, BinaryCorpus, CorpusBuilders, IVFCorpus, QuantizedCorpus, Uint8Corpus, _no_rescore  # noqa: F401  (re-exported)
 
 # torch dtype <-> element-type code of include/sgpt_hip.h
 DT_CODE = {torch.float32: SGPT_F32, torch.bfloat16: SGPT_BF16, torch.float16: SGPT_F16}

@@ -123,13 +123,38 @@ def quantize_embeddings(embeddings, precision: str = "fp8", normalize: bool = Tr
     return ctx.quantize_corpus(e, normalize=normalize)
 
 
+def build_ivf_index(embeddings, nlist=None, n_iter: int = 10, train_size=None, seed: int = 0, nprobe=None):
+    """Corpus embeddings [N, d] (d % 8 == 0) -> an IVFCorpus for semantic_search / Context.score_topk (Context.ivf_index): the rows
+    L2-normalised, cut into `nlist` lists by spherical k-means on the device (nlist None: the power of two nearest 4 sqrt(N)); a query
+    then scans its `nprobe` best lists only (corpus.with_nprobe(p) changes that).  Cosine only.  Deterministic for a given seed."""
+    if isinstance(embeddings, list):
+        embeddings = torch.stack(embeddings)
+    e = _wrap(embeddings)
+    ctx, _ = _ctx_for(e)
+    return ctx.ivf_index(e, nlist=nlist, n_iter=n_iter, train_size=train_size, seed=seed, nprobe=nprobe)
+
+
+def kmeans(embeddings, k: int, n_iter: int = 10, seed: int = 0):
+    """Spherical k-means of the L2-normalised rows on the device, the steps an IVF build takes (Context.spherical_kmeans) ->
+    (centroids fp32 [k, d] unit rows, labels int64 [N]: every row's best centroid by the f16 scorer, ties to the lowest)."""
+    if isinstance(embeddings, list):
+        embeddings = torch.stack(embeddings)
+    e = _wrap(embeddings)
+    ctx, home = _ctx_for(e)
+    x16 = ctx.l2_normalize(e, out_dtype=torch.float16)
+    centroids = ctx.spherical_kmeans(x16, int(k), n_iter, seed)
+    labels = ctx.ivf_assign(x16, ctx.to_16(centroids))
+    return (centroids, labels) if home.type == "cuda" else (centroids.cpu(), labels.cpu())
+
+
 def _binary_rescore(corpus: BinaryCorpus) -> str:
     return corpus.default_rescore
 
 
 def _hits(val: torch.Tensor, idx: torch.Tensor, n: int) -> List[List[dict]]:
     val, idx = val.cpu().tolist(), idx.cpu().tolist()
-    return [[{"corpus_id": j, "score": s} for j, s in zip(ii[:n], vv[:n])] for vv, ii in zip(val, idx)]
+    # (index -1: a slot that found no document -- an IVFCorpus whose probed lists hold fewer than top_k rows; no other list has one before n)
+    return [[{"corpus_id": j, "score": s} for j, s in zip(ii[:n], vv[:n]) if j >= 0] for vv, ii in zip(val, idx)]
 
 
 def semantic_search(query_embeddings, corpus_embeddings, query_chunk_size: int = 100,
@@ -142,7 +167,7 @@ def semantic_search(query_embeddings, corpus_embeddings, query_chunk_size: int =
     fp8 copy when it has one and is not centred, with its sign bits otherwise."""
     if isinstance(query_embeddings, list):
         query_embeddings = torch.stack(query_embeddings)
-    if isinstance(corpus_embeddings, CORPUS_KINDS):        # fp8 codes, uint8 codes or packed sign bits (corpus.py, quantize_embeddings)
+    if isinstance(corpus_embeddings, CORPUS_KINDS):        # fp8 codes, uint8 codes, packed sign bits or IVF lists (corpus.py)
         corpus, q = corpus_embeddings, _wrap(query_embeddings)
         cosine = corpus.check_search(score_function, top_k)           # (refusals come before anything reaches for the device)
         ctx, _ = _ctx_for(corpus.data, q)
