@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGPT_ABI_VERSION 26
+#define SGPT_ABI_VERSION 27
 
 /* The longest sequence (ABI v23): the token rows one sequence may own in the packed layout of sgpt_encode*, sgpt_attention_ex and
  * sgpt_attention_gqa (max_alloc_len <= SGPT_MAX_SEQ_LEN; a larger value is SGPT_ERR_INVALID, nothing launched).  32 768 is the
@@ -718,6 +718,56 @@ sgpt_status sgpt_ivf_search(sgpt_ctx* ctx, const float* q, const void* centroids
                             const int64_t* offsets, int32_t nq, int64_t N, int32_t d, int32_t nlist, int64_t max_list, int32_t nprobe,
                             int32_t k, int64_t idx_base, float* run_val, int64_t* run_idx, int32_t n_run, int32_t* n_out,
                             int64_t* probe_out /* int64[nq, nprobe] or NULL */, void* stream);
+
+/* IVF corpus over uint8 lists (ABI v27; csrc/ivf.hip): the index above with the uint8 codes of the uint8 corpus (one range per DIMENSION,
+ * sgpt_u8_quantize_rows) in its lists instead of f16 rows -- IVF-SQ8: ld bytes per stored row instead of 2 d.
+ *   format    centroids16, ids, offsets as above; codes device uint8 [N, ld] in list-major order, ld = ceil(d / 128) * 128, pad columns hold
+ *             128; start, step device fp32 [ld], pad columns 0.  Stored row n stands for x^[n][j] = start[j] + codes[n][j] * step[j].
+ *
+ * sgpt_u8_gather_quantize_rows: codes[p] = the rule of sgpt_u8_quantize_rows applied to x[perm[p]], p < n.
+ *   format    x device [n_x, d], x_dtype SGPT_F32 | SGPT_F16 (f16 elements are widened exactly), 16-byte aligned; perm device int64 [n];
+ *             start, step device fp32 [ld] (read for j < d); codes device uint8 [n, ld], 16-byte aligned.
+ *   value     codes[p][j] = clamp(rint((x[perm[p]][j] - start[j]) / step[j]), 0, 255) in fp32 (IEEE subtraction and division,
+ *             round-half-even; step == 0 or a NaN element gives 128) for j < d, 128 for d <= j < ld.  A perm entry outside [0, n_x) gives a
+ *             row of 128s.  Integer codes: no error beyond the rule's own.
+ *   result    bit-equal to sgpt_u8_quantize_rows of the gathered rows as fp32.  An index build needs the f16 rows once plus the codes,
+ *             never a second list-major f16 copy.
+ *   shapes    any n, n_x >= 1; one thread per 8 columns, 16- or 32-byte loads and one 8-byte store each.
+ *   SGPT_ERR_INVALID (nothing launched, outputs untouched): null pointers, another x_dtype, d <= 0, d % 8, d > SGPT_IVF_MAX_DIM, ld % 128,
+ *   d > ld, n or n_x <= 0, x or codes not 16-byte aligned.
+ *
+ * sgpt_ivf_search_u8: sgpt_ivf_search over such lists.
+ *   q         device fp32 [nq, d], L2-normalised by the caller, 16-byte aligned.
+ *   stage 1   that of sgpt_ivf_search, launch for launch: equal q and centroids16 give the same probe sets, bit for bit, as the f16 index.
+ *   stage 2   the work items of sgpt_ivf_search: one per (query, probed list, chunk of SGPT_IVF_CHUNK rows), the grid from max_list, no host
+ *             synchronisation; rows of a list beyond max_list are not scanned.
+ *   value     <q_i, x^_n> = qbias_i + sum_j q'_ij (code_nj - 128), q'_ij = q_ij * step_j (fp32, one rounding), qbias_i = sum_j q_ij * mid_j,
+ *             mid_j = start_j + 128 * step_j: q' and qbias are those of sgpt_u8_rescore, made by its prologue in one launch per call.
+ *             code - 128 and its conversion to fp32 are exact; accumulation is fp32; NaN -> -1.
+ *   order     fixed by ld alone.  G(ld) lanes of a wavefront cover a row, G = 8 for ld = 128, 16 for ld = 256, 32 for ld = 384 and 512, 64
+ *             beyond (a wavefront walks 64 / G rows at once): lane l of the G owns the 16-byte pieces l, l + G, ...; per lane four
+ *             accumulators (one per dword of a piece) take their four products by fma, bytes ascending, pieces ascending;
+ *             s = (a0 + a1) + (a2 + a3); the G lanes are added in the xor butterfly G / 2, .., 1; value = s + qbias.  The same
+ *             (q, code row) pair gives the same bits in any list, position, nq, nprobe or launch shape.
+ *   error     |value - <q, x^_n> in exact arithmetic| <= gamma_n (sum_j |q_j step_j c_nj| + sum_j |q_j mid_j|), c = code - 128,
+ *             gamma_n = n u / (1 - n u), u = 2^-24, n = max(4 ceil(ld / (16 G)) + log2(G) + 4, ceil(d / 256) + 12): a product passes the
+ *             rounding of q', at most 4 ceil(ld / (16 G)) fmas, 2 joining and log2(G) butterfly additions and the addition of qbias; a
+ *             term of qbias the two roundings of mid, its product, at most ceil(d / 256) + 8 additions of the prologue and that last
+ *             addition.  Quantisation: as sgpt_score_topk_u8.
+ *   select    as sgpt_ivf_search: every item keeps its min(k, SGPT_IVF_CHUNK) best (score descending, then original index ascending), the
+ *             items' pairs and the running list go through the select kernel of sgpt_topk_merge, in the same query groups.
+ *   result    as sgpt_ivf_search: rows sorted, indices ids[...] + idx_base, running list in/out (it must hold values of this entry);
+ *             *n_out = min(k, n_run + N), slots that found no row are (-inf, -1) inside that count.
+ *   shapes    any nq <= 65535; speed is claimed for nq <= 64 only, as there.
+ * SGPT_ERR_INVALID (nothing launched, outputs untouched): everything sgpt_ivf_search refuses (codes in the place of rows); null start or
+ * step; ld % 128; d > ld; ld > SGPT_IVF_MAX_DIM; codes not 16-byte aligned. */
+sgpt_status sgpt_u8_gather_quantize_rows(sgpt_ctx* ctx, const void* x, int32_t x_dtype, int64_t n_x, const int64_t* perm, int64_t n, int32_t d,
+                                         int32_t ld, const float* start, const float* step, uint8_t* codes, void* stream);
+sgpt_status sgpt_ivf_search_u8(sgpt_ctx* ctx, const float* q, const void* centroids16, const uint8_t* codes, const float* start,
+                               const float* step, const int64_t* ids, const int64_t* offsets, int32_t nq, int64_t N, int32_t d, int32_t ld,
+                               int32_t nlist, int64_t max_list, int32_t nprobe, int32_t k, int64_t idx_base, float* run_val,
+                               int64_t* run_idx, int32_t n_run, int32_t* n_out, int64_t* probe_out /* int64[nq, nprobe] or NULL */,
+                               void* stream);
 
 /* Diagnostics (ABI v19): of the filtered chunks of the LAST score + top-k pass on this context (sgpt_score_topk, _q8, _u8; _bits: its last
  * query group), how many overflowed their candidate lists and were recomputed by the predicated fallback.  Synchronises `stream`. */

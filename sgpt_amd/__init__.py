@@ -7,5 +7,5 @@ surface (biencoder/beir, biencoder/useb of Muennighoff/sgpt)."""
 __version__ = "0.1.0"
 
 from .model import EncodeGraph, SGPTConfig, SGPTModel, synthetic_bert_weights, synthetic_llama_weights, synthetic_qwen_weights, synthetic_weights  # noqa: F401
-from .corpus import BinaryCorpus, IVFCorpus, QuantizedCorpus, Uint8Corpus  # noqa: F401
+from .corpus import BinaryCorpus, IVFCorpus, IVFUint8Corpus, QuantizedCorpus, Uint8Corpus  # noqa: F401
 from .runtime import Context, get_context  # noqa: F401

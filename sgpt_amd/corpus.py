@@ -1,4 +1,4 @@
-"""The corpus kinds a search can run against besides plain rows -- QuantizedCorpus (fp8), Uint8Corpus, BinaryCorpus, IVFCorpus -- in one place:
+"""The corpus kinds a search can run against besides plain rows -- QuantizedCorpus (fp8), Uint8Corpus, BinaryCorpus, IVFCorpus, IVFUint8Corpus -- in one place:
 what each holds, what a search over it may ask (`check_search`, device-free), how it is scored (`score_topk`, the C entry of its
 format) and how it is built from embeddings (`CorpusBuilders`, the methods Context inherits).  util.semantic_search and
 Context.score_topk dispatch on CORPUS_KINDS once and know no kind by name.
@@ -258,7 +258,85 @@ class BinaryCorpus:
 IVF_CHUNK, IVF_MAX_DIM, IVF_MAX_LISTS = 256, 4096, 65536      # SGPT_IVF_CHUNK, SGPT_IVF_MAX_DIM, SGPT_IVF_MAX_LISTS of include/sgpt_hip.h
 
 
-class IVFCorpus:
+class _IVFLists:
+    """What the two IVF kinds share (f16 lists, uint8 lists): `centroids` [nlist, d], `nprobe` and its range, and what a search over
+    lists may ask."""
+    default_rescore = "sign"         # (score_topk's default: re-scoring belongs to a BinaryCorpus)
+
+    @property
+    def nlist(self) -> int:
+        return int(self.centroids.shape[0])
+
+    def _check_nprobe(self, nprobe) -> int:
+        top = min(self.nlist, 1024)
+        if isinstance(nprobe, bool) or not isinstance(nprobe, (int, np.integer)) or nprobe < 1 or nprobe > top:
+            raise ValueError(f"{type(self).__name__}: nprobe must be an integer in [1, {top}] (min(nlist, 1024)), got {nprobe!r}")
+        return int(nprobe)
+
+    def with_nprobe(self, nprobe: int):
+        """The same index (shared tensors) probing `nprobe` lists per query."""
+        view = copy.copy(self)
+        view.nprobe = self._check_nprobe(nprobe)
+        return view
+
+    def check_search(self, score_function, top_k: int) -> bool:
+        """As _CodesCorpus.check_search: cos_sim only (the rows are normalised, k-means is spherical), top_k <= 1024, nprobe in range."""
+        name = type(self).__name__
+        if not _score_kind(score_function):
+            raise ValueError(f"semantic_search over an {name} scores with cos_sim only: the lists come from spherical k-means over "
+                             "L2-normalised rows, so dot_score and arbitrary score functions are not served")
+        if top_k > 1024:
+            raise ValueError(f"semantic_search over an {name} takes top_k <= 1024, got {top_k}")
+        self._check_nprobe(self.nprobe)
+        return True
+
+    def _search_operands(self, ctx, q, k: int, run, return_probes: bool):
+        """The checks and buffers of a search call: (q fp32 on the device, nprobe, values, indices, n_run, probes or None)."""
+        nprobe = self._check_nprobe(self.nprobe)
+        if k < 1 or k > 1024:
+            raise ValueError(f"score_topk over an {type(self).__name__} takes 1 <= k <= 1024, got {k}")
+        q = ctx._dev_f32(q)
+        if q.shape[1] != self.dim:
+            raise ValueError(f"embedding dims differ: {q.shape[1]} vs {self.dim}")
+        val, idx, n_run = ctx._run_list(run, q.shape[0], k)
+        probes = torch.empty((q.shape[0], nprobe), dtype=torch.int64, device=ctx.device) if return_probes else None
+        return q, nprobe, val, idx, n_run, probes
+
+    def score_topk(self, ctx, q, k, idx_base, run, dtype, rescore, rescore_multiplier):
+        _no_rescore(rescore, rescore_multiplier)
+        if dtype is not None:
+            raise ValueError(f"an {type(self).__name__} is scored from fp32 queries (the call rounds them to f16 for the centroids itself): dtype "
+                             f"must be None, got {dtype}")
+        return self.search(ctx, q, k, idx_base, run)
+
+
+def _check_lists(name: str, centroids, N: int, ids, offsets, centroids16, max_list) -> Tuple[torch.Tensor, int]:
+    """What the constructors of the two IVF kinds ask of the parts they share -> (centroids16, max_list)."""
+    nlist, d = (int(v) for v in centroids.shape)
+    if ids.dtype != torch.int64 or tuple(ids.shape) != (N,):
+        raise ValueError(f"{name}: ids must be int64 [{N}], got {ids.dtype} {tuple(ids.shape)}")
+    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (nlist + 1,):
+        raise ValueError(f"{name}: offsets must be int64 [{nlist + 1}], got {offsets.dtype} {tuple(offsets.shape)}")
+    if centroids16 is None:
+        centroids16 = centroids.to(torch.float16)      # (a conversion: round-to-nearest-even, as sgpt_f32_to_16)
+    if centroids16.dtype != torch.float16 or tuple(centroids16.shape) != (nlist, d):
+        raise ValueError(f"{name}: centroids16 must be f16 [{nlist}, {d}], got {centroids16.dtype} {tuple(centroids16.shape)}")
+    max_list = int(max_list)
+    if max_list < 0 or max_list > N:
+        raise ValueError(f"{name}: max_list (the longest list) must lie in [0, {N}], got {max_list}")
+    return centroids16, max_list
+
+
+def _check_centroids(name: str, centroids) -> Tuple[int, int]:
+    if centroids.dim() != 2 or centroids.dtype != torch.float32 or centroids.shape[0] == 0:
+        raise ValueError(f"{name}: centroids are fp32 [nlist, d], got {centroids.dtype} {tuple(centroids.shape)}")
+    nlist, d = (int(v) for v in centroids.shape)
+    if d == 0 or d % 8 or d > IVF_MAX_DIM or nlist > IVF_MAX_LISTS:
+        raise ValueError(f"{name}: d % 8 == 0, d <= {IVF_MAX_DIM} and nlist <= {IVF_MAX_LISTS} are required, got d = {d}, nlist = {nlist}")
+    return nlist, d
+
+
+class IVFCorpus(_IVFLists):
     """A corpus held as inverted lists over spherical k-means centroids (include/sgpt_hip.h::sgpt_ivf_search): `centroids` fp32 [nlist, d]
     unit rows and `centroids16`, their f16 rounding; `rows` f16 [N, d] in list-major order, list c = rows[offsets[c]:offsets[c + 1]];
     `ids` int64 [N], the original row number of every stored row, ascending inside every list; `offsets` int64 [nlist + 1]; `max_list`, a
@@ -266,35 +344,14 @@ class IVFCorpus:
     scores the centroids with the f16 scorer and scans the nprobe best lists with fp32 accumulation: cosine only, approximate -- a hit
     outside the probed lists is missed, and slots that found no row come back as (-inf, -1).  Built by Context.ivf_index /
     util.build_ivf_index."""
-    default_rescore = "sign"         # (score_topk's default: re-scoring belongs to a BinaryCorpus)
-
     def __init__(self, centroids: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, max_list: int,
                  nprobe: Optional[int] = None, centroids16: Optional[torch.Tensor] = None):
-        if centroids.dim() != 2 or centroids.dtype != torch.float32 or centroids.shape[0] == 0:
-            raise ValueError(f"IVFCorpus: centroids are fp32 [nlist, d], got {centroids.dtype} {tuple(centroids.shape)}")
-        nlist, d = (int(v) for v in centroids.shape)
-        if d == 0 or d % 8 or d > IVF_MAX_DIM or nlist > IVF_MAX_LISTS:
-            raise ValueError(f"IVFCorpus: d % 8 == 0, d <= {IVF_MAX_DIM} and nlist <= {IVF_MAX_LISTS} are required, got d = {d}, nlist = {nlist}")
+        nlist, d = _check_centroids("IVFCorpus", centroids)
         if rows.dim() != 2 or rows.dtype != torch.float16 or rows.shape[0] == 0 or rows.shape[1] != d:
             raise ValueError(f"IVFCorpus: rows are f16 [N, {d}] with N >= 1, got {rows.dtype} {tuple(rows.shape)}")
-        N = int(rows.shape[0])
-        if ids.dtype != torch.int64 or tuple(ids.shape) != (N,):
-            raise ValueError(f"IVFCorpus: ids must be int64 [{N}], got {ids.dtype} {tuple(ids.shape)}")
-        if offsets.dtype != torch.int64 or tuple(offsets.shape) != (nlist + 1,):
-            raise ValueError(f"IVFCorpus: offsets must be int64 [{nlist + 1}], got {offsets.dtype} {tuple(offsets.shape)}")
-        if centroids16 is None:
-            centroids16 = centroids.to(torch.float16)      # (a conversion: round-to-nearest-even, as sgpt_f32_to_16)
-        if centroids16.dtype != torch.float16 or tuple(centroids16.shape) != (nlist, d):
-            raise ValueError(f"IVFCorpus: centroids16 must be f16 [{nlist}, {d}], got {centroids16.dtype} {tuple(centroids16.shape)}")
-        max_list = int(max_list)
-        if max_list < 0 or max_list > N:
-            raise ValueError(f"IVFCorpus: max_list (the longest list) must lie in [0, {N}], got {max_list}")
+        centroids16, max_list = _check_lists("IVFCorpus", centroids, int(rows.shape[0]), ids, offsets, centroids16, max_list)
         self.centroids, self.centroids16, self.rows, self.ids, self.offsets, self.max_list = centroids, centroids16, rows, ids, offsets, max_list
         self.nprobe = self._check_nprobe(min(nlist, 32) if nprobe is None else nprobe)
-
-    @property
-    def nlist(self) -> int:
-        return int(self.centroids.shape[0])
 
     @property
     def dim(self) -> int:
@@ -311,58 +368,94 @@ class IVFCorpus:
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in (self.centroids, self.centroids16, self.rows, self.ids, self.offsets))
 
-    def _check_nprobe(self, nprobe) -> int:
-        top = min(self.nlist, 1024)
-        if isinstance(nprobe, bool) or not isinstance(nprobe, (int, np.integer)) or nprobe < 1 or nprobe > top:
-            raise ValueError(f"IVFCorpus: nprobe must be an integer in [1, {top}] (min(nlist, 1024)), got {nprobe!r}")
-        return int(nprobe)
-
-    def with_nprobe(self, nprobe: int) -> "IVFCorpus":
-        """The same index (shared tensors) probing `nprobe` lists per query."""
-        view = copy.copy(self)
-        view.nprobe = self._check_nprobe(nprobe)
-        return view
-
-    def check_search(self, score_function, top_k: int) -> bool:
-        """As _CodesCorpus.check_search: cos_sim only (the rows are normalised, k-means is spherical), top_k <= 1024, nprobe in range."""
-        if not _score_kind(score_function):
-            raise ValueError("semantic_search over an IVFCorpus scores with cos_sim only: the lists come from spherical k-means over "
-                             "L2-normalised rows, so dot_score and arbitrary score functions are not served")
-        if top_k > 1024:
-            raise ValueError(f"semantic_search over an IVFCorpus takes top_k <= 1024, got {top_k}")
-        self._check_nprobe(self.nprobe)
-        return True
-
     def search(self, ctx, q, k: int, idx_base: int = 0, run=None, return_probes: bool = False):
         """sgpt_ivf_search: q [nq, d] L2-normalised (upcast to fp32) -> (values fp32 [nq, k], indices int64 [nq, k], n_valid[, the probe
         sets int64 [nq, nprobe]]); slots that found no row are (-inf, -1) inside n_valid."""
-        nprobe = self._check_nprobe(self.nprobe)
-        if k < 1 or k > 1024:
-            raise ValueError(f"score_topk over an IVFCorpus takes 1 <= k <= 1024, got {k}")
-        q = ctx._dev_f32(q)
-        nq, d = q.shape
-        if d != self.dim:
-            raise ValueError(f"embedding dims differ: {d} vs {self.dim}")
+        q, nprobe, val, idx, n_run, probes = self._search_operands(ctx, q, k, run, return_probes)
         dev = dict(device=ctx.device)
         c16, rows = self.centroids16.to(**dev).contiguous(), self.rows.to(**dev).contiguous()
         ids, offsets = self.ids.to(**dev).contiguous(), self.offsets.to(**dev).contiguous()
-        val, idx, n_run = ctx._run_list(run, nq, k)
-        probes = torch.empty((nq, nprobe), dtype=torch.int64, device=ctx.device) if return_probes else None
         n_out = C.c_int32(0)
-        ctx._chk(ctx.lib.sgpt_ivf_search(ctx.handle, _p(q), _p(c16), _p(rows), _p(ids), _p(offsets), nq, len(self), d, self.nlist, self.max_list,
-                                         nprobe, k, idx_base, _p(val), _p(idx), n_run, C.byref(n_out), _p(probes), _stream_ptr(ctx.device)),
-                 "sgpt_ivf_search")
+        ctx._chk(ctx.lib.sgpt_ivf_search(ctx.handle, _p(q), _p(c16), _p(rows), _p(ids), _p(offsets), q.shape[0], len(self), self.dim, self.nlist,
+                                         self.max_list, nprobe, k, idx_base, _p(val), _p(idx), n_run, C.byref(n_out), _p(probes),
+                                         _stream_ptr(ctx.device)), "sgpt_ivf_search")
         return (val, idx, int(n_out.value), probes) if return_probes else (val, idx, int(n_out.value))
 
-    def score_topk(self, ctx, q, k, idx_base, run, dtype, rescore, rescore_multiplier):
-        _no_rescore(rescore, rescore_multiplier)
-        if dtype is not None:
-            raise ValueError(f"an IVFCorpus is scored from fp32 queries (the call rounds them to f16 for the centroids itself): dtype must be "
-                             f"None, got {dtype}")
-        return self.search(ctx, q, k, idx_base, run)
+
+class IVFUint8Corpus(_IVFLists):
+    """An IVFCorpus whose lists hold uint8 codes with one range per dimension instead of f16 rows (include/sgpt_hip.h::sgpt_ivf_search_u8;
+    IVF-SQ8): `centroids`, `centroids16`, `ids`, `offsets`, `max_list`, `nprobe` as there; `codes` uint8 [N, ld] in list-major order,
+    ld = ceil(dim / 128) * 128, pad columns 128; `start`, `step` fp32 [ld], pad columns 0 -- stored row n stands for start + codes[n] *
+    step, the format of a Uint8Corpus.  ld bytes per row instead of 2 dim.  The probe sets are the f16 index's; the values are those of
+    the de-quantised rows.  Built by Context.ivf_index(precision="uint8") / util.build_ivf_index(precision="uint8")."""
+
+    def __init__(self, centroids: torch.Tensor, codes: torch.Tensor, start: torch.Tensor, step: torch.Tensor, ids: torch.Tensor,
+                 offsets: torch.Tensor, max_list: int, nprobe: Optional[int] = None, centroids16: Optional[torch.Tensor] = None,
+                 dim: Optional[int] = None):
+        nlist, d = _check_centroids("IVFUint8Corpus", centroids)
+        if codes.dim() != 2 or codes.dtype != torch.uint8 or codes.shape[0] == 0 or codes.shape[1] == 0 or codes.shape[1] % 128:
+            raise ValueError(f"IVFUint8Corpus: codes are uint8 [N, ld] with N >= 1 and ld % 128 == 0, got {codes.dtype} {tuple(codes.shape)}")
+        N, ld = (int(v) for v in codes.shape)
+        dim = d if dim is None else int(dim)
+        if dim != d or (dim + 127) // 128 * 128 != ld:
+            raise ValueError(f"IVFUint8Corpus: {ld} bytes per row do not hold dim = {dim} of centroids [{nlist}, {d}] (ld = ceil(dim / 128) * 128)")
+        for name, t in (("start", start), ("step", step)):
+            if t.dtype != torch.float32 or tuple(t.shape) != (ld,):
+                raise ValueError(f"IVFUint8Corpus: {name} must be fp32 [{ld}], got {t.dtype} {tuple(t.shape)}")
+        centroids16, max_list = _check_lists("IVFUint8Corpus", centroids, N, ids, offsets, centroids16, max_list)
+        self.centroids, self.centroids16, self.codes, self.start, self.step = centroids, centroids16, codes, start, step
+        self.ids, self.offsets, self.max_list, self.dim = ids, offsets, max_list, dim
+        self.nprobe = self._check_nprobe(min(nlist, 32) if nprobe is None else nprobe)
+
+    def __len__(self) -> int:
+        return int(self.codes.shape[0])
+
+    @property
+    def data(self) -> torch.Tensor:
+        return self.codes
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.centroids, self.centroids16, self.codes, self.start, self.step, self.ids,
+                                                          self.offsets))
+
+    def as_uint8_corpus(self) -> Uint8Corpus:
+        """The same codes (no copy) as a Uint8Corpus in LIST-MAJOR order: document p of it is row ids[p] of the embeddings.  What
+        Context.rescore_u8 and the full uint8 scan take."""
+        return Uint8Corpus(self.codes, self.start, self.step, True, self.dim)
+
+    def dequantize(self, dtype=torch.float32) -> torch.Tensor:
+        """The rows the scan stands for, start + codes * step, in list-major order (Uint8Corpus.dequantize)."""
+        return self.as_uint8_corpus().dequantize(dtype)
+
+    def search(self, ctx, q, k: int, idx_base: int = 0, run=None, return_probes: bool = False):
+        """sgpt_ivf_search_u8: as IVFCorpus.search; a running list must hold values of this kind."""
+        q, nprobe, val, idx, n_run, probes = self._search_operands(ctx, q, k, run, return_probes)
+        dev = dict(device=ctx.device)
+        c16 = self.centroids16.to(**dev).contiguous()
+        codes, start, step = ctx._u8_operands(self)
+        ids, offsets = self.ids.to(**dev).contiguous(), self.offsets.to(**dev).contiguous()
+        n_out = C.c_int32(0)
+        ctx._chk(ctx.lib.sgpt_ivf_search_u8(ctx.handle, _p(q), _p(c16), _p(codes), _p(start), _p(step), _p(ids), _p(offsets), q.shape[0],
+                                            len(self), self.dim, codes.shape[1], self.nlist, self.max_list, nprobe, k, idx_base, _p(val),
+                                            _p(idx), n_run, C.byref(n_out), _p(probes), _stream_ptr(ctx.device)), "sgpt_ivf_search_u8")
+        return (val, idx, int(n_out.value), probes) if return_probes else (val, idx, int(n_out.value))
 
 
-CORPUS_KINDS = (QuantizedCorpus, Uint8Corpus, BinaryCorpus, IVFCorpus)
+CORPUS_KINDS = (QuantizedCorpus, Uint8Corpus, BinaryCorpus, IVFCorpus, IVFUint8Corpus)
+
+
+def check_ivf_precision(who: str, precision, ranges, calibration_embeddings) -> None:
+    """What an IVF build may be asked to hold in its lists (device-free): "f16" rows or "uint8" codes with their ranges."""
+    if precision == "int8":
+        raise ValueError(f"{who}: precision 'int8' is not built -- the same scalar quantisation is precision=\"uint8\" (its codes are the "
+                         "int8 codes + 128)")
+    if precision not in ("f16", "uint8"):
+        raise ValueError(f"{who}: unknown precision {precision!r} (only 'f16' and 'uint8' lists are built)")
+    if precision == "f16" and (ranges is not None or calibration_embeddings is not None):
+        raise ValueError(f"{who}: ranges / calibration_embeddings belong to precision='uint8'")
+    if ranges is not None and calibration_embeddings is not None:
+        raise ValueError(f"{who}: give ranges or calibration_embeddings, not both")
 
 
 def _matrix(emb, who: str) -> torch.Tensor:
@@ -471,37 +564,42 @@ class CorpusBuilders:
             self.u8_quantize_rows(rows, start, step, out=codes[r0:r0 + block_rows])
         return Uint8Corpus(codes, start, step, bool(normalize), d)
 
-    def _u8_ranges(self, emb: torch.Tensor, normalize: bool, ranges, calibration_embeddings, block_rows: int):
+    def _u8_ranges(self, emb: torch.Tensor, normalize: bool, ranges, calibration_embeddings, block_rows: int,
+                   who: str = "scalar_quantize_corpus", blocks=None):
         """(start, step) fp32 [ld] of scalar_quantize_corpus's rule for the rows of emb [N, d]: from `ranges`, from
-        `calibration_embeddings`, or from emb itself."""
+        `calibration_embeddings`, or from emb itself.  blocks(src): the fp32 row blocks of a source as they are quantised (default: _row_blocks
+        under `normalize`)."""
+        if blocks is None:
+            def blocks(src):
+                return (rows for _, rows in self._row_blocks(src, normalize, block_rows))
         if ranges is not None and calibration_embeddings is not None:
-            raise ValueError("scalar_quantize_corpus: give ranges or calibration_embeddings, not both")
+            raise ValueError(f"{who}: give ranges or calibration_embeddings, not both")
         N, d = emb.shape
         ld = (d + 127) // 128 * 128
         if ranges is not None:
             ranges = torch.as_tensor(np.asarray(ranges.cpu() if isinstance(ranges, torch.Tensor) else ranges)).to(torch.float32)
             if tuple(ranges.shape) != (2, d):
-                raise ValueError(f"scalar_quantize_corpus: ranges must be [2, {d}] (min row, max row), got {tuple(ranges.shape)}")
+                raise ValueError(f"{who}: ranges must be [2, {d}] (min row, max row), got {tuple(ranges.shape)}")
             mn, mx = ranges[0].to(self.device).contiguous(), ranges[1].to(self.device).contiguous()
         else:
             src = emb if calibration_embeddings is None else calibration_embeddings
             if not isinstance(src, torch.Tensor):
                 src = torch.as_tensor(np.asarray(src))
             if src.dim() != 2 or src.shape[0] == 0 or src.shape[1] != d:
-                raise ValueError(f"scalar_quantize_corpus: calibration_embeddings must be a non-empty [n, {d}] matrix, got {tuple(src.shape)}")
+                raise ValueError(f"{who}: calibration_embeddings must be a non-empty [n, {d}] matrix, got {tuple(src.shape)}")
             run = None
-            for _, rows in self._row_blocks(src, normalize, block_rows):
+            for rows in blocks(src):
                 run = self.u8_col_minmax(rows, run)
             mn, mx = run
         if not bool(torch.isfinite(mn).all()) or not bool(torch.isfinite(mx).all()) or bool((mx < mn).any()):
-            raise ValueError("scalar_quantize_corpus: the ranges are not finite, or a max lies below its min (a NaN or inf in the rows they "
+            raise ValueError(f"{who}: the ranges are not finite, or a max lies below its min (a NaN or inf in the rows they "
                              "come from)")
         start = torch.zeros((ld,), dtype=torch.float32, device=self.device)
         step = torch.zeros((ld,), dtype=torch.float32, device=self.device)
         start[:d] = mn
         step[:d] = (mx - mn) / torch.full_like(mx, 255.0)      # (a tensor divisor: one IEEE division per column, not a multiplication by 1 / 255)
         if not bool(torch.isfinite(step).all()):
-            raise ValueError("scalar_quantize_corpus: max - min overflows fp32")
+            raise ValueError(f"{who}: max - min overflows fp32")
         return start, step
 
     def rescore_u8(self, q, corpus_u8: Uint8Corpus, idx: torch.Tensor, idx_base: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -637,6 +735,23 @@ class CorpusBuilders:
                                             _stream_ptr(self.device)), "sgpt_gather_rows")
         return out
 
+    def gather_quantize_rows(self, x: torch.Tensor, perm: torch.Tensor, start: torch.Tensor, step: torch.Tensor) -> torch.Tensor:
+        """codes[p] = the uint8 rule of u8_quantize_rows applied to x[perm[p]]: x fp32 or f16 [n_x, d], start / step fp32 [ld],
+        ld = ceil(d / 128) * 128 -> uint8 [len(perm), ld], pad columns 128; a perm entry outside [0, n_x) gives a row of 128s
+        (include/sgpt_hip.h::sgpt_u8_gather_quantize_rows)."""
+        x = self._ivf_rows(x, "gather_quantize_rows")
+        perm = perm.to(device=self.device, dtype=torch.int64).contiguous()
+        start = start.to(device=self.device, dtype=torch.float32).contiguous()
+        step = step.to(device=self.device, dtype=torch.float32).contiguous()
+        ld = int(start.shape[0])
+        if tuple(step.shape) != (ld,):
+            raise ValueError(f"gather_quantize_rows: start and step must be [ld], got {tuple(start.shape)} and {tuple(step.shape)}")
+        out = torch.empty((perm.shape[0], ld), dtype=torch.uint8, device=self.device)
+        self._chk(self.lib.sgpt_u8_gather_quantize_rows(self.handle, _p(x), _rt.DT_CODE[x.dtype], x.shape[0], _p(perm), perm.shape[0], x.shape[1],
+                                                        ld, _p(start), _p(step), _p(out), _stream_ptr(self.device)),
+                  "sgpt_u8_gather_quantize_rows")
+        return out
+
     def ivf_assign(self, x16: torch.Tensor, centroids16: torch.Tensor, block_rows: int = 65536) -> torch.Tensor:
         """The list of every row: the k = 1 result of the f16 scorer with the rows as queries against the centroids (ties to the lowest
         list), in blocks of `block_rows` queries -> int64 [n]."""
@@ -662,12 +777,17 @@ class CorpusBuilders:
         return centroids
 
     def ivf_index(self, emb, nlist: Optional[int] = None, n_iter: int = 10, train_size: Optional[int] = None, seed: int = 0,
-                  block_rows: int = 65536, nprobe: Optional[int] = None) -> IVFCorpus:
+                  block_rows: int = 65536, nprobe: Optional[int] = None, precision: str = "f16", ranges=None, calibration_embeddings=None):
         """Embeddings [N, d] (d % 8 == 0) -> IVFCorpus: rows L2-normalised and rounded to f16, spherical k-means (spherical_kmeans) on a
         strided sample of `train_size` rows (default min(N, 256 nlist)), a final assignment of all N rows, the lists, the rows gathered in
         list-major order.  nlist None: the power of two nearest 4 sqrt(N).  Works in blocks of `block_rows` rows: the fp32 copy of a large
         corpus never exists whole on the device (its f16 copy does, twice while the rows are gathered); `emb` may live on the host.  torch
-        allocates and copies; every sum, score and sort is a kernel of this library."""
+        allocates and copies; every sum, score and sort is a kernel of this library.
+        precision="uint8" -> IVFUint8Corpus: the same clustering and lists (same seed: the same centroids, ids and offsets, bit for bit),
+        the lists holding uint8 codes of the f16-rounded unit rows by scalar_quantize_corpus's rule (gather_quantize_rows: the f16 rows
+        exist once, beside the codes).  The ranges are `ranges` ([2, d]: min row, max row), or those of `calibration_embeddings`
+        (normalised and rounded to f16 like the corpus), or the corpus's own; elements outside them clamp."""
+        check_ivf_precision("ivf_index", precision, ranges, calibration_embeddings)
         emb = _matrix(emb, "ivf_index")
         N, d = emb.shape
         if d % 8 or d > IVF_MAX_DIM:
@@ -688,9 +808,18 @@ class CorpusBuilders:
         centroids = self.spherical_kmeans(train, nlist, n_iter, seed, block_rows)
         centroids16 = self.to_16(centroids)
         offsets, perm = self.ivf_lists(self.ivf_assign(x16, centroids16, block_rows), nlist)
-        rows = self.gather_rows(x16, perm)
         sizes = offsets.cpu().numpy()
-        return IVFCorpus(centroids, rows, perm, offsets, int((sizes[1:] - sizes[:-1]).max()), nprobe, centroids16)
+        max_list = int((sizes[1:] - sizes[:-1]).max())
+        if precision == "f16":
+            return IVFCorpus(centroids, self.gather_rows(x16, perm), perm, offsets, max_list, nprobe, centroids16)
+
+        def blocks(src):      # the rows as they are quantised: unit rows rounded to f16 (the corpus's are x16 already), widened exactly
+            for r0 in range(0, src.shape[0], block_rows):
+                b = src[r0:r0 + block_rows]
+                yield (b if src is x16 else self.l2_normalize(b, out_dtype=torch.float16)).to(torch.float32)
+        start, qstep = self._u8_ranges(x16, True, ranges, calibration_embeddings, block_rows, "ivf_index", blocks)
+        codes = self.gather_quantize_rows(x16, perm, start, qstep)
+        return IVFUint8Corpus(centroids, codes, start, qstep, perm, offsets, max_list, nprobe, centroids16, d)
 
 
 from . import runtime as _rt  # noqa: E402  (last: runtime.py imports the names above, whichever of the two modules is loaded first)

@@ -379,6 +379,15 @@ void launch_u8_col_minmax(const float* x, long n, int d, int accumulate, float* 
 void launch_u8_quant_rows(const float* x, long n, int d, int ld, const float* start, const float* step, uint8_t* codes, hipStream_t s);
 void launch_u8_dequant_rows(const uint8_t* codes, long n, int ld, const float* start, const float* step, void* out, int out_dtype,
                             hipStream_t s);
+// (scoreu8.hip, ivf.hip) code of one element by the rule of include/sgpt_hip.h: clamp(rint((x - start) / step), 0, 255) in fp32 (IEEE subtraction and
+// division, round-half-even); step == 0, a NaN element or a NaN quotient give 128
+__device__ __forceinline__ uint32_t u8_code(float x, float start, float step) {
+    if (step == 0.f) return 128u;
+    const float t = rintf(__fdiv_rn(__fsub_rn(x, start), step));
+    if (t != t) return 128u;
+    return (uint32_t)fminf(fmaxf(t, 0.f), 255.f);
+}
+
 // re-scoring of candidate lists from the codes (sgpt_u8_rescore, stage 2 of sgpt_score_topk_bits_u8).  prepare: q fp32 [nq][d] (any nq)
 // -> qs fp32 [nq][ld] = q_j step_j (pad columns zero), qbias fp32 [nq] = sum_j q_j mid_j.  rescore: the value qbias + <qs, code - 128> of
 // every slot of idx [nq, ld_idx] (m per row) into the first m columns of a [nq, ld_out] list (launch_rescore's layout and slot rules)

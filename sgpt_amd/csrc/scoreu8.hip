@@ -139,15 +139,6 @@ __global__ __launch_bounds__(256) void u8_col_minmax_kernel(const float* __restr
     }
 }
 
-// code of one element by the rule of include/sgpt_hip.h: clamp(rint((x - start) / step), 0, 255) in fp32 (IEEE subtraction and
-// division, round-half-even); step == 0, a NaN element or a NaN quotient give 128
-__device__ __forceinline__ uint32_t u8_code(float x, float start, float step) {
-    if (step == 0.f) return 128u;
-    const float t = rintf(__fdiv_rn(__fsub_rn(x, start), step));
-    if (t != t) return 128u;
-    return (uint32_t)fminf(fmaxf(t, 0.f), 255.f);
-}
-
 // x fp32 [n][d] -> codes [n][ld] (ld % 4 == 0; pad columns 128): one thread per 4 codes, one 4-byte store
 __global__ __launch_bounds__(256) void u8_quant_rows_kernel(const float* __restrict__ x, long n, int d, int ld,
                                                             const float* __restrict__ start, const float* __restrict__ step,

@@ -9,7 +9,7 @@ import torch
 
 from . import _lib
 from ._lib import SGPT_BF16, SGPT_F16, SGPT_F32, POOL_MODES
-from .corpus import CORPUS_KINDS, RESCORE_MODES, BinaryCorpus, CorpusBuilders, IVFCorpus, QuantizedCorpus, Uint8Corpus, _no_rescore  # noqa: F401  (re-exported)
+from .corpus import CORPUS_KINDS, RESCORE_MODES, BinaryCorpus, CorpusBuilders, IVFCorpus, IVFUint8Corpus, QuantizedCorpus, Uint8Corpus, _no_rescore  # noqa: F401  (re-exported)
 
 # torch dtype <-> element-type code of include/sgpt_hip.h
 DT_CODE = {torch.float32: SGPT_F32, torch.bfloat16: SGPT_BF16, torch.float16: SGPT_F16}
@@ -41,8 +41,8 @@ def get_context(device=None) -> "Context":
 
 
 class Context(CorpusBuilders):
-    """(The corpus builders and the row conversions under them -- quantize_corpus, scalar_quantize_corpus, binarize_corpus, u8_*,
-    pack_sign_bits, rescore_u8 -- are inherited from corpus.py.)"""
+    """(The corpus builders and the row conversions under them -- quantize_corpus, scalar_quantize_corpus, binarize_corpus, ivf_index, u8_*,
+    pack_sign_bits, rescore_u8, gather_rows, gather_quantize_rows -- are inherited from corpus.py.)"""
 
     def __init__(self, device_index: int):
         self.lib = _lib.load()

@@ -6,7 +6,7 @@ from typing import Callable, List
 import numpy as np
 import torch
 
-from .corpus import CORPUS_KINDS, BinaryCorpus
+from .corpus import CORPUS_KINDS, BinaryCorpus, check_ivf_precision
 from .runtime import get_context
 
 
@@ -123,15 +123,24 @@ def quantize_embeddings(embeddings, precision: str = "fp8", normalize: bool = Tr
     return ctx.quantize_corpus(e, normalize=normalize)
 
 
-def build_ivf_index(embeddings, nlist=None, n_iter: int = 10, train_size=None, seed: int = 0, nprobe=None):
+def build_ivf_index(embeddings, nlist=None, n_iter: int = 10, train_size=None, seed: int = 0, nprobe=None, precision: str = "f16",
+                    ranges=None, calibration_embeddings=None):
     """Corpus embeddings [N, d] (d % 8 == 0) -> an IVFCorpus for semantic_search / Context.score_topk (Context.ivf_index): the rows
     L2-normalised, cut into `nlist` lists by spherical k-means on the device (nlist None: the power of two nearest 4 sqrt(N)); a query
-    then scans its `nprobe` best lists only (corpus.with_nprobe(p) changes that).  Cosine only.  Deterministic for a given seed."""
+    then scans its `nprobe` best lists only (corpus.with_nprobe(p) changes that).  Cosine only.  Deterministic for a given seed.
+    precision="uint8": an IVFUint8Corpus -- the same lists holding uint8 codes with one range per dimension instead of f16 rows, half
+    the bytes per row; `ranges` / `calibration_embeddings` as quantize_embeddings(precision="uint8") takes them.  Its signed spelling
+    'int8' stays refused."""
+    check_ivf_precision("build_ivf_index", precision, ranges, calibration_embeddings)
     if isinstance(embeddings, list):
         embeddings = torch.stack(embeddings)
     e = _wrap(embeddings)
     ctx, _ = _ctx_for(e)
-    return ctx.ivf_index(e, nlist=nlist, n_iter=n_iter, train_size=train_size, seed=seed, nprobe=nprobe)
+    if isinstance(calibration_embeddings, list):
+        calibration_embeddings = torch.stack(calibration_embeddings)
+    cal = None if calibration_embeddings is None else _wrap(calibration_embeddings)
+    return ctx.ivf_index(e, nlist=nlist, n_iter=n_iter, train_size=train_size, seed=seed, nprobe=nprobe, precision=precision,
+                         ranges=ranges, calibration_embeddings=cal)
 
 
 def kmeans(embeddings, k: int, n_iter: int = 10, seed: int = 0):
@@ -167,7 +176,7 @@ def semantic_search(query_embeddings, corpus_embeddings, query_chunk_size: int =
     fp8 copy when it has one and is not centred, with its sign bits otherwise."""
     if isinstance(query_embeddings, list):
         query_embeddings = torch.stack(query_embeddings)
-    if isinstance(corpus_embeddings, CORPUS_KINDS):        # fp8 codes, uint8 codes, packed sign bits or IVF lists (corpus.py)
+    if isinstance(corpus_embeddings, CORPUS_KINDS):        # fp8 codes, uint8 codes, packed sign bits or IVF lists of f16 rows / uint8 codes (corpus.py)
         corpus, q = corpus_embeddings, _wrap(query_embeddings)
         cosine = corpus.check_search(score_function, top_k)           # (refusals come before anything reaches for the device)
         ctx, _ = _ctx_for(corpus.data, q)
